@@ -1,7 +1,16 @@
 #!/usr/bin/env python3
 """Headline benchmark: BT.709 NV12 -> sRGB BGRA decode throughput on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 4k|1080p|8k-half|4k-batch8]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 4k|1080p|8k-half|4k-batch8] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times EXACTLY K steps once (`value`, `ms_per_step` = that region / K), writes its outputs if
+--dump-outputs is given and prints the line -- nothing else.  --full adds everything else this file measures or checks, as
+described below: the headline from repeated regions stretched to >= 100 ms (median), the parity spot check against the CPU
+oracle, the first-allocation, smooth-content and same-run copy legs and the CPU baseline.
+
+--dump-outputs DIR: after the timed steps, a fixed sample of what the last timed step wrote (BGRA8 output rows, as float32)
+goes to DIR/<name>.npy (dump_plan); the frames are seeded, so two builds given the same arguments can be compared output for
+output.
 
 A "step" is one pass of the hot path over one batch of synthetic frames already resident in HBM: the whole ring of
 `--ring` distinct frames (default 256 x 4K = 3.2 GB in + 8.5 GB out, far beyond the 256 MB Infinity Cache, so the kernel
@@ -20,13 +29,14 @@ scaling.  --share M runs a single rank with the share of an 8/M-GPU job; --graph
 graph; --coalesce n turns on the decoder's coalescing submit (one-frame calls gathered n to a launch).
 
 Timing: W warmup steps, then the region of EXACTLY K steps -- barrier + stream sync, K steps, stream sync + barrier, MAX
-over ranks -- is timed (`k_step_region_ms`).  With the driver's K = 20 that is ~36 ms of work, so the reported figure comes
-from regions of m * K steps bracketed the same way, m the smallest integer that makes a region >= 100 ms (`region_steps`),
-measured `repeats` times (>= 5); the MEDIAN is reported (min / max beside it) and `ms_per_step` is per step.
+over ranks -- is timed (`k_step_region_ms`); a plain run reports it.  With --full, since with the driver's K = 20 that is ~36 ms
+of work, the reported figure comes from regions of m * K steps bracketed the same way, m the smallest integer that makes a
+region >= 100 ms (`region_steps`), measured `repeats` times (>= 5); the MEDIAN is reported (min / max beside it) and
+`ms_per_step` is per step.
 roofline.achieved comes from HIP events recorded on the launch stream around the same steps of the median region;
 roofline.same_run_copy_GBps is a 16-byte-per-lane non-temporal copy over the same slabs, timed in the same process.  Every
 region that counts is bracketed by two sentinel dispatches outside both clocks, so a rocprofv3 kernel trace of this command
-can be cut down to the timed launches (tools/pmc_summary.py).  cpu_baseline (rank 0, N=1 only) times the reference's own
+can be cut down to the timed launches (tools/pmc_summary.py).  cpu_baseline (--full; rank 0, N=1 only) times the reference's own
 per-pixel function (oracle/_ref, kind "reference") or, when that library is absent, the CPU oracle (kind "port") on WHOLE
 seeded frames: a 1080p and a 4K frame on one thread, then the workload's frame row-partitioned over the host cores.
 
@@ -121,6 +131,11 @@ def parse_args(argv=None):
                     help="let ranks wrap onto fewer GPUs than ranks (functional runs of the N > 1 path on a smaller box); the line then says "
                          "\"shared_devices\": true and n_gpus counts the DISTINCT devices.  Without it such a job is refused")
     ap.add_argument("--dry-run", action="store_true", help="no GPU: sleep instead of decoding (control-flow test)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: repeated stretched regions (median), the parity spot check, the "
+                         "first-allocation, smooth-content and copy legs, the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write a fixed sample of the last timed step's output to DIR/<name>.npy (float32; rank 0's ring)")
     return ap.parse_args(argv)
 
 
@@ -323,10 +338,12 @@ class GpuRunner:
         g, n = self.g, self.g["per_launch"]
         if g["batch8"]:  # one launch of this rank's share, walking the ring (and the streams)
             lane = self.turn % self.nstreams
+            self.last_frames = list(range(self.pos, self.pos + n))
             self.launch(self.pos, n, self.extra_streams[lane - 1] if lane else None)
             self.turn += 1
             self.pos = (self.pos + n) % g["ring"]
             return
+        self.last_frames = list(range(g["ring"]))
         for j in range(g["launches"]):
             self.launch(j * n, n)
 
@@ -351,7 +368,8 @@ class GpuRunner:
                 self._capi.check(self.lib.bt709hip_event_record(self.h, e, s))
                 self._capi.check(self.lib.bt709hip_stream_wait_event(self.h, self.stream, e))
             self._capi.check(self.lib.bt709hip_graph_end_capture(self.h, self.stream, C.byref(g)), "end capture")
-            self.graph = (k, g)
+            self.graph = (k, g, self.last_frames)
+        self.last_frames = self.graph[2]  # a replay decodes the frames recorded, not the ring position of now
         self._capi.check(self.lib.bt709hip_graph_launch(self.h, self.graph[1], self.stream), "graph launch")
 
     def sync(self):
@@ -404,6 +422,12 @@ class GpuRunner:
         decode dispatches between an opening and a closing sentinel of a rocprofv3 kernel trace."""
         self._capi.check(self.lib.bt709hip_copy_probe(self.h, self.scratch.value + (64 << 10), self.scratch.value,
                                                       (32 << 10) if closing else (4 << 10), self.stream), "sentinel")
+
+    def output_sample(self):
+        """--dump-outputs: dump_plan's rows of what the last step wrote into this rank's ring."""
+        self.sync()
+        return read_output_rows(self.np, self._capi, self.lib, self.h, self.stream, self.g, self.last_frames,
+                                lambda i: (self.surfs[i].bgra, self.surfs[i].stride))
 
     def spot_check(self, gamma):
         """Untimed parity tripwire over the launch the headline times: 16 output rows at the top, middle and bottom of one frame
@@ -520,6 +544,51 @@ def compare_with_oracle(np, _capi, lib, ctx, stream, g, gamma, picks, host_frame
                 return "MISMATCH in ring frame %d at output row %d" % (i, r0), checked
         checked.append(i)
     return "ok", checked
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SEED = 0x709D
+
+
+def dump_plan(g, frames):
+    """The fixed sample --dump-outputs writes, {name: [(ring frame, first output row, rows)]} over `frames` (the ring frames the
+    last timed step decoded): "bgra_band_rows" = `rows` (16) output rows at the top, middle and bottom of one frame per eighth of
+    them (the spot check's picks, sample_frames), "bgra_sampled_rows" = 64 single rows drawn with a fixed seed from all of them.
+    Fewer band rows when a row is so wide that the float32 copy would pass DUMP_MAX_BYTES."""
+    import numpy as np
+    OW, OH = g["OW"], g["OH"]
+    row_bytes = OW * 4 * 4  # BGRA, one float32 per byte
+    picks = [frames[i] for i in sample_frames(len(frames))]
+    n_sampled = 64
+    rows = max(1, min(16, OH, (DUMP_MAX_BYTES // row_bytes - n_sampled) // (3 * len(picks))))
+    band = [(f, r0, rows) for f in picks for r0 in (0, min((OH // 2) // 4 * 4, OH - rows), OH - rows)]
+    rng = np.random.default_rng(DUMP_SEED)
+    which, at = rng.integers(0, len(frames), n_sampled), rng.integers(0, OH, n_sampled)
+    return {"bgra_band_rows": band, "bgra_sampled_rows": [(frames[int(i)], int(r), 1) for i, r in zip(which, at)]}
+
+
+def read_output_rows(np, _capi, lib, ctx, stream, g, frames, surface_of):
+    """dump_plan's rows downloaded from the output surfaces: {name: float32 array (rows, OW, 4)} of BGRA byte values.  Untimed."""
+    out = {}
+    for name, parts in dump_plan(g, frames).items():
+        host = np.empty((sum(n for _, _, n in parts), g["OW"] * 4), np.uint8)
+        at = 0
+        for f, r0, n in parts:
+            ptr, stride = surface_of(f)
+            _capi.check(lib.bt709hip_download(ctx, host[at:].ctypes.data, host.shape[1], ptr + r0 * stride, stride, host.shape[1], n, stream),
+                        "download")
+            at += n
+        _capi.check(lib.bt709hip_stream_synchronize(ctx, stream))
+        out[name] = host.reshape(-1, g["OW"], 4).astype(np.float32)
+    return out
+
+
+def write_outputs(runner, directory):
+    """--dump-outputs DIR: DIR/<name>.npy for every array of runner.output_sample()."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, arr in runner.output_sample().items():
+        np.save(os.path.join(directory, name + ".npy"), arr)
 
 
 def ring_options(_capi, args):
@@ -683,6 +752,13 @@ class SetRunner:
     def sentinel(self, closing):
         for ctx, sc in zip(self.ctxs, self.scratch):
             self._capi.check(self.lib.bt709hip_copy_probe(ctx, sc.value + (64 << 10), sc.value, (32 << 10) if closing else (4 << 10), None), "sentinel")
+
+    def output_sample(self):
+        """--dump-outputs: dump_plan's rows of lane 0's ring (every step decodes the whole ring of every lane)."""
+        self.sync()
+        surfs = self.surfs[0]
+        return read_output_rows(self.np, self._capi, self.lib, self.ctxs[0], None, self.g, list(range(self.g["ring"])),
+                                lambda i: (surfs[i].bgra, surfs[i].stride))
 
     def spot_checks(self, gamma):
         self.run_steps(1)
@@ -868,6 +944,8 @@ def timed_region(runner, steps, barrier, headline=False):
 
 def main(argv=None):
     args = parse_args(argv)
+    if args.dump_outputs and args.dry_run:
+        sys.exit("--dump-outputs: a dry run computes no outputs")
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -964,10 +1042,10 @@ def main(argv=None):
     if not args.dry_run and not kernel_name.startswith("decode_nv12"):
         sys.exit("bench.py: the step launched %r, not a decode kernel" % kernel_name)
     # The contract's region: EXACTLY K steps between barrier + sync on both sides.  It is timed first and reported
-    # (`k_step_region_ms`); with the driver's K = 20 it is ~10 ms of GPU work, too short to quote alone (SURVEY 8(d)
-    # asks for >= 100 ms per timing), so the figure that is reported as `value` comes from regions of m * K steps,
-    # m the smallest integer that makes a region >= 100 ms (every rank must agree: MAX over ranks), bracketed the
-    # same way; `ms_per_step` = median region / (m * K).
+    # (`k_step_region_ms`); a plain run quotes it as `value` and stops timing there.  With --full: with the driver's K = 20
+    # it is ~10 ms of GPU work, too short to quote alone (SURVEY 8(d) asks for >= 100 ms per timing), so the figure that is
+    # reported as `value` comes from regions of m * K steps, m the smallest integer that makes a region >= 100 ms (every
+    # rank must agree: MAX over ranks), bracketed the same way; `ms_per_step` = median region / (m * K).
     own = []  # this process's own (host seconds, [event ms per lane]) of every region that counts: per_rank below
 
     def region(steps):
@@ -975,19 +1053,23 @@ def main(argv=None):
         own.append((steps, mine[0], list(runner.lane_ms)))
         return max_over_ranks(mine)
     first = region(args.steps)
-    stretch = int(max(1, min(4096, -(-0.100 // max(first[0], 1e-6)))))
-    stretch = int(max_over_ranks([float(stretch)])[0])
-    region_steps = args.steps * stretch
-    samples = [first] if stretch == 1 else []
-    repeats = args.repeats
-    if repeats <= 0:
-        repeats = int(max(5, min(40, -(-0.150 // (first[0] * stretch)))))
-        repeats = int(max_over_ranks([float(repeats)])[0])
-    while len(samples) < repeats:
-        samples.append(region(region_steps))
+    region_steps, samples = args.steps, [first]
+    if args.full:
+        stretch = int(max(1, min(4096, -(-0.100 // max(first[0], 1e-6)))))
+        stretch = int(max_over_ranks([float(stretch)])[0])
+        region_steps = args.steps * stretch
+        samples = [first] if stretch == 1 else []
+        repeats = args.repeats
+        if repeats <= 0:
+            repeats = int(max(5, min(40, -(-0.150 // (first[0] * stretch)))))
+            repeats = int(max_over_ranks([float(repeats)])[0])
+        while len(samples) < repeats:
+            samples.append(region(region_steps))
     samples.sort()
     elapsed, ev_ms = samples[len(samples) // 2]  # the median region (by host time) and ITS event time
     fastest, slowest = samples[0][0], samples[-1][0]
+    if args.dump_outputs and rank == 0:  # before anything else touches the ring
+        write_outputs(runner, args.dump_outputs)
 
     # whole job per step: every rank decodes frames_per_step frames (4k-batch8: the ranks' shares add up to 8)
     out_px_per_step = units * g["frames_per_step"] * g["OW"] * g["OH"]
@@ -1003,9 +1085,12 @@ def main(argv=None):
     # clocks), its device and its ring's placement.
     mine = sorted((host_s, lane_ms) for steps, host_s, lane_ms in own if steps == region_steps)
     my_host_s, my_lane_ms = mine[len(mine) // 2]
-    # Parity tripwire on EVERY unit, each over its OWN ring (the frames differ: seed 0x709 + i + 1000 unit); a mismatch on any of
-    # them nulls `value` and fails the whole job.  Untimed.
-    checks = runner.spot_checks(GAMMAS[args.gamma])
+    # Parity tripwire (--full) on EVERY unit, each over its OWN ring (the frames differ: seed 0x709 + i + 1000 unit); a mismatch on
+    # any of them nulls `value` and fails the whole job.  Untimed.
+    if args.full:
+        checks = runner.spot_checks(GAMMAS[args.gamma])
+    else:
+        checks = [("not run (--full runs it)", [])] * lanes
     my_records = []
     for lane in range(lanes):
         launch_s = (my_lane_ms[lane] / 1e3) / (region_steps * g["launches"])
@@ -1021,7 +1106,7 @@ def main(argv=None):
                                           "hunt_ms": pl.get("hunt_ms"), "peak_bytes": pl.get("peak_bytes")},
                                parity_spot_check=checks[lane][0], parity_spot_frames=checks[lane][1]))
     per_rank = [r for records in gather(my_records) for r in records]
-    failed = any(r["parity_spot_check"] != "ok" for r in per_rank)
+    failed = args.full and any(r["parity_spot_check"] != "ok" for r in per_rank)
     devices = sorted({(r["pci_bus_id"], r["uuid"]) for r in per_rank})
     n_distinct = len(devices)
 
@@ -1088,14 +1173,14 @@ def main(argv=None):
         # every rank's own clocks over the headline's regions (value comes from the MAX over ranks), device, placement, spot check
         "per_rank": [{k: r[k] for k in ("rank", "ordinal", "pci_bus_id", "ms_per_step", "avg_launch_us", "frac", "placement",
                                         "parity_spot_check")} for r in per_rank],
-        "parity_spot_check": "ok" if not failed else "; ".join("rank %d: %s" % (r["rank"], r["parity_spot_check"]) for r in per_rank
+        "parity_spot_check": per_rank[0]["parity_spot_check"] if not failed else "; ".join("rank %d: %s" % (r["rank"], r["parity_spot_check"]) for r in per_rank
                                                                 if r["parity_spot_check"] != "ok"),
-        "parity_spot_check_ranks": len(per_rank),  # every rank checks its own ring
+        "parity_spot_check_ranks": len(per_rank) if args.full else 0,  # every rank checks its own ring (--full)
         "parity_spot_frames": per_rank[0]["parity_spot_frames"],  # one ring frame per XCD band, 48 rows each; the same picks on every rank
     }
     result["roofline"].update(load_traffic(args.workload, g))
 
-    if rank == 0 and not args.dry_run and not failed and units == 1:
+    if args.full and rank == 0 and not args.dry_run and not failed and units == 1:
         result["roofline"].update(first_allocation_leg(runner, args, g, barrier, region_steps, achieved))
         if args.workload in ("4k", "8k-half") and args.content == "random" and not args.no_smooth_leg:
             result["roofline"]["smooth_content"] = smooth_leg(runner, args, g, barrier, region_steps)

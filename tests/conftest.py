@@ -1,5 +1,6 @@
 import json
 import os
+import subprocess
 import sys
 
 import numpy as np
@@ -26,11 +27,20 @@ def oracle():
 
 @pytest.fixture(scope="session")
 def reference():
-    """The reference's own headers compiled in place; container only."""
-    from oracle_lib import REF_SO, Reference
-    if not os.path.isdir("/root/reference") and not os.path.exists(REF_SO):
-        pytest.skip("reference tree not available on this machine")
-    return Reference()
+    """The reference's own headers compiled in place (oracle/_ref), or None where they have not been built: the tests that
+    take it hold the oracle to the reference's recorded outputs (live_reference) everywhere, and to the library itself
+    where it exists."""
+    from oracle_lib import Reference
+    try:
+        return Reference()
+    except (OSError, subprocess.CalledProcessError):
+        return None
+
+
+@pytest.fixture(scope="session")
+def live_reference():
+    """The reference's outputs for the inputs of tests/live_reference_cases.py (tests/golden/make_golden.py --live-reference)."""
+    return np.load(os.path.join(GOLDEN, "live_reference.npz"))
 
 
 @pytest.fixture(scope="session")

@@ -22,6 +22,8 @@ Outputs (all committed):
   pass2.json        sha256 of decode + pass 2 (2:1 and any-ratio rescale) composed of the reference's
                     own inlines (oracle/ref_harness.c) on seeded frames and on the pattern crops;
                     pass2_small.npz holds the small outputs themselves
+  live_reference.npz the reference headers' outputs for the seeded inputs of tests/live_reference_cases.py
+                    (`python tests/golden/make_golden.py --live-reference` regenerates only this one)
 """
 import hashlib
 import json
@@ -343,10 +345,23 @@ def collect_pass2(ref, pattern_arrays):
     return out, stored
 
 
+def write_live_reference(ref):
+    import live_reference_cases as lrc
+    out = {}
+    for collect in (lrc.pixel_outputs, lrc.encode_frame_outputs, lrc.pass2_outputs):
+        out.update({lrc.npz_key(k): v for k, v in collect(ref).items()})
+    path = os.path.join(HERE, "live_reference.npz")
+    np.savez_compressed(path, **out)
+    print("live_reference.npz", len(out), "arrays,", os.path.getsize(path), "bytes")
+
+
 def main():
     ref = Reference()
     if "--full-patterns" in sys.argv:
         write_full_patterns(ref)
+        return
+    if "--live-reference" in sys.argv:
+        write_live_reference(ref)
         return
     vec = collect_vectors()
     vec["histograms"] = collect_histograms()
@@ -365,6 +380,7 @@ def main():
     np.savez_compressed(os.path.join(HERE, "pass2_small.npz"), **{k.replace("/", "_"): v for k, v in stored.items()})
     print("pass2.json", len(p2["cases"]), "cases,", len(p2["patterns"]), "patterns")
     write_full_patterns(ref)
+    write_live_reference(ref)
 
 
 if __name__ == "__main__":

@@ -1471,7 +1471,7 @@ def test_bench_line_on_the_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--ring", "48", "--steps", "3", "--warmup", "1",
-                        "--placement-tries", "2", "--no-cpu-baseline", "--no-smooth-leg"], capture_output=True, text=True,
+                        "--placement-tries", "2", "--no-cpu-baseline", "--no-smooth-leg", "--full"], capture_output=True, text=True,
                        timeout=600, cwd=root, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -1485,6 +1485,42 @@ def test_bench_line_on_the_gpu():
     pl = d["config"]["placement"]
     assert pl["tries"] == 2 and pl["rings_resident"] == ["first", "hunted"] and pl["pairings_probed"] >= 2
     assert abs(d["value"] - 48 * 3840 * 2160 / (d["ms_per_step"] * 1e-3) / 1e9) / d["value"] < 1e-3
+
+
+def test_bench_dump_outputs_on_the_gpu(tmp_path):
+    """bench.py --dump-outputs DIR, a plain run on a short ring: the sample of the last timed step's output it writes (float32
+    BGRA rows, dump_plan) is exactly the oracle's decode of the same seeded frames (seed 0x709 + i), within 64 MB."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import bench
+    from oracle_lib import Oracle
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--ring", "48", "--steps", "2", "--warmup", "1",
+                        "--placement-tries", "1", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=root, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads(r.stdout.splitlines()[-1])
+    assert d["steps"] == 2 and d["region_steps"] == 2 and d["value"] > 100.0
+    g = bench.geometry("4k", 48, 65535)
+    plan = bench.dump_plan(g, list(range(g["ring"])))
+    assert sorted(os.listdir(out)) == sorted(name + ".npy" for name in plan)
+    assert sum(os.path.getsize(out / (name + ".npy")) for name in plan) <= 64 << 20
+    oracle, frames = Oracle(), {}
+    for name, parts in plan.items():
+        got = np.load(out / (name + ".npy"))
+        assert got.dtype == np.float32 and got.shape == (sum(n for _, _, n in parts), g["OW"], 4)
+        at = 0
+        for f, r0, n in parts:
+            if f not in frames:
+                buf = np.random.default_rng(0x709 + f).integers(0, 256, (1, g["y_bytes"] + g["c_bytes"]), dtype=np.uint8).reshape(-1)
+                frames[f] = bench.split_planes(buf, g)
+            y, c = frames[f]
+            want = oracle.decode_nv12(0, y, c, rows=(r0 - r0 % 2, r0 + n))[r0:r0 + n]  # the oracle starts on an even row
+            assert np.array_equal(got[at:at + n].reshape(n, -1), want.astype(np.float32)), (name, f, r0)
+            at += n
 
 
 @pytest.mark.gpu

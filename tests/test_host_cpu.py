@@ -615,7 +615,7 @@ def test_bench_two_ranks_gloo_dry_run():
     whole-job value = 2 x per-rank work / slowest rank."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "1", "--dry-run"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "1", "--dry-run", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -643,7 +643,7 @@ def test_bench_two_ranks_gloo_dry_run_batch8():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "1", "--dry-run",
-           "--workload", "4k-batch8"]
+           "--workload", "4k-batch8", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -713,7 +713,7 @@ def _plain_bench(n, extra=(), env_extra=None, timeout=300):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(env_extra or {})
     return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "5", "--warmup", "1", "--dry-run",
-                           *extra], capture_output=True, text=True, timeout=timeout, cwd=ROOT, env=env)
+                           "--full", *extra], capture_output=True, text=True, timeout=timeout, cwd=ROOT, env=env)
 
 
 @pytest.mark.parametrize("n", [2, 8])
@@ -834,6 +834,53 @@ def test_bench_spot_check_samples_every_xcd_band():
         assert len(picks) == 8 and picks[0] == 0 and picks[-1] == ring - 1
         assert sorted({p * 8 // ring for p in picks}) == list(range(8))
     assert bench.sample_frames(4) == [0, 1, 2, 3]
+
+
+def test_bench_plain_run_times_exactly_the_steps():
+    """A plain run (no --full) times ONE region of exactly --steps steps and does nothing its headline does not need: no
+    stretched repeats, no parity spot check, no CPU baseline; ms_per_step is that region over --steps."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--dry-run"],
+                       capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = r.stdout.splitlines()
+    assert len(lines) == 1
+    res = json.loads(lines[0])
+    assert res["steps"] == 7 and res["warmup"] == 2 and res["region_steps"] == 7 and res["repeats"] == 1
+    assert res["value_min"] == res["value"] == res["value_max"]
+    assert abs(res["ms_per_step"] * 7 - res["k_step_region_ms"]) < 1e-3 * res["k_step_region_ms"] + 1e-3
+    px = 7 * 256 * 3840 * 2160
+    assert abs(res["value"] - px / (res["ms_per_step"] * 7e-3) / 1e9) / res["value"] < 1e-3
+    for key in ("metric", "unit", "higher_is_better", "dtype"):
+        assert key in res
+    assert "cpu_baseline" not in res and res["parity_spot_check_ranks"] == 0 and res["parity_spot_check"].startswith("not run")
+    assert "first_allocation_frac" not in res["roofline"] and "same_run_copy_GBps" not in res["roofline"]
+    # a dry run computes nothing to dump: refused before it starts
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--dump-outputs", os.path.join(ROOT, "no_such_dir")],
+                       capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
+    assert r.returncode != 0 and "--dump-outputs" in r.stderr and not os.path.exists(os.path.join(ROOT, "no_such_dir"))
+
+
+def test_bench_dump_plan_is_fixed_and_bounded():
+    """--dump-outputs samples the last step's output by a fixed plan: the same rows every run, inside the frames that step
+    decoded and inside each frame, one frame per XCD band among them, at most 64 MB as float32 for every workload."""
+    import bench
+    sizes = [bench.geometry(wl, 0, 65535) for wl in bench.WORKLOADS]
+    sizes.append(dict(bench.geometry("4k", 0, 65535), OW=7680, OH=4320))  # a wide clip (--y4m)
+    sizes.append(dict(bench.geometry("4k", 0, 65535), OW=64, OH=8))       # a tiny one
+    for g in sizes:
+        for frames in (list(range(g["ring"])), list(range(16, 24)), [5]):
+            plan = bench.dump_plan(g, frames)
+            assert plan == bench.dump_plan(g, frames) and set(plan) == {"bgra_band_rows", "bgra_sampled_rows"}
+            rows = 0
+            for parts in plan.values():
+                for f, r0, n in parts:
+                    assert f in frames and 0 <= r0 and n >= 1 and r0 + n <= g["OH"]
+                    rows += n
+            assert rows * g["OW"] * 4 * 4 <= 64 << 20
+            assert len(plan["bgra_sampled_rows"]) == 64
+            band_frames = sorted({f for f, _, _ in plan["bgra_band_rows"]})
+            assert band_frames == [frames[i] for i in bench.sample_frames(len(frames))]
 
 
 def build_cpp_selftest(tmpdir):

@@ -340,7 +340,7 @@ def test_bench_n_greater_than_one_on_the_gpu(gh, launcher):
     than one device is visible, N = the device count without it.  The line counts the distinct devices, spot-checks every
     rank's own ring and names every rank's device."""
     ndev = visible()
-    common = ["--ring", "48", "--steps", "3", "--warmup", "1", "--placement-tries", "1", "--no-cpu-baseline", "--launcher", launcher]
+    common = ["--ring", "48", "--steps", "3", "--warmup", "1", "--placement-tries", "1", "--no-cpu-baseline", "--full", "--launcher", launcher]
     r, d = _bench(["--gpus", str(2 * ndev)] + common)
     assert r.returncode == 2 and d is None and "--allow-shared-devices" in r.stderr
     r, d = _bench(["--gpus", str(2 * ndev), "--allow-shared-devices"] + common)

@@ -4,7 +4,8 @@
     parsed by tests/golden/make_golden.py, file:line kept per record),
   * outputs of the reference's header functions run in the build container
     (tests/golden/reference.json + patterns.npz),
-  * and, when /root/reference is present, the reference headers themselves, live.
+  * outputs of the reference's header functions for seeded inputs (tests/golden/live_reference.npz) and, where
+    oracle/_ref has been built, the reference headers themselves, live.
 
 CPU only.  The oracle is the checker for the GPU parity tests, so it is pinned first.
 """
@@ -181,24 +182,27 @@ def test_whole_bundled_patterns(oracle, full_patterns):
 
 # ------------------------------------------------------------ live reference (here)
 
-def test_live_reference_pixels(oracle, reference):
-    rng = np.random.default_rng(1)
-    for gamma in GAMMAS:
-        for Y, Cb, Cr in rng.integers(0, 256, (2000, 3)):
-            assert oracle.decode_pixel(gamma, int(Y), int(Cb), int(Cr)) == \
-                reference.decode_pixel(gamma, int(Y), int(Cb), int(Cr))
-        for R, G, B in rng.integers(0, 256, (2000, 3)):
-            assert oracle.encode_pixel(gamma, int(R), int(G), int(B)) == \
-                reference.encode_pixel(gamma, int(R), int(G), int(B))
+def _against_reference(collect, oracle, reference, live_reference):
+    """The oracle's outputs for one group of live_reference_cases: equal to the recorded ones, and to the reference library's
+    own where it has been built."""
+    import live_reference_cases as lrc
+    got = collect(oracle)
+    assert got
+    for key, value in got.items():
+        assert np.array_equal(value, live_reference[lrc.npz_key(key)]), key
+    if reference is not None:
+        for key, value in collect(reference).items():
+            assert np.array_equal(got[key], value), key
 
 
-def test_live_reference_encode_frame(oracle, reference):
-    rng = np.random.default_rng(2)
-    bgra = rng.integers(0, 1 << 24, 32 * 16, dtype=np.uint32)
-    for ig, og in ((1, 0), (1, 1), (0, 0), (2, 2)):
-        y0, uv0 = reference.encode_nv12(bgra, 32, 16, ig, og)
-        y1, uv1 = oracle.encode_nv12(bgra, 32, 16, ig, og)
-        assert np.array_equal(y0, y1) and np.array_equal(uv0, uv1)
+def test_live_reference_pixels(oracle, reference, live_reference):
+    import live_reference_cases as lrc
+    _against_reference(lrc.pixel_outputs, oracle, reference, live_reference)
+
+
+def test_live_reference_encode_frame(oracle, reference, live_reference):
+    import live_reference_cases as lrc
+    _against_reference(lrc.encode_frame_outputs, oracle, reference, live_reference)
 
 
 # ------------------------------------------------------------------ frame semantics
@@ -289,16 +293,8 @@ def test_pass2_oracle_equals_reference_composed_fixture(oracle, pass2, patterns)
                 assert _sha(oracle.decode_nv12_scaled(gamma, y, c, ow, oh)) == rec["scaled/g%d/%dx%d" % (gamma, ow, oh)]
 
 
-def test_pass2_oracle_equals_reference_live(oracle, reference):
-    """Container only: the same comparison against the reference library itself on fresh frames."""
-    rng = np.random.default_rng(77)
-    for case in range(12):
-        w, h = 4 * int(rng.integers(1, 40)), 4 * int(rng.integers(1, 12))
-        gamma = int(rng.integers(0, 4))
-        y = rng.integers(0, 256, (h, w), dtype=np.uint8)
-        c = rng.integers(0, 256, (h // 2, w), dtype=np.uint8)
-        a = rng.integers(0, 256, (h, w), dtype=np.uint8) if case % 3 == 0 else None
-        assert np.array_equal(oracle.decode_nv12_half(gamma, y, c, alpha=a), reference.decode_nv12_half(gamma, y, c, alpha=a))
-        ow, oh = int(rng.integers(1, 2 * w)), int(rng.integers(1, 2 * h))
-        assert np.array_equal(oracle.decode_nv12_scaled(gamma, y, c, ow, oh, alpha=a),
-                              reference.decode_nv12_scaled(gamma, y, c, ow, oh, alpha=a))
+def test_pass2_oracle_equals_reference_live(oracle, reference, live_reference):
+    """The same comparison on fresh seeded frames of random size: against the reference's recorded outputs, and against the
+    reference library itself where it has been built."""
+    import live_reference_cases as lrc
+    _against_reference(lrc.pass2_outputs, oracle, reference, live_reference)

@@ -173,7 +173,7 @@ def test_bench_path_decodes_a_generated_clip(gh, tmp_path):
         frames = list(r)
     assert len(frames) == 64 and not np.array_equal(frames[0][0], frames[1][0])  # the pan moves the picture
     res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--y4m", str(clip), "--steps", "3", "--warmup", "1",
-                          "--no-cpu-baseline", "--placement-tries", "1"], capture_output=True, text=True, timeout=900)
+                          "--no-cpu-baseline", "--placement-tries", "1", "--full"], capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-2000:]
     d = json.loads(res.stdout)
     assert d["data"] == "y4m" and d["value"] and d["parity_spot_check"] == "ok" and len(d["parity_spot_frames"]) == 8

@@ -2,7 +2,7 @@
 # BASELINE config 5's per-GPU unit (SHARE frames per step, default 1 = the n = 8 point): HIP streams the steps rotate over,
 # and the same fork / join pattern recorded into one graph with parallel branches (--graph --streams N).
 cd "${GRAFT_REPO_ROOT:-.}"
-one() { python bench.py --workload 4k-batch8 --share ${SHARE:-1} --no-cpu-baseline --steps ${STEPS:-400} "$@" 2>&1 | python -c "
+one() { python bench.py --full --workload 4k-batch8 --share ${SHARE:-1} --no-cpu-baseline --steps ${STEPS:-400} "$@" 2>&1 | python -c "
 import sys,json
 t=sys.stdin.read().strip().splitlines()
 try:

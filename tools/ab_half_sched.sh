@@ -1,5 +1,5 @@
 cd "${GRAFT_REPO_ROOT:-.}"
-half() { python bench.py --workload 8k-half --no-cpu-baseline --steps 40 "$@" 2>/dev/null |
+half() { python bench.py --full --workload 8k-half --no-cpu-baseline --steps 40 "$@" 2>/dev/null |
   python -c "import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print(d['value'], 'Gpx/s', d['roofline']['avg_launch_us'], 'us', d['roofline']['frac'], d['parity_spot_check'])"; }
 for round in 1 2; do
   echo "== base (batch 6, U=2)"; half

@@ -8,7 +8,7 @@ IFS=';' read -ra LB <<< "$LIBS"
 for i in $(seq $N); do
   for l in "${LB[@]}"; do
     name=${l%%=*}; lib=${l#*=}; L=""; [ -n "$lib" ] && L="--library $lib"
-    timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-smooth-leg $L "$@" 2>>$O.err | python -c '
+    timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-smooth-leg $L "$@" 2>>$O.err | python -c '
 import sys, json
 d = json.loads(sys.stdin.read()); p = d["config"]["placement"]; r = d["roofline"]
 print("%-34s frac %.4f first_allocation %.4f hunt_ms %5.0f peak %.1f GB candidates %s chosen %s probe_chosen %.0f prescan %s" % (sys.argv[1], r["frac"], r["first_allocation_frac"],

@@ -8,7 +8,7 @@ cd "${GRAFT_REPO_ROOT:-.}"
 for round in 1 2 3; do
   for v in rne rtz; do echo "== decode_lab $v (round $round)"; tools/bin/decode_lab_$v 0 5 | head -2; done
 done
-half() { python bench.py --workload 8k-half --no-cpu-baseline --steps 40 "$@" 2>/dev/null |
+half() { python bench.py --full --workload 8k-half --no-cpu-baseline --steps 40 "$@" 2>/dev/null |
   python -c "import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print(d['value'], 'Gpx/s', d['roofline']['avg_launch_us'], 'us', d['roofline']['frac'], d['parity_spot_check'])"; }
 for round in 1 2 3; do
   echo "== half rne (round $round)"; half

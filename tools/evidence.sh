@@ -6,30 +6,30 @@ cd "${GRAFT_REPO_ROOT:-.}"
 O=gpurun_out/$R; mkdir -p $O
 python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1; echo "pytest rc=$?" >> $O/pytest.log; tail -3 $O/pytest.log
 python bench.py --steps 20 --warmup 5 > $O/bench_4k_driver_args.json 2> $O/bench_4k.err
-python bench.py --no-cpu-baseline > $O/bench_4k.json 2>/dev/null
-python bench.py --workload 1080p > $O/bench_1080p.json 2>/dev/null
+python bench.py --full --no-cpu-baseline > $O/bench_4k.json 2>/dev/null
+python bench.py --full --workload 1080p > $O/bench_1080p.json 2>/dev/null
 # round 6: the reference's own on-disk format as the bench's input -- a 64-frame 1080p clip written through the GPU encoder, then bench.py --y4m
 python tools/make_y4m_clip.py /tmp/qt_pattern_1080p.y4m --frames 64 > $O/make_y4m_clip.txt 2>&1
-python bench.py --y4m /tmp/qt_pattern_1080p.y4m > $O/bench_y4m.json 2> $O/bench_y4m.err
-python bench.py --workload 8k-half > $O/bench_8k-half.json 2>/dev/null
-for sh in 8 4 2 1; do python bench.py --workload 4k-batch8 --share $sh --no-cpu-baseline --steps 400 > $O/bench_batch8_share$sh.json 2>/dev/null; done
-python bench.py --workload 4k-batch8 --share 1 --streams 1 --no-cpu-baseline --steps 400 > $O/bench_batch8_share1_1stream.json 2>/dev/null
-python bench.py --workload 4k-batch8 --share 1 --streams 2 --no-cpu-baseline --steps 400 > $O/bench_batch8_share1_2streams.json 2>/dev/null
-python bench.py --workload 4k-batch8 --share 1 --graph --no-cpu-baseline --steps 400 > $O/bench_batch8_share1_graph.json 2>/dev/null
+python bench.py --full --y4m /tmp/qt_pattern_1080p.y4m > $O/bench_y4m.json 2> $O/bench_y4m.err
+python bench.py --full --workload 8k-half > $O/bench_8k-half.json 2>/dev/null
+for sh in 8 4 2 1; do python bench.py --full --workload 4k-batch8 --share $sh --no-cpu-baseline --steps 400 > $O/bench_batch8_share$sh.json 2>/dev/null; done
+python bench.py --full --workload 4k-batch8 --share 1 --streams 1 --no-cpu-baseline --steps 400 > $O/bench_batch8_share1_1stream.json 2>/dev/null
+python bench.py --full --workload 4k-batch8 --share 1 --streams 2 --no-cpu-baseline --steps 400 > $O/bench_batch8_share1_2streams.json 2>/dev/null
+python bench.py --full --workload 4k-batch8 --share 1 --graph --no-cpu-baseline --steps 400 > $O/bench_batch8_share1_graph.json 2>/dev/null
 # round 4: the reference's cadence (one frame per call, one stream) with the coalescing submit; the plain multi-rank command on one GPU
-for c in 8 32; do python bench.py --workload 4k-batch8 --share 1 --streams 1 --coalesce $c --no-cpu-baseline --steps 400 > $O/bench_batch8_share1_1stream_coalesce$c.json 2>/dev/null; done
+for c in 8 32; do python bench.py --full --workload 4k-batch8 --share 1 --streams 1 --coalesce $c --no-cpu-baseline --steps 400 > $O/bench_batch8_share1_1stream_coalesce$c.json 2>/dev/null; done
 # round 5: ranks that outnumber the visible GPUs are REFUSED (rc 2, no line) ...
-python bench.py --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_4k_plain_command_2ranks_refused.json 2> $O/bench_4k_plain_command_2ranks_refused.txt; echo "rc=$?" >> $O/bench_4k_plain_command_2ranks_refused.txt
+python bench.py --full --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_4k_plain_command_2ranks_refused.json 2> $O/bench_4k_plain_command_2ranks_refused.txt; echo "rc=$?" >> $O/bench_4k_plain_command_2ranks_refused.txt
 # ... unless asked for: the functional N > 1 run on this one-GPU box (shared_devices: true, n_gpus 1, every rank spot-checked)
-python bench.py --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline --allow-shared-devices > $O/bench_4k_plain_command_2ranks_one_gpu.json 2> $O/bench_4k_plain_command_2ranks_one_gpu.err
-python bench.py --gpus 4 --steps 20 --warmup 5 --no-cpu-baseline --allow-shared-devices > $O/bench_4k_plain_command_4ranks_one_gpu.json 2> $O/bench_4k_plain_command_4ranks_one_gpu.err
+python bench.py --full --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline --allow-shared-devices > $O/bench_4k_plain_command_2ranks_one_gpu.json 2> $O/bench_4k_plain_command_2ranks_one_gpu.err
+python bench.py --full --gpus 4 --steps 20 --warmup 5 --no-cpu-baseline --allow-shared-devices > $O/bench_4k_plain_command_4ranks_one_gpu.json 2> $O/bench_4k_plain_command_4ranks_one_gpu.err
 # ONE process driving N GPUs (bt709hip_ringset_*): two and four lanes wrapped onto this GPU
-python bench.py --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline --allow-shared-devices --launcher threads > $O/bench_4k_threads_2lanes_one_gpu.json 2> $O/bench_4k_threads_2lanes_one_gpu.err
-python bench.py --gpus 4 --steps 20 --warmup 5 --no-cpu-baseline --allow-shared-devices --launcher threads --ring 64 > $O/bench_4k_threads_4lanes_one_gpu.json 2> $O/bench_4k_threads_4lanes_one_gpu.err
+python bench.py --full --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline --allow-shared-devices --launcher threads > $O/bench_4k_threads_2lanes_one_gpu.json 2> $O/bench_4k_threads_2lanes_one_gpu.err
+python bench.py --full --gpus 4 --steps 20 --warmup 5 --no-cpu-baseline --allow-shared-devices --launcher threads --ring 64 > $O/bench_4k_threads_4lanes_one_gpu.json 2> $O/bench_4k_threads_4lanes_one_gpu.err
 # and the driver's launcher line, 2 ranks wrapped onto this one GPU
-python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline --allow-shared-devices > $O/bench_4k_torchrun_2ranks_one_gpu.json 2> $O/bench_4k_torchrun_2ranks_one_gpu.err
+python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline --allow-shared-devices > $O/bench_4k_torchrun_2ranks_one_gpu.json 2> $O/bench_4k_torchrun_2ranks_one_gpu.err
 python __graft_entry__.py smoke > $O/smoke.log 2>&1; tail -1 $O/smoke.log
-python bench.py --workload 8k-half --content flat --no-cpu-baseline > $O/bench_8k-half_flat.json 2>/dev/null
+python bench.py --full --workload 8k-half --content flat --no-cpu-baseline > $O/bench_8k-half_flat.json 2>/dev/null
 { tools/ab_batch8.sh; echo "# two frames per step"; SHARE=2 STREAMS="1 2 3 4" tools/ab_batch8.sh; } > $O/batch8_streams.txt 2>&1
 tools/encode_single_shapes.sh "320 512" "1 3" > $O/encode_single_shapes.txt 2>&1
 tools/ab_bands.sh > $O/ab_bands.txt 2>&1

@@ -5,6 +5,6 @@
 cd "${GRAFT_REPO_ROOT:-.}"
 for u in 1 2 3 4; do
   [ -f tools/bin/libbt709hip_u$u.so ] || python -m metalbt709decoder_amd.build --variant tools/bin/libbt709hip_u$u.so BT709_REP_STEP=$u >/dev/null
-  python bench.py --library tools/bin/libbt709hip_u$u.so --workload 8k-half --no-cpu-baseline --steps 100 2>/dev/null |
+  python bench.py --full --library tools/bin/libbt709hip_u$u.so --workload 8k-half --no-cpu-baseline --steps 100 2>/dev/null |
     python -c "import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print('step $u', d['value'], d['roofline']['avg_launch_us'])"
 done
