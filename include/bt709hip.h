@@ -40,7 +40,7 @@ extern "C" {
 
 /* ABI version of bt709hip.h + bt709hip_ext.h together: bumped whenever a struct layout or a signature changes or an
  * export is added.  Bindings compare it with bt709hip_abi_version() and refuse an older library. */
-#define BT709HIP_VERSION 502
+#define BT709HIP_VERSION 503
 
 typedef struct bt709hip_context bt709hip_context; /* ~ MetalRenderContext */
 typedef struct bt709hip_decoder bt709hip_decoder; /* ~ MetalBT709Decoder  */

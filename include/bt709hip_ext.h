@@ -343,6 +343,22 @@ typedef struct {
   int32_t launches, xcd_bands;
 } bt709hip_launch_info;
 int bt709hip_last_launch_info(bt709hip_launch_info *info);
+/* The plan of the last bt709hip_decode_scaled(_batch) / bt709hip_render_scaled(_batch) this thread issued, as its launcher settled it
+ * (tests assert the regime a shape ran in through it: tap form, strip length, persistent item loop, one-generation cut or per-CU
+ * rule).  BT709HIP_ERR_NOT_SETUP while this thread has launched neither (ABI 503). */
+enum { BT709HIP_SCALED_TAPS_BYTES = 0, BT709HIP_SCALED_TAPS_PAIRS = 1, BT709HIP_SCALED_TAPS_WIDE = 2, BT709HIP_SCALED_TAPS_SHARED = 3,
+       BT709HIP_SCALED_TAPS_ONCE = 4 };
+typedef struct {
+  uint32_t grid[3], block[3];
+  uint32_t taps;        /* tap form as launched (BT709HIP_SCALED_TAPS_*); render_scaled: 0 */
+  uint32_t rows;        /* output rows per strip */
+  uint32_t persistent;  /* 1: workgroups walk `items` by gridDim.x */
+  uint32_t balanced;    /* 1: the one-generation cut chose `rows`, 0: the per-CU rule */
+  uint32_t resident;    /* workgroups the chip holds at once, as the launcher worked it out (0 for render_scaled) */
+  uint32_t reserved;
+  uint64_t items;       /* work items = column tiles x strips x frames */
+} bt709hip_scaled_launch_info;
+int bt709hip_last_scaled_launch_info(bt709hip_scaled_launch_info *info);
 
 #ifdef __cplusplus
 }

@@ -24,7 +24,7 @@ class Surface(C.Structure):  # bt709hip_surface
                 ("format", C.c_int32), ("reserved", C.c_int32)]
 
 
-ABI_VERSION = 502  # BT709HIP_VERSION of the two headers these bindings were written against
+ABI_VERSION = 503  # BT709HIP_VERSION of the two headers these bindings were written against
 
 # bt709hip_format
 FORMAT_BGRA8_SRGB = 0
@@ -60,6 +60,16 @@ class RingOptions(C.Structure):  # bt709hip_ring_options
 
 class LaunchInfo(C.Structure):  # bt709hip_launch_info
     _fields_ = [("grid", C.c_uint32 * 3), ("block", C.c_uint32 * 3), ("launches", C.c_int32), ("xcd_bands", C.c_int32)]
+
+
+class ScaledLaunchInfo(C.Structure):  # bt709hip_scaled_launch_info
+    _fields_ = [("grid", C.c_uint32 * 3), ("block", C.c_uint32 * 3), ("taps", C.c_uint32), ("rows", C.c_uint32),
+                ("persistent", C.c_uint32), ("balanced", C.c_uint32), ("resident", C.c_uint32), ("reserved", C.c_uint32),
+                ("items", C.c_uint64)]
+
+
+# bt709hip_scaled_launch_info.taps (BT709HIP_SCALED_TAPS_*)
+SCALED_TAPS_BYTES, SCALED_TAPS_PAIRS, SCALED_TAPS_WIDE, SCALED_TAPS_SHARED, SCALED_TAPS_ONCE = range(5)
 
 
 class DeviceInfo(C.Structure):  # bt709hip_device_info
@@ -197,6 +207,7 @@ SYMBOLS = {
     "bt709hip_half_lookup": (_I, [_I, C.c_float, _I, C.POINTER(C.c_int)]),
     "bt709hip_last_kernel_name": (C.c_char_p, []),
     "bt709hip_last_launch_info": (_I, [C.POINTER(LaunchInfo)]),
+    "bt709hip_last_scaled_launch_info": (_I, [C.POINTER(ScaledLaunchInfo)]),
 }
 
 _lib = None

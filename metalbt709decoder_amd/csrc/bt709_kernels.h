@@ -129,6 +129,17 @@ struct RenderParams {
   uint32_t encode_log_first;
   int64_t in_step, out_step;  // batched launches: surface i of the launch = surface 0 + i * step (evenly spaced, as in a ring)
 };
+// The plan a rescale launcher settled on (bt709hip_last_scaled_launch_info: tests assert the regime a shape ran in through it).
+// The tap forms' values are part of the C ABI (BT709HIP_SCALED_TAPS_*).
+enum : int { TAPS_BYTES = 0, TAPS_PAIRS = 1, TAPS_WIDE = 2, TAPS_SHARED = 3, TAPS_ONCE = 4 };
+struct ScaledLaunchRecord {
+  uint32_t grid[3], block[3];
+  uint32_t taps, rows, persistent, balanced, resident, reserved;
+  uint64_t items;  // cols x strips x frames
+};
+// The two rescale launchers hand the plan of every launch they make to the host shim, which keeps it per thread next to the kernel
+// name (shim_core.cpp defines this).  A call and not an out-parameter: the launchers' signatures stay what test doubles link against.
+void record_scaled_launch(const ScaledLaunchRecord &record);
 // grid = (column tiles, strips of `rows` output rows, frames)
 const char *launch_render_scaled(const RenderParams &p, int frames, bool in_rgba16f, uint32_t compute_units, hipStream_t stream);
 

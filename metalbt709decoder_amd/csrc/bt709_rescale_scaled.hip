@@ -39,7 +39,7 @@ namespace bt709 {
 //   TAPS_BYTES any layout: byte loads.
 // 4-byte coalesced stores.
 // ---------------------------------------------------------------------------
-enum : int { TAPS_BYTES = 0, TAPS_PAIRS = 1, TAPS_WIDE = 2, TAPS_SHARED = 3, TAPS_ONCE = 4 };
+// the tap forms: enum TAPS_* of bt709_kernels.h
 
 // output rows whose source rows are fetched ahead of the row being produced (scaled_strip, "HOW FAR AHEAD"): per-lane tap
 // fetches (8 VGPRs per row in flight) and the two by-wave forms (4 per row)
@@ -660,6 +660,7 @@ const char *launch_render_scaled(const RenderParams &p_in, int frames, bool in_r
   if (static_cast<uint64_t>(p.height) * p.in_stride >= (1ull << 31) || static_cast<uint64_t>(p.out_height) * p.out_stride >= (1ull << 31)) return nullptr;
   const dim3 grid(cols, (p.out_height + rows - 1) / rows, static_cast<uint32_t>(frames));
   const size_t lds = static_cast<size_t>(p.table_encode_bytes) + 1024;
+  record_scaled_launch(ScaledLaunchRecord{{grid.x, grid.y, grid.z}, {kBlockThreads, 1, 1}, 0, rows, 0, 0, 0, 0, static_cast<uint64_t>(grid.x) * grid.y * grid.z});
   if (in_rgba16f) hipLaunchKernelGGL(render_scaled<true>, grid, dim3(kBlockThreads), lds, stream, p);
   else hipLaunchKernelGGL(render_scaled<false>, grid, dim3(kBlockThreads), lds, stream, p);
   return in_rgba16f ? "render_scaled<rgba16f>" : "render_scaled<bgra8>";
@@ -729,6 +730,7 @@ const char *launch_decode_scaled(const DecodeParams &p_in, int frames, bool has_
   else BT709_PICK_SCALED(TAPS_BYTES, true);
 #undef BT709_PICK_SCALED
   uint64_t resident = 0;
+  bool balanced = false;
   {
     // as many workgroups as the chip holds at once (what the registers and the tables' LDS allow per CU).  The answer
     // depends on the kernel variant, on the dynamic LDS (the decode-side table's size follows the gamma's bucket count)
@@ -770,7 +772,7 @@ const char *launch_decode_scaled(const DecodeParams &p_in, int frames, bool has_
     if (BT709_SCALED_BALANCE && kScaledStrips == 1 && static_cast<uint64_t>(cols) * p.out_height * static_cast<uint32_t>(frames) <= resident * max_rows) {
       for (uint32_t r = 4; r <= max_rows; r += step)
         if (static_cast<uint64_t>(cols) * ((p.out_height + r - 1) / r) * static_cast<uint32_t>(frames) <= resident) {
-          rows = r;
+          rows = r, balanced = true;
           break;
         }
     }
@@ -779,13 +781,15 @@ const char *launch_decode_scaled(const DecodeParams &p_in, int frames, bool has_
   const uint32_t strips = (p.out_height + rows - 1) / rows;
   const uint32_t strip_groups = (strips + kScaledStrips - 1) / kScaledStrips;
   dim3 grid(cols, strip_groups, static_cast<uint32_t>(frames));
+  const uint64_t items = static_cast<uint64_t>(cols) * strip_groups * static_cast<uint32_t>(frames);
   if (persistent) {
-    const uint64_t items = static_cast<uint64_t>(cols) * strip_groups * static_cast<uint32_t>(frames);
     if (items > 0x7fffffffull) return nullptr;
     p.tiles_x = cols;
     p.tile_rows = static_cast<uint32_t>(items);
     grid = dim3(static_cast<uint32_t>(items < resident ? items : resident), 1, 1);
   }
+  record_scaled_launch(ScaledLaunchRecord{{grid.x, grid.y, grid.z}, {block.x, block.y, block.z}, static_cast<uint32_t>(taps), rows, persistent ? 1u : 0u,
+                                          balanced ? 1u : 0u, static_cast<uint32_t>(resident), 0, items});
   void *args[] = {&p};
   (void)hipLaunchKernel(fn, grid, block, args, lds, stream);  // a failure is picked up by the caller's hipGetLastError
   return has_alpha ? "decode_nv12_scaled<alpha>" : "decode_nv12_scaled";

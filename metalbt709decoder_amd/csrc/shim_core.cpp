@@ -15,11 +15,15 @@ namespace bt709shim __attribute__((visibility("hidden"))) {
 namespace {
 thread_local hipError_t tl_hip_error = hipSuccess;
 thread_local const char *tl_kernel_name = "";
+thread_local bt709::ScaledLaunchRecord tl_scaled_launch = {};
+thread_local bool tl_scaled_launched = false;
 }  // namespace
 
 void set_kernel_name(const char *name) { tl_kernel_name = name; }
 const char *kernel_name() { return tl_kernel_name; }
 hipError_t last_hip_error() { return tl_hip_error; }
+const bt709::ScaledLaunchRecord *scaled_launch() { return tl_scaled_launched ? &tl_scaled_launch : nullptr; }
+static void store_scaled_launch(const bt709::ScaledLaunchRecord &record) { tl_scaled_launch = record, tl_scaled_launched = true; }
 
 int hip_fail(hipError_t e) {
   tl_hip_error = e;
@@ -435,3 +439,6 @@ int bt709hip_last_hip_error(void) { return static_cast<int>(tl_hip_error); }
 const char *bt709hip_last_hip_error_string(void) { return hipGetErrorString(tl_hip_error); }
 
 }  // extern "C"
+
+// what the rescale launchers call with the plan of each launch (bt709_kernels.h)
+void bt709::record_scaled_launch(const bt709::ScaledLaunchRecord &record) { bt709shim::store_scaled_launch(record); }

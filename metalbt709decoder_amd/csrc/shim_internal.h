@@ -121,6 +121,7 @@ namespace bt709shim __attribute__((visibility("hidden"))) {
 void set_kernel_name(const char *name);  // bt709hip_last_kernel_name
 const char *kernel_name();
 hipError_t last_hip_error();             // bt709hip_last_hip_error
+const bt709::ScaledLaunchRecord *scaled_launch();  // bt709hip_last_scaled_launch_info (bt709::record_scaled_launch stores it); nullptr: no rescale launched by this thread yet
 
 int hip_fail(hipError_t e);  // records e for bt709hip_last_hip_error, clears the runtime's sticky copy -> BT709HIP_ERR_HIP
 

@@ -101,6 +101,19 @@ int bt709hip_last_launch_info(bt709hip_launch_info *info) {
   return BT709HIP_OK;
 }
 
+int bt709hip_last_scaled_launch_info(bt709hip_scaled_launch_info *info) {
+  static_assert(int{TAPS_BYTES} == int{BT709HIP_SCALED_TAPS_BYTES} && int{TAPS_PAIRS} == int{BT709HIP_SCALED_TAPS_PAIRS} && int{TAPS_WIDE} == int{BT709HIP_SCALED_TAPS_WIDE} &&
+                    int{TAPS_SHARED} == int{BT709HIP_SCALED_TAPS_SHARED} && int{TAPS_ONCE} == int{BT709HIP_SCALED_TAPS_ONCE},
+                "the launcher's tap forms are the header's enumerators");
+  if (info == nullptr) return BT709HIP_ERR_INVALID_ARG;
+  const ScaledLaunchRecord *s = scaled_launch();
+  if (s == nullptr) return BT709HIP_ERR_NOT_SETUP;
+  for (int i = 0; i < 3; ++i) info->grid[i] = s->grid[i], info->block[i] = s->block[i];
+  info->taps = s->taps, info->rows = s->rows, info->persistent = s->persistent, info->balanced = s->balanced;
+  info->resident = s->resident, info->reserved = 0, info->items = s->items;
+  return BT709HIP_OK;
+}
+
 int bt709hip_gamma_thresholds(int gamma, float thresholds[255]) {
   if (thresholds == nullptr) return BT709HIP_ERR_INVALID_ARG;
   TransferTable t;

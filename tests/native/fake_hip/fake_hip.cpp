@@ -42,7 +42,7 @@ struct Runtime {
   Device dev[kMaxDevices];
   std::vector<fake_hip_op> log;
   std::atomic<uint64_t> ops{0};
-  std::atomic<int64_t> fail_malloc{0}, fail_launch{0};
+  std::atomic<int64_t> fail_malloc{0}, fail_launch{0}, fail_launch_after_free{0};
   std::atomic<uint64_t> host_allocs{0}, streams{0}, events{0};
   std::vector<double> order_rates;
   size_t order_next = 0;
@@ -311,6 +311,8 @@ hipError_t hipFree(void *ptr) {
     dv.rates.erase(reinterpret_cast<uintptr_t>(ptr));
     auto rv = dv.reserved.find(reinterpret_cast<uintptr_t>(ptr));
     if (rv != dv.reserved.end()) {
+      const int64_t nth = r.fail_launch_after_free.exchange(0);  // a slab of a ring: arm the injected launch failure now
+      if (nth > 0) r.fail_launch.store(nth);
       munmap(ptr, bytes);
       dv.reserved.erase(rv);
     } else {
@@ -550,10 +552,18 @@ const char *launch_decode_half(const DecodeParams &p, int frames, bool, bool, bo
 const char *launch_decode_half_rep(const DecodeParams &p, int frames, bool, bool, uint32_t, uint32_t, hipStream_t stream) {
   return launch(stream, "decode_nv12_half_rep", frames, p.frames[0].y, p.frames[0].out, frames * frame_bytes(p, 4.0));
 }
+// the two rescale launchers fill a plausible record: one 256-lane workgroup per column tile, strip of 4 rows and frame
+static void fill_scaled_record(uint32_t out_width, uint32_t out_height, int frames, uint32_t taps) {
+  const uint32_t cols = (out_width + kBlockThreads - 1) / kBlockThreads, strips = (out_height + 3) / 4;
+  record_scaled_launch(ScaledLaunchRecord{{cols, strips, static_cast<uint32_t>(frames)}, {kBlockThreads, 1, 1}, taps, 4, 0, 0, 0, 0,
+                                          static_cast<uint64_t>(cols) * strips * static_cast<uint32_t>(frames)});
+}
 const char *launch_decode_scaled(const DecodeParams &p, int frames, bool, uint32_t, uint32_t, hipStream_t stream) {
+  fill_scaled_record(p.out_width, p.out_height, frames, TAPS_BYTES);
   return launch(stream, "decode_nv12_scaled", frames, p.frames[0].y, p.frames[0].out, frames * frame_bytes(p, 4.0));
 }
 const char *launch_render_scaled(const RenderParams &p, int frames, bool, uint32_t, hipStream_t stream) {
+  fill_scaled_record(p.out_width, p.out_height, frames, 0);
   return launch(stream, "render_scaled", frames, p.in, p.out, frames * 4.0 * (static_cast<double>(p.width) * p.height + static_cast<double>(p.out_width) * p.out_height));
 }
 const char *launch_encode(const EncodeParams &p, int frames, bool, bool, hipStream_t stream) {
@@ -583,6 +593,7 @@ void fake_hip_reset(void) {
   r.ops.store(0);
   r.fail_malloc.store(0);
   r.fail_launch.store(0);
+  r.fail_launch_after_free.store(0);
   r.order_rates.clear();
   r.order_next = 0;
 }
@@ -617,7 +628,8 @@ uint64_t fake_hip_host_allocations(void) { return rt().host_allocs.load(); }
 uint64_t fake_hip_live_streams(void) { return rt().streams.load(); }
 uint64_t fake_hip_live_events(void) { return rt().events.load(); }
 void fake_hip_fail_malloc_at(int64_t nth) { rt().fail_malloc.store(nth); }
-void fake_hip_fail_launch_at(int64_t nth) { rt().fail_launch.store(nth); }
+void fake_hip_fail_launch_at(int64_t nth) { rt().fail_launch.store(nth), rt().fail_launch_after_free.store(0); }
+void fake_hip_fail_launch_after_free(int64_t nth) { rt().fail_launch_after_free.store(nth); }
 void fake_hip_set_output_rate(const void *ptr, uint64_t bytes, double GBps) {
   Device &d = rt().dev[tl_device];
   std::lock_guard<std::mutex> lk(d.m);

@@ -26,6 +26,7 @@ uint64_t fake_hip_live_streams(void);
 uint64_t fake_hip_live_events(void);
 void fake_hip_fail_malloc_at(int64_t nth); /* the nth hipMalloc from now (1 = the next) returns hipErrorOutOfMemory; 0 = none */
 void fake_hip_fail_launch_at(int64_t nth); /* the nth kernel launch from now leaves hipErrorInvalidValue as the thread's last error */
+void fake_hip_fail_launch_after_free(int64_t nth); /* the same, counted from the next hipFree of a LARGE (address-reserved) slab; 0 = none */
 /* decode launches that write into [ptr, ptr + bytes) stream at this rate (GB/s) on the fake device clock; default 6000 */
 void fake_hip_set_output_rate(const void *ptr, uint64_t bytes, double GBps);
 void fake_hip_set_rate_by_allocation_order(const double *GBps, int n); /* the k-th LARGE (>= 64 MiB) hipMalloc from now gets GBps[k % n] */

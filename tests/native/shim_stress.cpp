@@ -282,22 +282,29 @@ static void test_ring_hunts() {
   OK(bt709hip_ring_create(dec, w, h, n, 0, 3, &ring));
   OK(bt709hip_ring_placement_info(ring, &p));
   CHECK(p.budget_bytes == frugal_budget && p.in_candidates == 1 && p.stopped_by == 1 && p.out_prescan_GBps[p.chosen_out] > 6500.0f);
+  CHECK(p.evicted >= 1 && p.out_prescan_GBps[0] < p.out_prescan_GBps[1]);  // output 0 is the slowest of the first two: the first slab the budget frees
   OK(bt709hip_ring_destroy(ring));
   CHECK(fake_hip_allocated(0) == base_bytes);
   // a probe that fails AFTER the budget has evicted (freed) the first output: the error comes back and nothing is freed twice
   // (round 5's advisor: the error path used to free outs[0] again; AddressSanitizer is the judge here)
   int failed_hunts = 0;
-  for (int k : {20, 45, 90, 150}) {
+  // (the warm-up of a probe runs on the wall clock, so a fixed launch number lands anywhere: k = 0 counts from the first
+  // eviction instead -- the second launch after the hunt's first hipFree of a slab is inside the third candidate's probe, with
+  // output 0 gone and still the best on record: the keep_out == nullptr path)
+  for (int k : {0, 20, 45, 90, 150}) {
     fake_hip_set_rate_by_allocation_order(rates + 2, static_cast<int>(sizeof rates / sizeof rates[0]) - 2);
-    fake_hip_fail_launch_at(k);
+    if (k == 0) fake_hip_fail_launch_after_free(2);
+    else fake_hip_fail_launch_at(k);
     ring = nullptr;
     const int rc = bt709hip_ring_create(dec, w, h, n, 0, 3, &ring);
     fake_hip_fail_launch_at(0);
     CHECK((rc == BT709HIP_ERR_HIP && ring == nullptr) || (rc == BT709HIP_OK && ring != nullptr));
     failed_hunts += rc == BT709HIP_ERR_HIP;
+    if (k == 0) CHECK(rc == BT709HIP_ERR_HIP);
     if (ring) OK(bt709hip_ring_destroy(ring));
     CHECK(fake_hip_allocated(0) == base_bytes);
   }
+  CHECK(failed_hunts >= 1);
 
   // allocation refused at candidate k (k = 1: the ring's own input; 2: its first output; later: a candidate): clean error or a
   // smaller hunt, never a leak

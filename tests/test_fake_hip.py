@@ -209,6 +209,47 @@ def test_every_stream_taking_export_issues_the_queued_frames_first(fake):
     assert lib.bt709hip_decoder_destroy(A) == 0 and lib.bt709hip_decoder_destroy(B) == 0
 
 
+def test_scaled_launch_record_is_per_thread_and_follows_the_last_rescale(fake):
+    """bt709hip_last_scaled_launch_info through the shim (the fake launchers fill a plausible record): a thread that has launched no
+    rescale has none; after a decode_scaled_batch / render_scaled_batch it holds THAT launch; another thread still has none."""
+    import threading
+    lib = fake
+    out = {}
+
+    def worker():
+        ctx, dec = C.c_void_p(), C.c_void_p()
+        info = _capi.ScaledLaunchInfo()
+        out["before"] = lib.bt709hip_last_scaled_launch_info(C.byref(info))
+        assert lib.bt709hip_context_create(0, C.byref(ctx)) == 0 and lib.bt709hip_decoder_create(ctx, 0, 0, C.byref(dec)) == 0
+        assert lib.bt709hip_decoder_setup(dec) == 0 and lib.bt709hip_render_scaled_prepare(ctx) == 0
+        w, h, ow, oh, n = 64, 16, 300, 10, 3
+        src, dst = C.c_void_p(), C.c_void_p()
+        assert lib.bt709hip_malloc(ctx, n * w * h * 4, C.byref(src)) == 0 and lib.bt709hip_malloc(ctx, n * ow * oh * 4, C.byref(dst)) == 0
+        frames = (_capi.Frame * n)(*[_capi.Frame(src.value + i * w * h * 4, w, src.value + i * w * h * 4 + w * h, w, w, h, 1, 1) for i in range(n)])
+        inters = (_capi.Surface * n)(*[_capi.Surface(src.value + i * w * h * 4, w * 4, w, h, 0, 0) for i in range(n)])
+        views = (_capi.Surface * n)(*[_capi.Surface(dst.value + i * ow * oh * 4, ow * 4, ow, oh, 0, 0) for i in range(n)])
+        assert lib.bt709hip_decode_batch(dec, n, frames, None, inters, None, 1) == 0  # a 1:1 decode leaves no record
+        out["after_plain"] = lib.bt709hip_last_scaled_launch_info(C.byref(info))
+        assert lib.bt709hip_decode_scaled_batch(dec, n, frames, None, views, None, 1) == 0
+        assert lib.bt709hip_last_scaled_launch_info(C.byref(info)) == 0
+        out["decode"] = (tuple(info.grid), tuple(info.block), info.rows, info.items, info.reserved)
+        assert lib.bt709hip_render_scaled_batch(ctx, 2, inters, views, None, 1) == 0
+        assert lib.bt709hip_last_scaled_launch_info(C.byref(info)) == 0
+        out["render"] = (tuple(info.grid), info.taps, info.resident, info.items)
+        assert lib.bt709hip_free(ctx, src) == 0 and lib.bt709hip_free(ctx, dst) == 0
+        assert lib.bt709hip_decoder_destroy(dec) == 0 and lib.bt709hip_context_destroy(ctx) == 0
+
+    def bystander():
+        out["bystander"] = lib.bt709hip_last_scaled_launch_info(C.byref(_capi.ScaledLaunchInfo()))
+
+    for fn in (worker, bystander):
+        t = threading.Thread(target=fn)
+        t.start(), t.join()
+    assert out["before"] == out["after_plain"] == out["bystander"] == _capi.ERR_NOT_SETUP
+    assert out["decode"] == ((2, 3, 3), (256, 1, 1), 4, 18, 0) and out["render"] == ((2, 3, 2), 0, 0, 12)
+    assert lib.bt709hip_last_scaled_launch_info(None) == _capi.ERR_INVALID_ARG
+
+
 def test_fake_runtime_is_not_part_of_the_product():
     """The fake runtime lives under tests/ only: the package, the public header and the build script never mention it."""
     for path in [os.path.join(ROOT, "include", "bt709hip.h"), os.path.join(ROOT, "include", "bt709hip_ext.h"), os.path.join(ROOT, "metalbt709decoder_amd", "build.py"),

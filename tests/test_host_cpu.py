@@ -9,6 +9,7 @@ import os
 import re
 import socket
 import subprocess
+import threading
 import sys
 
 import numpy as np
@@ -35,7 +36,7 @@ def test_library_is_not_older_than_its_sources(lib):
 def test_library_exports_every_declared_symbol(lib):
     header = re.sub(r"/\*.*?\*/", "", abi_headers.text(), flags=re.S)
     declared = set(re.findall(r"\b(bt709hip_[a-z0-9_]+)\s*\(", header))
-    assert len(declared) == 102  # ABI 502: frozen in round 6 (the split into two headers moved declarations, it added none)
+    assert len(declared) == 103  # ABI 503: bt709hip_last_scaled_launch_info joined the 102 of ABI 502
     for name in declared:
         assert hasattr(lib, name), "library does not export " + name
     # and the ctypes table binds exactly that set
@@ -86,7 +87,7 @@ def test_boundary_is_split_into_reference_twins_and_extensions():
     core = set(re.findall(r"\b(bt709hip_[a-z0-9_]+)\s*\(", strip(abi_headers.core_text())))
     ext = set(re.findall(r"\b(bt709hip_[a-z0-9_]+)\s*\(", strip(abi_headers.ext_text())))
     assert core == REFERENCE_TWINNED
-    assert not core & ext and len(core | ext) == 102
+    assert not core & ext and len(core | ext) == 103
     assert abi_headers.core_text().count("\n") <= 250
     assert '#include "bt709hip.h"' in abi_headers.ext_text() and "bt709hip_ext.h" not in strip(abi_headers.core_text())
     csrc = os.path.join(os.path.dirname(mb.__file__), "csrc")
@@ -245,6 +246,17 @@ def test_decoder_and_context_options(lib):
     assert lib.bt709hip_ring_placement_info(None, None) == _capi.ERR_INVALID_ARG
     assert lib.bt709hip_mem_info(None, None, None) == _capi.ERR_INVALID_ARG
     assert lib.bt709hip_last_launch_info(None) == _capi.ERR_INVALID_ARG
+    # the rescale launchers' record: NULL is an argument error; a thread that has launched no rescale has no record, and the struct is left alone
+    assert lib.bt709hip_last_scaled_launch_info(None) == _capi.ERR_INVALID_ARG
+    seen = []
+
+    def fresh_thread():
+        info = _capi.ScaledLaunchInfo()
+        C.memset(C.byref(info), 0x5A, C.sizeof(info))
+        seen.append((lib.bt709hip_last_scaled_launch_info(C.byref(info)), bytes(info)))
+    t = threading.Thread(target=fresh_thread)
+    t.start(), t.join()
+    assert seen == [(_capi.ERR_NOT_SETUP, b"\x5a" * C.sizeof(_capi.ScaledLaunchInfo))]
     assert lib.bt709hip_context_set_option(None, _capi.CTX_OPT_GRID_MULT, 2) == _capi.ERR_INVALID_ARG
     assert lib.bt709hip_abi_version() == _capi.ABI_VERSION
     hdr = abi_headers.core_text()
@@ -955,7 +967,8 @@ def test_ctypes_structs_match_the_header(tmp_path):
     compiled against the header prints sizeof and the offset of every field, and they must equal ctypes' own layout -- a field
     added to the header alone (or to the bindings alone) fails here, before it mis-calls the library."""
     pairs = {"bt709hip_frame": _capi.Frame, "bt709hip_surface": _capi.Surface, "bt709hip_ring_placement": _capi.RingPlacement,
-             "bt709hip_ring_options": _capi.RingOptions, "bt709hip_launch_info": _capi.LaunchInfo, "bt709hip_device_info": _capi.DeviceInfo}
+             "bt709hip_ring_options": _capi.RingOptions, "bt709hip_launch_info": _capi.LaunchInfo, "bt709hip_device_info": _capi.DeviceInfo,
+             "bt709hip_scaled_launch_info": _capi.ScaledLaunchInfo}
     lines = ['#include <stddef.h>', '#include <stdio.h>', '#include "bt709hip_ext.h"', 'int main(void) {']
     for cname, cls in pairs.items():
         lines.append('  printf("%s size %%zu\\n", sizeof(%s));' % (cname, cname))
@@ -992,3 +1005,6 @@ def test_ctypes_constants_match_the_header():
             assert getattr(_capi, name) == int(value), (enum, name)
             seen += 1
     assert seen >= 12 + 2 + 5 + 7
+    # the tap forms of bt709hip_scaled_launch_info.taps (an anonymous enum)
+    taps = re.findall(r"BT709HIP_(SCALED_TAPS_\w+)\s*=\s*(\d+)", re.sub(r"/\*.*?\*/", "", hdr, flags=re.S))
+    assert len(taps) == 5 and all(getattr(_capi, name) == int(value) for name, value in taps)

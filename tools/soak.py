@@ -1,7 +1,7 @@
 """Random soak of every GPU path against the oracle (runs on the GPU box):
     python tools/soak.py [seed] [cases]
 decode (opaque / alpha, 8-bit and RGBA16Float targets), exact 2:1 (both kernels, with alpha), any-ratio
-(with alpha), the reference's two passes through both intermediate formats, the encoder, the frame ring and the
+(with alpha; one case in eight a narrow, tall batch in the launch regimes the README quotes), the reference's two passes through both intermediate formats, the encoder, the frame ring and the
 coalescing submit (round 4); round 5: ring sets on every visible device, batched RGBA16Float launches of both kernel
 shapes, +unconvert: batches, the LINEAR mode's log-bucket kernel at many batch sizes.
 Fresh seeds every time it is used; the committed tests hold the fixed-seed fuzz."""
@@ -11,6 +11,7 @@ sys.path.insert(0, os.getcwd()); sys.path.insert(0, os.path.join(os.getcwd(), "t
 import numpy as np
 import gpu_helpers as gh
 from oracle_lib import Oracle
+import test_rescale as regimes
 import metalbt709decoder_amd as mb
 from metalbt709decoder_amd import _capi
 oracle = Oracle()
@@ -32,6 +33,21 @@ for case in range(int(sys.argv[2]) if len(sys.argv) > 2 else 300):
         dec = gh.make_decoder(g, has_alpha=a is not None, options={_capi.OPT_HALF_KERNEL: int(rng.integers(-1, 2)),
                                                                     _capi.OPT_HALF_WORKGROUPS: int(rng.integers(1, 400))})
         got = gh.gpu_decode_half(y, c, g, decoder=dec, alpha=a); want = oracle.decode_nv12_half(g, y, c, alpha=a)
+    elif kind == 2 and rng.integers(0, 8) == 0:
+        # the regimes the README's numbers are taken in (the 8-per-CU rule at 16 / 32-row strips, persistent workgroups with two
+        # and more items): a narrow, tall batch from the parity tests' own table, fresh bytes, any gamma
+        rc = regimes.REGIME_CASES[int(rng.integers(0, len(regimes.REGIME_CASES)))]
+        rg = rc["gamma"] if rc["alpha"] else gamma
+        plan, check = regimes._run_decode_scaled(gh, oracle, "soak " + rc["name"], rc["src"], rc["dst"],
+                                                 regimes._regime_frames(rc, ctx.info().compute_units), rc["layout"], rc["spacing"], rg,
+                                                 rc["alpha"], seed=int(rng.integers(0, 1 << 30)))
+        got = want = np.zeros(1)
+        try:
+            assert plan["taps"] in rc["taps"] and plan["rows"] == regimes.MAX_ROWS[plan["taps"]] and not plan["balanced"], plan
+            check()
+        except AssertionError as exc:
+            print(exc)
+            got = None
     elif kind == 2:
         ow, oh = int(rng.integers(1, 2 * w)), int(rng.integers(1, 2 * h))
         if rng.integers(0, 4) == 0:  # tall, narrow views: several output rows per strip, ragged last wave
@@ -44,6 +60,14 @@ for case in range(int(sys.argv[2]) if len(sys.argv) > 2 else 300):
         got = ctx.getBGRATexturePixels(tex).view(np.uint16); want = oracle.decode_nv12_rgba16f(g, y, c, alpha=a).view(np.uint16)
     elif kind == 4:  # two passes, either intermediate
         fmt = mb.MTLPixelFormatRGBA16Float if rng.integers(0, 2) else mb.MTLPixelFormatBGRA8Unorm_sRGB
+        if rng.integers(0, 8) == 0:  # pass 2 alone at its 16-row strips: a narrow, tall ring of random intermediates
+            name, _, src, dst, n = regimes.RENDER_CASES[int(rng.integers(0, 4))]
+            try:
+                plan = regimes._run_render_scaled(gh, oracle, "soak " + name, fmt, src, dst, n, seed=int(rng.integers(0, 1 << 30)))
+                assert plan["rows"] == 16, plan
+            except AssertionError as exc:
+                bad += 1; print("MISMATCH", case, kind, exc)
+            continue
         ow, oh = int(rng.integers(1, 2 * w)), int(rng.integers(1, 2 * h))
         if rng.integers(0, 4) == 0:
             ow, oh = int(rng.integers(1, 140)), int(rng.integers(4100, 12000))
