@@ -335,7 +335,8 @@ int bt709hip_half_thresholds(int gamma, float *thresholds, int capacity);
 int bt709hip_half_lookup(int gamma, float x, int candidate_offset, int *table_entries);
 /* Name of the kernel the last decode on this thread launched (for profiling). */
 const char *bt709hip_last_kernel_name(void);
-/* Launch shape of the last bt709hip_decode / _decode_batch (1:1, BGRA8 or RGBA16F target) this thread issued: grid and block of its
+/* Launch shape of the last decode or encode this thread issued -- bt709hip_decode / _decode_batch (1:1, BGRA8 or RGBA16F target) or
+ * bt709hip_encode / _encode_batch (grid = tiles [x 8 under the XCD-aware map], row-pair groups, pictures [per band]): grid and block of its
  * first kernel launch, the number of launches it took (2: the XCD-aware map over a multiple of 8 frames plus the plain map
  * over the rest) and the work map of the first (bt709hip_decoder_option BT709HIP_OPT_XCD_BANDS value actually used; 0 plain). */
 typedef struct {

@@ -43,6 +43,7 @@
 
 #include "bt709_constants.h"
 #include "bt709_kernels.h"
+#include "bt709_split_lookup.h"
 #include "bt709_stage.h"
 
 namespace bt709 {
@@ -83,13 +84,13 @@ __device__ __forceinline__ u32x2 byte_entry(const EncodeLds &t, uint32_t word) {
   return *reinterpret_cast<LdsPairPtr>(a);
 }
 
+// BT709_from_linear through the two-resolution table in LDS: the arithmetic is bt709_split_lookup.h's (shared with the
+// every-float host sweep), the ds_read_b64 is this file's
 __device__ __forceinline__ uint32_t from_linear(const EncodeLds &t, float xs) {
-  // fine index below the split, coarse above; the two index functions cross at the split and the
-  // fine one grows faster, so the smaller is the right one
-  const uint32_t qf = static_cast<uint32_t>(xs);
-  const uint32_t q = min(qf, (qf >> t.coarse_shift) + t.offset);
-  const u32x2 e = *reinterpret_cast<LdsPairPtr>((q << 3) + t.fl);
-  return e.y + (xs >= __uint_as_float(e.x) ? 1u : 0u);
+  return split_table_lookup(xs, t.coarse_shift, t.offset, [&](uint32_t q) {
+    const u32x2 e = *reinterpret_cast<LdsPairPtr>((q << 3) + t.fl);
+    return TransferBucket{__uint_as_float(e.x), e.y};
+  });
 }
 
 // v = e * scale + offset as the reference's float expression, plus the exact 0.5f: trunc(result)
@@ -170,7 +171,7 @@ __device__ __forceinline__ EncodeLds stage_encode_tables(unsigned char *lds_raw,
     __builtin_trap();
   t.fl = 256u * static_cast<uint32_t>(sizeof(EncodeByteEntry));
   t.offset = p.from_linear_offset;
-  t.coarse_shift = 127u - (__float_as_uint(p.from_linear_coarse) >> 23);  // log2(1 / coarse), coarse = 2^-k
+  t.coarse_shift = split_coarse_shift(__float_as_uint(p.from_linear_coarse));
   t.three = 3u;
   asm("" : "+v"(t.three));
   return t;
@@ -276,6 +277,16 @@ encode_bgra_nv12_blocks(const EncodeParams p) {
   }
 }
 
+// the plan of the call's first launch, for bt709hip_last_launch_info (as launch_decode keeps it)
+static void record_launch(const dim3 &grid, uint32_t threads, int32_t xcd_bands) {
+  LaunchShape &shape = last_launch_shape();
+  if (shape.launches++ == 0) {
+    shape.grid[0] = grid.x, shape.grid[1] = grid.y, shape.grid[2] = grid.z;
+    shape.block[0] = threads, shape.block[1] = shape.block[2] = 1;
+    shape.xcd_bands = xcd_bands;
+  }
+}
+
 const char *launch_encode(const EncodeParams &params, int frames, bool fast, bool xcd_bands, hipStream_t stream) {
   if (fast && xcd_bands && params.uniform && frames > kXcdBandMinFrames && frames % 8 != 0) {
     // any count of 64 pictures or more: the XCD-aware map over the multiple of 8, the plain map over the rest (launch_decode)
@@ -309,10 +320,12 @@ const char *launch_encode(const EncodeParams &params, int frames, bool fast, boo
       p.frames_per_band = static_cast<uint32_t>(frames) / 8u;
       grid = dim3(grid.x * 8u, grid.y, p.frames_per_band);
     }
+    record_launch(grid, threads, static_cast<int32_t>(p.xcd_bands));
     hipLaunchKernelGGL(encode_bgra_nv12, grid, dim3(threads), lds, stream, p);
     return "encode_bgra_nv12";
   }
   const dim3 grid((p.width / 2 + kBlockThreads - 1) / kBlockThreads, p.height / 2, frames);
+  record_launch(grid, kBlockThreads, 0);
   hipLaunchKernelGGL(encode_bgra_nv12_blocks, grid, dim3(kBlockThreads), lds, stream, p);
   return "encode_bgra_nv12_blocks";
 }

@@ -199,8 +199,9 @@ const char *launch_planes(const PlaneParams &p, bool interleave, hipStream_t str
 // 16-byte-per-lane non-temporal streaming copy (bt709_planes.hip): the same-box copy ceiling benchmarks report.
 const char *launch_copy_probe(void *dst, const void *src, size_t bytes, hipStream_t stream);
 
-// Shape of the kernel launches the last bt709hip_decode[_batch] call of this thread made (tests assert the XCD-aware map
-// through it: bt709hip_last_launch_info): grid and block of its FIRST launch, how many launches it took.
+// Shape of the kernel launches the last bt709hip_decode[_batch] or bt709hip_encode[_batch] call of this thread made (tests
+// assert the XCD-aware map and the encoder's launch regimes through it: bt709hip_last_launch_info): grid and block of its FIRST
+// launch, how many launches it took.
 struct LaunchShape {
   uint32_t grid[3], block[3];
   int32_t launches, xcd_bands;

@@ -277,6 +277,7 @@ int bt709hip_encode_batch(bt709hip_context *ctx, int count, const bt709hip_surfa
   p.bgra_stride = static_cast<uint32_t>(in0.stride);
   p.y_stride = static_cast<uint32_t>(out0.y_stride);
   p.cbcr_stride = static_cast<uint32_t>(out0.cbcr_stride);
+  last_launch_shape() = LaunchShape{};
   set_kernel_name(launch_encode(p, count, fast, ctx->xcd_bands != 0, s));
   HIP_TRY(hipGetLastError());
   if (wait_until_completed) HIP_TRY(hipStreamSynchronize(s));

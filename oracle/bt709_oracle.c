@@ -526,18 +526,32 @@ static int from_linear(int gamma, float v) {
   return bt709o_quantize(nl);
 }
 
-void bt709o_subsample_block(const int rgb[12], int in_gamma, int out_gamma,
-                            int y4[4], int *cb, int *cr) {
-  float lin[4][3];
+/* the first half of BT709_average_pixel_values: the three averaged, gamma encoded bytes (BT709.h:1400-1420) */
+static void average_bytes(const int rgb[12], int in_gamma, int out_gamma, float lin[4][3], int avg[3]) {
   for (int i = 0; i < 4; i++)
     for (int c = 0; c < 3; c++) lin[i][c] = to_linear(in_gamma, rgb[3 * i + c]);
 
   /* BT709.h:1404-1406 via 1171-1190: ((a+b)+c)+d then /4.0f */
-  int avg[3];
   for (int c = 0; c < 3; c++) {
     float sum = (lin[0][c] + lin[1][c] + lin[2][c] + lin[3][c]);
     avg[c] = from_linear(out_gamma, sum / 4.0f); /* BT709.h:1412-1414 */
   }
+}
+
+void bt709o_average_bytes(const int rgb[12], int in_gamma, int out_gamma, int avg[3]) {
+  float lin[4][3];
+  average_bytes(rgb, in_gamma, out_gamma, lin, avg);
+}
+
+void bt709o_to_linear_table(int gamma, float lin[256]) {
+  for (int b = 0; b < 256; b++) lin[b] = to_linear(gamma, b);
+}
+
+void bt709o_subsample_block(const int rgb[12], int in_gamma, int out_gamma,
+                            int y4[4], int *cb, int *cr) {
+  float lin[4][3];
+  int avg[3];
+  average_bytes(rgb, in_gamma, out_gamma, lin, avg);
   int v[3];
   bt709o_encode_pixel(BT709O_GAMMA_SRGB, avg[0], avg[1], avg[2], v); /* :1418 */
   *cb = v[1];

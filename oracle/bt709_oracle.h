@@ -205,6 +205,11 @@ void bt709o_nv12_to_packed(const uint8_t *y, size_t y_stride,
  * enum (APPLE/SRGB/LINEAR).  rgb = {R1,G1,B1,...,R4,G4,B4}. */
 void bt709o_subsample_block(const int rgb[12], int in_gamma, int out_gamma,
                             int y4[4], int *cb, int *cr);
+/* The averaged bytes of that block alone -- BT709_from_linear(average of the four linear values, out_gamma) per channel,
+ * the input of its Cb,Cr (BT709.h:1400-1420): what tests that aim 2x2 averages at a threshold check their aim with. */
+void bt709o_average_bytes(const int rgb[12], int in_gamma, int out_gamma, int avg[3]);
+/* BT709_tolinearNorm of every byte for one input gamma (BT709.h:1100-1146). */
+void bt709o_to_linear_table(int gamma, float lin[256]);
 /* cvpbu_ycbcr_subsample (CVPixelBufferUtils.h:241-399): BGRA frame -> NV12. */
 int bt709o_encode_nv12(const uint32_t *bgra, int width, int height,
                        int in_gamma, int out_gamma,

@@ -151,6 +151,16 @@ void ref_subsample_block(const int rgb[12], int in_gamma, int out_gamma, int out
                              to_ref_gamma(in_gamma), to_ref_gamma(out_gamma));
 }
 
+/* The averaged bytes inside BT709_average_pixel_values (which does not hand them out), by the same three
+ * inlines in the same order (BT709.h:1400-1420): avg = {R,G,B}. */
+void ref_average_bytes(const int rgb[12], int in_gamma, int out_gamma, int avg[3]) {
+  float n[4][3];
+  for (int i = 0; i < 4; i++)
+    BT709_tolinearNorm(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2], &n[i][0], &n[i][1], &n[i][2], to_ref_gamma(in_gamma));
+  for (int c = 0; c < 3; c++)
+    avg[c] = BT709_from_linear(BT709_average_cbcr_linear(n[0][c], n[1][c], n[2][c], n[3][c]), to_ref_gamma(out_gamma));
+}
+
 /* BGRA words -> tight NV12 via repeated BT709_average_pixel_values, walking
  * blocks the way cvpbu_ycbcr_subsample does (that function itself needs
  * CoreVideo and cannot be built here). */

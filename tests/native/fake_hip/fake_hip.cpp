@@ -566,7 +566,18 @@ const char *launch_render_scaled(const RenderParams &p, int frames, bool, uint32
   fill_scaled_record(p.out_width, p.out_height, frames, 0);
   return launch(stream, "render_scaled", frames, p.in, p.out, frames * 4.0 * (static_cast<double>(p.width) * p.height + static_cast<double>(p.out_width) * p.out_height));
 }
-const char *launch_encode(const EncodeParams &p, int frames, bool, bool, hipStream_t stream) {
+const char *launch_encode(const EncodeParams &p, int frames, bool fast, bool xcd_bands, hipStream_t stream) {
+  // the plan the real launcher would record for a plain (single-launch) call: tiles x row-pair groups x pictures
+  LaunchShape &shape = last_launch_shape();
+  if (shape.launches++ == 0) {
+    const uint32_t threads = fast ? (p.block_threads ? p.block_threads : encode_block_threads(p.width)) : static_cast<uint32_t>(kBlockThreads);
+    const uint32_t rp = p.row_pairs_per_block ? p.row_pairs_per_block : encode_row_pairs_per_block(p.width, p.height, static_cast<uint32_t>(frames));
+    shape.grid[0] = fast ? (p.width / 4 + threads - 1) / threads : (p.width / 2 + threads - 1) / threads;
+    shape.grid[1] = fast ? (p.height / 2 + rp - 1) / rp : p.height / 2;
+    shape.grid[2] = static_cast<uint32_t>(frames);
+    shape.block[0] = threads, shape.block[1] = shape.block[2] = 1;
+    shape.xcd_bands = fast && xcd_bands && frames >= kXcdBandMinFrames && frames % 8 == 0 ? 1 : 0;
+  }
   return launch(stream, "encode_bgra_nv12", frames, p.frames[0].bgra, p.frames[0].y, frames * 5.5 * p.width * p.height);
 }
 const char *launch_planes(const PlaneParams &p, bool interleave, hipStream_t stream) {

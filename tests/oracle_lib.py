@@ -72,6 +72,8 @@ class Oracle:
         L.bt709o_nv12_to_packed.argtypes = [_u8p, C.c_size_t, _u8p, C.c_size_t,
                                             C.c_int, C.c_int, _u32p]
         L.bt709o_subsample_block.argtypes = [_i32p, C.c_int, C.c_int, _i32p, _i32p, _i32p]
+        L.bt709o_average_bytes.argtypes = [_i32p, C.c_int, C.c_int, _i32p]
+        L.bt709o_to_linear_table.argtypes = [C.c_int, _f32p]
         L.bt709o_encode_nv12.restype = C.c_int
         L.bt709o_encode_nv12.argtypes = [_u32p, C.c_int, C.c_int, C.c_int, C.c_int,
                                          _u8p, C.c_size_t, _u8p, C.c_size_t]
@@ -251,6 +253,18 @@ class Oracle:
         self.lib.bt709o_subsample_block(rgb, in_gamma, out_gamma, y4, C.byref(cb), C.byref(cr))
         return tuple(y4) + (cb.value, cr.value)
 
+    def average_bytes(self, rgb12, in_gamma, out_gamma):
+        """The (R, G, B) bytes subsample_block feeds its Cb, Cr matrix with."""
+        rgb = (C.c_int * 12)(*rgb12)
+        avg = (C.c_int * 3)()
+        self.lib.bt709o_average_bytes(rgb, in_gamma, out_gamma, avg)
+        return tuple(avg)
+
+    def to_linear_table(self, gamma):
+        t = np.zeros(256, dtype=np.float32)
+        self.lib.bt709o_to_linear_table(gamma, _ptr(t, _f32p))
+        return t
+
     def encode_nv12(self, bgra, width, height, in_gamma=GAMMA_SRGB, out_gamma=GAMMA_APPLE):
         bgra = np.ascontiguousarray(bgra, dtype=np.uint32)
         y = np.zeros((height, width), dtype=np.uint8)
@@ -408,6 +422,32 @@ class Reference:
             self.lib.ref_subsample_block(rgb, in_gamma, out_gamma, out)
         finally:
             self.lib.ref_quiet_end()
+        return tuple(out)
+
+    def average_bytes(self, rgb12, in_gamma, out_gamma):
+        """The averaged (R, G, B) bytes inside BT709_average_pixel_values.  A library built from this tree's ref_harness.c has
+        ref_average_bytes (the reference's three inlines, composed in C); one built from an earlier harness (a prebuilt
+        oracle/_ref that travelled without the reference tree) has not, and the same steps are composed here from the exports
+        every build has: the to-linear curves, the float32 sum in the reference's order, the from-linear curve, round(255 v)."""
+        if hasattr(self.lib, "ref_average_bytes"):
+            fn = self.lib.ref_average_bytes
+            fn.restype, fn.argtypes = None, [_i32p, C.c_int, C.c_int, _i32p]
+            rgb = (C.c_int * 12)(*rgb12)
+            avg = (C.c_int * 3)()
+            fn(rgb, in_gamma, out_gamma, avg)
+            return tuple(avg)
+        to_lin = {GAMMA_SRGB: self.lib.ref_srgb_to_linear, GAMMA_APPLE: self.lib.ref_apple196_to_linear}.get(in_gamma)
+        out = []
+        for c in range(3):
+            n = [np.float32(rgb12[3 * i + c]) * np.float32(1.0 / 255.0) for i in range(4)]  # byteNorm, sRGB.h:32-36
+            l = [np.float32(to_lin(float(v))) if to_lin else v for v in n]
+            ave = np.float32(np.float32(np.float32(np.float32(l[0] + l[1]) + l[2]) + l[3]) / np.float32(4.0))  # BT709.h:1182-1183
+            if out_gamma == GAMMA_SRGB:
+                out.append(self.transfer_to_byte(GAMMA_LINEAR, ave))   # round(255 * sRGB_linearNormToNonLinear(v))
+            elif out_gamma == GAMMA_APPLE:
+                out.append(self.transfer_to_byte(GAMMA_SRGB, np.float32(self.lib.ref_linear_to_apple196(float(ave)))))
+            else:
+                out.append(self.transfer_to_byte(GAMMA_SRGB, ave))     # round(255 * v)
         return tuple(out)
 
     def encode_nv12(self, bgra, width, height, in_gamma=GAMMA_SRGB, out_gamma=GAMMA_APPLE):

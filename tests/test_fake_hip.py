@@ -250,6 +250,31 @@ def test_scaled_launch_record_is_per_thread_and_follows_the_last_rescale(fake):
     assert lib.bt709hip_last_scaled_launch_info(None) == _capi.ERR_INVALID_ARG
 
 
+def test_encode_leaves_its_launch_on_record(fake):
+    """bt709hip_last_launch_info after bt709hip_encode_batch holds THAT launch (cleared by the call, filled by launch_encode: the fake
+    launcher records the plan of a plain launch from the header's own geometry functions), not the decode before it."""
+    lib = fake
+    ctx, dec = C.c_void_p(), C.c_void_p()
+    assert lib.bt709hip_context_create(0, C.byref(ctx)) == 0 and lib.bt709hip_decoder_create(ctx, 0, 0, C.byref(dec)) == 0
+    assert lib.bt709hip_decoder_setup(dec) == 0
+    w, h, n = 64, 16, 4
+    src, dst = C.c_void_p(), C.c_void_p()
+    assert lib.bt709hip_malloc(ctx, n * w * h * 4, C.byref(src)) == 0 and lib.bt709hip_malloc(ctx, n * w * h * 3 // 2, C.byref(dst)) == 0
+    frames = (_capi.Frame * n)(*[_capi.Frame(dst.value + i * w * h * 3 // 2, w, dst.value + i * w * h * 3 // 2 + w * h, w, w, h, 1, 1) for i in range(n)])
+    surfs = (_capi.Surface * n)(*[_capi.Surface(src.value + i * w * h * 4, w * 4, w, h, 0, 0) for i in range(n)])
+    info = _capi.LaunchInfo()
+    assert lib.bt709hip_decode_batch(dec, n, frames, None, surfs, None, 1) == 0
+    assert lib.bt709hip_last_launch_info(C.byref(info)) == 0 and info.launches == 1 and info.grid[1] == h // 2
+    assert lib.bt709hip_encode_batch(ctx, n, surfs, frames, 1, 0, None, 1) == 0
+    assert lib.bt709hip_last_launch_info(C.byref(info)) == 0
+    # 16 quads -> one tile of one wave; 8 row pairs in groups of 3; 4 pictures; one launch, plain map
+    assert (tuple(info.grid), tuple(info.block), info.launches, info.xcd_bands) == ((1, 3, n), (64, 1, 1), 1, 0)
+    assert lib.bt709hip_encode(ctx, surfs, frames, 1, 0, None, 1) == 0
+    assert lib.bt709hip_last_launch_info(C.byref(info)) == 0 and (tuple(info.grid), info.launches) == ((1, 3, 1), 1)
+    assert lib.bt709hip_free(ctx, src) == 0 and lib.bt709hip_free(ctx, dst) == 0
+    assert lib.bt709hip_decoder_destroy(dec) == 0 and lib.bt709hip_context_destroy(ctx) == 0
+
+
 def test_fake_runtime_is_not_part_of_the_product():
     """The fake runtime lives under tests/ only: the package, the public header and the build script never mention it."""
     for path in [os.path.join(ROOT, "include", "bt709hip.h"), os.path.join(ROOT, "include", "bt709hip_ext.h"), os.path.join(ROOT, "metalbt709decoder_amd", "build.py"),
