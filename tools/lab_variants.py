@@ -365,14 +365,12 @@ constexpr bool kRepUniformEncode = true;
     # (matrix + 3 lookups each) go.  The stub deletes exactly that share outright -- on every odd source row the second tap
     # reuses the first tap's values, no pixel_rgb, no lookups for it -- and keeps everything else: an upper bound on the gain.
     ("bt709_rescale.hip",
-     """    float x[6];
+     """    float x[6], lin[6];  // R, G, B of tap 0; R, G, B of tap 1
     pixel_rgb(byte_of(fr.yy, 0), ch0, x[0], x[1], x[2]);
     pixel_rgb(byte_of(fr.yy, 1), ch1, x[3], x[4], x[5]);
-    RowLin rl;
-    linearise6(r, x, rl.v);
+    linearise6(r, x, lin);
 """,
-     """    float x[6];
-    RowLin rl;
+     """    float x[6], lin[6];
 #if defined(BT709_LAB_SCALED_HALF_FEWER_TAPS) || defined(BT709_LAB_SCALED_PAIR_DPP)  // WRONG OUTPUT: tap 0 decoded, tap 1 a copy of it / of the next lane's
     pixel_rgb(byte_of(fr.yy, 0), ch0, x[0], x[1], x[2]);
     {
@@ -385,11 +383,11 @@ constexpr bool kRepUniformEncode = true;
       asm volatile("" : "+v"(e3[0]), "+v"(e3[1]), "+v"(e3[2]));
 #pragma unroll
       for (int i = 0; i < 3; ++i) {
-        rl.v[i] = __builtin_amdgcn_fmed3f(__uint_as_float(e3[i].y), __uint_as_float(e3[i].z), __fadd_rn(x[i], -__uint_as_float(e3[i].x)));
+        lin[i] = __builtin_amdgcn_fmed3f(__uint_as_float(e3[i].y), __uint_as_float(e3[i].z), __fadd_rn(x[i], -__uint_as_float(e3[i].x)));
 #if defined(BT709_LAB_SCALED_PAIR_DPP)  // the lane-pair exchange as a DPP move (row_shl:1): what sharing between lane l and l + 1 costs
-        rl.v[3 + i] = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, rl.v[i]), 0x101, 0xf, 0xf, false));
+        lin[3 + i] = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, lin[i]), 0x101, 0xf, 0xf, false));
 #else
-        rl.v[3 + i] = rl.v[i];
+        lin[3 + i] = lin[i];
 #endif
       }
     }
@@ -405,15 +403,15 @@ constexpr bool kRepUniformEncode = true;
       asm volatile("" : "+v"(e3[0]), "+v"(e3[1]), "+v"(e3[2]));
 #pragma unroll
       for (int i = 0; i < 3; ++i)
-        rl.v[i] = rl.v[3 + i] = __builtin_amdgcn_fmed3f(__uint_as_float(e3[i].y), __uint_as_float(e3[i].z), __fadd_rn(x[i], -__uint_as_float(e3[i].x)));
+        lin[i] = lin[3 + i] = __builtin_amdgcn_fmed3f(__uint_as_float(e3[i].y), __uint_as_float(e3[i].z), __fadd_rn(x[i], -__uint_as_float(e3[i].x)));
     } else {
       pixel_rgb(byte_of(fr.yy, 1), ch1, x[3], x[4], x[5]);
-      linearise6(r, x, rl.v);
+      linearise6(r, x, lin);
     }
 #else
     pixel_rgb(byte_of(fr.yy, 0), ch0, x[0], x[1], x[2]);
     pixel_rgb(byte_of(fr.yy, 1), ch1, x[3], x[4], x[5]);
-    linearise6(r, x, rl.v);
+    linearise6(r, x, lin);
 #endif
 """),
     # round 6: where the placement hunt's wall-clock time goes (stderr, one line per ring): allocation, free, hipMemGetInfo, warm-up launches, probes
@@ -531,27 +529,26 @@ double *lab_trace() {  // seconds: malloc, free, mem_info, warm-up, probe
      """  auto decode_row = [&](const Fetched1 &raw, int srow) {
 #if defined(BT709_LAB_SCALED_NO_DECODE)  // no matrix, no decode-side lookups: six floats straight from the fetched bytes
     {
-      RowLin rl;
+      RowLin<N> rl = {};
       const float tiny = __uint_as_float(0x2b800000u);
 #pragma unroll
-      for (int k = 0; k < 6; ++k) rl.v[k] = __fmul_rn(byte_of(k < 4 ? raw.y[0] : raw.c[0], k & 3), tiny);
-      rl.a[0] = rl.a[1] = 0.0f;
+      for (int k = 0; k < 6; ++k) rl.v[k / 3][k % 3] = __fmul_rn(byte_of(k < 4 ? raw.y[0] : raw.c[0], k & 3), tiny);
       (void)srow;
       if (true) return rl;
     }
 #endif
     if (TAPS == TAPS_ONCE) {"""),
     ("bt709_rescale.hip",
-     """    const uint32_t R = UNIFORM_ENCODE ? encode_byte_uniform(r, acc[0]) : encode_byte(r, acc[0]);
-    const uint32_t G = UNIFORM_ENCODE ? encode_byte_uniform(r, acc[1]) : encode_byte(r, acc[1]);
-    const uint32_t B = UNIFORM_ENCODE ? encode_byte_uniform(r, acc[2]) : encode_byte(r, acc[2]);
+     """    const uint32_t R = encode_byte(r, acc[0]);
+    const uint32_t G = encode_byte(r, acc[1]);
+    const uint32_t B = encode_byte(r, acc[2]);
 """,
      """#if defined(BT709_LAB_SCALED_NO_ENCODE)  // no encode-side lookups: a byte cut out of each float
     const uint32_t R = (__float_as_uint(acc[0]) >> 15) & 0xffu, G = (__float_as_uint(acc[1]) >> 15) & 0xffu, B = (__float_as_uint(acc[2]) >> 15) & 0xffu;
 #else
-    const uint32_t R = UNIFORM_ENCODE ? encode_byte_uniform(r, acc[0]) : encode_byte(r, acc[0]);
-    const uint32_t G = UNIFORM_ENCODE ? encode_byte_uniform(r, acc[1]) : encode_byte(r, acc[1]);
-    const uint32_t B = UNIFORM_ENCODE ? encode_byte_uniform(r, acc[2]) : encode_byte(r, acc[2]);
+    const uint32_t R = encode_byte(r, acc[0]);
+    const uint32_t G = encode_byte(r, acc[1]);
+    const uint32_t B = encode_byte(r, acc[2]);
 #endif
 """),
     ("bt709_rescale.hip",
@@ -631,55 +628,51 @@ double *lab_trace() {  // seconds: malloc, free, mem_info, warm-up, probe
 """),
     # round 6: the wave-decodes-once form's exchange through a wave-private LDS tile instead of ds_bpermute (same bytes out)
     ("bt709_rescale.hip",
-     """      RowLin rl;
-      rl.a[0] = rl.a[1] = 0.0f;
+     """      RowLin<N> rl;
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
 #pragma unroll
-        for (int k = 0; k < 3; ++k)
-          rl.v[3 * t + k] = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(static_cast<int>(tap_lane[t]), __builtin_bit_cast(int, own[k])));
-        if (HAS_ALPHA) rl.a[t] = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(static_cast<int>(tap_lane[t]), __builtin_bit_cast(int, own[3])));
+        for (int k = 0; k < N; ++k)
+          rl.v[t][k] = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(static_cast<int>(tap_lane[t]), __builtin_bit_cast(int, own[k])));
       }
       return rl;
 """,
-     """      RowLin rl;
-      rl.a[0] = rl.a[1] = 0.0f;
+     """      RowLin<N> rl;
 #if defined(BT709_LAB_SCALED_ONCE_LDS)  // the decode-once TILE: own pixel written to LDS (16 bytes per lane, behind the tables), taps read back
       {
         typedef __attribute__((address_space(3))) u32x4 *LdsQuadW;
-        const uint32_t tile = p.lab_tile_off + (threadIdx.y * blockDim.x + (threadIdx.x & ~63u)) * 16u;  // this wave's 1 KiB
+        const uint32_t tile = p.lab_tile_off + (threadIdx.x & ~63u) * 16u;  // this wave's 1 KiB
         if (!HAS_ALPHA) own[3] = 0.0f;
         u32x4 w = {__float_as_uint(own[0]), __float_as_uint(own[1]), __float_as_uint(own[2]), __float_as_uint(own[3])};
         *reinterpret_cast<LdsQuadW>(tile + lane * 16u) = w;
         asm volatile("" ::: "memory");
         const u32x4 t0 = *reinterpret_cast<LdsQuadPtr>(tile + tap_lane[0] * 4u), t1 = *reinterpret_cast<LdsQuadPtr>(tile + tap_lane[1] * 4u);
         asm volatile("" ::: "memory");
-        rl.v[0] = __uint_as_float(t0.x), rl.v[1] = __uint_as_float(t0.y), rl.v[2] = __uint_as_float(t0.z);
-        rl.v[3] = __uint_as_float(t1.x), rl.v[4] = __uint_as_float(t1.y), rl.v[5] = __uint_as_float(t1.z);
-        if (HAS_ALPHA) rl.a[0] = __uint_as_float(t0.w), rl.a[1] = __uint_as_float(t1.w);
+        rl.v[0][0] = __uint_as_float(t0.x), rl.v[0][1] = __uint_as_float(t0.y), rl.v[0][2] = __uint_as_float(t0.z);
+        rl.v[1][0] = __uint_as_float(t1.x), rl.v[1][1] = __uint_as_float(t1.y), rl.v[1][2] = __uint_as_float(t1.z);
+        if (HAS_ALPHA) rl.v[0][N - 1] = __uint_as_float(t0.w), rl.v[1][N - 1] = __uint_as_float(t1.w);
       }
 #else
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
 #pragma unroll
-        for (int k = 0; k < 3; ++k)
-          rl.v[3 * t + k] = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(static_cast<int>(tap_lane[t]), __builtin_bit_cast(int, own[k])));
-        if (HAS_ALPHA) rl.a[t] = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(static_cast<int>(tap_lane[t]), __builtin_bit_cast(int, own[3])));
+        for (int k = 0; k < N; ++k)
+          rl.v[t][k] = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(static_cast<int>(tap_lane[t]), __builtin_bit_cast(int, own[k])));
       }
 #endif
       return rl;
 """),
     ("bt709_rescale.hip",
-     """  const size_t lds = (static_cast<size_t>(p.table_linear_bytes) << kScaledDecCopiesLog2) + ((kScaledUniform ? p.table_encode_u_bytes : p.table_encode_bytes) << kScaledEncCopiesLog2);
-  const dim3 block(kBlockThreads, kScaledStrips);""",
+     """  const size_t lds = static_cast<size_t>(p.table_linear_bytes) + p.table_encode_bytes;
+  const dim3 block(kBlockThreads);""",
      """#if defined(BT709_LAB_SCALED_ONCE_LDS)
-  const size_t lds_tables = (static_cast<size_t>(p.table_linear_bytes) << kScaledDecCopiesLog2) + ((kScaledUniform ? p.table_encode_u_bytes : p.table_encode_bytes) << kScaledEncCopiesLog2);
+  const size_t lds_tables = static_cast<size_t>(p.table_linear_bytes) + p.table_encode_bytes;
   p.lab_tile_off = static_cast<uint32_t>(lds_tables);  // the kernel's dynamic LDS starts at address 0 (no static LDS)
-  const size_t lds = lds_tables + 16u * kBlockThreads * kScaledStrips;
+  const size_t lds = lds_tables + 16u * kBlockThreads;
 #else
-  const size_t lds = (static_cast<size_t>(p.table_linear_bytes) << kScaledDecCopiesLog2) + ((kScaledUniform ? p.table_encode_u_bytes : p.table_encode_bytes) << kScaledEncCopiesLog2);
+  const size_t lds = static_cast<size_t>(p.table_linear_bytes) + p.table_encode_bytes;
 #endif
-  const dim3 block(kBlockThreads, kScaledStrips);"""),
+  const dim3 block(kBlockThreads);"""),
     ("bt709_kernels.h",
      """  uint32_t scaled_rows;  // output rows of a strip (filled by launch_decode_scaled)""",
      """  uint32_t lab_tile_off;  // BT709_LAB_SCALED_ONCE_LDS
