@@ -41,6 +41,7 @@
 #include "bt709_kernels.h"
 #include "bt709_quantise.h"
 #include "bt709_stage.h"
+#include "bt709_tile.h"
 
 namespace bt709 {
 namespace {
@@ -177,30 +178,8 @@ __device__ __forceinline__ void stage_table(void *lds, const void *src, uint32_t
     for (uint32_t i = tid; i < n; i += nthreads) d[i] = s[i];
     return;
   }
-  // Large tables (the LINEAR mode's 4 096 buckets = 33 KiB: five rounds for 512 lanes): all of a lane's loads are issued
-  // before its first write.  As a plain loop every round was its own L2 round trip inside the workgroup's lifetime
-  // (SQ_WAIT_INST_LDS 442 M against 33 M cycles per launch for the 4 KiB table, +28 % wave cycles; round 3).
-  constexpr int kBatch = 5;
-  for (uint32_t base = tid; base < n; base += nthreads * kBatch) {
-    u32x4 v[kBatch];
-#pragma unroll
-    for (int k = 0; k < kBatch; ++k) {
-      const uint32_t i = base + static_cast<uint32_t>(k) * nthreads;
-      if (i < n) v[k] = s[i];
-    }
-#pragma unroll
-    for (int k = 0; k < kBatch; ++k) {
-      const uint32_t i = base + static_cast<uint32_t>(k) * nthreads;
-      if (i < n) d[i] = v[k];
-    }
-  }
-}
-
-// Frame bytes are touched exactly once: stream them past the caches (measured +1.3 % on 4K)
-template <bool NT>
-__device__ __forceinline__ uint32_t load32(const uint8_t *p) {
-  if (NT) return __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(p));
-  return *reinterpret_cast<const uint32_t *>(p);
+  // large tables (the LINEAR mode's 4 096 buckets = 33 KiB: five rounds for 512 lanes): all of a lane's loads before its first write
+  stage_batched<5>(d, n, tid, nthreads, [&](uint32_t i) { return s[i]; });
 }
 
 template <bool NT>

@@ -42,9 +42,10 @@
 #include <cstdint>
 
 #include "bt709_constants.h"
-#include "bt709_kernels.h"
+#include "bt709_launch.h"
 #include "bt709_split_lookup.h"
 #include "bt709_stage.h"
+#include "bt709_tile.h"
 
 namespace bt709 {
 namespace {
@@ -193,13 +194,11 @@ __device__ __forceinline__ EncodeFrame encode_frame(const EncodeParams &p, uint3
 __global__ void __launch_bounds__(kMaxBlockThreads)
 encode_bgra_nv12(const EncodeParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-  // XCD-aware work map (p.xcd_bands; launches of a multiple of 8 pictures): grid.x = 8 x tiles, x & 7 = the workgroup's place in
-  // the round-robin over the XCDs, which owns a contiguous band of the launch's pictures (bt709_kernels.hip decode_nv12_quads)
-  const uint32_t tile = p.xcd_bands ? blockIdx.x >> 3 : blockIdx.x;
-  const EncodeFrame f = encode_frame(p, p.xcd_bands ? (blockIdx.x & 7u) * p.frames_per_band + blockIdx.z : blockIdx.z);
+  const BandedWork work = banded_work(p.xcd_bands, p.frames_per_band);  // XCD-aware work map: bt709_tile.h
+  const EncodeFrame f = encode_frame(p, work.frame);
   const uint32_t quads = p.width >> 2;
   const uint32_t row_pairs = p.height >> 1;
-  const uint32_t q_raw = tile * blockDim.x + threadIdx.x;
+  const uint32_t q_raw = work.tile * blockDim.x + threadIdx.x;
   const uint32_t q = min(q_raw, quads - 1);
   const uint32_t rp0 = blockIdx.y * p.row_pairs_per_block;
   const uint32_t rp_end = min(rp0 + p.row_pairs_per_block, row_pairs);
@@ -277,26 +276,13 @@ encode_bgra_nv12_blocks(const EncodeParams p) {
   }
 }
 
-// the plan of the call's first launch, for bt709hip_last_launch_info (as launch_decode keeps it)
-static void record_launch(const dim3 &grid, uint32_t threads, int32_t xcd_bands) {
-  LaunchShape &shape = last_launch_shape();
-  if (shape.launches++ == 0) {
-    shape.grid[0] = grid.x, shape.grid[1] = grid.y, shape.grid[2] = grid.z;
-    shape.block[0] = threads, shape.block[1] = shape.block[2] = 1;
-    shape.xcd_bands = xcd_bands;
-  }
-}
-
 const char *launch_encode(const EncodeParams &params, int frames, bool fast, bool xcd_bands, hipStream_t stream) {
-  if (fast && xcd_bands && params.uniform && frames > kXcdBandMinFrames && frames % 8 != 0) {
-    // any count of 64 pictures or more: the XCD-aware map over the multiple of 8, the plain map over the rest (launch_decode)
-    const int head = frames - frames % 8;
-    launch_encode(params, head, fast, xcd_bands, stream);
+  const BandPlan plan = plan_bands(frames, fast && xcd_bands, params.uniform, kXcdBandMinFrames);
+  if (plan.banded && plan.tail) {
+    launch_encode(params, plan.banded, fast, xcd_bands, stream);
     EncodeParams tail = params;
-    tail.frames[0].bgra += static_cast<int64_t>(head) * tail.step_bgra;
-    tail.frames[0].y += static_cast<int64_t>(head) * tail.step_y;
-    tail.frames[0].cbcr += static_cast<int64_t>(head) * tail.step_cbcr;
-    return launch_encode(tail, frames - head, fast, false, stream);
+    advance_frames(tail, plan.banded);
+    return launch_encode(tail, plan.tail, fast, false, stream);
   }
   EncodeParams p = params;
   if (p.row_pairs_per_block == 0) p.row_pairs_per_block = encode_row_pairs_per_block(p.width, p.height, frames);
@@ -315,28 +301,20 @@ const char *launch_encode(const EncodeParams &params, int frames, bool fast, boo
     if (threads > static_cast<uint32_t>(kMaxBlockThreads)) threads = kMaxBlockThreads;
     dim3 grid((quads + threads - 1) / threads,
               (p.height / 2 + p.row_pairs_per_block - 1) / p.row_pairs_per_block, frames);
-    if (xcd_bands && frames >= kXcdBandMinFrames && frames % 8 == 0) {
-      p.xcd_bands = 1;
-      p.frames_per_band = static_cast<uint32_t>(frames) / 8u;
-      grid = dim3(grid.x * 8u, grid.y, p.frames_per_band);
-    }
-    record_launch(grid, threads, static_cast<int32_t>(p.xcd_bands));
+    if (plan.banded) grid = band_grid(p, 1, grid);
+    record_launch(grid, dim3(threads), p.xcd_bands);
     hipLaunchKernelGGL(encode_bgra_nv12, grid, dim3(threads), lds, stream, p);
     return "encode_bgra_nv12";
   }
   const dim3 grid((p.width / 2 + kBlockThreads - 1) / kBlockThreads, p.height / 2, frames);
-  record_launch(grid, kBlockThreads, 0);
+  record_launch(grid, dim3(kBlockThreads), 0);
   hipLaunchKernelGGL(encode_bgra_nv12_blocks, grid, dim3(kBlockThreads), lds, stream, p);
   return "encode_bgra_nv12_blocks";
 }
 
 hipError_t prepare_encode_kernels() {
-  const int cap = 160 * 1024;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&encode_bgra_nv12),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-  if (e != hipSuccess) return e;
-  return hipFuncSetAttribute(reinterpret_cast<const void *>(&encode_bgra_nv12_blocks),
-                             hipFuncAttributeMaxDynamicSharedMemorySize, cap);
+  const void *fns[] = {reinterpret_cast<const void *>(&encode_bgra_nv12), reinterpret_cast<const void *>(&encode_bgra_nv12_blocks)};
+  return raise_lds_cap(fns, kRepLdsBytes);
 }
 
 }  // namespace bt709

@@ -20,7 +20,7 @@ constexpr int kBlockThreads = 256;     // general-path workgroup: 4 waves of 64
 constexpr int kMaxBlockThreads = BT709_MAX_BLOCK_THREADS;  // fast-path workgroup is sized per frame width, up to 8 waves
 constexpr int kQuadsPerLane = BT709_QUADS_PER_LANE;        // 4x2-pixel quads a fast-path lane owns per row pair
 constexpr int kMaxBatch = 32;          // == BT709HIP_MAX_BATCH: frames in the kernarg table
-// XCD-aware work map (bt709_kernels.hip decode_nv12_quads): used for launches of a multiple of 8 frames from this many on.
+// XCD-aware work map (bt709_tile.h banded_work; bt709_launch.h plan_bands): used for launches of a multiple of 8 frames from this many on.
 // Measured (round 3, same call, plain vs banded): decode 32 frames 0.756 / 0.741-0.761, 64 0.741 / 0.745-0.760, 128 0.72 / 0.77,
 // 256 0.70 / 0.76-0.81; encoder 32 pictures 0.70 / 0.67, 256 0.69 / 0.73: a band needs ~8 frames to pay.
 #ifndef BT709_XCD_BAND_MIN_FRAMES
@@ -98,11 +98,9 @@ struct HalfParams {
   const void *table;     // float T[]: T[i] = smallest x with H(x) >= h_min + i, then the candidate entries; nullptr: no curve (LINEAR)
   uint32_t table_bytes;  // 0 without a table; else thresholds + candidates
   uint32_t cand_offset;  // byte offset of the candidate entries {intercept, slope} (transfer_tables.h HalfTable::cand) in `table` = bytes of the thresholds
-  uint32_t h_min, h_max; // codes the table covers
-  float split, low_scale;
   float index_scale;     // HalfTable::index_scale: the split point lands on the bucket boundary 2^-4
-  uint32_t row_pairs_per_block;  // filled by the launcher
-  uint32_t wide_store;           // 16-byte stores (target 16-byte aligned), else 8-byte
+  uint32_t h_min;        // first code the table covers
+  uint32_t wide_store;   // 16-byte stores (target 16-byte aligned), else 8-byte; filled by the launcher
 };
 // LDS plan of decode_nv12_rgba16f: the thresholds from byte 0, the candidate entries from this FIXED byte on -- so that the
 // address of a bucket's entry is its binary16 bits plus a compile-time constant (the ds_read's immediate offset).  Above the
@@ -271,7 +269,7 @@ inline uint32_t quads_rows_per_block(uint32_t block_threads, uint32_t tiles) {
   return by < 1 ? 1 : by;
 }
 
-// Raise the dynamic-LDS cap of the kernels (tables can exceed the 64 KiB default).
+// Raise the dynamic-LDS cap of the kernels (bt709_launch.h raise_lds_cap).
 hipError_t prepare_kernels();          // bt709_kernels.hip
 hipError_t prepare_rescale_kernels();  // bt709_rescale_half.hip (+ bt709_rescale_scaled.hip's)
 

@@ -9,7 +9,7 @@
 //
 // Memory plan (HBM-bound: 1.5 B read + 4 B written per pixel, no reuse between workgroups -- nothing to keep in an L2 --
 // but the ORDER in which the eight XCDs walk a long launch decides how the DRAM streams interleave: batched launches of 64
-// frames or more give each XCD a contiguous band of the frames, see decode_nv12_quads below):
+// frames or more give each XCD a contiguous band of the frames, bt709_tile.h banded_work):
 //   * a lane owns 4-wide x 2-high pixel "quads": one dword of each luma row, one dword of CbCr
 //     (two Cb,Cr pairs, each shared by a 2x2 block -- chroma is REPLICATED, not interpolated:
 //     AAPLShaders.metal:350, BGRAToBT709Converter.m:267-277) and two 16-byte non-temporal
@@ -28,6 +28,7 @@
 #include <cstring>
 
 #include "bt709_device.h"
+#include "bt709_launch.h"
 
 namespace bt709 {
 namespace {
@@ -106,25 +107,13 @@ __device__ __forceinline__ void decode_block(const UnitLookup &u, const float y[
 // alpha pointers and strides 4-byte aligned; output pointer and stride 16-byte
 // aligned.  grid = (tiles, H/2, frames); a tile is blockDim * kQuadsPerLane quads.
 // ---------------------------------------------------------------------------
-// RP: consecutive row pairs a workgroup covers, all of them loaded before the table is staged (1 in every shipped kernel; 2 and 4
-// served the LINEAR mode's 33 KiB uniform table in the first half of round 5, until its log-bucket table made it 5 KiB:
-// decode_nv12_quads_log below).  LOGIDX: the table is in log-bucket form (one shift more per channel).
-template <bool HAS_ALPHA, bool NT, bool QUANT, int RP, bool LOGIDX = false>
+// LOGIDX: the table is in log-bucket form (one shift more per channel).  (The body once covered 2 or 4 row pairs per workgroup: that
+// served the LINEAR mode's 33 KiB uniform table until its log-bucket form made it 5 KiB, decode_nv12_quads_log below.)
+template <bool HAS_ALPHA, bool NT, bool QUANT, bool LOGIDX = false>
 __device__ __forceinline__ void quads_body(const DecodeParams &p, unsigned char *lds_raw) {
   constexpr int UNROLL = kQuadsPerLane;
-
-  // XCD-AWARE WORK MAP (p.xcd_bands; launches of 64 frames or more, in multiples of 8: launch_decode).  Workgroups are dealt round-robin
-  // over the 8 XCDs in dispatch order, so with the plain map (tile, row pair, frame) XCD k owns the tile rows = k mod 8 of
-  // ONE address stream -- and an XCD that runs a few percent ahead of another (they sit at different distances from
-  // the HBM stacks) widens the band of rows in flight for the whole launch: measured, the longer a launch, the slower
-  // (64 / 128 / 256 frames per launch: 0.75 / 0.71 / 0.70 of the roofline against 0.77 for 32).  Here grid.x = 8 x tiles, so
-  // x & 7 IS the workgroup's position in the round-robin, and XCD-class b gets a contiguous band of the launch's frames
-  // [b F/8, (b + 1) F/8): eight sequential streams that cannot drift into each other.  Long launches then GAIN (no tail,
-  // no boundary): 256 frames per launch 0.80-0.81.  Speed only: nothing depends on which XCD a workgroup really lands on.
-  const uint32_t tile = p.xcd_bands ? blockIdx.x >> 3 : blockIdx.x;
-  const uint32_t frame = p.xcd_bands == 1 ? (blockIdx.x & 7u) * p.frames_per_band + blockIdx.z
-                       : (p.xcd_bands == 2 ? blockIdx.z * 8u + (blockIdx.x & 7u) : blockIdx.z);
-  const FramePlanes f = frame_planes(p, frame);
+  const BandedWork work = banded_work<true>(p.xcd_bands, p.frames_per_band);  // XCD-aware work map: bt709_tile.h
+  const FramePlanes f = frame_planes(p, work.frame);
   const uint32_t quads = p.width >> 2;
   const uint32_t row_pairs = p.height >> 1;
   // blockDim.y > 1 only for narrow frames: a workgroup then covers blockDim.y consecutive row
@@ -132,66 +121,29 @@ __device__ __forceinline__ void quads_body(const DecodeParams &p, unsigned char 
   // waves, so threadIdx.y is the same in every lane of a wave: taking it from the first lane
   // makes the row pointers scalar (SGPR base + per-lane offset addressing, no 64-bit VALU
   // address arithmetic).
-  const uint32_t rp_first = (blockIdx.y * blockDim.y + __builtin_amdgcn_readfirstlane(threadIdx.y)) * RP;
-  // quad u of this lane: consecutive lanes own consecutive quads (a store instruction must fill whole
-  // lines: a lane owning ADJACENT quads measured 3x slower, tools/lab_quads_variants.hip)
-  const uint32_t q0 = tile * (blockDim.x * UNROLL) + threadIdx.x;
+  const uint32_t rp_raw = blockIdx.y * blockDim.y + __builtin_amdgcn_readfirstlane(threadIdx.y);
+  const uint32_t q0 = work.tile * (blockDim.x * UNROLL) + threadIdx.x;
 
-  // Straight-line code: lanes past the row's end load a clamped (valid) quad and only their
-  // stores are predicated.  A divergent `if (q < quads)` around the arithmetic made hipcc put
-  // s_waitcnt vmcnt(0) at the join, i.e. each wave waited for the write acknowledgement of its
-  // first quad's stores before touching its second quad.
-  uint32_t ya[RP][UNROLL], yb[RP][UNROLL], cw[RP][UNROLL], aa[RP][UNROLL], ab[RP][UNROLL];
-#pragma unroll
-  for (int r = 0; r < RP; ++r) {
-    const uint32_t rp = min(rp_first + r, row_pairs - 1);
-    const uint8_t *y0 = f.y + static_cast<size_t>(2 * rp) * p.y_stride;
-    const uint8_t *y1 = y0 + p.y_stride;
-    const uint8_t *cc = f.cbcr + static_cast<size_t>(rp) * p.cbcr_stride;
-    const uint8_t *a0 = HAS_ALPHA ? f.alpha + static_cast<size_t>(2 * rp) * p.alpha_stride : nullptr;
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {
-      const uint32_t q = min((q0 + u * blockDim.x), quads - 1);
-      ya[r][u] = load32<NT>(y0 + 4 * q);
-      yb[r][u] = load32<NT>(y1 + 4 * q);
-      cw[r][u] = load32<NT>(cc + 4 * q);
-      if (HAS_ALPHA) {
-        aa[r][u] = load32<NT>(a0 + 4 * q);
-        ab[r][u] = load32<NT>(a0 + p.alpha_stride + 4 * q);
-      }
-    }
-  }
+  // straight-line: loads, table, pin, arithmetic, predicated stores (bt709_tile.h TileIn)
+  TileIn<UNROLL, HAS_ALPHA> in;
+  in.template load<NT>(f, p, rp_raw, row_pairs, q0, quads);
   if (!QUANT) {  // the sRGB mode needs no table (decode_quad)
     stage_table(lds_raw, p.table_unit, p.table_unit_bytes);  // after the tile's loads are in flight
     __syncthreads();
   }
-  // Pin every loaded dword here: hipcc then waits for all of the tile's loads once, before any
-  // store is issued, instead of emitting s_waitcnt vmcnt(0) between the first quad's stores and
-  // the second quad's arithmetic (which would wait for the stores' write acknowledgements).
-#pragma unroll
-  for (int r = 0; r < RP; ++r)
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {
-      asm volatile("" : "+v"(ya[r][u]), "+v"(yb[r][u]), "+v"(cw[r][u]));
-      if (HAS_ALPHA) asm volatile("" : "+v"(aa[r][u]), "+v"(ab[r][u]));
-    }
+  in.pin();
 
   const UnitLookup ul = unit_lookup(p, lds_raw);
+  uint8_t *o0 = f.out + static_cast<size_t>(2 * min(rp_raw, row_pairs - 1)) * p.out_stride;
+  uint8_t *o1 = o0 + p.out_stride;
 #pragma unroll
-  for (int r = 0; r < RP; ++r) {
-    const uint32_t rp_raw = rp_first + r;
-    uint8_t *o0 = f.out + static_cast<size_t>(2 * min(rp_raw, row_pairs - 1)) * p.out_stride;
-    uint8_t *o1 = o0 + p.out_stride;
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {
-      const uint32_t q = (q0 + u * blockDim.x);
-      u32x4 top, bot;
-      decode_quad<HAS_ALPHA, QUANT, LOGIDX>(ul, ya[r][u], yb[r][u], cw[r][u], HAS_ALPHA ? aa[r][u] : 0u, HAS_ALPHA ? ab[r][u] : 0u, p.alpha_word, top,
-                             bot);
-      if (q < quads && rp_raw < row_pairs) {
-        store16<NT>(o0 + 16 * q, top);
-        store16<NT>(o1 + 16 * q, bot);
-      }
+  for (int u = 0; u < UNROLL; ++u) {
+    const uint32_t q = q0 + u * blockDim.x;
+    u32x4 top, bot;
+    decode_quad<HAS_ALPHA, QUANT, LOGIDX>(ul, in.ya[u], in.yb[u], in.cw[u], HAS_ALPHA ? in.aa[u] : 0u, HAS_ALPHA ? in.ab[u] : 0u, p.alpha_word, top, bot);
+    if (q < quads && rp_raw < row_pairs) {
+      store16<NT>(o0 + 16 * q, top);
+      store16<NT>(o1 + 16 * q, bot);
     }
   }
 }
@@ -200,7 +152,7 @@ template <bool HAS_ALPHA, bool NT, bool QUANT>
 __global__ void __launch_bounds__(kMaxBlockThreads)
 decode_nv12_quads(const DecodeParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-  quads_body<HAS_ALPHA, NT, QUANT, 1>(p, lds_raw);
+  quads_body<HAS_ALPHA, NT, QUANT>(p, lds_raw);
 }
 
 // The plain kernel over a LOG-bucket table (DecodeParams::unit1_shift == 16; transfer_tables.h TransferTable::buckets_log):
@@ -213,7 +165,7 @@ template <bool NT>
 __global__ void __launch_bounds__(kMaxBlockThreads)
 decode_nv12_quads_log(const DecodeParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-  quads_body<false, NT, false, 1, true>(p, lds_raw);
+  quads_body<false, NT, false, true>(p, lds_raw);
 }
 
 // ---------------------------------------------------------------------------
@@ -392,37 +344,21 @@ const char *launch_decode(const DecodeParams &p_in, int frames, int variant, boo
                           int xcd_bands, uint32_t grid_x, uint32_t block_threads, hipStream_t stream) {
   const bool quant = quantiser || has_alpha;  // the sRGB mode: arithmetic, no table
   const size_t lds = quant ? 0 : p_in.table_unit_bytes;
-  if (variant == kVariantQuads && xcd_bands && p_in.uniform && frames > kXcdBandMinFrames && frames % 8 != 0) {
-    // a long launch of a frame count that is not a multiple of 8: the XCD-aware map over the multiple of 8, the plain map over
-    // the (up to 7) frames left, back to back on the stream
-    const int head = frames - frames % 8;
-    launch_decode(p_in, head, variant, has_alpha, quantiser, nontemporal, xcd_bands, grid_x, block_threads, stream);
+  const BandPlan plan = plan_bands(frames, variant == kVariantQuads && xcd_bands, p_in.uniform, kXcdBandMinFrames);
+  if (plan.banded && plan.tail) {
+    launch_decode(p_in, plan.banded, variant, has_alpha, quantiser, nontemporal, xcd_bands, grid_x, block_threads, stream);
     DecodeParams tail = p_in;
-    FramePlanes &f = tail.frames[0];
-    f.y += static_cast<int64_t>(head) * tail.step_y;
-    f.cbcr += static_cast<int64_t>(head) * tail.step_cbcr;
-    if (f.alpha) f.alpha += static_cast<int64_t>(head) * tail.step_alpha;
-    f.out += static_cast<int64_t>(head) * tail.step_out;
-    return launch_decode(tail, frames - head, variant, has_alpha, quantiser, nontemporal, 0, grid_x, block_threads, stream);
+    advance_frames(tail, plan.banded);
+    return launch_decode(tail, plan.tail, variant, has_alpha, quantiser, nontemporal, 0, grid_x, block_threads, stream);
   }
+  DecodeParams p = p_in;
   if (variant == kVariantQuads) {
     // grid_x = tiles per row pair; narrow frames stack row pairs in blockDim.y
     const uint32_t by = quads_rows_per_block(block_threads, grid_x);
-    dim3 grid(grid_x, (p_in.height / 2 + by - 1) / by, static_cast<uint32_t>(frames));
+    dim3 grid(grid_x, (p.height / 2 + by - 1) / by, static_cast<uint32_t>(frames));
     const dim3 block(block_threads, by, 1);
-    DecodeParams banded = p_in;
-    if (xcd_bands && frames >= kXcdBandMinFrames && frames % 8 == 0) {  // see the kernel: 8 contiguous bands of frames, one per XCD class
-      banded.xcd_bands = static_cast<uint32_t>(xcd_bands);
-      banded.frames_per_band = static_cast<uint32_t>(frames) / 8u;
-      grid = dim3(grid_x * 8u, grid.y, banded.frames_per_band);
-    }
-    const DecodeParams &p = banded;
-    LaunchShape &shape = last_launch_shape();
-    if (shape.launches++ == 0) {
-      shape.grid[0] = grid.x, shape.grid[1] = grid.y, shape.grid[2] = grid.z;
-      shape.block[0] = block.x, shape.block[1] = block.y, shape.block[2] = block.z;
-      shape.xcd_bands = static_cast<int32_t>(banded.xcd_bands);
-    }
+    if (plan.banded) grid = band_grid(p, static_cast<uint32_t>(xcd_bands), grid);
+    record_launch(grid, block, p.xcd_bands);
     if (has_alpha) {
       hipLaunchKernelGGL((decode_nv12_quads<true, true, true>), grid, block, lds, stream, p);
       return "decode_nv12_quads<alpha>";
@@ -445,15 +381,9 @@ const char *launch_decode(const DecodeParams &p_in, int frames, int variant, boo
     return "decode_nv12_quads";
   }
   // grid_x = workgroups per frame, grid-strided over row pairs
-  const DecodeParams &p = p_in;
   const dim3 grid(grid_x, static_cast<uint32_t>(frames), 1);
   const dim3 block(kBlockThreads, 1, 1);
-  LaunchShape &shape = last_launch_shape();
-  if (shape.launches++ == 0) {
-    shape.grid[0] = grid.x, shape.grid[1] = grid.y, shape.grid[2] = grid.z;
-    shape.block[0] = block.x, shape.block[1] = block.y, shape.block[2] = block.z;
-    shape.xcd_bands = 0;
-  }
+  record_launch(grid, block, 0);
   if (has_alpha) {
     hipLaunchKernelGGL((decode_nv12_blocks<true, true>), grid, block, lds, stream, p);
     return "decode_nv12_blocks<alpha>";
@@ -467,7 +397,6 @@ const char *launch_decode(const DecodeParams &p_in, int frames, int variant, boo
 }
 
 hipError_t prepare_kernels() {
-  const int cap = 160 * 1024;  // gfx950: 160 KiB LDS per workgroup
   const void *fns[] = {
       reinterpret_cast<const void *>(&decode_nv12_quads<true, true, true>),
       reinterpret_cast<const void *>(&decode_nv12_quads<false, true, true>),
@@ -482,11 +411,7 @@ hipError_t prepare_kernels() {
       reinterpret_cast<const void *>(&decode_nv12_blocks<false, true>),
       reinterpret_cast<const void *>(&decode_nv12_blocks<false, false>),
   };
-  for (const void *fn : fns) {
-    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  return raise_lds_cap(fns, kRepLdsBytes);
 }
 
 }  // namespace bt709

@@ -15,6 +15,7 @@
 #include <cstdint>
 
 #include "bt709_device.h"
+#include "bt709_launch.h"
 
 namespace bt709 {
 namespace {

@@ -151,50 +151,37 @@ decode_nv12_half(const DecodeParams p) {
   const uint32_t out_rows = p.height >> 1;
   const uint32_t orow_raw = blockIdx.y * blockDim.y + __builtin_amdgcn_readfirstlane(threadIdx.y);  // wave-uniform
   const uint32_t orow = min(orow_raw, out_rows - 1);
-  const uint8_t *y0 = f.y + static_cast<size_t>(2 * orow) * p.y_stride;
-  const uint8_t *y1 = y0 + p.y_stride;
-  const uint8_t *cc = f.cbcr + static_cast<size_t>(orow) * p.cbcr_stride;
-  const uint8_t *a0 = HAS_ALPHA ? f.alpha + static_cast<size_t>(2 * orow) * p.alpha_stride : nullptr;
-  const uint8_t *a1 = HAS_ALPHA ? a0 + p.alpha_stride : nullptr;
   uint8_t *o = f.out + static_cast<size_t>(orow) * p.out_stride;
 
   if (WIDE) {
     constexpr int UNROLL = kQuadsPerLane;
     const uint32_t quads = p.width >> 2;
     const uint32_t q0 = blockIdx.x * (blockDim.x * UNROLL) + threadIdx.x;
-    uint32_t ya[UNROLL], yb[UNROLL], cw[UNROLL], aa[UNROLL], ab[UNROLL];
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {
-      const uint32_t q = min(q0 + u * blockDim.x, quads - 1);  // clamped load, predicated store (see 1:1 kernel)
-      ya[u] = load32<NT>(y0 + 4 * q);
-      yb[u] = load32<NT>(y1 + 4 * q);
-      cw[u] = load32<NT>(cc + 4 * q);
-      if (HAS_ALPHA) {
-        aa[u] = load32<NT>(a0 + 4 * q);
-        ab[u] = load32<NT>(a1 + 4 * q);
-      }
-    }
+    // straight-line: loads, tables, pin, arithmetic, predicated stores (bt709_tile.h TileIn)
+    TileIn<UNROLL, HAS_ALPHA> in;
+    in.template load<NT>(f, p, orow_raw, out_rows, q0, quads);
     const RescaleLookup r = stage_rescale_tables(lds_raw, p, 0, 0);  // after the tile's loads are in flight
     __syncthreads();
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {  // see 1:1 kernel
-      asm volatile("" : "+v"(ya[u]), "+v"(yb[u]), "+v"(cw[u]));
-      if (HAS_ALPHA) asm volatile("" : "+v"(aa[u]), "+v"(ab[u]));
-    }
+    in.pin();
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u) {
       const uint32_t q = q0 + u * blockDim.x;
       uint32_t aw0 = p.alpha_word, aw1 = p.alpha_word;
       if (HAS_ALPHA) {
-        aw0 = half_alpha_arith(byte_of(aa[u], 0), byte_of(aa[u], 1), byte_of(ab[u], 0), byte_of(ab[u], 1));
-        aw1 = half_alpha_arith(byte_of(aa[u], 2), byte_of(aa[u], 3), byte_of(ab[u], 2), byte_of(ab[u], 3));
+        aw0 = half_alpha_arith(byte_of(in.aa[u], 0), byte_of(in.aa[u], 1), byte_of(in.ab[u], 0), byte_of(in.ab[u], 1));
+        aw1 = half_alpha_arith(byte_of(in.aa[u], 2), byte_of(in.aa[u], 3), byte_of(in.ab[u], 2), byte_of(in.ab[u], 3));
       }
-      const u32x2 v = half_quad(r, ya[u], yb[u], cw[u], aw0, aw1);
+      const u32x2 v = half_quad(r, in.ya[u], in.yb[u], in.cw[u], aw0, aw1);
       if (q < quads && orow_raw < out_rows) store8<NT>(o + 8 * q, v);
     }
   } else {
     const RescaleLookup r = stage_rescale_tables(lds_raw, p, 0, 0);
     __syncthreads();
+    const uint8_t *y0 = f.y + static_cast<size_t>(2 * orow) * p.y_stride;
+    const uint8_t *y1 = y0 + p.y_stride;
+    const uint8_t *cc = f.cbcr + static_cast<size_t>(orow) * p.cbcr_stride;
+    const uint8_t *a0 = HAS_ALPHA ? f.alpha + static_cast<size_t>(2 * orow) * p.alpha_stride : nullptr;
+    const uint8_t *a1 = HAS_ALPHA ? a0 + p.alpha_stride : nullptr;
     const uint32_t out_w = p.width >> 1;
     for (uint32_t ox = blockIdx.x * blockDim.x + threadIdx.x; ox < out_w && orow_raw < out_rows;
          ox += gridDim.x * blockDim.x) {
@@ -415,7 +402,6 @@ const char *launch_decode_half_rep(const DecodeParams &p_in, int frames, bool ha
 }
 
 hipError_t prepare_rescale_kernels() {
-  const int cap = static_cast<int>(kRepLdsBytes);  // gfx950: 160 KiB LDS per workgroup
   const void *fns[] = {
       reinterpret_cast<const void *>(&decode_nv12_half<true, true, false>),
       reinterpret_cast<const void *>(&decode_nv12_half<false, true, false>),
@@ -427,11 +413,8 @@ hipError_t prepare_rescale_kernels() {
       reinterpret_cast<const void *>(&decode_nv12_half_rep<true, BT709_REP_STEP, true>),
       reinterpret_cast<const void *>(&decode_nv12_half_rep<false, BT709_REP_STEP, true>),
   };
-  for (const void *fn : fns) {
-    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-    if (e != hipSuccess) return e;
-  }
-  return prepare_scaled_kernels();
+  const hipError_t e = raise_lds_cap(fns, kRepLdsBytes);
+  return e != hipSuccess ? e : prepare_scaled_kernels();
 }
 
 }  // namespace bt709

@@ -748,7 +748,6 @@ const char *launch_decode_scaled(const DecodeParams &p_in, int frames, bool has_
 }
 
 hipError_t prepare_scaled_kernels() {
-  const int cap = static_cast<int>(kRepLdsBytes);  // gfx950: 160 KiB LDS per workgroup
   const void *fns[] = {
       scaled_kernel(TAPS_BYTES, false), scaled_kernel(TAPS_PAIRS, false), scaled_kernel(TAPS_WIDE, false),
       scaled_kernel(TAPS_SHARED, false), scaled_kernel(TAPS_ONCE, false),
@@ -757,11 +756,7 @@ hipError_t prepare_scaled_kernels() {
       reinterpret_cast<const void *>(&render_scaled<true>),
       reinterpret_cast<const void *>(&render_scaled<false>),
   };
-  for (const void *fn : fns) {
-    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  return raise_lds_cap(fns, kRepLdsBytes);
 }
 
 }  // namespace bt709

@@ -31,6 +31,7 @@
 #include <cstdint>
 
 #include "bt709_device.h"
+#include "bt709_launch.h"
 
 namespace bt709 {
 namespace {
@@ -51,28 +52,14 @@ constexpr uint32_t kCandBias = kHalfCandLds - kHalfCandFloor;
 static_assert((kHalfCandFloor & 7u) == 0 && (kHalfCandLds & 15u) == 0 && kHalfCandLds - kHalfCandFloor + 0x3ff8u < 0x10000u, "candidate entries: aligned, and the offset fits the instruction");
 
 // The table image of a launch (thresholds, then candidate entries) -> LDS: the thresholds to byte 0, the entries to
-// kHalfCandLds.  Every load of a lane is issued before its first write (bt709_device.h stage_table: a round of the loop is an
-// L2 round trip inside the workgroup's lifetime), five at a time: at most 40 KiB = 2 560 sixteen-byte words, one round for a
-// 512-lane workgroup, two for 256 lanes, more for the 64-lane workgroups of very narrow frames.
+// kHalfCandLds.  Batched staging (bt709_stage.h), five loads at a time: at most 40 KiB = 2 560 sixteen-byte words, one round for
+// a 512-lane workgroup, two for 256 lanes, more for the 64-lane workgroups of very narrow frames.
 __device__ __forceinline__ void stage_half_tables(unsigned char *lds, const void *src, uint32_t cand_offset, uint32_t bytes) {
   const u32x4 *s = reinterpret_cast<const u32x4 *>(src);
   const uint32_t tid = threadIdx.y * blockDim.x + threadIdx.x, nthreads = blockDim.x * blockDim.y;
   const uint32_t n = bytes / 16, n_thresholds = cand_offset / 16, gap = (kHalfCandLds - cand_offset) / 16;
-  u32x4 *d = reinterpret_cast<u32x4 *>(lds);
-  constexpr int kBatch = 5;
-  for (uint32_t base = tid; base < n; base += nthreads * kBatch) {
-    u32x4 v[kBatch];
-#pragma unroll
-    for (int k = 0; k < kBatch; ++k) {
-      const uint32_t i = base + static_cast<uint32_t>(k) * nthreads;
-      if (i < n) v[k] = s[i];
-    }
-#pragma unroll
-    for (int k = 0; k < kBatch; ++k) {
-      const uint32_t i = base + static_cast<uint32_t>(k) * nthreads;
-      if (i < n) d[i < n_thresholds ? i : i + gap] = v[k];
-    }
-  }
+  stage_batched<5>(reinterpret_cast<u32x4 *>(lds), n, tid, nthreads, [&](uint32_t i) { return s[i]; },
+                   [&](uint32_t i) { return i < n_thresholds ? i : i + gap; });
 }
 
 // two values -> their binary16 codes in one word (v_cvt_pk_f16_f32, round to nearest even: the same conversion as
@@ -204,21 +191,20 @@ decode_nv12_rgba16f(const DecodeParams p, const HalfParams hp) {
   constexpr bool HAS_TABLE = CURVE != 0;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
 
-  // XCD-aware work map (p.xcd_bands, launches of a multiple of 8 frames): see bt709_kernels.hip decode_nv12_quads
-  const uint32_t tile = p.xcd_bands ? blockIdx.x >> 3 : blockIdx.x;
-  const FramePlanes f = frame_planes(p, p.xcd_bands ? (blockIdx.x & 7u) * p.frames_per_band + blockIdx.z : blockIdx.z);
+  const BandedWork work = banded_work(p.xcd_bands, p.frames_per_band);  // XCD-aware work map: bt709_tile.h
+  const FramePlanes f = frame_planes(p, work.frame);
   const uint32_t blocks = p.width >> 1, row_pairs = p.height >> 1;
   // blockDim.y SLICES of a workgroup share its table, each with row pairs of its own (narrow frames: a 1080p row pair keeps 240
   // lanes busy -- two slices make the 512-lane workgroup a 4K row pair gets).  blockDim.x is a multiple of 64: a wave lies in one
   // slice, its row pointers stay scalar.
   const uint32_t slice = __builtin_amdgcn_readfirstlane(threadIdx.y);
   const uint32_t rp_base = (blockIdx.y * blockDim.y + slice) * RP;
-  const uint32_t bx0 = tile * (blockDim.x * NB) + threadIdx.x;
+  const uint32_t bx0 = work.tile * (blockDim.x * NB) + threadIdx.x;
 
-  // Every load of the tile first: the bytes of a 2x2 block as loaded -- Y top | Y bottom, CbCr, alpha top | alpha bottom (two
-  // bytes each).  Lanes past the row's end and row pairs past the frame's load a clamped (valid) block; only their stores are
-  // predicated (a divergent region around the arithmetic would put a wait for the stores at its join, bt709_kernels.hip).
-  // Frame bytes are read once: non-temporal.
+  // The straight-line rule of bt709_tile.h (TileIn), in this kernel's own words: every load of the tile first -- the bytes of a
+  // 2x2 block as loaded, Y top | Y bottom, CbCr, alpha top | alpha bottom (two bytes each), clamped to a valid block -- then the
+  // table, then the pin; only the stores are predicated.  Frame bytes are read once: non-temporal.  (Over TileIn with 2-byte units
+  // hipcc re-derives a block index it keeps in a register here: +1 VALU in the NB = 4 kernels, profiles/r08_refactor_tile_isa.txt.)
   uint32_t ya[RP][NB], yb[RP][NB], cw[RP][NB], aa[RP][NB], ab[RP][NB];
 #pragma unroll
   for (int r = 0; r < RP; ++r) {
@@ -257,7 +243,6 @@ decode_nv12_rgba16f(const DecodeParams p, const HalfParams hp) {
     stage_half_tables(lds_raw, hp.table, hp.cand_offset, hp.table_bytes);
     __syncthreads();
   }
-  // pin every loaded word here: one wait for all of the tile's loads, before the first store (bt709_kernels.hip)
 #pragma unroll
   for (int r = 0; r < RP; ++r)
 #pragma unroll
@@ -306,20 +291,24 @@ decode_nv12_rgba16f(const DecodeParams p, const HalfParams hp) {
   }
 }
 
+// The 24 instantiations the launcher picks from: [shape: 0 large, 1 narrow, 2 small][curve][alpha plane][2-byte loads]
+typedef void (*F16Kernel)(DecodeParams, HalfParams);
+#define BT709_F16_AP(C, SH)                                                                                                    \
+  {{&decode_nv12_rgba16f<C, false, false, SH.nb, SH.rp>, &decode_nv12_rgba16f<C, false, true, SH.nb, SH.rp>},                  \
+   {&decode_nv12_rgba16f<C, true, false, SH.nb, SH.rp>, &decode_nv12_rgba16f<C, true, true, SH.nb, SH.rp>}}
+#define BT709_F16_SHAPE(SH) {BT709_F16_AP(0, SH), BT709_F16_AP(1, SH)}
+static const F16Kernel kF16Kernels[3][2][2][2] = {BT709_F16_SHAPE(kF16Large), BT709_F16_SHAPE(kF16Narrow), BT709_F16_SHAPE(kF16Small)};
+#undef BT709_F16_SHAPE
+#undef BT709_F16_AP
+
 const char *launch_decode_rgba16f(const DecodeParams &p_in, const HalfParams &hp_in, int frames, bool has_alpha,
                                   uint32_t in_align, uint32_t out_align, uint32_t compute_units, bool xcd_bands, hipStream_t stream) {
-  if (xcd_bands && p_in.uniform && frames > kXcdBandMinFrames && frames % 8 != 0) {
-    // any count of 64 frames or more: the XCD-aware map over the multiple of 8, the plain map over the rest (launch_decode); shorter
-    // launches take the map only when their count IS a multiple of 8 (a second launch would cost more than the map returns)
-    const int head = frames - frames % 8;
-    launch_decode_rgba16f(p_in, hp_in, head, has_alpha, in_align, out_align, compute_units, xcd_bands, stream);
+  const BandPlan plan = plan_bands(frames, xcd_bands, p_in.uniform, kF16BandMinFrames);
+  if (plan.banded && plan.tail) {
+    launch_decode_rgba16f(p_in, hp_in, plan.banded, has_alpha, in_align, out_align, compute_units, xcd_bands, stream);
     DecodeParams tail = p_in;
-    FramePlanes &f = tail.frames[0];
-    f.y += static_cast<int64_t>(head) * tail.step_y;
-    f.cbcr += static_cast<int64_t>(head) * tail.step_cbcr;
-    if (f.alpha) f.alpha += static_cast<int64_t>(head) * tail.step_alpha;
-    f.out += static_cast<int64_t>(head) * tail.step_out;
-    return launch_decode_rgba16f(tail, hp_in, frames - head, has_alpha, in_align, out_align, compute_units, false, stream);
+    advance_frames(tail, plan.banded);
+    return launch_decode_rgba16f(tail, hp_in, plan.tail, has_alpha, in_align, out_align, compute_units, false, stream);
   }
   HalfParams hp = hp_in;
   DecodeParams p = p_in;
@@ -335,7 +324,6 @@ const char *launch_decode_rgba16f(const DecodeParams &p_in, const HalfParams &hp
   const uint32_t tiles = tiles_of(sh);
   uint32_t threads = ((blocks + tiles - 1) / tiles + static_cast<uint32_t>(sh.nb) - 1) / static_cast<uint32_t>(sh.nb);
   threads = (threads + 63) / 64 * 64;
-  hp.row_pairs_per_block = static_cast<uint32_t>(sh.rp);
   hp.wide_store = out_align >= 16 ? 1 : 0;
   dim3 grid(tiles, (row_pairs + static_cast<uint32_t>(sh.rp) - 1) / static_cast<uint32_t>(sh.rp), static_cast<uint32_t>(frames));
   // slices (see the kernel), for rows that fill fewer than 256 lanes: as many as make a 512-lane workgroup, fewer while the launch
@@ -354,18 +342,9 @@ const char *launch_decode_rgba16f(const DecodeParams &p_in, const HalfParams &hp
     while (slices > 1 && static_cast<uint64_t>(tiles) * ((grid.y + slices - 1) / slices) * static_cast<uint32_t>(frames) < BT709_RGBA16F_SLICE_MIN_FILL * fill) --slices;
     grid.y = (grid.y + slices - 1) / slices;
   }
-  if (xcd_bands && frames >= kF16BandMinFrames && frames % 8 == 0) {
-    p.xcd_bands = 1;
-    p.frames_per_band = static_cast<uint32_t>(frames) / 8u;
-    grid = dim3(tiles * 8u, grid.y, p.frames_per_band);
-  }
+  if (plan.banded) grid = band_grid(p, 1, grid);
   const dim3 block(threads, slices);
-  LaunchShape &shape = last_launch_shape();
-  if (shape.launches++ == 0) {
-    shape.grid[0] = grid.x, shape.grid[1] = grid.y, shape.grid[2] = grid.z;
-    shape.block[0] = block.x, shape.block[1] = block.y, shape.block[2] = block.z;
-    shape.xcd_bands = static_cast<int32_t>(p.xcd_bands);
-  }
+  record_launch(grid, block, p.xcd_bands);
   const bool pairs = in_align >= 2;
   const int curve = hp.table_bytes == 0 ? 0 : 1;
   // thresholds from byte 0, candidate entries from kHalfCandLds (bt709_kernels.h); the host refuses a table that does not fit
@@ -373,38 +352,14 @@ const char *launch_decode_rgba16f(const DecodeParams &p_in, const HalfParams &hp
 #define BT709_RGBA16F_LDS_FLOOR 0  // lab: a larger allocation = fewer workgroups per CU (41 KiB: three instead of four)
 #endif
   const size_t lds = curve ? std::max<size_t>(kHalfCandLds + (hp.table_bytes - hp.cand_offset), BT709_RGBA16F_LDS_FLOOR) : 16;
-#define BT709_LAUNCH_RGBA16F(C, A, P)                                                                                               \
-  do {                                                                                                                              \
-    if (which == 2) hipLaunchKernelGGL((decode_nv12_rgba16f<C, A, P, kF16Small.nb, kF16Small.rp>), grid, block, lds, stream, p, hp);        \
-    else if (which == 1) hipLaunchKernelGGL((decode_nv12_rgba16f<C, A, P, kF16Narrow.nb, kF16Narrow.rp>), grid, block, lds, stream, p, hp); \
-    else hipLaunchKernelGGL((decode_nv12_rgba16f<C, A, P, kF16Large.nb, kF16Large.rp>), grid, block, lds, stream, p, hp);                  \
-  } while (0)
-#define BT709_LAUNCH_RGBA16F_AP(C)                                                            \
-  do {                                                                                        \
-    if (has_alpha) { if (pairs) BT709_LAUNCH_RGBA16F(C, true, true); else BT709_LAUNCH_RGBA16F(C, true, false); } \
-    else { if (pairs) BT709_LAUNCH_RGBA16F(C, false, true); else BT709_LAUNCH_RGBA16F(C, false, false); }         \
-  } while (0)
-  if (curve == 0) BT709_LAUNCH_RGBA16F_AP(0);
-  else BT709_LAUNCH_RGBA16F_AP(1);
-#undef BT709_LAUNCH_RGBA16F_AP
-#undef BT709_LAUNCH_RGBA16F
+  hipLaunchKernelGGL(kF16Kernels[which][curve][has_alpha][pairs], grid, block, lds, stream, p, hp);
   return has_alpha ? "decode_nv12_rgba16f<alpha>" : "decode_nv12_rgba16f";
 }
 
 hipError_t prepare_rgba16f_kernels() {
-  const int cap = 160 * 1024;
-#define BT709_F16_FNS(NB, RP)                                                                                                              \
-  reinterpret_cast<const void *>(&decode_nv12_rgba16f<0, true, true, NB, RP>), reinterpret_cast<const void *>(&decode_nv12_rgba16f<0, true, false, NB, RP>),   \
-  reinterpret_cast<const void *>(&decode_nv12_rgba16f<0, false, true, NB, RP>), reinterpret_cast<const void *>(&decode_nv12_rgba16f<0, false, false, NB, RP>), \
-  reinterpret_cast<const void *>(&decode_nv12_rgba16f<1, true, true, NB, RP>), reinterpret_cast<const void *>(&decode_nv12_rgba16f<1, true, false, NB, RP>),   \
-  reinterpret_cast<const void *>(&decode_nv12_rgba16f<1, false, true, NB, RP>), reinterpret_cast<const void *>(&decode_nv12_rgba16f<1, false, false, NB, RP>)
-  const void *fns[] = {BT709_F16_FNS(kF16Large.nb, kF16Large.rp), BT709_F16_FNS(kF16Narrow.nb, kF16Narrow.rp), BT709_F16_FNS(kF16Small.nb, kF16Small.rp)};
-#undef BT709_F16_FNS
-  for (const void *fn : fns) {
-    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  const void *fns[24];
+  for (int i = 0; i < 24; ++i) fns[i] = reinterpret_cast<const void *>((&kF16Kernels[0][0][0][0])[i]);
+  return raise_lds_cap(fns, kRepLdsBytes);
 }
 
 }  // namespace bt709

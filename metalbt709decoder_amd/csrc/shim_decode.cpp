@@ -61,16 +61,13 @@ int ensure_half_table(bt709hip_decoder *dec, void *stream) {
   HalfTable t;
   if (!build_half_table(dec->gamma, &t)) return BT709HIP_ERR_UNSUPPORTED;
   HalfParams hp = {};
-  hp.split = t.split;
-  hp.low_scale = t.low_scale;
   hp.index_scale = t.index_scale;
   hp.h_min = t.h_min;
   if (t.split <= 1.0f) {  // a curve: the table covers [h_min, H(1.0)]; its last real entry is followed by +inf
     size_t real = t.thresholds.size();
     while (real > 0 && t.thresholds[real - 1] == std::numeric_limits<float>::infinity()) --real;
-    hp.h_max = t.h_min + static_cast<uint32_t>(real) - 1;
     // device image: a guard entry below (T[h_min - 1] = 0: no x is "below" it) and two +inf above
-    // (T[h_max + 1], T[h_max + 2]), so a candidate one code off either end needs no clamp; 16-byte multiple
+    // (behind the last real entry), so a candidate one code off either end needs no clamp; 16-byte multiple
     std::vector<float> image;
     image.push_back(0.0f);
     image.insert(image.end(), t.thresholds.begin(), t.thresholds.begin() + static_cast<std::ptrdiff_t>(real));

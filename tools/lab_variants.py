@@ -47,17 +47,17 @@ LAB_SRC = os.path.join(ROOT, "tools", "bin", "lab_src")
 
 # (file, product text, lab text).  Every product text must occur exactly once.
 GATES = [
-    ("bt709_kernels.hip",
-     """      ya[r][u] = load32<NT>(y0 + 4 * q);
-      yb[r][u] = load32<NT>(y1 + 4 * q);
-      cw[r][u] = load32<NT>(cc + 4 * q);
+    ("bt709_tile.h",  # TileIn::load: the 1:1 kernel and the WIDE branch of the short-lived 2:1 kernel
+     """      ya[j] = load32<NT>(y0 + 4 * q);
+      yb[j] = load32<NT>(y1 + 4 * q);
+      cw[j] = load32<NT>(cc + 4 * q);
 """,
      """#if defined(BT709_LAB_NO_LOADS)  // with BT709_LAB_NO_ARITH: the launch's stores alone
-      ya[r][u] = q * 3u, yb[r][u] = q * 5u, cw[r][u] = q * 7u + rp;
+      ya[j] = q * 3u, yb[j] = q * 5u, cw[j] = q * 7u + rp;
 #else
-      ya[r][u] = load32<NT>(y0 + 4 * q);
-      yb[r][u] = load32<NT>(y1 + 4 * q);
-      cw[r][u] = load32<NT>(cc + 4 * q);
+      ya[j] = load32<NT>(y0 + 4 * q);
+      yb[j] = load32<NT>(y1 + 4 * q);
+      cw[j] = load32<NT>(cc + 4 * q);
 #endif
 """),
     ("bt709_kernels.hip",
@@ -74,21 +74,19 @@ GATES = [
 #endif
 """),
     ("bt709_kernels.hip",
-     """      decode_quad<HAS_ALPHA, QUANT, LOGIDX>(ul, ya[r][u], yb[r][u], cw[r][u], HAS_ALPHA ? aa[r][u] : 0u, HAS_ALPHA ? ab[r][u] : 0u, p.alpha_word, top,
-                             bot);
-      if (q < quads && rp_raw < row_pairs) {
+     """    decode_quad<HAS_ALPHA, QUANT, LOGIDX>(ul, in.ya[u], in.yb[u], in.cw[u], HAS_ALPHA ? in.aa[u] : 0u, HAS_ALPHA ? in.ab[u] : 0u, p.alpha_word, top, bot);
+    if (q < quads && rp_raw < row_pairs) {
 """,
      """#if defined(BT709_LAB_NO_ARITH)  // WRONG OUTPUT: the launch's loads and stores with (almost) no arithmetic
-      top = u32x4{ya[r][u], yb[r][u], cw[r][u], ya[r][u] ^ cw[r][u]};
-      bot = u32x4{yb[r][u], cw[r][u], ya[r][u], yb[r][u] ^ cw[r][u]};
+    top = u32x4{in.ya[u], in.yb[u], in.cw[u], in.ya[u] ^ in.cw[u]};
+    bot = u32x4{in.yb[u], in.cw[u], in.ya[u], in.yb[u] ^ in.cw[u]};
 #else
-      decode_quad<HAS_ALPHA, QUANT, LOGIDX>(ul, ya[r][u], yb[r][u], cw[r][u], HAS_ALPHA ? aa[r][u] : 0u, HAS_ALPHA ? ab[r][u] : 0u, p.alpha_word, top,
-                             bot);
+    decode_quad<HAS_ALPHA, QUANT, LOGIDX>(ul, in.ya[u], in.yb[u], in.cw[u], HAS_ALPHA ? in.aa[u] : 0u, HAS_ALPHA ? in.ab[u] : 0u, p.alpha_word, top, bot);
 #endif
 #if defined(BT709_LAB_NO_STORES)  // with BT709_LAB_NO_ARITH: the loads alone (a store about once in 2^32 quads keeps them alive)
-      if (q < quads && rp_raw < row_pairs && (top.w ^ bot.w) == 0x9e3779b9u) {
+    if (q < quads && rp_raw < row_pairs && (top.w ^ bot.w) == 0x9e3779b9u) {
 #else
-      if (q < quads && rp_raw < row_pairs) {
+    if (q < quads && rp_raw < row_pairs) {
 #endif
 """),
     ("bt709_device.h",
@@ -257,9 +255,7 @@ constexpr bool kRepUniformEncode = true;
 """),
     # CORRECT output: the table staged by LDS DMA (global_load_lds_dwordx4: L2 -> LDS without the trip through VGPRs and ds_write)
     ("bt709_rgba16f.hip",
-     """  u32x4 *d = reinterpret_cast<u32x4 *>(lds);
-  constexpr int kBatch = 5;
-  for (uint32_t base = tid; base < n; base += nthreads * kBatch) {
+     """  stage_batched<5>(reinterpret_cast<u32x4 *>(lds), n, tid, nthreads, [&](uint32_t i) { return s[i]; },
 """,
      """#if defined(BT709_LAB_F16_DMA_STAGING)
   {
@@ -274,9 +270,7 @@ constexpr bool kRepUniformEncode = true;
     return;
   }
 #endif
-  u32x4 *d = reinterpret_cast<u32x4 *>(lds);
-  constexpr int kBatch = 5;
-  for (uint32_t base = tid; base < n; base += nthreads * kBatch) {
+  stage_batched<5>(reinterpret_cast<u32x4 *>(lds), n, tid, nthreads, [&](uint32_t i) { return s[i]; },
 """),
     # the two gathers of the packed-pair form, one at a time (WRONG OUTPUT; the VALU work around them stays)
     ("bt709_rgba16f.hip",
@@ -617,13 +611,14 @@ double *lab_trace() {  // seconds: malloc, free, mem_info, warm-up, probe
       store8<NT>(o + 8 * q, v);
 """),
     # round 6: which XCD takes which band of the launch's frames (rotation / reversal of the band index): does a placement's level follow it?
-    ("bt709_kernels.hip",
-     """  const uint32_t frame = p.xcd_bands == 1 ? (blockIdx.x & 7u) * p.frames_per_band + blockIdx.z
+    # (banded_work: every kernel that uses the map, and both of its banded forms)
+    ("bt709_tile.h",
+     """  const uint32_t band = blockIdx.x & 7u;
 """,
      """#if defined(BT709_LAB_BAND_ROT)
-  const uint32_t frame = p.xcd_bands == 1 ? ((((blockIdx.x & 7u) + BT709_LAB_BAND_ROT) & 7u) ^ BT709_LAB_BAND_XOR) * p.frames_per_band + blockIdx.z
+  const uint32_t band = (((blockIdx.x & 7u) + BT709_LAB_BAND_ROT) & 7u) ^ BT709_LAB_BAND_XOR;
 #else
-  const uint32_t frame = p.xcd_bands == 1 ? (blockIdx.x & 7u) * p.frames_per_band + blockIdx.z
+  const uint32_t band = blockIdx.x & 7u;
 #endif
 """),
     # round 6: the wave-decodes-once form's exchange through a wave-private LDS tile instead of ds_bpermute (same bytes out)
