@@ -40,7 +40,7 @@ extern "C" {
 
 /* ABI version of bt709hip.h + bt709hip_ext.h together: bumped whenever a struct layout or a signature changes or an
  * export is added.  Bindings compare it with bt709hip_abi_version() and refuse an older library. */
-#define BT709HIP_VERSION 503
+#define BT709HIP_VERSION 504
 
 typedef struct bt709hip_context bt709hip_context; /* ~ MetalRenderContext */
 typedef struct bt709hip_decoder bt709hip_decoder; /* ~ MetalBT709Decoder  */
@@ -100,10 +100,14 @@ typedef struct {
 } bt709hip_frame;
 
 /* MTLPixelFormat of a render target: BGRA8Unorm_sRGB, or RGBA16Float holding LINEAR light where sRGB texture writes
- * are unavailable (Renderer/AAPLRenderer.m:143-170). */
+ * are unavailable (Renderer/AAPLRenderer.m:143-170).  BGRA8_ALPHA is an INPUT reading of bt709hip_encode[_batch] only:
+ * the texels of BGRA8_SRGB read as the grey picture (A,A,A) the reference builds before it encodes an alpha clip
+ * (srgb_to_bt709/srgb_to_bt709.m:842-954, written as <name>_alpha.y4m :1120-1183).  Every other entry point treats it
+ * as an unknown format.  The value 2 is unassigned. */
 typedef enum {
   BT709HIP_FORMAT_BGRA8_SRGB = 0, /* default: 4 bytes per pixel, gamma-encoded sRGB */
-  BT709HIP_FORMAT_RGBA16F = 1     /* 8 bytes per pixel: IEEE binary16 R,G,B,A in that memory order, linear light */
+  BT709HIP_FORMAT_RGBA16F = 1,    /* 8 bytes per pixel: IEEE binary16 R,G,B,A in that memory order, linear light */
+  BT709HIP_FORMAT_BGRA8_ALPHA = 3 /* BGRA8 texels, only A is read: encodes to the alpha frame bt709hip_decode takes */
 } bt709hip_format;
 
 /* Render target; replaces id<MTLTexture>.  BGRA8_SRGB: memory order B,G,R,A = little-endian word
@@ -208,7 +212,10 @@ int bt709hip_unconvert(bt709hip_decoder *dec, const void *ycbcr_words, size_t in
  * (BGRAToBT709Converter.h:73-76, .m:532-569) -> cvpbu_ycbcr_subsample (CVPixelBufferUtils.h:241-399) ->
  * BT709_average_pixel_values (BT709.h:1349-1509).  Gammas are bt709hip_gamma values APPLE, SRGB or LINEAR; the app
  * encodes with (SRGB, APPLE), (SRGB, SRGB) or (LINEAR, LINEAR) (.m:919-935).  `in` is read (alpha ignored), the planes
- * `out` points to are written (its tags are ignored).  Even, equal sizes on both sides. */
+ * `out` points to are written (its tags are ignored).  Even, equal sizes on both sides.
+ * in->format BGRA8_ALPHA: the ALPHA frame of `in` -- Y = the reference's luma of the grey (A,A,A), every Cb, Cr = 128.
+ * Both gammas must be LINEAR (else BT709HIP_ERR_ALPHA_TRANSFER); out->cbcr may be NULL: only Y is written then (a
+ * decoder reads nothing else of an alpha frame).  R, G, B are not read and not premultiplied (.m:805-841). */
 int bt709hip_encode(bt709hip_context *ctx, const bt709hip_surface *in, const bt709hip_frame *out, int input_gamma,
                     int output_gamma, void *stream, int wait_until_completed);
 /* The reference's on-disk 4:2:0 format is YUV4MPEG2 "C420jpeg": planar Y, U (Cb), V (Cr) per frame

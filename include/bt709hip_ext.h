@@ -135,7 +135,8 @@ int bt709hip_decoder_flush_all(bt709hip_decoder *dec);
  * - item 0) in every plane.  No reference twin (the reference converts, rescales and encodes one frame per call: a 4K frame
  * is a 12-22 us kernel, too short to fill the chip; one 4K +unconvert: per call runs at 0.58 of the roofline).  Differing sizes,
  * strides or formats: BT709HIP_ERR_SIZE_MISMATCH.  bt709hip_render_scaled_batch takes evenly spaced surfaces only
- * (BT709HIP_ERR_UNSUPPORTED otherwise). */
+ * (BT709HIP_ERR_UNSUPPORTED otherwise).  bt709hip_encode_batch with BT709HIP_FORMAT_BGRA8_ALPHA input (alpha frames, bt709hip.h):
+ * every out[i].cbcr NULL or none (else BT709HIP_ERR_INVALID_ARG); bt709hip_encoder_prepare(ctx, LINEAR, LINEAR) also builds its table. */
 int bt709hip_unconvert_batch(bt709hip_decoder *dec, int count, const void *const *ycbcr_words, size_t in_stride, int width, int height,
                              const bt709hip_surface *outs, void *stream, int wait_until_completed);
 int bt709hip_decode_half_batch(bt709hip_decoder *dec, int count, const bt709hip_frame *frames, const bt709hip_frame *alphas,

@@ -24,11 +24,12 @@ class Surface(C.Structure):  # bt709hip_surface
                 ("format", C.c_int32), ("reserved", C.c_int32)]
 
 
-ABI_VERSION = 503  # BT709HIP_VERSION of the two headers these bindings were written against
+ABI_VERSION = 504  # BT709HIP_VERSION of the two headers these bindings were written against
 
 # bt709hip_format
 FORMAT_BGRA8_SRGB = 0
 FORMAT_RGBA16F = 1
+FORMAT_BGRA8_ALPHA = 3  # input of bt709hip_encode[_batch] only: BGRA8 texels read as the grey picture (A,A,A); 2 is unassigned
 
 # bt709hip_decoder_option / bt709hip_context_option
 OPT_NONTEMPORAL = 1

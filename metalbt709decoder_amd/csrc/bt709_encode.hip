@@ -276,6 +276,100 @@ encode_bgra_nv12_blocks(const EncodeParams p) {
   }
 }
 
+// ---------------------------------------------------------------- alpha frames (BT709HIP_FORMAT_BGRA8_ALPHA)
+// The reference's alpha clip is the ordinary encode of the grey picture (A,A,A) under (Linear, Linear)
+// (srgb_to_bt709/srgb_to_bt709.m:842-954), which is Y = T[A] per pixel and Cb = Cr = 128 (bt709_alpha_luma.h).  Same tile
+// shape, work map, prefetch and clamps as encode_bgra_nv12; the arithmetic is one byte lookup per pixel.
+// TABLE, not arithmetic: the float expression costs a conversion, four multiplies, three adds and a converting pack per pixel
+// (9 VALU, 4 of them 4-cycle); the lookup is a shift, a ds_read_u8 and a share of three v_perm/v_lshl_or per word.  The 256
+// bytes are 64 dwords = one per LDS bank: lanes that hit the same dword broadcast, different dwords never conflict.
+namespace {
+
+typedef __attribute__((address_space(3))) const uint8_t *LdsBytePtr;
+
+__device__ __forceinline__ void stage_alpha_luma(uint32_t *lut, const EncodeParams &p) {
+  if (threadIdx.x < 64) lut[threadIdx.x] = p.alpha_luma[threadIdx.x];  // every workgroup has at least one wave
+}
+
+// T[byte 3] of four BGRA words, packed in memory order
+__device__ __forceinline__ uint32_t alpha_luma4(const uint32_t *lut, const u32x4 w) {
+  const uint8_t *t = reinterpret_cast<const uint8_t *>(lut);
+  return static_cast<uint32_t>(t[w.x >> 24]) | (static_cast<uint32_t>(t[w.y >> 24]) << 8) |
+         (static_cast<uint32_t>(t[w.z >> 24]) << 16) | (static_cast<uint32_t>(t[w.w >> 24]) << 24);
+}
+
+}  // namespace
+
+// grid = (tiles, row-pair groups, frames), as encode_bgra_nv12
+__global__ void __launch_bounds__(kMaxBlockThreads)
+encode_alpha_y(const EncodeParams p) {
+  __shared__ uint32_t lut[64];
+  const BandedWork work = banded_work(p.xcd_bands, p.frames_per_band);
+  const EncodeFrame f = encode_frame(p, work.frame);
+  const uint32_t quads = p.width >> 2;
+  const uint32_t row_pairs = p.height >> 1;
+  const uint32_t q_raw = work.tile * blockDim.x + threadIdx.x;
+  const uint32_t q = min(q_raw, quads - 1);
+  const uint32_t rp0 = blockIdx.y * p.row_pairs_per_block;
+  const uint32_t rp_end = min(rp0 + p.row_pairs_per_block, row_pairs);
+  const bool with_cbcr = p.frames[0].cbcr != nullptr;  // uniform over the launch
+
+  const uint8_t *s0 = f.bgra + static_cast<size_t>(2 * rp0) * p.bgra_stride;
+  u32x4 top = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(s0 + 16u * q));
+  u32x4 bot = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(s0 + p.bgra_stride + 16u * q));
+
+  stage_alpha_luma(lut, p);  // after the first loads are in flight
+  __syncthreads();
+
+  for (uint32_t rp = rp0; rp < rp_end; ++rp) {
+    u32x4 ntop = top, nbot = bot;
+    if (rp + 1 < rp_end) {  // nothing on the workgroup's last pair, as encode_bgra_nv12
+      const uint8_t *s1 = f.bgra + static_cast<size_t>(2 * (rp + 1)) * p.bgra_stride;
+      ntop = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(s1 + 16u * q));
+      nbot = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(s1 + p.bgra_stride + 16u * q));
+    }
+    const uint32_t ytop = alpha_luma4(lut, top), ybot = alpha_luma4(lut, bot);
+    if (q_raw < quads) {
+      uint8_t *y0 = f.y + static_cast<size_t>(2 * rp) * p.y_stride;
+      __builtin_nontemporal_store(ytop, reinterpret_cast<uint32_t *>(y0 + 4u * q));
+      __builtin_nontemporal_store(ybot, reinterpret_cast<uint32_t *>(y0 + p.y_stride + 4u * q));
+      if (with_cbcr)
+        __builtin_nontemporal_store(
+            0x80808080u, reinterpret_cast<uint32_t *>(f.cbcr + static_cast<size_t>(rp) * p.cbcr_stride + 4u * q));
+    }
+    top = ntop;
+    bot = nbot;
+  }
+}
+
+// General layout: one lane per 2x2 block, byte loads of the four A's and byte stores, any alignment.
+__global__ void __launch_bounds__(kBlockThreads)
+encode_alpha_y_blocks(const EncodeParams p) {
+  __shared__ uint32_t lut[64];
+  stage_alpha_luma(lut, p);
+  __syncthreads();
+  const uint8_t *t = reinterpret_cast<const uint8_t *>(lut);
+  const EncodeFrame f = encode_frame(p, blockIdx.z);
+  const bool with_cbcr = p.frames[0].cbcr != nullptr;
+  const uint32_t bw = p.width >> 1;
+  const uint32_t rp = blockIdx.y;
+  for (uint32_t bx = blockIdx.x * blockDim.x + threadIdx.x; bx < bw; bx += gridDim.x * blockDim.x) {
+    const uint8_t *r0 = f.bgra + static_cast<size_t>(2 * rp) * p.bgra_stride + 8u * bx;
+    const uint8_t *r1 = r0 + p.bgra_stride;
+    uint8_t *y0 = f.y + static_cast<size_t>(2 * rp) * p.y_stride + 2u * bx;
+    uint8_t *y1 = y0 + p.y_stride;
+    y0[0] = t[r0[3]];
+    y0[1] = t[r0[7]];
+    y1[0] = t[r1[3]];
+    y1[1] = t[r1[7]];
+    if (with_cbcr) {
+      uint8_t *c = f.cbcr + static_cast<size_t>(rp) * p.cbcr_stride + 2u * bx;
+      c[0] = 128;
+      c[1] = 128;
+    }
+  }
+}
+
 const char *launch_encode(const EncodeParams &params, int frames, bool fast, bool xcd_bands, hipStream_t stream) {
   const BandPlan plan = plan_bands(frames, fast && xcd_bands, params.uniform, kXcdBandMinFrames);
   if (plan.banded && plan.tail) {
@@ -286,7 +380,8 @@ const char *launch_encode(const EncodeParams &params, int frames, bool fast, boo
   }
   EncodeParams p = params;
   if (p.row_pairs_per_block == 0) p.row_pairs_per_block = encode_row_pairs_per_block(p.width, p.height, frames);
-  const size_t lds = 256 * sizeof(EncodeByteEntry) + p.from_linear_bytes;
+  const bool alpha = p.alpha_luma != nullptr;  // BT709HIP_FORMAT_BGRA8_ALPHA: same plan, the alpha kernels (static LDS)
+  const size_t lds = alpha ? 0 : 256 * sizeof(EncodeByteEntry) + p.from_linear_bytes;
   if (fast) {
     const uint32_t quads = p.width / 4;
     uint32_t threads = p.block_threads ? p.block_threads : encode_block_threads(p.width);
@@ -303,11 +398,19 @@ const char *launch_encode(const EncodeParams &params, int frames, bool fast, boo
               (p.height / 2 + p.row_pairs_per_block - 1) / p.row_pairs_per_block, frames);
     if (plan.banded) grid = band_grid(p, 1, grid);
     record_launch(grid, dim3(threads), p.xcd_bands);
+    if (alpha) {
+      hipLaunchKernelGGL(encode_alpha_y, grid, dim3(threads), lds, stream, p);
+      return "encode_alpha_y";
+    }
     hipLaunchKernelGGL(encode_bgra_nv12, grid, dim3(threads), lds, stream, p);
     return "encode_bgra_nv12";
   }
   const dim3 grid((p.width / 2 + kBlockThreads - 1) / kBlockThreads, p.height / 2, frames);
   record_launch(grid, dim3(kBlockThreads), 0);
+  if (alpha) {
+    hipLaunchKernelGGL(encode_alpha_y_blocks, grid, dim3(kBlockThreads), lds, stream, p);
+    return "encode_alpha_y_blocks";
+  }
   hipLaunchKernelGGL(encode_bgra_nv12_blocks, grid, dim3(kBlockThreads), lds, stream, p);
   return "encode_bgra_nv12_blocks";
 }

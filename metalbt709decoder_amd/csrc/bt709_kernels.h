@@ -145,7 +145,7 @@ const char *launch_render_scaled(const RenderParams &p, int frames, bool in_rgba
 struct EncodeFrame {
   const uint8_t *bgra;  // W x H words (A<<24)|(R<<16)|(G<<8)|B, alpha ignored
   uint8_t *y;
-  uint8_t *cbcr;
+  uint8_t *cbcr;        // alpha kernels: nullptr in EVERY frame of the launch = write no CbCr plane
 };
 struct EncodeParams {
   EncodeFrame frames[kMaxBatch];
@@ -164,6 +164,9 @@ struct EncodeParams {
   uint32_t width, height;
   uint32_t bgra_stride, y_stride, cbcr_stride;
   uint32_t xcd_bands, frames_per_band;  // XCD-aware work map, as in DecodeParams (filled by launch_encode)
+  // BT709HIP_FORMAT_BGRA8_ALPHA: non-null selects the alpha kernels (encode_alpha_y / encode_alpha_y_blocks): 256 bytes
+  // T[A], four per word (bt709_alpha_luma.h); per_byte / from_linear* are not read then
+  const uint32_t *alpha_luma;
 };
 const char *launch_encode(const EncodeParams &p, int frames, bool fast, bool xcd_bands, hipStream_t stream);
 hipError_t prepare_encode_kernels();

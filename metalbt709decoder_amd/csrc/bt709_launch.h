@@ -42,7 +42,7 @@ inline void advance_frames(DecodeParams &p, int head) {
 inline void advance_frames(EncodeParams &p, int head) {
   p.frames[0].bgra += static_cast<int64_t>(head) * p.step_bgra;
   p.frames[0].y += static_cast<int64_t>(head) * p.step_y;
-  p.frames[0].cbcr += static_cast<int64_t>(head) * p.step_cbcr;
+  if (p.frames[0].cbcr) p.frames[0].cbcr += static_cast<int64_t>(head) * p.step_cbcr;  // alpha frames may have none
 }
 
 // the plan of the call's FIRST launch, for bt709hip_last_launch_info

@@ -4,6 +4,8 @@
 // of the reference's Y4M files (Renderer/y4m_writer.h:194-241).
 #include "shim_internal.h"
 
+#include "bt709_alpha_luma.h"
+
 namespace bt709shim __attribute__((visibility("hidden"))) {
 
 // Builds (once) the device tables of one (input gamma, output gamma) encoder pair.  Both uploads go
@@ -34,6 +36,19 @@ int encoder_tables(bt709hip_context *ctx, int input_gamma, int output_gamma, hip
   t.d_from_linear = d_fl;
   t.d_per_byte = d_pb;  // the "built" marker: last
   return BT709HIP_OK;
+}
+
+// Builds (once) the device copy of T[A], the luma table of BGRA8_ALPHA input (bt709_alpha_luma.h), from the product's own
+// (Linear, Linear) per-byte table.  Same rules as encoder_tables: refused while `s` records a graph.
+int alpha_luma_table(bt709hip_context *ctx, hipStream_t s) {
+  std::lock_guard<std::mutex> lock(ctx->encoder_mutex);
+  if (ctx->d_alpha_luma != nullptr) return BT709HIP_OK;
+  if (capturing(s)) return BT709HIP_ERR_NOT_SETUP;
+  EncodeTables host;
+  if (!build_encode_tables(kGammaLinear, kGammaLinear, &host)) return BT709HIP_ERR_UNSUPPORTED;
+  alignas(4) uint8_t luma[256];
+  build_alpha_luma(host.per_byte, luma);
+  return upload_table(luma, sizeof luma, &ctx->d_alpha_luma);
 }
 
 }  // namespace bt709shim
@@ -216,8 +231,12 @@ int bt709hip_encode_batch(bt709hip_context *ctx, int count, const bt709hip_surfa
   if (count == 0) return BT709HIP_OK;
   const bt709hip_surface &in0 = ins[0];
   const bt709hip_frame &out0 = outs[0];
+  // BGRA8_ALPHA: the texels read as the grey picture (A,A,A) of the reference's alpha clip; only its Y plane is ever decoded,
+  // so cbcr may be NULL -- in every frame of the call or in none -- and cbcr_stride is not looked at then
+  const bool alpha = in0.format == BT709HIP_FORMAT_BGRA8_ALPHA;
+  const bool no_cbcr = alpha && out0.cbcr == nullptr;
   bool uniform = count > 1;
-  bool fast = (in0.width % 4) == 0 && (in0.stride % 16) == 0 && (out0.y_stride % 4) == 0 && (out0.cbcr_stride % 4) == 0;
+  bool fast = (in0.width % 4) == 0 && (in0.stride % 16) == 0 && (out0.y_stride % 4) == 0 && (no_cbcr || (out0.cbcr_stride % 4) == 0);
   EncodeParams p;
   std::memset(&p, 0, sizeof p);
   for (int i = 0; i < count; ++i) {
@@ -227,16 +246,19 @@ int bt709hip_encode_batch(bt709hip_context *ctx, int count, const bt709hip_surfa
     if (in.width != out.width || in.height != out.height) return BT709HIP_ERR_SIZE_MISMATCH;
     if ((in.width & 1) || (in.height & 1)) return BT709HIP_ERR_ODD_DIMENSIONS;  // BGRAToBT709Converter.m:540-541
     if (in.height / 2 > kMaxGridYZ) return BT709HIP_ERR_UNSUPPORTED;            // row pairs live in gridDim.y
-    if (in.format != BT709HIP_FORMAT_BGRA8_SRGB || in.reserved != 0) return BT709HIP_ERR_UNSUPPORTED;
-    if (in.width != in0.width || in.height != in0.height || in.stride != in0.stride || out.y_stride != out0.y_stride ||
-        out.cbcr_stride != out0.cbcr_stride)
+    if ((in.format != BT709HIP_FORMAT_BGRA8_SRGB && in.format != BT709HIP_FORMAT_BGRA8_ALPHA) || in.reserved != 0)
+      return BT709HIP_ERR_UNSUPPORTED;
+    if (in.width != in0.width || in.height != in0.height || in.stride != in0.stride || in.format != in0.format ||
+        out.y_stride != out0.y_stride || (!(alpha && (no_cbcr || out.cbcr == nullptr)) && out.cbcr_stride != out0.cbcr_stride))
       return BT709HIP_ERR_SIZE_MISMATCH;
+    // the reference forces an alpha clip's gamma to linear (srgb_to_bt709.m:842-954); anything else is "alpha is not linear"
+    if (alpha && (input_gamma != BT709HIP_GAMMA_LINEAR || output_gamma != BT709HIP_GAMMA_LINEAR)) return BT709HIP_ERR_ALPHA_TRANSFER;
     if (in.width == 0 || in.height == 0) continue;
-    if (in.bgra == nullptr || out.y == nullptr || out.cbcr == nullptr) return BT709HIP_ERR_INVALID_ARG;
+    if (in.bgra == nullptr || out.y == nullptr || (out.cbcr == nullptr) != no_cbcr) return BT709HIP_ERR_INVALID_ARG;
     const size_t w = static_cast<size_t>(in.width);
-    if (in.stride < 4 * w || (in.stride & 3) || !aligned(in.bgra, 4) || out.y_stride < w || out.cbcr_stride < w)
+    if (in.stride < 4 * w || (in.stride & 3) || !aligned(in.bgra, 4) || out.y_stride < w || (!no_cbcr && out.cbcr_stride < w))
       return BT709HIP_ERR_STRIDE;
-    if (in.stride > 0xffffffffu || out.y_stride > 0xffffffffu || out.cbcr_stride > 0xffffffffu) return BT709HIP_ERR_STRIDE;
+    if (in.stride > 0xffffffffu || out.y_stride > 0xffffffffu || (!no_cbcr && out.cbcr_stride > 0xffffffffu)) return BT709HIP_ERR_STRIDE;
     fast = fast && aligned(in.bgra, 16) && aligned(out.y, 4) && aligned(out.cbcr, 4);
     if (i >= 2)
       uniform = uniform && byte_step(ins[0].bgra, in.bgra) == byte_step(ins[0].bgra, ins[1].bgra) * i &&
@@ -254,8 +276,20 @@ int bt709hip_encode_batch(bt709hip_context *ctx, int count, const bt709hip_surfa
   FLUSH_STREAM(ctx, stream);
 
   hipStream_t s = pick(ctx, stream);
-  EncoderTables &t = ctx->encoders[input_gamma][output_gamma];
-  if (int rc = encoder_tables(ctx, input_gamma, output_gamma, s)) return rc;
+  if (alpha) {
+    if (int rc = alpha_luma_table(ctx, s)) return rc;
+    p.alpha_luma = static_cast<const uint32_t *>(ctx->d_alpha_luma);
+  } else {
+    EncoderTables &t = ctx->encoders[input_gamma][output_gamma];
+    if (int rc = encoder_tables(ctx, input_gamma, output_gamma, s)) return rc;
+    p.per_byte = static_cast<const EncodeByteEntry *>(t.d_per_byte);
+    p.from_linear = static_cast<const TransferBucket *>(t.d_from_linear);
+    p.from_linear_bytes = t.from_linear_bytes;
+    p.from_linear_scale = static_cast<float>(t.from_linear_n);
+    p.from_linear_split = t.split;
+    p.from_linear_coarse = t.coarse_scale;
+    p.from_linear_offset = t.coarse_offset;
+  }
 
   if (uniform) {
     p.uniform = 1;
@@ -263,20 +297,13 @@ int bt709hip_encode_batch(bt709hip_context *ctx, int count, const bt709hip_surfa
     p.step_y = byte_step(outs[0].y, outs[1].y);
     p.step_cbcr = byte_step(outs[0].cbcr, outs[1].cbcr);
   }
-  p.per_byte = static_cast<const EncodeByteEntry *>(t.d_per_byte);
-  p.from_linear = static_cast<const TransferBucket *>(t.d_from_linear);
-  p.from_linear_bytes = t.from_linear_bytes;
-  p.from_linear_scale = static_cast<float>(t.from_linear_n);
-  p.from_linear_split = t.split;
-  p.from_linear_coarse = t.coarse_scale;
-  p.from_linear_offset = t.coarse_offset;
   p.row_pairs_per_block = static_cast<uint32_t>(ctx->encode_row_pairs);  // 0: sized per launch
   p.block_threads = static_cast<uint32_t>(ctx->encode_threads);
   p.width = static_cast<uint32_t>(in0.width);
   p.height = static_cast<uint32_t>(in0.height);
   p.bgra_stride = static_cast<uint32_t>(in0.stride);
   p.y_stride = static_cast<uint32_t>(out0.y_stride);
-  p.cbcr_stride = static_cast<uint32_t>(out0.cbcr_stride);
+  p.cbcr_stride = no_cbcr ? 0u : static_cast<uint32_t>(out0.cbcr_stride);
   last_launch_shape() = LaunchShape{};
   set_kernel_name(launch_encode(p, count, fast, ctx->xcd_bands != 0, s));
   HIP_TRY(hipGetLastError());
@@ -288,6 +315,8 @@ int bt709hip_encoder_prepare(bt709hip_context *ctx, int input_gamma, int output_
   if (ctx == nullptr) return BT709HIP_ERR_INVALID_ARG;
   if (input_gamma < 0 || input_gamma > 2 || output_gamma < 0 || output_gamma > 2) return BT709HIP_ERR_INVALID_ARG;
   if (int rc = bind(ctx)) return rc;
+  if (input_gamma == BT709HIP_GAMMA_LINEAR && output_gamma == BT709HIP_GAMMA_LINEAR)  // the one pair BGRA8_ALPHA input encodes with
+    if (int rc = alpha_luma_table(ctx, nullptr)) return rc;
   return encoder_tables(ctx, input_gamma, output_gamma, nullptr);
 }
 

@@ -151,6 +151,7 @@ int bt709hip_context_destroy(bt709hip_context *ctx) {
         if (t.d_per_byte) (void)hipFree(t.d_per_byte);
         if (t.d_from_linear) (void)hipFree(t.d_from_linear);
       }
+    if (ctx->d_alpha_luma) (void)hipFree(ctx->d_alpha_luma);
     if (ctx->d_render_encode) (void)hipFree(ctx->d_render_encode);
     if (ctx->d_render_lin) (void)hipFree(ctx->d_render_lin);
   }

@@ -42,6 +42,7 @@ struct bt709hip_context {
   int streaming_tries = 4;                       // BT709HIP_CTX_OPT_STREAMING_TRIES: placement candidates for buffers of 256 MB and more that the library allocates itself
   std::mutex encoder_mutex;
   EncoderTables encoders[3][3];  // [input gamma][output gamma], built on first use
+  void *d_alpha_luma = nullptr;  // T[256] of BGRA8_ALPHA input (bt709_alpha_luma.h), built on first use under encoder_mutex
   // bt709hip_render_scaled (pass 2 alone): built on first use under encoder_mutex
   void *d_render_encode = nullptr, *d_render_lin = nullptr;
   uint32_t render_encode_bytes = 0, render_encode_log_first = 0;
@@ -175,6 +176,7 @@ int decode_batch_now(bt709hip_decoder *dec, int count, const bt709hip_frame *fra
 
 // shim_convert.cpp
 int encoder_tables(bt709hip_context *ctx, int input_gamma, int output_gamma, hipStream_t s);
+int alpha_luma_table(bt709hip_context *ctx, hipStream_t s);
 
 // shim_coalesce.cpp (BT709HIP_OPT_COALESCE)
 int issue_queue(bt709hip_decoder *dec, PendingQueue &q);

@@ -438,6 +438,8 @@ class CVPixelBuffer:
     attachments -processBT709ToSRGB: validates (MetalBT709Decoder.m:311-368)."""
 
     def __init__(self, ctx, width, height, y_stride=None, cbcr_stride=None, planes=None):
+        """planes: (y, cbcr) device pointers somebody else owns; cbcr may be None for an ALPHA buffer (a decoder reads only
+        the Y plane of one, and convertAlphaIntoCoreVideoBuffer then writes only that)."""
         self.ctx, self.width, self.height = ctx, int(width), int(height)
         self.y_stride = int(y_stride) if y_stride else _align_up(self.width, 16)
         self.cbcr_stride = int(cbcr_stride) if cbcr_stride else _align_up(self.width, 16)
@@ -472,16 +474,18 @@ class CVPixelBuffer:
         self.ctx._sync(commandBuffer)
 
     def download_planes(self, commandBuffer=None):
-        """Tight (H, W) luma and (H/2, W) interleaved CbCr arrays read back from the device."""
+        """Tight (H, W) luma and (H/2, W) interleaved CbCr arrays read back from the device (CbCr None for an alpha buffer
+        made without that plane)."""
         y = np.empty((self.height, self.width), dtype=np.uint8)
-        c = np.empty((self.height // 2, self.width), dtype=np.uint8)
+        c = np.empty((self.height // 2, self.width), dtype=np.uint8) if self.cbcr_ptr else None
         if self.width and self.height:
             stream = commandBuffer.stream if commandBuffer else None
             lib, h = self.ctx.lib, self.ctx.handle
             _capi.check(lib.bt709hip_download(h, y.ctypes.data, self.width, self.y_ptr, self.y_stride, self.width,
                                               self.height, stream), "download Y")
-            _capi.check(lib.bt709hip_download(h, c.ctypes.data, self.width, self.cbcr_ptr, self.cbcr_stride,
-                                              self.width, self.height // 2, stream), "download CbCr")
+            if c is not None:
+                _capi.check(lib.bt709hip_download(h, c.ctypes.data, self.width, self.cbcr_ptr, self.cbcr_stride,
+                                                  self.width, self.height // 2, stream), "download CbCr")
             self.ctx._sync(commandBuffer)
         return y, c
 
@@ -670,6 +674,47 @@ class BGRAToBT709Converter:
         if rc != _capi.OK:
             log.error("convertIntoCoreVideoBuffers: %s", _capi.strerror(rc))
             return False
+        return True
+
+    @staticmethod
+    def setAlphaAttributes(buf):
+        """The tags -decodeBT709:alphaPixelBuffer: asks of an alpha buffer (MetalBT709Decoder.m:357-368)."""
+        buf.setAttachment("YCbCrMatrix", kCVImageBufferYCbCrMatrix_ITU_R_709_2)
+        buf.setAttachment("TransferFunction", kCVImageBufferTransferFunction_Linear)
+        return True
+
+    @staticmethod
+    def convertAlphaIntoCoreVideoBuffer(bgraTexture, cvPixelBuffer, commandBuffer=None, waitUntilCompleted=True):
+        """The ALPHA frame of a BGRA8 texture, on the GPU: what `srgb_to_bt709 -alpha` makes by copying each pixel's A over
+        R, G and B, forcing the gamma to linear and encoding (srgb_to_bt709/srgb_to_bt709.m:842-954) -- Y = the luma of the
+        grey (A,A,A), every Cb, Cr = 128 (not written when the buffer was made with planes=(y, None)).  R, G, B are not
+        read and not premultiplied.  The buffer leaves tagged ITU_R_709_2 / Linear, i.e. accepted as alphaPixelBuffer."""
+        return BGRAToBT709Converter.convertAlphaIntoCoreVideoBuffers([bgraTexture], [cvPixelBuffer], commandBuffer, waitUntilCompleted)
+
+    @staticmethod
+    def convertAlphaIntoCoreVideoBuffers(bgraTextures, cvPixelBuffers, commandBuffer=None, waitUntilCompleted=True):
+        """`count` same-sized alpha frames in one launch (bt709hip_encode_batch with BT709HIP_FORMAT_BGRA8_ALPHA input)."""
+        n = len(bgraTextures)
+        if n != len(cvPixelBuffers):
+            raise ValueError("one output buffer per input texture")
+        if n == 0:
+            return True
+        ctx = bgraTextures[0].ctx
+        surfs = (Surface * n)(*[t.surface() for t in bgraTextures])
+        for s in surfs:
+            if s.format != _capi.FORMAT_BGRA8_SRGB:
+                log.error("convertAlphaIntoCoreVideoBuffers: the source must be a BGRA8 texture")
+                return False
+            s.format = _capi.FORMAT_BGRA8_ALPHA
+        frames = (Frame * n)(*[b.frame() for b in cvPixelBuffers])
+        stream = commandBuffer.stream if commandBuffer is not None else None
+        rc = ctx.lib.bt709hip_encode_batch(ctx.handle, n, surfs, frames, MetalBT709GammaLinear, MetalBT709GammaLinear, stream,
+                                           int(bool(waitUntilCompleted)))
+        if rc != _capi.OK:
+            log.error("convertAlphaIntoCoreVideoBuffers: %s", _capi.strerror(rc))
+            return False
+        for b in cvPixelBuffers:
+            BGRAToBT709Converter.setAlphaAttributes(b)
         return True
 
     @staticmethod

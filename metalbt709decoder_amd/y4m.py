@@ -8,6 +8,10 @@ Format written by the reference (Renderer/y4m_writer.h):
     frame   "FRAME\\n" + Y (w*h bytes) + U (w/2*h/2) + V (w/2*h/2)    (:194-241)
 fps choices are those of Y4MHeaderFPS (:22-30).
 
+An ALPHA clip is the same container (srgb_to_bt709/srgb_to_bt709.m:1120-1183 writes it as <name>_alpha.y4m): its frames
+are what BGRAToBT709Converter.convertAlphaIntoCoreVideoBuffer leaves in a buffer that HAS a CbCr plane (Y = the luma of the
+grey (A,A,A), every U and V byte 128), and write_pixel_buffer writes them like any other frame.
+
 The writer reproduces those bytes exactly; the reader also accepts files without the XYSCSS
 line and with other header tags (as long as the chroma tag is a 4:2:0 one).
 """
