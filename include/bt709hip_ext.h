@@ -336,7 +336,9 @@ int bt709hip_half_thresholds(int gamma, float *thresholds, int capacity);
 int bt709hip_half_lookup(int gamma, float x, int candidate_offset, int *table_entries);
 /* Name of the kernel the last decode on this thread launched (for profiling). */
 const char *bt709hip_last_kernel_name(void);
-/* Launch shape of the last decode or encode this thread issued -- bt709hip_decode / _decode_batch (1:1, BGRA8 or RGBA16F target) or
+/* Launch shape of the last decode or encode this thread issued -- bt709hip_decode / _decode_batch (1:1, BGRA8 or RGBA16F target),
+ * bt709hip_decode_half / _decode_half_batch (the short-lived 2:1 kernel: grid = tiles, groups of output rows, frames; the persistent one:
+ * grid = (workgroups, 1, 1), block = the lanes of a tile row; launches 1, xcd_bands 0) or
  * bt709hip_encode / _encode_batch (grid = tiles [x 8 under the XCD-aware map], row-pair groups, pictures [per band]): grid and block of its
  * first kernel launch, the number of launches it took (2: the XCD-aware map over a multiple of 8 frames plus the plain map
  * over the rest) and the work map of the first (bt709hip_decoder_option BT709HIP_OPT_XCD_BANDS value actually used; 0 plain). */

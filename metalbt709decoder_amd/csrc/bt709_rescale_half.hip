@@ -351,6 +351,7 @@ const char *launch_decode_half(const DecodeParams &p, int frames, bool wide, boo
   const dim3 grid(grid_x, (p.height / 2 + by - 1) / by, static_cast<uint32_t>(frames));
   const dim3 block(block_threads, by, 1);
   const size_t lds = static_cast<size_t>(p.table_linear_bytes) + p.table_encode_bytes;
+  record_launch(grid, block, 0);
   if (has_alpha) {
     if (wide) hipLaunchKernelGGL((decode_nv12_half<true, true, true>), grid, block, lds, stream, p);
     else hipLaunchKernelGGL((decode_nv12_half<false, false, true>), grid, block, lds, stream, p);
@@ -389,6 +390,7 @@ const char *launch_decode_half_rep(const DecodeParams &p_in, int frames, bool ha
   p.cursor_rp = (workgroups / p.tiles_x) % row_pairs;
   p.cursor_f = (workgroups / p.tiles_x) / row_pairs;
   const size_t lds = (static_cast<size_t>(p.table_linear_bytes) << r1) + (static_cast<size_t>(enc_bytes) << r2);
+  record_launch(dim3(workgroups), dim3(threads), 0);
   if (has_alpha) {
     if (nontemporal) hipLaunchKernelGGL((decode_nv12_half_rep<true, BT709_REP_STEP, true>), dim3(workgroups), dim3(threads), lds, stream, p);
     else hipLaunchKernelGGL((decode_nv12_half_rep<false, BT709_REP_STEP, true>), dim3(workgroups), dim3(threads), lds, stream, p);

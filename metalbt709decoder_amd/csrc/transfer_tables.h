@@ -134,9 +134,10 @@ bool build_split_table(int kind, SplitTable *out);
 bool build_transfer_table(int gamma, TransferTable *out);
 
 // Uniform bucket table with ANY bucket count n (not a power of two): the smallest n that still keeps
-// one threshold per bucket.  The sRGB-encode composite needs n >= 3296 only because its thresholds
-// are 1/(255 * 12.92) apart near zero; a power of two would cost 4096 buckets = 33 KiB, n = 33xx costs
-// 26 KiB, and the index is ONE fma instead of the two-resolution table's convert + shift + add + min:
+// one threshold per bucket.  The sRGB-encode composite's thresholds are 1/(255 * 12.92) = 1/3295 apart near zero,
+// but only the ten of the curve's linear piece are, and a rounding index files those apart from n = 3008 on (24 KiB;
+// tests/rescale_arith_cases.py replays the rule): a power of two would cost 4096 buckets = 33 KiB,
+// and the index is ONE fma instead of the two-resolution table's convert + shift + add + min:
 //     q = bits(fma(v, n, 2^23)) - bits(2^23) = round(v n);  byte = buckets[q].base + (v >= buckets[q].edge)
 // (edge is the threshold itself, in v units: the rounding only moves bucket boundaries, which the builder
 // replays exactly, never the comparison).  n + 2 buckets (q <= n, one spare), padded to 16 bytes.

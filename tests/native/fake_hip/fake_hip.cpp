@@ -546,10 +546,21 @@ const char *launch_unconvert(const DecodeParams &, const UnconvertBatch &b, size
                              hipStream_t stream) {
   return launch(stream, "unconvert_packed444", b.count, b.in[0], b.out[0], 8.0 * width * height * b.count);
 }
-const char *launch_decode_half(const DecodeParams &p, int frames, bool, bool, bool, uint32_t, uint32_t, hipStream_t stream) {
+// the two 2:1 launchers record a plausible plan: one workgroup per tile and output row / the persistent grid
+static void fill_half_record(uint32_t gx, uint32_t gy, uint32_t gz, uint32_t threads) {
+  LaunchShape &shape = last_launch_shape();
+  if (shape.launches++ == 0) {
+    shape.grid[0] = gx, shape.grid[1] = gy, shape.grid[2] = gz;
+    shape.block[0] = threads, shape.block[1] = shape.block[2] = 1;
+    shape.xcd_bands = 0;
+  }
+}
+const char *launch_decode_half(const DecodeParams &p, int frames, bool, bool, bool, uint32_t grid_x, uint32_t block_threads, hipStream_t stream) {
+  fill_half_record(grid_x, p.height / 2, static_cast<uint32_t>(frames), block_threads);
   return launch(stream, "decode_nv12_half", frames, p.frames[0].y, p.frames[0].out, frames * frame_bytes(p, 4.0));
 }
-const char *launch_decode_half_rep(const DecodeParams &p, int frames, bool, bool, uint32_t, uint32_t, hipStream_t stream) {
+const char *launch_decode_half_rep(const DecodeParams &p, int frames, bool, bool, uint32_t workgroups, uint32_t, hipStream_t stream) {
+  fill_half_record(workgroups ? workgroups : 1, 1, 1, kRepBlockThreads);
   return launch(stream, "decode_nv12_half_rep", frames, p.frames[0].y, p.frames[0].out, frames * frame_bytes(p, 4.0));
 }
 // the two rescale launchers fill a plausible record: one 256-lane workgroup per column tile, strip of 4 rows and frame
