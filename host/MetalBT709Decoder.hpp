@@ -383,6 +383,18 @@ class MetalBT709Decoder {
     return rc == BT709HIP_OK ? ok() : fail(rc);
   }
 
+  // The format of the intermediate decodeBT709Scaled filters: the reference's _resizeTexture is BGRA8Unorm_sRGB where sRGB texture
+  // writes exist (BT709HIP_FORMAT_BGRA8_SRGB, the default) and RGBA16Float holding linear light where they do not
+  // (AAPLRenderer.m:143-170; BT709HIP_FORMAT_RGBA16F).  With RGBA16F the output equals -decodeBT709: into such a texture followed
+  // by -renderScaled:, bit for bit, in one launch and without the texture (include/bt709hip_ext.h BT709HIP_OPT_SCALE_INTERMEDIATE);
+  // a decoder without an alpha channel then writes A = 0xFF whatever the alpha fill says.
+  bool setResizeTexturePixelFormat(int format) { return setOption(BT709HIP_OPT_SCALE_INTERMEDIATE, format); }
+  int resizeTexturePixelFormat() const {
+    int format = BT709HIP_FORMAT_BGRA8_SRGB;
+    if (dec_ != nullptr) (void)bt709hip_decoder_get_option(dec_, BT709HIP_OPT_SCALE_INTERMEDIATE, &format);
+    return format;
+  }
+
   // The coalescing submit (include/bt709hip_ext.h BT709HIP_OPT_COALESCE): keep the reference's one-decodeBT709-call-per-frame cadence
   // on device-resident frames and let `frames` (2..32; 0 = off) queued calls go out as one launch; maxAgeMicroseconds > 0: a queue
   // older than that is issued by the context's next call on ANY stream (BT709HIP_OPT_COALESCE_MAX_AGE_US), so an idle caller's

@@ -95,10 +95,26 @@ typedef enum {
   BT709HIP_OPT_HALF_LDS_KB = 4,      /* persistent 2:1 kernel: KiB of LDS a workgroup may fill with table copies; 0 (default) = 160 */
   BT709HIP_OPT_XCD_BANDS = 5,        /* 1 (default): batched 1:1 launches of 64 frames or more give each XCD a contiguous band of the frames (a count that is not a multiple of 8: that map over the multiple of 8, the plain map over the rest); 0: plain (tile, row pair, frame) order */
   BT709HIP_OPT_COALESCE = 6,         /* 0 (default) off; n in 2..32: coalescing submit, see bt709hip_decode */
-  BT709HIP_OPT_COALESCE_MAX_AGE_US = 7 /* 0 (default): queued frames wait for their stream's next call, however long; t > 0: a queue whose oldest frame was queued more than t microseconds ago is issued by the next bt709hip_* call that touches ANY stream of the context (or any decode of any decoder of it) */
+  BT709HIP_OPT_COALESCE_MAX_AGE_US = 7, /* 0 (default): queued frames wait for their stream's next call, however long; t > 0: a queue whose oldest frame was queued more than t microseconds ago is issued by the next bt709hip_* call that touches ANY stream of the context (or any decode of any decoder of it) */
+  BT709HIP_OPT_SCALE_INTERMEDIATE = 8  /* the intermediate the FUSED rescales filter, a bt709hip_format: BT709HIP_FORMAT_BGRA8_SRGB (default) or BT709HIP_FORMAT_RGBA16F; any other value: BT709HIP_ERR_INVALID_ARG, option unchanged.  See below */
 } bt709hip_decoder_option;
 int bt709hip_decoder_set_option(bt709hip_decoder *dec, int option, int value);
 int bt709hip_decoder_get_option(const bt709hip_decoder *dec, int option, int *value);
+/* BT709HIP_OPT_SCALE_INTERMEDIATE.  The reference renders pass 1 into BGRA8Unorm_sRGB where sRGB texture writes exist and into
+ * RGBA16Float holding linear light where they do not (Renderer/AAPLRenderer.m:132-207), then runs -renderScaled: over whichever
+ * it made.  With the option at BT709HIP_FORMAT_RGBA16F, bt709hip_decode_scaled[_batch] and bt709hip_decode_half[_batch] produce,
+ * bit for bit and in one launch without the surface, what bt709hip_decode into an RGBA16F surface of the frame's size followed
+ * by bt709hip_render_scaled from it produces: the filter sees linear light at half precision instead of bytes quantised to
+ * 8-bit sRGB (about 3 output pixels in 10 differ by one code).  The output stays BGRA8_SRGB.  Differences from the 8-bit mode:
+ *   - a decoder WITHOUT an alpha channel writes A = 0xFF whatever bt709hip_decoder_set_alpha_fill says (the half target holds
+ *     1.0 and the two passes do the same);
+ *   - bt709hip_decode_half[_batch] runs the any-ratio kernel at ratio 2.0: there is no persistent 2:1 variant, and
+ *     BT709HIP_OPT_HALF_KERNEL, _HALF_WORKGROUPS, _HALF_LDS_KB and _NONTEMPORAL are ignored; the limits are
+ *     bt709hip_decode_scaled's, and bt709hip_last_scaled_launch_info reports the plan;
+ *   - the half lookup table is built on the first such call, as for RGBA16F targets: before a graph capture call
+ *     bt709hip_decoder_prepare_format(dec, BT709HIP_FORMAT_RGBA16F) (a call that finds it missing during a capture returns
+ *     BT709HIP_ERR_NOT_SETUP).
+ * bt709hip_last_kernel_name: "decode_nv12_scaled_f16" / "decode_nv12_scaled_f16<alpha>".  Definition: DESIGN.md 3.3. */
 
 /* COALESCING SUBMIT (extension, opt-in: bt709hip_decoder_set_option(dec, BT709HIP_OPT_COALESCE, n), n = 2..32).
  * The reference's cadence is one -decodeBT709: call per frame (MetalBT709Decoder.h:65-72, AAPLRenderer.m:914-957), each call

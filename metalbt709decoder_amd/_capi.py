@@ -39,6 +39,7 @@ OPT_HALF_LDS_KB = 4
 OPT_XCD_BANDS = 5
 OPT_COALESCE = 6
 OPT_COALESCE_MAX_AGE_US = 7
+OPT_SCALE_INTERMEDIATE = 8  # value: FORMAT_BGRA8_SRGB (default) or FORMAT_RGBA16F
 CTX_OPT_GRID_MULT = 1
 CTX_OPT_ENCODE_ROW_PAIRS = 2
 CTX_OPT_ENCODE_THREADS = 3

@@ -90,6 +90,13 @@ struct DecodeParams {
   // XCD-aware work map of the short-lived kernels (filled by the launchers): grid.x = 8 x tiles, x & 7 = the workgroup's
   // place in the round-robin over the XCDs, which owns frames [(x & 7) * frames_per_band, ...) of the launch
   uint32_t xcd_bands, frames_per_band;
+  // The any-ratio rescale through the RGBA16Float intermediate (bt709_rescale_f16.hip decode_nv12_scaled_f16;
+  // BT709HIP_OPT_SCALE_INTERMEDIATE): scale_f16 != 0 selects it in launch_decode_scaled, and the decoder's half lookup rides
+  // along -- HalfParams' table (nullptr / 0 bytes: no curve), where its candidate entries start, and the lookup's two constants
+  uint32_t scale_f16;
+  uint32_t half_table_bytes, half_cand_offset, half_h_min;
+  float half_index_scale;
+  const void *half_table;
 };
 
 // Pass 1 into an RGBA16Float target (bt709_rgba16f.hip): the threshold table of transfer_tables.h
@@ -107,6 +114,9 @@ struct HalfParams {
 // largest threshold image (sRGB: 8 602 floats), and low enough that thresholds + candidates stay under 40 KiB: four
 // workgroups per CU.
 constexpr uint32_t kHalfCandLds = 34560;
+// decode_nv12_scaled_f16 keeps the same plan and puts its sRGB-encode buckets behind it: the host holds thresholds + candidates
+// under 40 KiB (shim_decode.cpp ensure_half_table)
+constexpr uint32_t kHalfPlanLds = 40u * 1024u;
 const char *launch_decode_rgba16f(const DecodeParams &p, const HalfParams &hp, int frames, bool has_alpha,
                                   uint32_t in_align, uint32_t out_align, uint32_t compute_units, bool xcd_bands, hipStream_t stream);
 hipError_t prepare_rgba16f_kernels();  // bt709_rgba16f.hip

@@ -32,42 +32,10 @@
 
 #include "bt709_device.h"
 #include "bt709_launch.h"
+#include "bt709_half_lookup.h"
 
 namespace bt709 {
 namespace {
-
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef uint16_t u16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) const float *LdsFloatPtr;
-
-struct HalfLookup {
-  float index_scale;  // HalfTable::index_scale
-  uint32_t below2;    // (h_min - 1) in both halves: the saturating subtraction that indexes T
-};
-// LDS address of a bucket's entry = its (masked) binary16 bits + this: the ds_read_b64's immediate offset.  ABSOLUTE LDS
-// addresses: the dynamic allocation is the kernel's only LDS and starts at byte 0 (no __shared__ variable in this file; a CPU
-// test reads .group_segment_fixed_size = 0 from the code object's metadata).
-constexpr uint32_t kCandBias = kHalfCandLds - kHalfCandFloor;
-static_assert((kHalfCandFloor & 7u) == 0 && (kHalfCandLds & 15u) == 0 && kHalfCandLds - kHalfCandFloor + 0x3ff8u < 0x10000u, "candidate entries: aligned, and the offset fits the instruction");
-
-// The table image of a launch (thresholds, then candidate entries) -> LDS: the thresholds to byte 0, the entries to
-// kHalfCandLds.  Batched staging (bt709_stage.h), five loads at a time: at most 40 KiB = 2 560 sixteen-byte words, one round for
-// a 512-lane workgroup, two for 256 lanes, more for the 64-lane workgroups of very narrow frames.
-__device__ __forceinline__ void stage_half_tables(unsigned char *lds, const void *src, uint32_t cand_offset, uint32_t bytes) {
-  const u32x4 *s = reinterpret_cast<const u32x4 *>(src);
-  const uint32_t tid = threadIdx.y * blockDim.x + threadIdx.x, nthreads = blockDim.x * blockDim.y;
-  const uint32_t n = bytes / 16, n_thresholds = cand_offset / 16, gap = (kHalfCandLds - cand_offset) / 16;
-  stage_batched<5>(reinterpret_cast<u32x4 *>(lds), n, tid, nthreads, [&](uint32_t i) { return s[i]; },
-                   [&](uint32_t i) { return i < n_thresholds ? i : i + gap; });
-}
-
-// two values -> their binary16 codes in one word (v_cvt_pk_f16_f32, round to nearest even: the same conversion as
-// v_cvt_f16_f32, two at a time)
-__device__ __forceinline__ uint32_t half_bits2(float lo, float hi) {
-  const f32x2 v = {lo, hi};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, f16x2));
-}
 
 // The twelve channels of a 2x2 block (x = R, G, B of its four pixels, saturated) and the pixels' alpha values (1.0f without an
 // alpha plane) -> the texels' words {R | G << 16, B | A << 16}.  The LDS reads are BATCHED: all twelve entry reads are issued,

@@ -209,6 +209,10 @@ int bt709hip_decoder_set_option(bt709hip_decoder *dec, int option, int value) {
     case BT709HIP_OPT_XCD_BANDS: dec->xcd_bands = clamp_int(value, 0, 2); return BT709HIP_OK;
     case BT709HIP_OPT_COALESCE: return set_coalescing(dec, value <= 1 ? 0 : clamp_int(value, 2, kMaxBatch));
     case BT709HIP_OPT_COALESCE_MAX_AGE_US: dec->coalesce_max_age_us = value < 0 ? 0 : value; return BT709HIP_OK;
+    case BT709HIP_OPT_SCALE_INTERMEDIATE:
+      if (value != BT709HIP_FORMAT_BGRA8_SRGB && value != BT709HIP_FORMAT_RGBA16F) return BT709HIP_ERR_INVALID_ARG;
+      dec->scale_intermediate = value;
+      return BT709HIP_OK;
     default: return BT709HIP_ERR_INVALID_ARG;
   }
 }
@@ -223,6 +227,7 @@ int bt709hip_decoder_get_option(const bt709hip_decoder *dec, int option, int *va
     case BT709HIP_OPT_XCD_BANDS: *value = dec->xcd_bands; return BT709HIP_OK;
     case BT709HIP_OPT_COALESCE: *value = dec->coalesce; return BT709HIP_OK;
     case BT709HIP_OPT_COALESCE_MAX_AGE_US: *value = dec->coalesce_max_age_us; return BT709HIP_OK;
+    case BT709HIP_OPT_SCALE_INTERMEDIATE: *value = dec->scale_intermediate; return BT709HIP_OK;
     default: return BT709HIP_ERR_INVALID_ARG;
   }
 }
@@ -391,6 +396,29 @@ int decode_batch_now(bt709hip_decoder *dec, int count, const bt709hip_frame *fra
   return finish_launch(s, wait_until_completed);
 }
 
+// The any-ratio launch of a gathered batch (p.out_width x p.out_height set): bt709hip_decode_scaled_batch, and
+// bt709hip_decode_half_batch when the rescale goes through the RGBA16Float intermediate (BT709HIP_OPT_SCALE_INTERMEDIATE)
+static int launch_scaled(bt709hip_decoder *dec, DecodeParams &p, const BatchInfo &info, int count, void *stream, int wait_until_completed) {
+  if (p.out_height > static_cast<uint32_t>(kMaxGridYZ)) return BT709HIP_ERR_UNSUPPORTED;
+  p.scale_x = static_cast<float>(p.width) / static_cast<float>(p.out_width);
+  p.scale_y = static_cast<float>(p.height) / static_cast<float>(p.out_height);
+  if (dec->scale_intermediate == BT709HIP_FORMAT_RGBA16F) {
+    if (int rc = ensure_half_table(dec, stream)) return rc;  // built on first use; not while recording a graph
+    p.scale_f16 = 1;
+    p.half_table = dec->half.table;
+    p.half_table_bytes = dec->half.table_bytes;
+    p.half_cand_offset = dec->half.cand_offset;
+    p.half_index_scale = dec->half.index_scale;
+    p.half_h_min = dec->half.h_min;
+  }
+  hipStream_t s = pick(dec->ctx, stream);
+  const char *name = launch_decode_scaled(p, count, dec->has_alpha != 0, info.in_align,
+                                          static_cast<uint32_t>(dec->ctx->props.multiProcessorCount), s);
+  if (name == nullptr) return BT709HIP_ERR_UNSUPPORTED;  // a plane of 2 GiB or more
+  set_kernel_name(name);
+  return finish_launch(s, wait_until_completed);
+}
+
 }  // namespace bt709shim
 
 extern "C" {
@@ -427,6 +455,8 @@ int bt709hip_decode_half_batch(bt709hip_decoder *dec, int count, const bt709hip_
   if (dec != nullptr) FLUSH_STREAM(dec->ctx, stream);
   if (int rc = gather_batch(dec, count, frames, alphas, outs, OutShape::kHalf, stream, &p, &info)) return rc;
   if (p.width == 0) return BT709HIP_OK;
+  // through the RGBA16Float intermediate: the any-ratio kernel at ratio 2.0 (no persistent 2:1 variant; the half-kernel options are not read)
+  if (dec->scale_intermediate == BT709HIP_FORMAT_RGBA16F) return launch_scaled(dec, p, info, count, stream, wait_until_completed);
   hipStream_t s = pick(dec->ctx, stream);
   // wide: same tiling as the 1:1 kernel over the source width; narrow: 256 output pixels per workgroup
   const bool wide = info.in_align >= 4 && info.out_align >= 8;
@@ -462,15 +492,7 @@ int bt709hip_decode_scaled_batch(bt709hip_decoder *dec, int count, const bt709hi
   if (dec != nullptr) FLUSH_STREAM(dec->ctx, stream);
   if (int rc = gather_batch(dec, count, frames, alphas, outs, OutShape::kAny, stream, &p, &info)) return rc;
   if (p.width == 0) return BT709HIP_OK;
-  if (p.out_height > static_cast<uint32_t>(kMaxGridYZ)) return BT709HIP_ERR_UNSUPPORTED;
-  p.scale_x = static_cast<float>(p.width) / static_cast<float>(p.out_width);
-  p.scale_y = static_cast<float>(p.height) / static_cast<float>(p.out_height);
-  hipStream_t s = pick(dec->ctx, stream);
-  const char *name = launch_decode_scaled(p, count, dec->has_alpha != 0, info.in_align,
-                                          static_cast<uint32_t>(dec->ctx->props.multiProcessorCount), s);
-  if (name == nullptr) return BT709HIP_ERR_UNSUPPORTED;  // a plane of 2 GiB or more
-  set_kernel_name(name);
-  return finish_launch(s, wait_until_completed);
+  return launch_scaled(dec, p, info, count, stream, wait_until_completed);
 }
 
 int bt709hip_decode_scaled(bt709hip_decoder *dec, const bt709hip_frame *frame, const bt709hip_frame *alpha,

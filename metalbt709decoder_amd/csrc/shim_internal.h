@@ -77,6 +77,7 @@ struct bt709hip_decoder {
   std::atomic<int> xcd_bands{1};        // BT709HIP_OPT_XCD_BANDS: XCD-aware work map of the batched 1:1 kernels (frames a multiple of 8)
   std::atomic<int> coalesce{0};         // BT709HIP_OPT_COALESCE: 0 off, else frames gathered per launch (2..32)
   std::atomic<int> coalesce_max_age_us{0};  // BT709HIP_OPT_COALESCE_MAX_AGE_US: 0 = no age limit
+  std::atomic<int> scale_intermediate{BT709HIP_FORMAT_BGRA8_SRGB};  // BT709HIP_OPT_SCALE_INTERMEDIATE: what the fused rescales filter
   std::mutex queue_mutex;   // guards queues
   std::vector<PendingQueue> queues;  // one per stream that has (had) queued frames
   std::mutex setup_mutex;

@@ -803,6 +803,22 @@ class MetalBT709Decoder:
             _capi.check(self.metalRenderContext.lib.bt709hip_decoder_set_option(self._handle, int(option), int(value)),
                         "decoder set option")
 
+    @property
+    def resizeTexturePixelFormat(self):
+        """The format of the intermediate the fused rescales (decodeBT709Scaled and the half-scale rings) filter: the reference's
+        _resizeTexture is MTLPixelFormatBGRA8Unorm_sRGB where sRGB texture writes exist (the default) and
+        MTLPixelFormatRGBA16Float holding linear light where they do not (AAPLRenderer.m:143-170).  With RGBA16Float the output
+        equals decodeBT709 into such a texture followed by renderScaled, bit for bit, in one launch and without the texture
+        (_capi.OPT_SCALE_INTERMEDIATE); a decoder without an alpha channel then writes A = 0xFF whatever alphaFill says."""
+        fmt = self._options.get(_capi.OPT_SCALE_INTERMEDIATE, _capi.FORMAT_BGRA8_SRGB)
+        return MTLPixelFormatRGBA16Float if fmt == _capi.FORMAT_RGBA16F else MTLPixelFormatBGRA8Unorm_sRGB
+
+    @resizeTexturePixelFormat.setter
+    def resizeTexturePixelFormat(self, pixelFormat):
+        if pixelFormat not in _FORMAT_OF:
+            raise ValueError("resizeTexturePixelFormat: MTLPixelFormatBGRA8Unorm_sRGB or MTLPixelFormatRGBA16Float")
+        self.setOption(_capi.OPT_SCALE_INTERMEDIATE, _FORMAT_OF[pixelFormat])
+
     def flush(self, commandBuffer=None, allStreams=False):
         """Coalescing submit (setOption(_capi.OPT_COALESCE, n)): issue the frames queued for the command buffer's stream (or
         for every stream).  A no-op without the option."""

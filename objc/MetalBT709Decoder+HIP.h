@@ -1,4 +1,4 @@
-// The two additions the HIP binding makes to MetalBT709Decoder's interface (Renderer/MetalBT709Decoder.h:27-72 itself
+// The additions the HIP binding makes to MetalBT709Decoder's interface (Renderer/MetalBT709Decoder.h:27-72 itself
 // does not change).  A class extension -- imported by objc/MetalBT709Decoder+HIP.m, which is the class's primary
 // implementation on an MI355X machine, so the property is synthesized there -- and by the one kind of caller that
 // needs it: a renderer that wants several frames in flight.  Every other reference call site compiles and behaves
@@ -18,6 +18,12 @@
 // goes through an in-flight pool slot with a stream of its own and is PCIe-bound.  Set before -setupMetal or at any time after.
 @property (nonatomic, assign) int hipCoalesceFrames;
 @property (nonatomic, assign) int hipCoalesceMaxAgeMicroseconds;
+// The format of the intermediate the FUSED rescales of the HIP decoder filter (bt709hip_decode_scaled / _decode_half through
+// hipDecoderHandle; include/bt709hip_ext.h BT709HIP_OPT_SCALE_INTERMEDIATE), named after the choice AAPLRenderer makes for its
+// _resizeTexture (AAPLRenderer.m:143-170): MTLPixelFormatBGRA8Unorm_sRGB (0 is read as that default) or
+// MTLPixelFormatRGBA16Float -- linear light at half precision, bit for bit what -decodeBT709: into such a texture followed by
+// -renderScaled: gives; a decoder without an alpha channel then writes A = 0xFF.  Set before -setupMetal or at any time after.
+@property (nonatomic, assign) MTLPixelFormat hipResizeTexturePixelFormat;
 // The bt709hip_decoder behind this object (NULL before -setupMetal), as a void * so that this header needs no bt709hip.h.
 - (void *) hipDecoderHandle;
 // Completes every frame still in flight: their pixels are copied into the textures passed with them.  Same thread

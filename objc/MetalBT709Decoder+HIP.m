@@ -71,14 +71,18 @@ static void BT709HIPCopyPlane(void *dst, size_t dstStride, CVPixelBufferRef pb, 
   return TRUE;
 }
 
-// hipCoalesceFrames / hipCoalesceMaxAgeMicroseconds (class extension): applied at setup and whenever they change
+// hipCoalesceFrames / hipCoalesceMaxAgeMicroseconds / hipResizeTexturePixelFormat (class extension): applied at setup and whenever they change
 - (void) applyHIPCoalescing {
   if (_hipDecoder == NULL) return;
   bt709hip_decoder_set_option(_hipDecoder, BT709HIP_OPT_COALESCE, self.hipCoalesceFrames);
   bt709hip_decoder_set_option(_hipDecoder, BT709HIP_OPT_COALESCE_MAX_AGE_US, self.hipCoalesceMaxAgeMicroseconds);
+  // hipResizeTexturePixelFormat: the intermediate the fused rescales filter, AAPLRenderer's _resizeTexture choice (AAPLRenderer.m:143-170)
+  bt709hip_decoder_set_option(_hipDecoder, BT709HIP_OPT_SCALE_INTERMEDIATE,
+                              self.hipResizeTexturePixelFormat == MTLPixelFormatRGBA16Float ? BT709HIP_FORMAT_RGBA16F : BT709HIP_FORMAT_BGRA8_SRGB);
 }
 - (void) setHipCoalesceFrames:(int)n { _hipCoalesceFrames = n; [self applyHIPCoalescing]; }
 - (void) setHipCoalesceMaxAgeMicroseconds:(int)us { _hipCoalesceMaxAgeMicroseconds = us; [self applyHIPCoalescing]; }
+- (void) setHipResizeTexturePixelFormat:(MTLPixelFormat)format { _hipResizeTexturePixelFormat = format; [self applyHIPCoalescing]; }
 - (void *) hipDecoderHandle { return _hipDecoder; }
 
 // Copies a finished slot's pinned BGRA rows into the texture the caller passed for that frame: its top-left

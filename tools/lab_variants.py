@@ -254,7 +254,7 @@ constexpr bool kRepUniformEncode = true;
 #endif
 """),
     # CORRECT output: the table staged by LDS DMA (global_load_lds_dwordx4: L2 -> LDS without the trip through VGPRs and ds_write)
-    ("bt709_rgba16f.hip",
+    ("bt709_half_lookup.h",
      """  stage_batched<5>(reinterpret_cast<u32x4 *>(lds), n, tid, nthreads, [&](uint32_t i) { return s[i]; },
 """,
      """#if defined(BT709_LAB_F16_DMA_STAGING)
@@ -359,12 +359,18 @@ constexpr bool kRepUniformEncode = true;
     # (matrix + 3 lookups each) go.  The stub deletes exactly that share outright -- on every odd source row the second tap
     # reuses the first tap's values, no pixel_rgb, no lookups for it -- and keeps everything else: an upper bound on the gain.
     ("bt709_rescale.hip",
-     """    float x[6], lin[6];  // R, G, B of tap 0; R, G, B of tap 1
+     """    float x[6];  // R, G, B of tap 0; R, G, B of tap 1
     pixel_rgb(byte_of(fr.yy, 0), ch0, x[0], x[1], x[2]);
     pixel_rgb(byte_of(fr.yy, 1), ch1, x[3], x[4], x[5]);
-    linearise6(r, x, lin);
+    RowLin<N> rl;
+    light.template two<N>(x, fr.aa, rl);
+    return rl;
 """,
-     """    float x[6], lin[6];
+     """    float x[6];
+#if defined(BT709_LAB_SCALED_HALF_FEWER_TAPS) || defined(BT709_LAB_SCALED_PAIR_DPP) || defined(BT709_LAB_SCALED_QUARTER_FEWER_TAPS)
+    float lin[6];
+    const RescaleLookup &r = light.r;  // the stubs are written against the 8-bit intermediate's lookup
+#endif
 #if defined(BT709_LAB_SCALED_HALF_FEWER_TAPS) || defined(BT709_LAB_SCALED_PAIR_DPP)  // WRONG OUTPUT: tap 0 decoded, tap 1 a copy of it / of the next lane's
     pixel_rgb(byte_of(fr.yy, 0), ch0, x[0], x[1], x[2]);
     {
@@ -405,8 +411,19 @@ constexpr bool kRepUniformEncode = true;
 #else
     pixel_rgb(byte_of(fr.yy, 0), ch0, x[0], x[1], x[2]);
     pixel_rgb(byte_of(fr.yy, 1), ch1, x[3], x[4], x[5]);
-    linearise6(r, x, lin);
 #endif
+    RowLin<N> rl;
+#if defined(BT709_LAB_SCALED_HALF_FEWER_TAPS) || defined(BT709_LAB_SCALED_PAIR_DPP) || defined(BT709_LAB_SCALED_QUARTER_FEWER_TAPS)
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) rl.v[t][k] = lin[3 * t + k];
+      if (HAS_ALPHA) rl.v[t][N - 1] = alpha_norm_arith(byte_of(fr.aa, t));
+    }
+#else
+    light.template two<N>(x, fr.aa, rl);
+#endif
+    return rl;
 """),
     # round 6: where the placement hunt's wall-clock time goes (stderr, one line per ring): allocation, free, hipMemGetInfo, warm-up launches, probes
     ("bt709_ring.cpp",
@@ -533,16 +550,16 @@ double *lab_trace() {  // seconds: malloc, free, mem_info, warm-up, probe
 #endif
     if (TAPS == TAPS_ONCE) {"""),
     ("bt709_rescale.hip",
-     """    const uint32_t R = encode_byte(r, acc[0]);
-    const uint32_t G = encode_byte(r, acc[1]);
-    const uint32_t B = encode_byte(r, acc[2]);
+     """    const uint32_t R = light.encode(acc[0]);
+    const uint32_t G = light.encode(acc[1]);
+    const uint32_t B = light.encode(acc[2]);
 """,
      """#if defined(BT709_LAB_SCALED_NO_ENCODE)  // no encode-side lookups: a byte cut out of each float
     const uint32_t R = (__float_as_uint(acc[0]) >> 15) & 0xffu, G = (__float_as_uint(acc[1]) >> 15) & 0xffu, B = (__float_as_uint(acc[2]) >> 15) & 0xffu;
 #else
-    const uint32_t R = encode_byte(r, acc[0]);
-    const uint32_t G = encode_byte(r, acc[1]);
-    const uint32_t B = encode_byte(r, acc[2]);
+    const uint32_t R = light.encode(acc[0]);
+    const uint32_t G = light.encode(acc[1]);
+    const uint32_t B = light.encode(acc[2]);
 #endif
 """),
     ("bt709_rescale.hip",
@@ -658,14 +675,14 @@ double *lab_trace() {  // seconds: malloc, free, mem_info, warm-up, probe
       return rl;
 """),
     ("bt709_rescale.hip",
-     """  const size_t lds = static_cast<size_t>(p.table_linear_bytes) + p.table_encode_bytes;
+     """  const size_t lds = f16 ? scaled_f16_lds(p) : static_cast<size_t>(p.table_linear_bytes) + p.table_encode_bytes;
   const dim3 block(kBlockThreads);""",
      """#if defined(BT709_LAB_SCALED_ONCE_LDS)
   const size_t lds_tables = static_cast<size_t>(p.table_linear_bytes) + p.table_encode_bytes;
   p.lab_tile_off = static_cast<uint32_t>(lds_tables);  // the kernel's dynamic LDS starts at address 0 (no static LDS)
   const size_t lds = lds_tables + 16u * kBlockThreads;
 #else
-  const size_t lds = static_cast<size_t>(p.table_linear_bytes) + p.table_encode_bytes;
+  const size_t lds = f16 ? scaled_f16_lds(p) : static_cast<size_t>(p.table_linear_bytes) + p.table_encode_bytes;
 #endif
   const dim3 block(kBlockThreads);"""),
     ("bt709_kernels.h",
@@ -731,7 +748,7 @@ MACROS = ["BT709_LAB_NO_ARITH", "BT709_LAB_NO_LOADS", "BT709_LAB_NO_STORES", "BT
           "BT709_LAB_SCALED_HALF_FEWER_TAPS", "BT709_LAB_SCALED_PAIR_DPP", "BT709_LAB_SCALED_ONCE_LDS", "BT709_LAB_HUNT_TRACE", "BT709_LAB_SCALED_NO_FETCH", "BT709_LAB_SCALED_NO_DECODE", "BT709_LAB_SCALED_NO_ENCODE", "BT709_LAB_SCALED_NO_STORE", "BT709_LAB_SCALED_STORE_ONE_LINE", "BT709_LAB_ANY_ORDER", "BT709_LAB_HALF_NO_FETCH", "BT709_LAB_HALF_NO_STORE", "BT709_LAB_BAND_ROT", "BT709_LAB_BAND_XOR"]
 
 
-RESCALE_FILES = ("bt709_rescale.h", "bt709_rescale_half.hip", "bt709_rescale_scaled.hip")  # round 6 split bt709_rescale.hip
+RESCALE_FILES = ("bt709_rescale.h", "bt709_rescale_half.hip", "bt709_rescale_scaled.hip", "bt709_scaled_strip.h")  # round 6 split bt709_rescale.hip; the strip shared with bt709_rescale_f16.hip moved to a header
 
 
 def resolve(csrc, name, product):
