@@ -395,6 +395,18 @@ class MetalBT709Decoder {
     return format;
   }
 
+  // What the 1:1 decode of an alpha decoder is blended over, inside the decode kernel (include/bt709hip_ext.h
+  // BT709HIP_OPT_COMPOSITE_OVER): BT709HIP_OVER_OFF (the default), BT709HIP_OVER_DESTINATION -- what the target
+  // holds when the kernel runs, the reference's non-opaque MTKView over a pattern image (AAPLViewController.m:30-66) -- or an
+  // opaque sRGB colour R<<16 | G<<8 | B (its black / white backgrounds: 0 / 0xFFFFFF).  BGRA8 targets of decodeBT709 only.
+  bool setCompositeOver(int background) { return setOption(BT709HIP_OPT_COMPOSITE_OVER, background); }
+  bool setCompositeOverColour(int r, int g, int b) { return setCompositeOver((r & 0xFF) << 16 | (g & 0xFF) << 8 | (b & 0xFF)); }
+  int compositeOver() const {
+    int background = BT709HIP_OVER_OFF;
+    if (dec_ != nullptr) (void)bt709hip_decoder_get_option(dec_, BT709HIP_OPT_COMPOSITE_OVER, &background);
+    return background;
+  }
+
   // The coalescing submit (include/bt709hip_ext.h BT709HIP_OPT_COALESCE): keep the reference's one-decodeBT709-call-per-frame cadence
   // on device-resident frames and let `frames` (2..32; 0 = off) queued calls go out as one launch; maxAgeMicroseconds > 0: a queue
   // older than that is issued by the context's next call on ANY stream (BT709HIP_OPT_COALESCE_MAX_AGE_US), so an idle caller's

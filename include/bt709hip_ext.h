@@ -96,6 +96,7 @@ typedef enum {
   BT709HIP_OPT_XCD_BANDS = 5,        /* 1 (default): batched 1:1 launches of 64 frames or more give each XCD a contiguous band of the frames (a count that is not a multiple of 8: that map over the multiple of 8, the plain map over the rest); 0: plain (tile, row pair, frame) order */
   BT709HIP_OPT_COALESCE = 6,         /* 0 (default) off; n in 2..32: coalescing submit, see bt709hip_decode */
   BT709HIP_OPT_COALESCE_MAX_AGE_US = 7, /* 0 (default): queued frames wait for their stream's next call, however long; t > 0: a queue whose oldest frame was queued more than t microseconds ago is issued by the next bt709hip_* call that touches ANY stream of the context (or any decode of any decoder of it) */
+  BT709HIP_OPT_COMPOSITE_OVER = 9,   /* alpha decoders: BT709HIP_OVER_OFF (default), BT709HIP_OVER_DESTINATION, or an sRGB colour R<<16 | G<<8 | B; see below */
   BT709HIP_OPT_SCALE_INTERMEDIATE = 8  /* the intermediate the FUSED rescales filter, a bt709hip_format: BT709HIP_FORMAT_BGRA8_SRGB (default) or BT709HIP_FORMAT_RGBA16F; any other value: BT709HIP_ERR_INVALID_ARG, option unchanged.  See below */
 } bt709hip_decoder_option;
 int bt709hip_decoder_set_option(bt709hip_decoder *dec, int option, int value);
@@ -115,6 +116,28 @@ int bt709hip_decoder_get_option(const bt709hip_decoder *dec, int option, int *va
  *     bt709hip_decoder_prepare_format(dec, BT709HIP_FORMAT_RGBA16F) (a call that finds it missing during a capture returns
  *     BT709HIP_ERR_NOT_SETUP).
  * bt709hip_last_kernel_name: "decode_nv12_scaled_f16" / "decode_nv12_scaled_f16<alpha>".  Definition: DESIGN.md 3.3. */
+/* BT709HIP_OPT_COMPOSITE_OVER (decoders created with has_alpha != 0).  The reference decodes an alpha clip into a non-opaque
+ * MTKView over a pattern image or over plain black / white (Application/AAPLViewController.m:30-66) and leaves the blend to the
+ * system compositor; the colour frame holds PREMULTIPLIED colour (srgb_to_bt709.m:805-811; AAPLShaders.metal:432-436).  With the
+ * option on, the 1:1 decode -- bt709hip_decode, bt709hip_decode_batch and everything that launches through them: ring, ring
+ * set, pool, shard, the coalescing submit -- blends each decoded pixel source-over a background in linear light inside the
+ * decode kernel, bit for bit what "decode, then blend the 8-bit result" gives (definition: DESIGN.md 3.5):
+ *   BT709HIP_OVER_OFF          nothing changes: the same kernels, names and bytes;
+ *   BT709HIP_OVER_DESTINATION  the background is what `out` holds when the kernel runs (Metal: loadAction = Load with blending
+ *                              on); each output word is read once and written once, by the same lane;
+ *   0 ... 0xFFFFFF             an opaque solid colour, sRGB bytes R<<16 | G<<8 | B (black 0, white 0xFFFFFF); `out` is not
+ *                              read and every output alpha is 255.
+ * Any other value: BT709HIP_ERR_INVALID_ARG; on a decoder without an alpha channel: BT709HIP_ERR_UNSUPPORTED; either way the
+ * option keeps its value.  Setting it never touches the device (frames a coalescing decoder has queued go out first, under the
+ * value they were queued with).  Targets are BGRA8_SRGB: with the option on, an RGBA16F target, bt709hip_decode_half[_batch]
+ * and bt709hip_decode_scaled[_batch] return BT709HIP_ERR_UNSUPPORTED after their usual validation and write nothing.  The
+ * kernels need one more 1 KiB device table: bt709hip_decoder_setup builds it when called with the option on (also on a decoder
+ * that is set up already), and so does the first such decode -- but a decode that finds it missing while its stream records a
+ * graph returns BT709HIP_ERR_NOT_SETUP.  bt709hip_last_kernel_name: "decode_nv12_quads<alpha,over>" /
+ * "decode_nv12_quads<alpha,over-colour>", and "decode_nv12_blocks<alpha,over>" / "decode_nv12_blocks<alpha,over-colour>" on the
+ * general path (ragged or misaligned frames). */
+#define BT709HIP_OVER_OFF (-1)
+#define BT709HIP_OVER_DESTINATION (-2)
 
 /* COALESCING SUBMIT (extension, opt-in: bt709hip_decoder_set_option(dec, BT709HIP_OPT_COALESCE, n), n = 2..32).
  * The reference's cadence is one -decodeBT709: call per frame (MetalBT709Decoder.h:65-72, AAPLRenderer.m:914-957), each call

@@ -40,6 +40,9 @@ OPT_XCD_BANDS = 5
 OPT_COALESCE = 6
 OPT_COALESCE_MAX_AGE_US = 7
 OPT_SCALE_INTERMEDIATE = 8  # value: FORMAT_BGRA8_SRGB (default) or FORMAT_RGBA16F
+OPT_COMPOSITE_OVER = 9  # alpha decoders: OVER_OFF (default), OVER_DESTINATION, or an sRGB colour R<<16 | G<<8 | B
+OVER_OFF = -1
+OVER_DESTINATION = -2
 CTX_OPT_GRID_MULT = 1
 CTX_OPT_ENCODE_ROW_PAIRS = 2
 CTX_OPT_ENCODE_THREADS = 3

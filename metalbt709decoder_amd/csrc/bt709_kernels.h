@@ -97,7 +97,16 @@ struct DecodeParams {
   uint32_t half_table_bytes, half_cand_offset, half_h_min;
   float half_index_scale;
   const void *half_table;
+  // BT709HIP_OPT_COMPOSITE_OVER (alpha decoders, the 1:1 kernels): the decoded word goes source-over a
+  // background in linear light before it is stored.  over_mode selects the *_over kernels in launch_decode; over_table_lin is
+  // lin[256] = sRGB_nonLinearNormToLinear(byteNorm(b)) as floats (the encode side is table_encode); kOverColour: the three
+  // lin[] of the solid colour's R, G, B, looked up on the host
+  uint32_t over_mode;  // kOverOff / kOverDestination / kOverColour
+  float over_lin[3];
+  const void *over_table_lin;
 };
+enum : uint32_t { kOverOff = 0, kOverDestination = 1, kOverColour = 2 };
+constexpr uint32_t kOverLinBytes = 256 * sizeof(float);
 
 // Pass 1 into an RGBA16Float target (bt709_rgba16f.hip): the threshold table of transfer_tables.h
 // HalfTable and the constants of the candidate.  Travels beside DecodeParams (frames, pitches).

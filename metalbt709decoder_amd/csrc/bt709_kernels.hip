@@ -100,6 +100,88 @@ __device__ __forceinline__ void decode_block(const UnitLookup &u, const float y[
                         bucket_byte(u, x[3 * px + 2], t[3 * px + 2]), alpha_word);
 }
 
+// ---------------------------------------------------------------------------
+// BT709HIP_OPT_COMPOSITE_OVER: an alpha decoder's word goes source-over a background in linear light, the
+// two-pass equivalent of "decode, then blend the 8-bit result".  Per pixel, s the word the plain alpha decode writes, d the
+// background (what the output held, or a solid colour with A_d = 255), every float operation rounded on its own:
+//     k     = float(255 - A_s) * (1/255f)                    byteNorm of the complement (sRGB.h:32-36)
+//     v_c   = min(1, lin[s_c] + k * lin[d_c])                lin[b] = sRGB_nonLinearNormToLinear(byteNorm(b)), the colour premultiplied
+//     out_c = the LINEAR-mode composite of v_c               the rescale kernels' log-bucket encode table
+//     out_A = A_s + ((255 - A_s) * A_d + 127) / 255          integer
+// LDS: the encode table (DecodeParams::table_encode, ~5 KiB) and lin[256] (1 KiB) behind it.
+// ---------------------------------------------------------------------------
+typedef __attribute__((address_space(3))) const float *LdsFloatPtr;  // ds_read_b32
+
+struct OverLookup {
+  float enc_add;     // encode table: bucket of v = (bits(v + enc_add) >> 16) - first
+  uint32_t enc_off;  // its LDS address - (first << 3)
+  uint32_t lin_off;  // LDS address of lin[256]
+};
+
+// Stages both tables (the caller synchronises) and returns the lookup constants.
+__device__ __forceinline__ OverLookup stage_over_tables(unsigned char *lds_raw, const DecodeParams &p) {
+  stage_table(lds_raw, p.table_encode, p.table_encode_bytes);
+  stage_table(lds_raw + p.table_encode_bytes, p.over_table_lin, kOverLinBytes);
+  OverLookup o;
+  o.enc_add = p.encode_log_add;
+  o.enc_off = lds_address(lds_raw) - (p.encode_log_first << 3);
+  o.lin_off = lds_address(lds_raw) + p.table_encode_bytes;
+  return o;
+}
+
+__device__ __forceinline__ float over_lin(const OverLookup &o, uint32_t byte) {
+  return *reinterpret_cast<LdsFloatPtr>((byte << 2) + o.lin_off);
+}
+
+// sRGB byte of a linear-light v in [0, 1]: the index is a plain add (the host files the thresholds under the same one,
+// transfer_tables.cpp bucket_index_log), the bucket's edge settles it
+__device__ __forceinline__ uint32_t over_encode(const OverLookup &o, float v) {
+  const uint32_t t = __float_as_uint(__fadd_rn(v, o.enc_add)) >> 16;
+  const u32x2 e = *reinterpret_cast<LdsPairPtr>((t << 3) + o.enc_off);
+  return e.y + (v >= __uint_as_float(e.x) ? 1u : 0u);
+}
+
+// One pixel: x = its saturated R, G, B (pixel_rgb), abyte its alpha-frame sample, bg the background word (kOverDestination) --
+// colour_lin the background's three linear values otherwise.
+template <int OVER>
+__device__ __forceinline__ uint32_t over_pixel(const OverLookup &o, const float *colour_lin, const float *x, float abyte, uint32_t bg) {
+  const uint32_t as = quantise_byte(alpha_value(abyte)), inv = 255u - as;
+  const float k = __fmul_rn(static_cast<float>(inv), kInv255);
+  float d[3];
+  uint32_t a = 255u;  // an opaque background: A_s + (255 - A_s)
+  if (OVER == kOverDestination) {
+    d[0] = over_lin(o, (bg >> 16) & 0xffu);
+    d[1] = over_lin(o, (bg >> 8) & 0xffu);
+    d[2] = over_lin(o, bg & 0xffu);
+    a = as + (inv * (bg >> 24) + 127u) / 255u;
+  } else {
+    d[0] = colour_lin[0], d[1] = colour_lin[1], d[2] = colour_lin[2];
+  }
+  uint32_t byte[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c)  // the sum is in [0, 2): the add's clamp is the min with 1
+    byte[c] = over_encode(o, add_sat(over_lin(o, quantise_byte(x[c])), __fmul_rn(k, d[c])));
+  return pack_bgra(byte[0], byte[1], byte[2], a << 24);
+}
+
+// decode_quad's pixels through over_pixel; bt / bb: what the output's two rows held (kOverDestination)
+template <int OVER>
+__device__ __forceinline__ void over_quad(const OverLookup &o, const DecodeParams &p, uint32_t ya, uint32_t yb, uint32_t cw, uint32_t aa,
+                                          uint32_t ab, const u32x4 &bt, const u32x4 &bb, u32x4 &top, u32x4 &bot) {
+  const Chroma c0 = chroma_terms(byte_of(cw, 0), byte_of(cw, 1));
+  const Chroma c1 = chroma_terms(byte_of(cw, 2), byte_of(cw, 3));
+  const uint32_t bg[8] = {bt.x, bt.y, bt.z, bt.w, bb.x, bb.y, bb.z, bb.w};
+  uint32_t w[8];
+#pragma unroll
+  for (int px = 0; px < 8; ++px) {
+    float x[3];
+    pixel_rgb(byte_of(px < 4 ? ya : yb, px & 3), (px & 2) ? c1 : c0, x[0], x[1], x[2]);
+    w[px] = over_pixel<OVER>(o, p.over_lin, x, byte_of(px < 4 ? aa : ab, px & 3), bg[px]);
+  }
+  top.x = w[0], top.y = w[1], top.z = w[2], top.w = w[3];
+  bot.x = w[4], bot.y = w[5], bot.z = w[6], bot.w = w[7];
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -109,7 +191,9 @@ __device__ __forceinline__ void decode_block(const UnitLookup &u, const float y[
 // ---------------------------------------------------------------------------
 // LOGIDX: the table is in log-bucket form (one shift more per channel).  (The body once covered 2 or 4 row pairs per workgroup: that
 // served the LINEAR mode's 33 KiB uniform table until its log-bucket form made it 5 KiB, decode_nv12_quads_log below.)
-template <bool HAS_ALPHA, bool NT, bool QUANT, bool LOGIDX = false>
+// OVER (kOverDestination / kOverColour; alpha decoders): the composite-over form -- the tile's front end also loads what the
+// output held (destination mode), both of its tables are staged behind the loads, and the quads go through over_quad.
+template <bool HAS_ALPHA, bool NT, bool QUANT, bool LOGIDX = false, int OVER = kOverOff>
 __device__ __forceinline__ void quads_body(const DecodeParams &p, unsigned char *lds_raw) {
   constexpr int UNROLL = kQuadsPerLane;
   const BandedWork work = banded_work<true>(p.xcd_bands, p.frames_per_band);  // XCD-aware work map: bt709_tile.h
@@ -125,8 +209,14 @@ __device__ __forceinline__ void quads_body(const DecodeParams &p, unsigned char 
   const uint32_t q0 = work.tile * (blockDim.x * UNROLL) + threadIdx.x;
 
   // straight-line: loads, table, pin, arithmetic, predicated stores (bt709_tile.h TileIn)
-  TileIn<UNROLL, HAS_ALPHA> in;
+  static_assert(OVER == kOverOff || HAS_ALPHA, "there is nothing to composite without an alpha channel");
+  TileIn<UNROLL, HAS_ALPHA, OVER == kOverDestination> in;
   in.template load<NT>(f, p, rp_raw, row_pairs, q0, quads);
+  OverLookup ol = {};
+  if constexpr (OVER != kOverOff) {
+    ol = stage_over_tables(lds_raw, p);  // after the tile's loads are in flight
+    __syncthreads();
+  }
   if (!QUANT) {  // the sRGB mode needs no table (decode_quad)
     stage_table(lds_raw, p.table_unit, p.table_unit_bytes);  // after the tile's loads are in flight
     __syncthreads();
@@ -136,6 +226,19 @@ __device__ __forceinline__ void quads_body(const DecodeParams &p, unsigned char 
   const UnitLookup ul = unit_lookup(p, lds_raw);
   uint8_t *o0 = f.out + static_cast<size_t>(2 * min(rp_raw, row_pairs - 1)) * p.out_stride;
   uint8_t *o1 = o0 + p.out_stride;
+  if constexpr (OVER != kOverOff) {  // the same walk, the quads through the blend
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) {
+      const uint32_t q = q0 + u * blockDim.x;
+      u32x4 top, bot;
+      over_quad<OVER>(ol, p, in.ya[u], in.yb[u], in.cw[u], in.aa[u], in.ab[u], in.da[OVER == kOverDestination ? u : 0], in.db[OVER == kOverDestination ? u : 0], top, bot);
+      if (q < quads && rp_raw < row_pairs) {
+        store16<NT>(o0 + 16 * q, top);
+        store16<NT>(o1 + 16 * q, bot);
+      }
+    }
+    return;
+  }
 #pragma unroll
   for (int u = 0; u < UNROLL; ++u) {
     const uint32_t q = q0 + u * blockDim.x;
@@ -166,6 +269,15 @@ __global__ void __launch_bounds__(kMaxBlockThreads)
 decode_nv12_quads_log(const DecodeParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   quads_body<false, NT, false, true>(p, lds_raw);
+}
+
+// The alpha decoder's kernel with the composite-over blend (BT709HIP_OPT_COMPOSITE_OVER): LDS- and VALU-bound where the plain
+// kernel is HBM-bound -- 48 to 72 LDS reads per quad.  Streaming accesses throughout.
+template <int OVER>
+__global__ void __launch_bounds__(kMaxBlockThreads)
+decode_nv12_quads_over(const DecodeParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+  quads_body<true, true, true, false, OVER>(p, lds_raw);
 }
 
 // ---------------------------------------------------------------------------
@@ -207,6 +319,49 @@ decode_nv12_blocks(const DecodeParams p) {
       }
       uint32_t out[4];
       decode_block<HAS_ALPHA, QUANT>(ul, y, byte_value(cc[2 * bx]), byte_value(cc[2 * bx + 1]), a, p.alpha_word, out);
+      o0[2 * bx] = out[0];
+      o0[2 * bx + 1] = out[1];
+      o1[2 * bx] = out[2];
+      o1[2 * bx + 1] = out[3];
+    }
+  }
+}
+
+// The alpha decoder's general path with the composite-over blend (BT709HIP_OPT_COMPOSITE_OVER): the same walk, each 2x2 block
+// through over_pixel.  A kernel of its own: the plain kernel's code stays what it was.  Each output word is read (destination
+// mode) and written by one lane alone.
+template <int OVER>
+__global__ void __launch_bounds__(kBlockThreads)
+decode_nv12_blocks_over(const DecodeParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+  const OverLookup ol = stage_over_tables(lds_raw, p);
+  __syncthreads();
+
+  const FramePlanes f = frame_planes(p, blockIdx.y);
+  const uint32_t bw = p.width >> 1;
+  const uint32_t row_pairs = p.height >> 1;
+
+  for (uint32_t rp = blockIdx.x; rp < row_pairs; rp += gridDim.x) {
+    const uint8_t *y0 = f.y + static_cast<size_t>(2 * rp) * p.y_stride;
+    const uint8_t *y1 = y0 + p.y_stride;
+    const uint8_t *a0 = f.alpha + static_cast<size_t>(2 * rp) * p.alpha_stride;
+    const uint8_t *a1 = a0 + p.alpha_stride;
+    const uint8_t *cc = f.cbcr + static_cast<size_t>(rp) * p.cbcr_stride;
+    uint32_t *o0 = reinterpret_cast<uint32_t *>(f.out + static_cast<size_t>(2 * rp) * p.out_stride);
+    uint32_t *o1 = reinterpret_cast<uint32_t *>(f.out + static_cast<size_t>(2 * rp + 1) * p.out_stride);
+    for (uint32_t bx = threadIdx.x; bx < bw; bx += kBlockThreads) {
+      const float y[4] = {byte_value(y0[2 * bx]), byte_value(y0[2 * bx + 1]), byte_value(y1[2 * bx]), byte_value(y1[2 * bx + 1])};
+      const float a[4] = {byte_value(a0[2 * bx]), byte_value(a0[2 * bx + 1]), byte_value(a1[2 * bx]), byte_value(a1[2 * bx + 1])};
+      uint32_t bg[4] = {0u, 0u, 0u, 0u};
+      if (OVER == kOverDestination) bg[0] = o0[2 * bx], bg[1] = o0[2 * bx + 1], bg[2] = o1[2 * bx], bg[3] = o1[2 * bx + 1];
+      const Chroma c = chroma_terms(byte_value(cc[2 * bx]), byte_value(cc[2 * bx + 1]));
+      uint32_t out[4];
+#pragma unroll
+      for (int px = 0; px < 4; ++px) {
+        float x[3];
+        pixel_rgb(y[px], c, x[0], x[1], x[2]);
+        out[px] = over_pixel<OVER>(ol, p.over_lin, x, a[px], bg[px]);
+      }
       o0[2 * bx] = out[0];
       o0[2 * bx + 1] = out[1];
       o1[2 * bx] = out[2];
@@ -343,7 +498,8 @@ LaunchShape &last_launch_shape() {
 const char *launch_decode(const DecodeParams &p_in, int frames, int variant, bool has_alpha, bool quantiser, bool nontemporal,
                           int xcd_bands, uint32_t grid_x, uint32_t block_threads, hipStream_t stream) {
   const bool quant = quantiser || has_alpha;  // the sRGB mode: arithmetic, no table
-  const size_t lds = quant ? 0 : p_in.table_unit_bytes;
+  const uint32_t over = has_alpha ? p_in.over_mode : kOverOff;  // BT709HIP_OPT_COMPOSITE_OVER: the *_over kernels and their two tables
+  const size_t lds = over != kOverOff ? p_in.table_encode_bytes + kOverLinBytes : (quant ? 0 : p_in.table_unit_bytes);
   const BandPlan plan = plan_bands(frames, variant == kVariantQuads && xcd_bands, p_in.uniform, kXcdBandMinFrames);
   if (plan.banded && plan.tail) {
     launch_decode(p_in, plan.banded, variant, has_alpha, quantiser, nontemporal, xcd_bands, grid_x, block_threads, stream);
@@ -359,6 +515,14 @@ const char *launch_decode(const DecodeParams &p_in, int frames, int variant, boo
     const dim3 block(block_threads, by, 1);
     if (plan.banded) grid = band_grid(p, static_cast<uint32_t>(xcd_bands), grid);
     record_launch(grid, block, p.xcd_bands);
+    if (over == kOverDestination) {
+      hipLaunchKernelGGL((decode_nv12_quads_over<kOverDestination>), grid, block, lds, stream, p);
+      return "decode_nv12_quads<alpha,over>";
+    }
+    if (over != kOverOff) {
+      hipLaunchKernelGGL((decode_nv12_quads_over<kOverColour>), grid, block, lds, stream, p);
+      return "decode_nv12_quads<alpha,over-colour>";
+    }
     if (has_alpha) {
       hipLaunchKernelGGL((decode_nv12_quads<true, true, true>), grid, block, lds, stream, p);
       return "decode_nv12_quads<alpha>";
@@ -384,6 +548,14 @@ const char *launch_decode(const DecodeParams &p_in, int frames, int variant, boo
   const dim3 grid(grid_x, static_cast<uint32_t>(frames), 1);
   const dim3 block(kBlockThreads, 1, 1);
   record_launch(grid, block, 0);
+  if (over == kOverDestination) {
+    hipLaunchKernelGGL((decode_nv12_blocks_over<kOverDestination>), grid, block, lds, stream, p);
+    return "decode_nv12_blocks<alpha,over>";
+  }
+  if (over != kOverOff) {
+    hipLaunchKernelGGL((decode_nv12_blocks_over<kOverColour>), grid, block, lds, stream, p);
+    return "decode_nv12_blocks<alpha,over-colour>";
+  }
   if (has_alpha) {
     hipLaunchKernelGGL((decode_nv12_blocks<true, true>), grid, block, lds, stream, p);
     return "decode_nv12_blocks<alpha>";

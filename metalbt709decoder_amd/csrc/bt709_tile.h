@@ -50,9 +50,13 @@ __device__ __forceinline__ uint32_t load32(const uint8_t *p) {
 // s_waitcnt vmcnt(0) at the join, and an unpinned word lets it put one between the first quad's stores and the second quad's
 // arithmetic -- either way each wave waits for the WRITE ACKNOWLEDGEMENT of its first stores before it touches its next quad.
 // Pinned, there is one wait for all of the tile's loads, before any store is issued.
-template <int N, bool HAS_ALPHA>
+// DEST (the composite-over kernels' destination mode): the lane also holds what the OUTPUT held -- the two 16-byte words of each
+// quad, loaded with the rest (the same clamp: a lane that stores nothing reads a quad it does not own and drops it) and pinned.
+typedef uint32_t TileWord16 __attribute__((ext_vector_type(4)));
+template <int N, bool HAS_ALPHA, bool DEST = false>
 struct TileIn {
   uint32_t ya[N], yb[N], cw[N], aa[N], ab[N];
+  TileWord16 da[DEST ? N : 1], db[DEST ? N : 1];  // top / bottom row of the background (DEST only)
 
   // quad j: min(q0 + j * blockDim.x, quads - 1) of row pair min(rp, row_pairs - 1) -- consecutive lanes own consecutive quads (a
   // store instruction must fill whole lines: a lane owning ADJACENT quads measured 3x slower, tools/lab_quads_variants.hip)
@@ -73,6 +77,11 @@ struct TileIn {
         aa[j] = load32<NT>(a0 + 4 * q);
         ab[j] = load32<NT>(a0 + p.alpha_stride + 4 * q);
       }
+      if (DEST) {  // touched once: non-temporal whatever NT says
+        const uint8_t *o0 = f.out + static_cast<size_t>(2 * rp) * p.out_stride + 16 * static_cast<size_t>(q);
+        da[DEST ? j : 0] = __builtin_nontemporal_load(reinterpret_cast<const TileWord16 *>(o0));
+        db[DEST ? j : 0] = __builtin_nontemporal_load(reinterpret_cast<const TileWord16 *>(o0 + p.out_stride));
+      }
     }
   }
 
@@ -81,6 +90,7 @@ struct TileIn {
     for (int j = 0; j < N; ++j) {
       asm volatile("" : "+v"(ya[j]), "+v"(yb[j]), "+v"(cw[j]));
       if (HAS_ALPHA) asm volatile("" : "+v"(aa[j]), "+v"(ab[j]));
+      if (DEST) asm volatile("" : "+v"(da[DEST ? j : 0]), "+v"(db[DEST ? j : 0]));
     }
   }
 };

@@ -89,6 +89,25 @@ int ensure_half_table(bt709hip_decoder *dec, void *stream) {
   return BT709HIP_OK;
 }
 
+// lin[256] of the composite-over kernels (BT709HIP_OPT_COMPOSITE_OVER), built by the first setup or decode that finds the
+// option on; not while recording a graph.  dec->setup_mutex held.
+static int build_over_table(bt709hip_decoder *dec, void *stream) {
+  if (dec->d_over_lin.load(std::memory_order_acquire) != nullptr) return BT709HIP_OK;
+  if (capturing(static_cast<hipStream_t>(stream))) return BT709HIP_ERR_NOT_SETUP;
+  float lin[256];
+  for (int b = 0; b < 256; ++b) lin[b] = srgb_to_linear(static_cast<float>(b) * (1.0f / 255.0f));
+  void *d = nullptr;
+  if (int rc = upload_table(lin, sizeof lin, &d)) return rc;
+  dec->d_over_lin.store(d, std::memory_order_release);
+  return BT709HIP_OK;
+}
+
+int ensure_over_table(bt709hip_decoder *dec, void *stream) {
+  if (dec->d_over_lin.load(std::memory_order_acquire) != nullptr) return BT709HIP_OK;
+  std::lock_guard<std::mutex> lock(dec->setup_mutex);
+  return build_over_table(dec, stream);
+}
+
 // Table pointers and lookup constants of a launch.
 void set_tables(DecodeParams *p, const bt709hip_decoder *dec) {
   p->table_unit = dec->d_table_unit;
@@ -167,6 +186,7 @@ int bt709hip_decoder_destroy(bt709hip_decoder *dec) {
     if (dec->d_encode) (void)hipFree(dec->d_encode);
     if (dec->d_encode_u) (void)hipFree(dec->d_encode_u);
     if (dec->half.table) (void)hipFree(const_cast<void *>(dec->half.table));
+    if (dec->d_over_lin.load()) (void)hipFree(dec->d_over_lin.load());
   }
   delete dec;
   return BT709HIP_OK;
@@ -213,6 +233,11 @@ int bt709hip_decoder_set_option(bt709hip_decoder *dec, int option, int value) {
       if (value != BT709HIP_FORMAT_BGRA8_SRGB && value != BT709HIP_FORMAT_RGBA16F) return BT709HIP_ERR_INVALID_ARG;
       dec->scale_intermediate = value;
       return BT709HIP_OK;
+    case BT709HIP_OPT_COMPOSITE_OVER:
+      if (value != BT709HIP_OVER_OFF && value != BT709HIP_OVER_DESTINATION && (value < 0 || value > 0xFFFFFF)) return BT709HIP_ERR_INVALID_ARG;
+      if (!dec->has_alpha) return BT709HIP_ERR_UNSUPPORTED;  // nothing to composite
+      dec->composite_over = value;
+      return BT709HIP_OK;
     default: return BT709HIP_ERR_INVALID_ARG;
   }
 }
@@ -228,6 +253,7 @@ int bt709hip_decoder_get_option(const bt709hip_decoder *dec, int option, int *va
     case BT709HIP_OPT_COALESCE: *value = dec->coalesce; return BT709HIP_OK;
     case BT709HIP_OPT_COALESCE_MAX_AGE_US: *value = dec->coalesce_max_age_us; return BT709HIP_OK;
     case BT709HIP_OPT_SCALE_INTERMEDIATE: *value = dec->scale_intermediate; return BT709HIP_OK;
+    case BT709HIP_OPT_COMPOSITE_OVER: *value = dec->composite_over; return BT709HIP_OK;
     default: return BT709HIP_ERR_INVALID_ARG;
   }
 }
@@ -236,8 +262,15 @@ int bt709hip_decoder_setup(bt709hip_decoder *dec) {
   if (dec == nullptr) return BT709HIP_ERR_INVALID_ARG;
   std::lock_guard<std::mutex> lock(dec->setup_mutex);
   if (dec->ctx == nullptr) return BT709HIP_ERR_NOT_SETUP;  // MetalBT709Decoder.m:48-54
-  if (dec->ready) return BT709HIP_OK;                      // second call is a nop (.m:66-70)
+  const bool over = dec->composite_over != BT709HIP_OVER_OFF;  // its table rides along, also on a decoder set up before the option was
+  if (dec->ready) {                                        // second call is a nop (.m:66-70)
+    if (!over || dec->d_over_lin.load(std::memory_order_acquire) != nullptr) return BT709HIP_OK;
+    if (int rc = bind(dec->ctx)) return rc;
+    return build_over_table(dec, nullptr);
+  }
   if (int rc = bind(dec->ctx)) return rc;
+  if (over)
+    if (int rc = build_over_table(dec, nullptr)) return rc;
 
   TransferTable t;
   TransferTable enc;  // sRGB encoder of the rescale kernels: the LINEAR composite's log-bucket form (5 KiB instead of 33)
@@ -376,8 +409,17 @@ int decode_batch_now(bt709hip_decoder *dec, int count, const bt709hip_frame *fra
   DecodeParams p;
   BatchInfo info;
   if (int rc = gather_batch(dec, count, frames, alphas, outs, OutShape::kSame, stream, &p, &info)) return rc;
+  const int over = dec->composite_over;  // BT709HIP_OPT_COMPOSITE_OVER: into BGRA8_SRGB targets only
+  if (over != BT709HIP_OVER_OFF && info.format == BT709HIP_FORMAT_RGBA16F) return BT709HIP_ERR_UNSUPPORTED;
   if (p.width == 0) return BT709HIP_OK;
   hipStream_t s = pick(dec->ctx, stream);
+  if (over != BT709HIP_OVER_OFF) {
+    if (int rc = ensure_over_table(dec, stream)) return rc;
+    p.over_table_lin = dec->d_over_lin.load(std::memory_order_acquire);
+    p.over_mode = over == BT709HIP_OVER_DESTINATION ? kOverDestination : kOverColour;
+    if (over >= 0)  // the colour's linear values: the entries of the kernels' own table
+      for (int c = 0; c < 3; ++c) p.over_lin[c] = srgb_to_linear(static_cast<float>((over >> (16 - 8 * c)) & 0xff) * (1.0f / 255.0f));
+  }
   if (info.format == BT709HIP_FORMAT_RGBA16F) {  // the reference's pre-10.14 intermediate: linear-light halves
     if (int rc = ensure_half_table(dec, stream)) return rc;
     last_launch_shape() = LaunchShape{};
@@ -454,6 +496,7 @@ int bt709hip_decode_half_batch(bt709hip_decoder *dec, int count, const bt709hip_
   BatchInfo info;
   if (dec != nullptr) FLUSH_STREAM(dec->ctx, stream);
   if (int rc = gather_batch(dec, count, frames, alphas, outs, OutShape::kHalf, stream, &p, &info)) return rc;
+  if (dec->composite_over != BT709HIP_OVER_OFF) return BT709HIP_ERR_UNSUPPORTED;  // BT709HIP_OPT_COMPOSITE_OVER: the 1:1 path only
   if (p.width == 0) return BT709HIP_OK;
   // through the RGBA16Float intermediate: the any-ratio kernel at ratio 2.0 (no persistent 2:1 variant; the half-kernel options are not read)
   if (dec->scale_intermediate == BT709HIP_FORMAT_RGBA16F) return launch_scaled(dec, p, info, count, stream, wait_until_completed);
@@ -491,6 +534,7 @@ int bt709hip_decode_scaled_batch(bt709hip_decoder *dec, int count, const bt709hi
   // the frames are validated like any decode input; the surfaces may have any (common) size
   if (dec != nullptr) FLUSH_STREAM(dec->ctx, stream);
   if (int rc = gather_batch(dec, count, frames, alphas, outs, OutShape::kAny, stream, &p, &info)) return rc;
+  if (dec->composite_over != BT709HIP_OVER_OFF) return BT709HIP_ERR_UNSUPPORTED;  // BT709HIP_OPT_COMPOSITE_OVER: the 1:1 path only
   if (p.width == 0) return BT709HIP_OK;
   return launch_scaled(dec, p, info, count, stream, wait_until_completed);
 }

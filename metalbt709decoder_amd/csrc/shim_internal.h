@@ -78,6 +78,7 @@ struct bt709hip_decoder {
   std::atomic<int> coalesce{0};         // BT709HIP_OPT_COALESCE: 0 off, else frames gathered per launch (2..32)
   std::atomic<int> coalesce_max_age_us{0};  // BT709HIP_OPT_COALESCE_MAX_AGE_US: 0 = no age limit
   std::atomic<int> scale_intermediate{BT709HIP_FORMAT_BGRA8_SRGB};  // BT709HIP_OPT_SCALE_INTERMEDIATE: what the fused rescales filter
+  std::atomic<int> composite_over{BT709HIP_OVER_OFF};  // BT709HIP_OPT_COMPOSITE_OVER: off, the destination, or an sRGB colour R<<16 | G<<8 | B
   std::mutex queue_mutex;   // guards queues
   std::vector<PendingQueue> queues;  // one per stream that has (had) queued frames
   std::mutex setup_mutex;
@@ -100,6 +101,9 @@ struct bt709hip_decoder {
   // first use under setup_mutex; half.table_bytes == 0 with half_ready: the gamma has no curve
   bool half_ready = false;  // under setup_mutex
   HalfParams half = {};
+  // BT709HIP_OPT_COMPOSITE_OVER: lin[256] = sRGB_nonLinearNormToLinear(byteNorm(b)), built by the first setup or decode that
+  // finds the option on (under setup_mutex; release-stored last, acquire-loaded by the decode)
+  std::atomic<void *> d_over_lin{nullptr};
 };
 
 struct bt709hip_pool {
@@ -157,6 +161,7 @@ int validate(const bt709hip_decoder *dec, const bt709hip_frame *f, const bt709hi
              int out_h, int render_w, int render_h);
 int ensure_setup(bt709hip_decoder *dec, void *stream);
 int ensure_half_table(bt709hip_decoder *dec, void *stream);
+int ensure_over_table(bt709hip_decoder *dec, void *stream);
 void set_tables(DecodeParams *p, const bt709hip_decoder *dec);
 int64_t byte_step(const void *a, const void *b);
 bool evenly_spaced(int count, const bt709hip_frame *frames, const bt709hip_frame *alphas, const bt709hip_surface *outs);

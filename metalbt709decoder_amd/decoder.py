@@ -819,6 +819,36 @@ class MetalBT709Decoder:
             raise ValueError("resizeTexturePixelFormat: MTLPixelFormatBGRA8Unorm_sRGB or MTLPixelFormatRGBA16Float")
         self.setOption(_capi.OPT_SCALE_INTERMEDIATE, _FORMAT_OF[pixelFormat])
 
+    @property
+    def compositeOver(self):
+        """What the 1:1 decode of an alpha decoder is blended over, inside the decode kernel (_capi.OPT_COMPOSITE_OVER): None (the
+        default: the decoded words as they are), "destination" (what the target texture holds when the kernel runs -- the
+        reference's non-opaque MTKView over a pattern image, AAPLViewController.m:30-66: tile the pattern into the texture
+        first) or an (r, g, b) tuple of sRGB bytes (its black / white backgrounds: (0, 0, 0) / (255, 255, 255)).  The colour frame
+        holds premultiplied colour; the blend runs in linear light.  BGRA8 targets of decodeBT709 only."""
+        v = self._options.get(_capi.OPT_COMPOSITE_OVER, _capi.OVER_OFF)
+        if v == _capi.OVER_OFF:
+            return None
+        return "destination" if v == _capi.OVER_DESTINATION else ((v >> 16) & 0xFF, (v >> 8) & 0xFF, v & 0xFF)
+
+    @compositeOver.setter
+    def compositeOver(self, background):
+        if background is None:
+            value = _capi.OVER_OFF
+            if not self._handle and not self.hasAlphaChannel:  # nothing to switch off: the option is an alpha decoder's
+                self._options.pop(_capi.OPT_COMPOSITE_OVER, None)
+                return
+        elif isinstance(background, str):
+            if background != "destination":
+                raise ValueError('compositeOver: None, "destination" or an (r, g, b) tuple of bytes')
+            value = _capi.OVER_DESTINATION
+        else:
+            r, g, b = (int(c) for c in background)
+            if not all(0 <= c <= 255 for c in (r, g, b)):
+                raise ValueError('compositeOver: None, "destination" or an (r, g, b) tuple of bytes')
+            value = r << 16 | g << 8 | b
+        self.setOption(_capi.OPT_COMPOSITE_OVER, value)
+
     def flush(self, commandBuffer=None, allStreams=False):
         """Coalescing submit (setOption(_capi.OPT_COALESCE, n)): issue the frames queued for the command buffer's stream (or
         for every stream).  A no-op without the option."""

@@ -24,6 +24,13 @@
 // MTLPixelFormatRGBA16Float -- linear light at half precision, bit for bit what -decodeBT709: into such a texture followed by
 // -renderScaled: gives; a decoder without an alpha channel then writes A = 0xFF.  Set before -setupMetal or at any time after.
 @property (nonatomic, assign) MTLPixelFormat hipResizeTexturePixelFormat;
+// What the 1:1 decode of a decoder with hasAlphaChannel is blended over, inside the decode kernel (device-resident frames through
+// hipDecoderHandle; include/bt709hip_ext.h BT709HIP_OPT_COMPOSITE_OVER): BT709HIPCompositeOverOff (the default),
+// BT709HIPCompositeOverDestination -- what the target holds when the kernel runs, the non-opaque MTKView over a pattern image of
+// AAPLViewController.m:30-66 -- or an opaque sRGB colour R<<16 | G<<8 | B (its black / white backgrounds: 0 / 0xFFFFFF).  The
+// property reads BT709HIPCompositeOverOff until it is set.  Set before -setupMetal or at any time after.
+enum { BT709HIPCompositeOverOff = -1, BT709HIPCompositeOverDestination = -2 };  // BT709HIP_OVER_OFF, BT709HIP_OVER_DESTINATION
+@property (nonatomic, assign) int hipCompositeOver;
 // The bt709hip_decoder behind this object (NULL before -setupMetal), as a void * so that this header needs no bt709hip.h.
 - (void *) hipDecoderHandle;
 // Completes every frame still in flight: their pixels are copied into the textures passed with them.  Same thread

@@ -26,6 +26,7 @@ enum { BT709HIPMaxInFlight = 3 };  // MaxBuffersInFlight, AAPLRenderer.m:34
   // (ARC object array): a renderer may drop its per-frame texture before the frame is finished.
   id<MTLTexture> _pendingTexture[BT709HIPMaxInFlight];   // nil = the slot owes nothing
   int _nextSlot;                   // the slot bt709hip_pool_acquire hands out next (follows every acquire)
+  BOOL _hipCompositeOverSet;       // hipCompositeOver has been assigned (an int property starts at 0, which is "over black")
 }
 - (BOOL) finishHIPSlot:(int)slot;
 - (void) applyHIPCoalescing;
@@ -79,10 +80,15 @@ static void BT709HIPCopyPlane(void *dst, size_t dstStride, CVPixelBufferRef pb, 
   // hipResizeTexturePixelFormat: the intermediate the fused rescales filter, AAPLRenderer's _resizeTexture choice (AAPLRenderer.m:143-170)
   bt709hip_decoder_set_option(_hipDecoder, BT709HIP_OPT_SCALE_INTERMEDIATE,
                               self.hipResizeTexturePixelFormat == MTLPixelFormatRGBA16Float ? BT709HIP_FORMAT_RGBA16F : BT709HIP_FORMAT_BGRA8_SRGB);
+  // hipCompositeOver: what an alpha decoder's 1:1 decode is blended over inside the kernel (refused without hasAlphaChannel)
+  if (self.hasAlphaChannel) bt709hip_decoder_set_option(_hipDecoder, BT709HIP_OPT_COMPOSITE_OVER, self.hipCompositeOver);
 }
 - (void) setHipCoalesceFrames:(int)n { _hipCoalesceFrames = n; [self applyHIPCoalescing]; }
 - (void) setHipCoalesceMaxAgeMicroseconds:(int)us { _hipCoalesceMaxAgeMicroseconds = us; [self applyHIPCoalescing]; }
 - (void) setHipResizeTexturePixelFormat:(MTLPixelFormat)format { _hipResizeTexturePixelFormat = format; [self applyHIPCoalescing]; }
+@synthesize hipCompositeOver = _hipCompositeOver;
+- (int) hipCompositeOver { return _hipCompositeOverSet ? _hipCompositeOver : BT709HIP_OVER_OFF; }
+- (void) setHipCompositeOver:(int)background { _hipCompositeOver = background; _hipCompositeOverSet = YES; [self applyHIPCoalescing]; }
 - (void *) hipDecoderHandle { return _hipDecoder; }
 
 // Copies a finished slot's pinned BGRA rows into the texture the caller passed for that frame: its top-left
