@@ -283,7 +283,9 @@ decode_nv12_quads_over(const DecodeParams p) {
 // ---------------------------------------------------------------------------
 // General path: any even width/height, any stride, byte-aligned planes, 4-byte
 // aligned output.  One lane per 2x2 block, grid-strided over row pairs.  Correctness
-// first; used for ragged or misaligned frames only.
+// first; used for ragged or misaligned frames only.  That correctness is pinned by tests/test_decode_variants.py: all 2^24
+// triples through every instantiation below, and the grid-stride loop, both forms of frame_planes and the over kernels at
+// launch shapes computed from the device.
 // ---------------------------------------------------------------------------
 template <bool HAS_ALPHA, bool QUANT>
 __global__ void __launch_bounds__(kBlockThreads)

@@ -6,24 +6,16 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import metalbt709decoder_amd as mb
 import over_cases as oc
 from metalbt709decoder_amd import _capi
-from metalbt709decoder_amd._capi import Frame, Surface
+from variant_cases import Job, Rig, assert_equal, random_backgrounds, random_planes
 
 pytestmark = pytest.mark.gpu
 
 OPT = _capi.OPT_COMPOSITE_OVER
 DEST = _capi.OVER_DESTINATION
-CANARY = 0x5A
-GUARD = 256
-MATRIX, SRGB, LINEAR = mb.kCVImageBufferYCbCrMatrix_ITU_R_709_2, mb.kCVImageBufferTransferFunction_sRGB, mb.kCVImageBufferTransferFunction_Linear
 NAME = {("quads", True): b"decode_nv12_quads<alpha,over>", ("quads", False): b"decode_nv12_quads<alpha,over-colour>",
         ("blocks", True): b"decode_nv12_blocks<alpha,over>", ("blocks", False): b"decode_nv12_blocks<alpha,over-colour>"}
-
-
-def _up(v, a):
-    return (v + a - 1) // a * a
 
 
 @pytest.fixture(scope="module")
@@ -38,52 +30,6 @@ def tabs(oracle):
     return oc.tables(oracle)
 
 
-class Rig:
-    def __init__(self, gh):
-        from metalbt709decoder_amd.decoder import DeviceBuffer
-        self.DeviceBuffer = DeviceBuffer
-        self.ctx = gh.context()
-        self.lib, self.h = self.ctx.lib, self.ctx.handle
-        self.decoders = []
-
-    def decoder(self, over=None, options=(), setup=True):
-        d = C.c_void_p()
-        _capi.check(self.lib.bt709hip_decoder_create(self.h, mb.MetalBT709GammaSRGB, 1, C.byref(d)))
-        self.decoders.append(d)
-        for opt, val in options:
-            _capi.check(self.lib.bt709hip_decoder_set_option(d, opt, val))
-        if over is not None:
-            self.set_over(d, over)
-        if setup:
-            _capi.check(self.lib.bt709hip_decoder_setup(d), "decoder setup")
-        return d
-
-    def set_over(self, dec, over):
-        _capi.check(self.lib.bt709hip_decoder_set_option(dec, OPT, over), "set composite over")
-
-    def sync(self, stream=None):
-        _capi.check(self.lib.bt709hip_stream_synchronize(self.h, stream))
-
-    def kernel(self):
-        return self.lib.bt709hip_last_kernel_name()
-
-    def upload(self, dptr, arr):
-        arr = np.ascontiguousarray(arr).reshape(-1)
-        _capi.check(self.lib.bt709hip_upload(self.h, dptr, arr.size, arr.ctypes.data, arr.size, arr.size, 1, None), "upload")
-        self.sync()
-
-    def download(self, dptr, nbytes):
-        out = np.empty(nbytes, np.uint8)
-        _capi.check(self.lib.bt709hip_download(self.h, out.ctypes.data, nbytes, dptr, nbytes, nbytes, 1, None), "download")
-        self.sync()
-        return out
-
-    def close(self):
-        for d in self.decoders:
-            self.lib.bt709hip_decoder_destroy(d)
-        self.decoders = []
-
-
 @pytest.fixture(scope="module")
 def rig(gh):
     r = Rig(gh)
@@ -91,97 +37,8 @@ def rig(gh):
     r.close()
 
 
-class Job:
-    """`n` frames of one geometry in device memory -- Y, CbCr and alpha planes with their own pitches in one slab, the targets in
-    another, each slab with guard bands -- and the descriptors for them.  pads: extra bytes per row of (Y, CbCr, alpha, output);
-    out_offset: bytes added to every output pointer; spacing "table": a gap before the last slot, so that no single step
-    reaches every frame and the launch takes the pointer table."""
-
-    def __init__(self, rig, planes, pads=(0, 0, 0, 0), out_offset=0, spacing="even", fmt=_capi.FORMAT_BGRA8_SRGB, out_size=None):
-        self.rig, self.n = rig, len(planes)
-        self.h, self.w = planes[0][0].shape
-        w, h = self.w, self.h
-        self.ow, self.oh = out_size or (w, h)
-        self.px = 8 if fmt == _capi.FORMAT_RGBA16F else 4
-        self.sy, self.sc, self.sa, self.so = w + pads[0], w + pads[1], w + pads[2], self.px * self.ow + pads[3]
-        c_off = _up(self.sy * h, 256)
-        a_off = c_off + _up(self.sc * (h // 2), 256)
-        in_pitch = a_off + _up(self.sa * h, 256)
-        out_pitch = _up(self.so * self.oh, 256)
-        gap = lambda i: GUARD if spacing == "table" and i == self.n - 1 and self.n > 1 else 0
-        self.in_off = [GUARD + i * in_pitch + gap(i) for i in range(self.n)]
-        self.out_off = [GUARD + i * out_pitch + gap(i) + out_offset for i in range(self.n)]
-        host = np.full(self.in_off[-1] + in_pitch + GUARD, CANARY, np.uint8)
-        for i, (y, uv, a) in enumerate(planes):
-            for plane, off, stride, rows in ((y, 0, self.sy, h), (uv, c_off, self.sc, h // 2), (a, a_off, self.sa, h)):
-                host[self.in_off[i] + off:self.in_off[i] + off + stride * rows].reshape(rows, stride)[:, :w] = plane
-        self.d_in = rig.DeviceBuffer(rig.ctx, host.size, placement_tries=1)
-        rig.upload(self.d_in.ptr, host)
-        self.out_bytes = self.out_off[-1] + out_pitch + GUARD
-        self.d_out = rig.DeviceBuffer(rig.ctx, self.out_bytes, placement_tries=1)
-        self.frames = (Frame * self.n)(*[Frame(self.d_in.ptr + o, self.sy, self.d_in.ptr + o + c_off, self.sc, w, h, MATRIX, SRGB) for o in self.in_off])
-        self.alphas = (Frame * self.n)(*[Frame(self.d_in.ptr + o + a_off, self.sa, self.d_in.ptr + o + c_off, self.sc, w, h, MATRIX, LINEAR) for o in self.in_off])
-        self.surfs = (Surface * self.n)(*[Surface(self.d_out.ptr + o, self.so, self.ow, self.oh, fmt, 0) for o in self.out_off])
-        self.fill(None)
-
-    def fill(self, backgrounds):
-        """The target slab: the canary everywhere, then background i (oh, ow, 4 bytes) in the pixels of slot i."""
-        self.before = np.full(self.out_bytes, CANARY, np.uint8)
-        for i, bg in enumerate(backgrounds or []):
-            self._pixels(self.before, i)[...] = np.asarray(bg, np.uint8).reshape(self.oh, self.px * self.ow)
-        self.rig.upload(self.d_out.ptr, self.before)
-
-    def _pixels(self, slab, i):
-        o = self.out_off[i]
-        return slab[o:o + self.so * self.oh].reshape(self.oh, self.so)[:, :self.px * self.ow]
-
-    def decode_batch(self, dec, stream=None, wait=1):
-        return self.rig.lib.bt709hip_decode_batch(dec, self.n, self.frames, self.alphas, self.surfs, stream, wait)
-
-    def decode_one(self, dec, i=0, stream=None, wait=1):
-        return self.rig.lib.bt709hip_decode(dec, C.byref(self.frames[i]), C.byref(self.alphas[i]), C.byref(self.surfs[i]), self.w, self.h, stream, wait)
-
-    def collect(self, label=""):
-        """-> the pixels of every slot [(oh, ow, 4)]; every byte outside them must be what it was."""
-        raw = self.rig.download(self.d_out.ptr, self.out_bytes)
-        outside = np.ones(raw.size, bool)
-        got = []
-        for i in range(self.n):
-            got.append(self._pixels(raw, i).reshape(self.oh, self.ow, self.px).copy())
-            self._pixels(outside, i)[...] = False
-        stray = np.flatnonzero(outside & (raw != self.before))
-        assert stray.size == 0, "%s: %d bytes written outside the pixels, first at slab offset %d" % (label, stray.size, stray[0])
-        return got
-
-    def untouched(self):
-        return np.array_equal(self.rig.download(self.d_out.ptr, self.out_bytes), self.before)
-
-    def free(self):
-        self.d_in.free()
-        self.d_out.free()
-
-
-def random_planes(w, h, seed, n=1):
-    rng = np.random.default_rng(seed)
-    return [(rng.integers(0, 256, (h, w), dtype=np.uint8), rng.integers(0, 256, (h // 2, w), dtype=np.uint8),
-             rng.integers(0, 256, (h, w), dtype=np.uint8)) for _ in range(n)]
-
-
-def random_backgrounds(w, h, seed, n=1):
-    rng = np.random.default_rng(seed)
-    return [rng.integers(0, 256, (h, w, 4), dtype=np.uint8) for _ in range(n)]
-
-
 def want_over(oracle, tabs, planes, background):
     return oc.composite_over(oc.expected_source(oracle, *planes), background, *tabs)
-
-
-def assert_equal(got, want, label):
-    if not np.array_equal(got, want):
-        bad = np.argwhere(got != want)
-        r, x, c = bad[0]
-        raise AssertionError("%s: differs first at row %d, column %d, channel %s (got %d, want %d); %d of %d pixels differ"
-                             % (label, r, x, "BGRA"[c], got[r, x, c], want[r, x, c], int((got != want).any(axis=2).sum()), got.shape[0] * got.shape[1]))
 
 
 # ------------------------------------------------------------------ 1. arithmetic sweep

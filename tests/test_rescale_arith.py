@@ -226,22 +226,33 @@ def _scaled_taps(ctx):
             _capi.SCALED_TAPS_SHARED: "shared", _capi.SCALED_TAPS_ONCE: "once"}[info.taps]
 
 
-# route -> (C entry point, OPT_HALF_KERNEL, plane layout, kernel name, tap form)
-ROUTES = {"half": ("bt709hip_decode_half", 0, "aligned", b"decode_nv12_half<wide>", None),
-          "half-rep": ("bt709hip_decode_half", 1, "aligned", b"decode_nv12_half_rep", None),
-          "scaled-wide": ("bt709hip_decode_scaled", None, "aligned", b"decode_nv12_scaled", "wide"),
-          "scaled-pairs": ("bt709hip_decode_scaled", None, "even", b"decode_nv12_scaled", "pairs"),
-          "scaled-bytes": ("bt709hip_decode_scaled", None, "odd", b"decode_nv12_scaled", "bytes"),
-          "scaled-shared": ("bt709hip_decode_scaled", None, "aligned", b"decode_nv12_scaled", "shared"),
-          "scaled-once": ("bt709hip_decode_scaled", None, "aligned", b"decode_nv12_scaled", "once")}
+# route -> (C entry point, OPT_HALF_KERNEL, plane layout, kernel name, tap form, further decoder options)
+ROUTES = {"half": ("bt709hip_decode_half", 0, "aligned", b"decode_nv12_half<wide>", None, {}),
+          "half-rep": ("bt709hip_decode_half", 1, "aligned", b"decode_nv12_half_rep", None, {}),
+          # odd pitches and plane addresses: one output pixel per lane, 256 per workgroup
+          "half-narrow": ("bt709hip_decode_half", None, "odd", b"decode_nv12_half<narrow>", None, {}),
+          # the wide kernel with the default cache policy: the same name, so the option is read back
+          "half-temporal": ("bt709hip_decode_half", 0, "aligned", b"decode_nv12_half<wide>", None, {_capi.OPT_NONTEMPORAL: 0}),
+          "scaled-wide": ("bt709hip_decode_scaled", None, "aligned", b"decode_nv12_scaled", "wide", {}),
+          "scaled-pairs": ("bt709hip_decode_scaled", None, "even", b"decode_nv12_scaled", "pairs", {}),
+          "scaled-bytes": ("bt709hip_decode_scaled", None, "odd", b"decode_nv12_scaled", "bytes", {}),
+          "scaled-shared": ("bt709hip_decode_scaled", None, "aligned", b"decode_nv12_scaled", "shared", {}),
+          "scaled-once": ("bt709hip_decode_scaled", None, "aligned", b"decode_nv12_scaled", "once", {})}
 
 
 def _run_route(gh, route, gamma, dev, ow, oh):
     """One frame through the route's C entry point (called directly: the Python wrapper reroutes an exact 2:1 to the 2:1 kernels);
     asserts the kernel, the tap form and the plan on record; -> the view's bytes."""
-    entry, half_kernel, layout, name, taps = ROUTES[route]
+    entry, half_kernel, layout, name, taps, options = ROUTES[route]
     ctx = gh.context()
-    dec = gh.make_decoder(gamma, options={} if half_kernel is None else {_capi.OPT_HALF_KERNEL: half_kernel})
+    options = dict(options)
+    if half_kernel is not None:
+        options[_capi.OPT_HALF_KERNEL] = half_kernel
+    dec = gh.make_decoder(gamma, options=options)
+    for opt, value in options.items():  # the options took: the kernel's name does not show every one
+        have = C.c_int(-1)
+        _capi.check(ctx.lib.bt709hip_decoder_get_option(dec._handle, opt, C.byref(have)))
+        assert have.value == value, (route, opt, have.value)
     frame, target = dev.frame(gamma), Target(ctx, ow, oh)
     surf = target.tex.surface()
     _capi.check(getattr(ctx.lib, entry)(dec._handle, C.byref(frame), None, C.byref(surf), None, 1), route)
@@ -256,6 +267,8 @@ def _run_route(gh, route, gamma, dev, ow, oh):
             assert (record["grid"], record["block"]) == (plan["grid"], plan["block"]), (record, plan)
         else:
             assert record["grid"][2] == 1 and record["grid"][1] * record["block"][1] >= oh and record["block"][0] % 64 == 0, record
+            if name.endswith(b"<narrow>"):  # 256 output pixels per workgroup, one output row per workgroup row
+                assert (record["grid"], record["block"]) == (((ow + 255) // 256, oh, 1), (256, 1, 1)), record
     return target.read()
 
 
@@ -263,21 +276,28 @@ def _run_route(gh, route, gamma, dev, ow, oh):
 
 @pytest.fixture(scope="module")
 def full_sweep(gh):
-    """All 2^24 triples as flat blocks, 8192 x 8192, uploaded once; the expected images are filled per gamma on first use."""
+    """All 2^24 triples as flat blocks, 8192 x 8192, uploaded once per plane layout; the expected images are filled per gamma on first use."""
     Y, Cb, Cr = rc.blocks_of(*gh.exhaustive_frame())
-    return dict(dev=DeviceFrame(gh, *rc.flat_frame(Y, Cb, Cr)), blocks=(Y, Cb, Cr), want={})
+    planes = rc.flat_frame(Y, Cb, Cr)
+    return dict(dev={"aligned": DeviceFrame(gh, *planes)}, planes=planes, blocks=(Y, Cb, Cr), want={})
+
+
+# the narrow 2:1 kernel in every gamma; the wide one with the default cache policy in one (its arithmetic is the wide kernel's)
+FULL_SWEEP_CASES = [(r, g) for r in ("half", "half-rep", "scaled-wide", "half-narrow") for g in GAMMAS] + [("half-temporal", 0)]
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("gamma", GAMMAS)
-@pytest.mark.parametrize("route", ["half", "half-rep", "scaled-wide"])
+@pytest.mark.parametrize("route,gamma", FULL_SWEEP_CASES, ids=["%s-%d" % c for c in FULL_SWEEP_CASES])
 def test_gpu_every_colour_as_flat_blocks(gh, oracle, full_sweep, route, gamma):
     """linearise12 + encode_byte, the pipelined copy + the uniform table, linearise6: an exact 2:1 rescale of the flat-block
     frame is, block for block, the oracle's 1:1 table (test_flat_blocks_rescale_to_their_decode holds the identity)."""
     if gamma not in full_sweep["want"]:
         full_sweep["want"][gamma] = rc.table_image(oracle.decode_table(gamma), *full_sweep["blocks"])
     want = full_sweep["want"][gamma]
-    got = _run_route(gh, route, gamma, full_sweep["dev"], 4096, 4096)
+    layout = ROUTES[route][2]
+    if layout not in full_sweep["dev"]:  # the narrow kernel's: uploaded once more, at odd pitches and addresses
+        full_sweep["dev"][layout] = DeviceFrame(gh, *full_sweep["planes"], layout)
+    got = _run_route(gh, route, gamma, full_sweep["dev"][layout], 4096, 4096)
     if not np.array_equal(got, want):
         r, b = np.argwhere(got != want)[0]
         Y, Cb, Cr = (int(a[r, b // 4]) for a in full_sweep["blocks"])
@@ -320,7 +340,7 @@ def test_gpu_every_r_and_b_input_through_the_other_tap_forms(gh, oracle, reduced
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("gamma", GAMMAS)
-@pytest.mark.parametrize("route", ["half", "half-rep", "scaled-wide", "scaled-pairs", "scaled-bytes"])
+@pytest.mark.parametrize("route", ["half", "half-rep", "scaled-wide", "scaled-pairs", "scaled-bytes", "half-narrow", "half-temporal"])
 def test_gpu_both_sides_of_every_encode_threshold(gh, oracle, route, gamma):
     """encode_byte (log buckets) and encode_load / encode_use (the uniform table, edges rescaled at staging): R sums on and one
     float below each of the 255 thresholds, every tap order, both halves of a lane's quad."""
