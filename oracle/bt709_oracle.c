@@ -411,6 +411,10 @@ int bt709o_decode_nv12_rgba16f(int gamma, const uint8_t *y, size_t y_stride, con
   return 0;
 }
 
+/* What a unorm render target stores of a float: saturated to [0, 1], a NaN as 0 -- both comparisons are false for a NaN, so
+ * it takes the last branch; clamp01 above hands a NaN on, and (int)round(NaN) is undefined. */
+static float unorm_sat(float v) { return v > 0.0f ? (v < 1.0f ? v : 1.0f) : 0.0f; }
+
 int bt709o_render_scaled(int in_format, const uint8_t *in, size_t in_stride, int width, int height, uint8_t *bgra,
                          size_t bgra_stride, int out_width, int out_height) {
   if (width <= 0 || height <= 0 || out_width <= 0 || out_height <= 0 || (in_format != 0 && in_format != 1)) return -1;
@@ -445,8 +449,8 @@ int bt709o_render_scaled(int in_format, const uint8_t *in, size_t in_stride, int
           acc[k] = t ? acc[k] + term : term;
         }
       }
-      for (int k = 0; k < 3; k++) out[4 * ox + 2 - k] = (uint8_t)bt709o_quantize(bt709o_linear_to_srgb(clamp01(acc[k])));
-      out[4 * ox + 3] = (uint8_t)bt709o_quantize(clamp01(acc[3]));
+      for (int k = 0; k < 3; k++) out[4 * ox + 2 - k] = (uint8_t)bt709o_quantize(bt709o_linear_to_srgb(unorm_sat(acc[k])));
+      out[4 * ox + 3] = (uint8_t)bt709o_quantize(unorm_sat(acc[3]));
     }
   }
   return 0;

@@ -177,7 +177,9 @@ int bt709o_decode_nv12_rgba16f(int gamma, const uint8_t *y, size_t y_stride, con
  * in_format 0 = BGRA8 sRGB intermediate (taps linearised like the sRGB8 sampler, alpha a plain unorm),
  * 1 = RGBA16Float (taps already linear); out = BGRA8 sRGB of any size.  Sampling geometry, weights and
  * summation order as bt709o_decode_nv12_scaled; the sum is saturated before the store as a unorm
- * render target does. */
+ * render target does: below 0 (and -0) -> 0, above 1 -> 1, a NaN sum -> 0 (v > 0 ? (v < 1 ? v : 1) : 0), colours and alpha.
+ * An RGBA16Float texel may hold any half: every product and every sum is rounded on its own and all four taps are
+ * multiplied whatever their weight, so an infinite texel under a weight of exactly 0 (0 * inf) makes the sum a NaN -> 0. */
 int bt709o_render_scaled(int in_format, const uint8_t *in, size_t in_stride, int width, int height, uint8_t *bgra,
                          size_t bgra_stride, int out_width, int out_height);
 
