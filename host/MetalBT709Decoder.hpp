@@ -406,6 +406,15 @@ class MetalBT709Decoder {
     if (dec_ != nullptr) (void)bt709hip_decoder_get_option(dec_, BT709HIP_OPT_COMPOSITE_OVER, &background);
     return background;
   }
+  // The same for the fused rescales (decodeScaled / decodeHalf; BT709HIP_OPT_SCALED_OVER): the alpha clip played
+  // view-fit over the app's background in one launch.  A value of its own: the 1:1 decode never reads it.
+  bool setScaledCompositeOver(int background) { return setOption(BT709HIP_OPT_SCALED_OVER, background); }
+  bool setScaledCompositeOverColour(int r, int g, int b) { return setScaledCompositeOver((r & 0xFF) << 16 | (g & 0xFF) << 8 | (b & 0xFF)); }
+  int scaledCompositeOver() const {
+    int background = BT709HIP_OVER_OFF;
+    if (dec_ != nullptr) (void)bt709hip_decoder_get_option(dec_, BT709HIP_OPT_SCALED_OVER, &background);
+    return background;
+  }
 
   // The coalescing submit (include/bt709hip_ext.h BT709HIP_OPT_COALESCE): keep the reference's one-decodeBT709-call-per-frame cadence
   // on device-resident frames and let `frames` (2..32; 0 = off) queued calls go out as one launch; maxAgeMicroseconds > 0: a queue

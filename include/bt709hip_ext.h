@@ -97,6 +97,7 @@ typedef enum {
   BT709HIP_OPT_COALESCE = 6,         /* 0 (default) off; n in 2..32: coalescing submit, see bt709hip_decode */
   BT709HIP_OPT_COALESCE_MAX_AGE_US = 7, /* 0 (default): queued frames wait for their stream's next call, however long; t > 0: a queue whose oldest frame was queued more than t microseconds ago is issued by the next bt709hip_* call that touches ANY stream of the context (or any decode of any decoder of it) */
   BT709HIP_OPT_COMPOSITE_OVER = 9,   /* alpha decoders: BT709HIP_OVER_OFF (default), BT709HIP_OVER_DESTINATION, or an sRGB colour R<<16 | G<<8 | B; see below */
+  BT709HIP_OPT_SCALED_OVER = 10,     /* alpha decoders, the rescale paths: the values of BT709HIP_OPT_COMPOSITE_OVER, held separately; see below */
   BT709HIP_OPT_SCALE_INTERMEDIATE = 8  /* the intermediate the FUSED rescales filter, a bt709hip_format: BT709HIP_FORMAT_BGRA8_SRGB (default) or BT709HIP_FORMAT_RGBA16F; any other value: BT709HIP_ERR_INVALID_ARG, option unchanged.  See below */
 } bt709hip_decoder_option;
 int bt709hip_decoder_set_option(bt709hip_decoder *dec, int option, int value);
@@ -130,12 +131,29 @@ int bt709hip_decoder_get_option(const bt709hip_decoder *dec, int option, int *va
  * Any other value: BT709HIP_ERR_INVALID_ARG; on a decoder without an alpha channel: BT709HIP_ERR_UNSUPPORTED; either way the
  * option keeps its value.  Setting it never touches the device (frames a coalescing decoder has queued go out first, under the
  * value they were queued with).  Targets are BGRA8_SRGB: with the option on, an RGBA16F target, bt709hip_decode_half[_batch]
- * and bt709hip_decode_scaled[_batch] return BT709HIP_ERR_UNSUPPORTED after their usual validation and write nothing.  The
+ * and bt709hip_decode_scaled[_batch] return BT709HIP_ERR_UNSUPPORTED after their usual validation and write nothing (the
+ * rescale paths blend under BT709HIP_OPT_SCALED_OVER, below, and then do not read this option).  The
  * kernels need one more 1 KiB device table: bt709hip_decoder_setup builds it when called with the option on (also on a decoder
  * that is set up already), and so does the first such decode -- but a decode that finds it missing while its stream records a
  * graph returns BT709HIP_ERR_NOT_SETUP.  bt709hip_last_kernel_name: "decode_nv12_quads<alpha,over>" /
  * "decode_nv12_quads<alpha,over-colour>", and "decode_nv12_blocks<alpha,over>" / "decode_nv12_blocks<alpha,over-colour>" on the
  * general path (ragged or misaligned frames). */
+/* BT709HIP_OPT_SCALED_OVER (decoders created with has_alpha != 0): the blend of BT709HIP_OPT_COMPOSITE_OVER for the alpha clip
+ * that is played view-fit -- pass 1, -renderScaled: to the view's size, then the compositor's blend over the app's background
+ * -- in the one fused launch.  Values, refusals and the device table are those of BT709HIP_OPT_COMPOSITE_OVER
+ * (BT709HIP_OVER_OFF the default, BT709HIP_OVER_DESTINATION, 0 ... 0xFFFFFF; INVALID_ARG / UNSUPPORTED with the option kept;
+ * setting it never touches the device; bt709hip_decoder_setup builds the table when either option is on, the first blended
+ * rescale otherwise, BT709HIP_ERR_NOT_SETUP inside a capture).  The two options are independent:
+ *   - bt709hip_decode_scaled[_batch] and bt709hip_decode_half[_batch], and everything that launches through them (a ring created
+ *     with half_scale), read THIS option: on, each output word is composite_over(s, d) of DESIGN.md 3.5 with s the 8-bit word the
+ *     same call writes with the option off -- in whichever intermediate BT709HIP_OPT_SCALE_INTERMEDIATE selects -- bit for bit
+ *     "decode_scaled, then blend" (definition: DESIGN.md 3.6), whatever BT709HIP_OPT_COMPOSITE_OVER holds; off, nothing changes,
+ *     the refusal under BT709HIP_OPT_COMPOSITE_OVER included;
+ *   - the 1:1 decode never reads it; bt709hip_render_scaled has no decoder and does not blend.
+ * On, bt709hip_decode_half[_batch] runs the any-ratio kernel at ratio 2.0 (as under BT709HIP_FORMAT_RGBA16F above: no persistent
+ * 2:1 variant, the half-kernel options ignored) and equals bt709hip_decode_scaled at exactly half.  Validation, limits and
+ * bt709hip_last_scaled_launch_info are the plain rescale's.  bt709hip_last_kernel_name: "decode_nv12_scaled<alpha,over>" /
+ * "decode_nv12_scaled<alpha,over-colour>", "decode_nv12_scaled_f16<alpha,over>" / "decode_nv12_scaled_f16<alpha,over-colour>". */
 #define BT709HIP_OVER_OFF (-1)
 #define BT709HIP_OVER_DESTINATION (-2)
 

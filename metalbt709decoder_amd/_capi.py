@@ -41,6 +41,7 @@ OPT_COALESCE = 6
 OPT_COALESCE_MAX_AGE_US = 7
 OPT_SCALE_INTERMEDIATE = 8  # value: FORMAT_BGRA8_SRGB (default) or FORMAT_RGBA16F
 OPT_COMPOSITE_OVER = 9  # alpha decoders: OVER_OFF (default), OVER_DESTINATION, or an sRGB colour R<<16 | G<<8 | B
+OPT_SCALED_OVER = 10  # alpha decoders, the rescale paths (decode_scaled / decode_half): the same three forms, held separately
 OVER_OFF = -1
 OVER_DESTINATION = -2
 CTX_OPT_GRID_MULT = 1

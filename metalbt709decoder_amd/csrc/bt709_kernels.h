@@ -97,8 +97,9 @@ struct DecodeParams {
   uint32_t half_table_bytes, half_cand_offset, half_h_min;
   float half_index_scale;
   const void *half_table;
-  // BT709HIP_OPT_COMPOSITE_OVER (alpha decoders, the 1:1 kernels): the decoded word goes source-over a
-  // background in linear light before it is stored.  over_mode selects the *_over kernels in launch_decode; over_table_lin is
+  // BT709HIP_OPT_COMPOSITE_OVER (alpha decoders, the 1:1 kernels) and BT709HIP_OPT_SCALED_OVER (the any-ratio
+  // rescale kernels; 3.6): the word goes source-over a background in linear light before it is stored.  over_mode selects the
+  // *_over kernels in launch_decode / launch_decode_scaled (each filled by the shim from its own option); over_table_lin is
   // lin[256] = sRGB_nonLinearNormToLinear(byteNorm(b)) as floats (the encode side is table_encode); kOverColour: the three
   // lin[] of the solid colour's R, G, B, looked up on the host
   uint32_t over_mode;  // kOverOff / kOverDestination / kOverColour

@@ -29,6 +29,7 @@
 
 #include "bt709_device.h"
 #include "bt709_launch.h"
+#include "bt709_over.h"
 
 namespace bt709 {
 namespace {
@@ -102,22 +103,9 @@ __device__ __forceinline__ void decode_block(const UnitLookup &u, const float y[
 
 // ---------------------------------------------------------------------------
 // BT709HIP_OPT_COMPOSITE_OVER: an alpha decoder's word goes source-over a background in linear light, the
-// two-pass equivalent of "decode, then blend the 8-bit result".  Per pixel, s the word the plain alpha decode writes, d the
-// background (what the output held, or a solid colour with A_d = 255), every float operation rounded on its own:
-//     k     = float(255 - A_s) * (1/255f)                    byteNorm of the complement (sRGB.h:32-36)
-//     v_c   = min(1, lin[s_c] + k * lin[d_c])                lin[b] = sRGB_nonLinearNormToLinear(byteNorm(b)), the colour premultiplied
-//     out_c = the LINEAR-mode composite of v_c               the rescale kernels' log-bucket encode table
-//     out_A = A_s + ((255 - A_s) * A_d + 127) / 255          integer
+// two-pass equivalent of "decode, then blend the 8-bit result".  The blend itself: bt709_over.h (shared with the rescale kernels).
 // LDS: the encode table (DecodeParams::table_encode, ~5 KiB) and lin[256] (1 KiB) behind it.
 // ---------------------------------------------------------------------------
-typedef __attribute__((address_space(3))) const float *LdsFloatPtr;  // ds_read_b32
-
-struct OverLookup {
-  float enc_add;     // encode table: bucket of v = (bits(v + enc_add) >> 16) - first
-  uint32_t enc_off;  // its LDS address - (first << 3)
-  uint32_t lin_off;  // LDS address of lin[256]
-};
-
 // Stages both tables (the caller synchronises) and returns the lookup constants.
 __device__ __forceinline__ OverLookup stage_over_tables(unsigned char *lds_raw, const DecodeParams &p) {
   stage_table(lds_raw, p.table_encode, p.table_encode_bytes);
@@ -129,39 +117,12 @@ __device__ __forceinline__ OverLookup stage_over_tables(unsigned char *lds_raw, 
   return o;
 }
 
-__device__ __forceinline__ float over_lin(const OverLookup &o, uint32_t byte) {
-  return *reinterpret_cast<LdsFloatPtr>((byte << 2) + o.lin_off);
-}
-
-// sRGB byte of a linear-light v in [0, 1]: the index is a plain add (the host files the thresholds under the same one,
-// transfer_tables.cpp bucket_index_log), the bucket's edge settles it
-__device__ __forceinline__ uint32_t over_encode(const OverLookup &o, float v) {
-  const uint32_t t = __float_as_uint(__fadd_rn(v, o.enc_add)) >> 16;
-  const u32x2 e = *reinterpret_cast<LdsPairPtr>((t << 3) + o.enc_off);
-  return e.y + (v >= __uint_as_float(e.x) ? 1u : 0u);
-}
-
 // One pixel: x = its saturated R, G, B (pixel_rgb), abyte its alpha-frame sample, bg the background word (kOverDestination) --
 // colour_lin the background's three linear values otherwise.
 template <int OVER>
 __device__ __forceinline__ uint32_t over_pixel(const OverLookup &o, const float *colour_lin, const float *x, float abyte, uint32_t bg) {
-  const uint32_t as = quantise_byte(alpha_value(abyte)), inv = 255u - as;
-  const float k = __fmul_rn(static_cast<float>(inv), kInv255);
-  float d[3];
-  uint32_t a = 255u;  // an opaque background: A_s + (255 - A_s)
-  if (OVER == kOverDestination) {
-    d[0] = over_lin(o, (bg >> 16) & 0xffu);
-    d[1] = over_lin(o, (bg >> 8) & 0xffu);
-    d[2] = over_lin(o, bg & 0xffu);
-    a = as + (inv * (bg >> 24) + 127u) / 255u;
-  } else {
-    d[0] = colour_lin[0], d[1] = colour_lin[1], d[2] = colour_lin[2];
-  }
-  uint32_t byte[3];
-#pragma unroll
-  for (int c = 0; c < 3; ++c)  // the sum is in [0, 2): the add's clamp is the min with 1
-    byte[c] = over_encode(o, add_sat(over_lin(o, quantise_byte(x[c])), __fmul_rn(k, d[c])));
-  return pack_bgra(byte[0], byte[1], byte[2], a << 24);
+  return over_blend<OVER>(o, colour_lin, quantise_byte(x[0]), quantise_byte(x[1]), quantise_byte(x[2]), quantise_byte(alpha_value(abyte)), bg,
+                          [&](float v) { return over_encode(o, v); });
 }
 
 // decode_quad's pixels through over_pixel; bt / bb: what the output's two rows held (kOverDestination)

@@ -193,7 +193,7 @@ __device__ __forceinline__ uint32_t half_alpha_arith(float a00, float a01, float
 hipError_t prepare_scaled_kernels();  // bt709_rescale_scaled.hip; called by prepare_rescale_kernels (bt709_rescale_half.hip)
 // bt709_rescale_f16.hip: the any-ratio kernel through the RGBA16Float intermediate (DecodeParams::scale_f16), launched by
 // launch_decode_scaled under its own plan -- the instantiation for a tap form, the dynamic LDS it needs
-const void *scaled_f16_kernel(int taps, bool has_alpha, bool curve);
+const void *scaled_f16_kernel(int taps, bool has_alpha, bool curve, uint32_t over = 0);  // over: kOverOff, or the *_over form of that mode (alpha decoders)
 size_t scaled_f16_lds(const DecodeParams &p);
 hipError_t prepare_scaled_f16_kernels();  // called by prepare_scaled_kernels
 

@@ -49,6 +49,7 @@ struct HalfLight {
     }
   }
   __device__ __forceinline__ uint32_t encode(float sum) const { return encode_byte(r, add_sat(sum, 0.0f)); }
+  __device__ __forceinline__ uint32_t encode_unit(float v) const { return encode_byte(r, v); }  // the blend's v: the table's own domain
   // Without an alpha plane pass 1 stores A = 1.0 and pass 2 filters four taps of it: alpha_word_of(((w00 + w01) + w10) + w11)
   // with w00 = gx gy, w01 = fx gy, w10 = gx fy, w11 = fx fy, gx = RN(1 - fx), gy = RN(1 - fy), fx, fy in [0, 1).  That is 255 for
   // EVERY weight set, so the constant is stored: gx + fx and gy + fy are within 2^-25 of 1 (1 - f is exact for f >= 1/2 and
@@ -59,49 +60,67 @@ struct HalfLight {
 
 }  // namespace
 
+// The kernel's body as TEXT: decode_nv12_scaled_f16_over below is the same kernel with lin[256] of the blend behind the encode
+// buckets and the strips in their over form, and the body has to sit in the kernel function itself (bt709_rescale_scaled.hip,
+// BT709_SCALED_WALK: the plain kernels' instruction streams are pinned).
+#define BT709_SCALED_F16_BODY(HAS_ALPHA, CURVE, OVER)                                                                                    \
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];                                                                \
+  constexpr uint32_t kEncodeLds = CURVE ? kHalfPlanLds : 0u;                                                                             \
+  OverLookup ov = {};                                                                                                                    \
+  {                                                                                                                                      \
+    if (CURVE) stage_half_tables(lds_raw, p.half_table, p.half_cand_offset, p.half_table_bytes);                                         \
+    const u32x4 *e = reinterpret_cast<const u32x4 *>(p.table_encode);                                                                    \
+    stage_batched(reinterpret_cast<u32x4 *>(lds_raw + kEncodeLds), p.table_encode_bytes / 16, threadIdx.x, blockDim.x, [&](uint32_t i) { return e[i]; }); \
+    /* the half lookup addresses LDS absolutely: this kernel has no static LDS, so its dynamic segment starts at byte 0 */               \
+    if (CURVE && lds_address(lds_raw) != 0u) __builtin_trap();                                                                           \
+    if constexpr (OVER != kOverOff) ov = stage_over_lin(lds_raw, p, kEncodeLds + p.table_encode_bytes);                                  \
+  }                                                                                                                                      \
+  __syncthreads();                                                                                                                       \
+  RescaleLookup r = {};                                                                                                                  \
+  r.enc_shift = 3;                                                                                                                       \
+  r.enc_off = lds_address(lds_raw) + kEncodeLds;                                                                                         \
+  r.enc_add = p.encode_log_add;                                                                                                          \
+  r.enc_log_off = r.enc_off - (p.encode_log_first << r.enc_shift);                                                                       \
+  asm volatile("" : "+v"(r.enc_log_off)); /* ONE addend of the v_lshl_add */                                                             \
+  r.quarter_unscale = 1.0f;               /* the sums are unit-range values: the table's own domain */                                   \
+  HalfLookup t;                                                                                                                          \
+  t.index_scale = p.half_index_scale;                                                                                                    \
+  t.below2 = (p.half_h_min - 1u) * 0x10001u;                                                                                             \
+  const HalfLight<CURVE> light = {t, r};                                                                                                 \
+  /* the persistent item loop of decode_nv12_scaled: an item = 256 columns x one strip of one frame, column tiles fastest */             \
+  const uint32_t strips = (p.out_height + p.scaled_rows - 1) / p.scaled_rows;                                                            \
+  for (uint32_t item = blockIdx.x; item < p.tile_rows; item += gridDim.x) {                                                              \
+    const uint32_t tile = item % p.tiles_x, rest = item / p.tiles_x;                                                                     \
+    const uint32_t strip = rest % strips, frame = rest / strips;                                                                         \
+    const FramePlanes f = frame_planes(p, frame);                                                                                        \
+    const uint32_t ox = tile * blockDim.x + threadIdx.x;                                                                                 \
+    const uint32_t oy0 = strip * p.scaled_rows;                                                                                          \
+    const StripTaps vt = strip_taps(oy0, p.scale_y); /* before any lane is masked off */                                                 \
+    if (TAPS == TAPS_SHARED || TAPS == TAPS_ONCE || ox < p.out_width)                                                                    \
+      scaled_strip<TAPS, HAS_ALPHA, OVER>(p, light, f, ox, oy0, min(oy0 + p.scaled_rows, p.out_height), vt, ov);                         \
+  }
+
 template <int TAPS, bool HAS_ALPHA, bool CURVE>
 __global__ void __launch_bounds__(kBlockThreads)
 decode_nv12_scaled_f16(const DecodeParams p) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-  constexpr uint32_t kEncodeLds = CURVE ? kHalfPlanLds : 0u;
-  {
-    if (CURVE) stage_half_tables(lds_raw, p.half_table, p.half_cand_offset, p.half_table_bytes);
-    const u32x4 *e = reinterpret_cast<const u32x4 *>(p.table_encode);
-    stage_batched(reinterpret_cast<u32x4 *>(lds_raw + kEncodeLds), p.table_encode_bytes / 16, threadIdx.x, blockDim.x, [&](uint32_t i) { return e[i]; });
-    // the half lookup addresses LDS absolutely: this kernel has no static LDS, so its dynamic segment starts at byte 0
-    if (CURVE && lds_address(lds_raw) != 0u) __builtin_trap();
-  }
-  __syncthreads();
-  RescaleLookup r = {};
-  r.enc_shift = 3;
-  r.enc_off = lds_address(lds_raw) + kEncodeLds;
-  r.enc_add = p.encode_log_add;
-  r.enc_log_off = r.enc_off - (p.encode_log_first << r.enc_shift);
-  asm volatile("" : "+v"(r.enc_log_off));  // ONE addend of the v_lshl_add
-  r.quarter_unscale = 1.0f;                // the sums are unit-range values: the table's own domain
-  HalfLookup t;
-  t.index_scale = p.half_index_scale;
-  t.below2 = (p.half_h_min - 1u) * 0x10001u;
-  const HalfLight<CURVE> light = {t, r};
-
-  // the persistent item loop of decode_nv12_scaled: an item = 256 columns x one strip of one frame, column tiles fastest
-  const uint32_t strips = (p.out_height + p.scaled_rows - 1) / p.scaled_rows;
-  for (uint32_t item = blockIdx.x; item < p.tile_rows; item += gridDim.x) {
-    const uint32_t tile = item % p.tiles_x, rest = item / p.tiles_x;
-    const uint32_t strip = rest % strips, frame = rest / strips;
-    const FramePlanes f = frame_planes(p, frame);
-    const uint32_t ox = tile * blockDim.x + threadIdx.x;
-    const uint32_t oy0 = strip * p.scaled_rows;
-    const StripTaps vt = strip_taps(oy0, p.scale_y);  // before any lane is masked off
-    if (TAPS == TAPS_SHARED || TAPS == TAPS_ONCE || ox < p.out_width)
-      scaled_strip<TAPS, HAS_ALPHA>(p, light, f, ox, oy0, min(oy0 + p.scaled_rows, p.out_height), vt);
-  }
+  BT709_SCALED_F16_BODY(HAS_ALPHA, CURVE, kOverOff)
 }
 
+// BT709HIP_OPT_SCALED_OVER through the RGBA16Float intermediate: an alpha decoder runs the sRGB mode, which has a
+// curve.  46 KiB of LDS: still three workgroups per CU.  Kernels of their own: the plain instantiations keep their code.
+template <int TAPS, int OVER>
+__global__ void __launch_bounds__(kBlockThreads)
+decode_nv12_scaled_f16_over(const DecodeParams p) {
+  BT709_SCALED_F16_BODY(true, true, OVER)
+}
+#undef BT709_SCALED_F16_BODY
+
 // An alpha decoder runs the sRGB mode, which has a curve: 5 tap forms x (curve, curve + alpha, no curve)
-const void *scaled_f16_kernel(int taps, bool has_alpha, bool curve) {
+const void *scaled_f16_kernel(int taps, bool has_alpha, bool curve, uint32_t over) {
 #define BT709_PICK_F16(T)                                                                                        \
   case T:                                                                                                        \
+    if (has_alpha && over == kOverDestination) return reinterpret_cast<const void *>(&decode_nv12_scaled_f16_over<T, kOverDestination>); \
+    if (has_alpha && over != kOverOff) return reinterpret_cast<const void *>(&decode_nv12_scaled_f16_over<T, kOverColour>);               \
     return has_alpha ? reinterpret_cast<const void *>(&decode_nv12_scaled_f16<T, true, true>)                    \
                      : (curve ? reinterpret_cast<const void *>(&decode_nv12_scaled_f16<T, false, true>)          \
                               : reinterpret_cast<const void *>(&decode_nv12_scaled_f16<T, false, false>))
@@ -120,9 +139,11 @@ size_t scaled_f16_lds(const DecodeParams &p) {
 }
 
 hipError_t prepare_scaled_f16_kernels() {
-  const void *fns[15];
+  const void *fns[25];
   int n = 0;
   for (int taps : {TAPS_BYTES, TAPS_PAIRS, TAPS_WIDE, TAPS_SHARED, TAPS_ONCE}) {
+    fns[n++] = scaled_f16_kernel(taps, true, true, kOverDestination);
+    fns[n++] = scaled_f16_kernel(taps, true, true, kOverColour);
     fns[n++] = scaled_f16_kernel(taps, true, true);
     fns[n++] = scaled_f16_kernel(taps, false, true);
     fns[n++] = scaled_f16_kernel(taps, false, false);

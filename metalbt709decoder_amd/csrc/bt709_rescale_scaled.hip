@@ -3,6 +3,7 @@
 // Renderer/AAPLShaders.metal:73-85).  Arithmetic and tables: bt709_rescale.h.
 //
 //   decode_nv12_scaled     any output size, bilinear taps, one lane per output column walking strips of rows
+//   decode_nv12_scaled_over   the same for an alpha decoder, each word blended over the destination or a colour before the store
 //   render_scaled          pass 2 alone from an 8-bit or RGBA16Float intermediate
 // Both walk a strip with walk_strip; each keeps its own fetch, its own conversion to linear light, its encode and its store.
 #include <atomic>
@@ -47,6 +48,32 @@ namespace bt709 {
 //  No one-generation cut of short launches: one 4K -> 1440p frame 19.6 against 18.8 us (profiles/r06_ab_scaled_ahead.txt).)
 
 
+// The kernel's walk behind its staged tables, as TEXT: decode_nv12_scaled_over below runs the same walk with scaled_strip in its
+// over form, and the walk has to sit in the kernel function itself -- in a function that both kernels call, hipcc takes blockIdx /
+// blockDim through the generic implicit-argument code and schedules the plain kernels' persistent forms differently, and their
+// instruction streams are pinned (profiles/LAB.md, "Round 11").
+#define BT709_SCALED_WALK(HAS_ALPHA, OVER, ov)                                                                                           \
+  if (PERSISTENT) {                                                                                                                      \
+    const uint32_t strips = (p.out_height + p.scaled_rows - 1) / p.scaled_rows;                                                          \
+    for (uint32_t item = blockIdx.x; item < p.tile_rows; item += gridDim.x) {                                                            \
+      const uint32_t tile = item % p.tiles_x, rest = item / p.tiles_x;                                                                   \
+      const uint32_t strip = rest % strips, frame = rest / strips;                                                                       \
+      const FramePlanes f = frame_planes(p, frame);                                                                                      \
+      const uint32_t ox = tile * blockDim.x + threadIdx.x;                                                                               \
+      const uint32_t oy0 = strip * p.scaled_rows;                                                                                        \
+      const StripTaps vt = strip_taps(oy0, p.scale_y); /* before any lane is masked off */                                               \
+      if (TAPS == TAPS_SHARED || TAPS == TAPS_ONCE || ox < p.out_width)                                                                  \
+        scaled_strip<TAPS, HAS_ALPHA, OVER>(p, Srgb8Light{r}, f, ox, oy0, min(oy0 + p.scaled_rows, p.out_height), vt, ov);               \
+    }                                                                                                                                    \
+    return;                                                                                                                              \
+  }                                                                                                                                      \
+  const FramePlanes f = frame_planes(p, blockIdx.z);                                                                                     \
+  const uint32_t ox = blockIdx.x * blockDim.x + threadIdx.x;                                                                             \
+  const uint32_t oy0 = blockIdx.y * p.scaled_rows; /* < out_height: the grid has exactly the strips */                                   \
+  const StripTaps vt = strip_taps(oy0, p.scale_y); /* before any lane leaves */                                                          \
+  if (TAPS != TAPS_SHARED && TAPS != TAPS_ONCE && ox >= p.out_width) return; /* TAPS_SHARED / TAPS_ONCE: the wave works together */      \
+  scaled_strip<TAPS, HAS_ALPHA, OVER>(p, Srgb8Light{r}, f, ox, oy0, min(oy0 + p.scaled_rows, p.out_height), vt, ov)
+
 // A workgroup = 256 output columns x one strip of `scaled_rows` output rows of one frame; its waves share nothing but
 // the single-copy tables (14 KiB staged per workgroup).
 // PERSISTENT: the launch has as many workgroups as the chip holds at once and workgroup g takes the work items g,
@@ -60,27 +87,22 @@ decode_nv12_scaled(const DecodeParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   const RescaleLookup r = stage_rescale_tables<false>(lds_raw, p, 0, 0, 0);
   __syncthreads();
-  if (PERSISTENT) {
-    const uint32_t strips = (p.out_height + p.scaled_rows - 1) / p.scaled_rows;
-    for (uint32_t item = blockIdx.x; item < p.tile_rows; item += gridDim.x) {
-      const uint32_t tile = item % p.tiles_x, rest = item / p.tiles_x;
-      const uint32_t strip = rest % strips, frame = rest / strips;
-      const FramePlanes f = frame_planes(p, frame);
-      const uint32_t ox = tile * blockDim.x + threadIdx.x;
-      const uint32_t oy0 = strip * p.scaled_rows;
-      const StripTaps vt = strip_taps(oy0, p.scale_y);  // before any lane is masked off
-      if (TAPS == TAPS_SHARED || TAPS == TAPS_ONCE || ox < p.out_width)
-        scaled_strip<TAPS, HAS_ALPHA>(p, Srgb8Light{r}, f, ox, oy0, min(oy0 + p.scaled_rows, p.out_height), vt);
-    }
-    return;
-  }
-  const FramePlanes f = frame_planes(p, blockIdx.z);
-  const uint32_t ox = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t oy0 = blockIdx.y * p.scaled_rows;  // < out_height: the grid has exactly the strips
-  const StripTaps vt = strip_taps(oy0, p.scale_y);  // before any lane leaves
-  if (TAPS != TAPS_SHARED && TAPS != TAPS_ONCE && ox >= p.out_width) return;  // TAPS_SHARED / TAPS_ONCE: the wave works together
-  scaled_strip<TAPS, HAS_ALPHA>(p, Srgb8Light{r}, f, ox, oy0, min(oy0 + p.scaled_rows, p.out_height), vt);
+  BT709_SCALED_WALK(HAS_ALPHA, kOverOff, OverLookup{});
 }
+
+// BT709HIP_OPT_SCALED_OVER (alpha decoders): decode_nv12_scaled<TAPS, true, PERSISTENT> whose strips blend each word
+// source-over the destination or a colour before they store it (scaled_strip's over form).  lin[256] rides behind the two tables:
+// 15 KiB per workgroup.  Kernels of their own: the plain instantiations keep their code.
+template <int TAPS, bool PERSISTENT, int OVER>
+__global__ void __launch_bounds__(kBlockThreads)
+decode_nv12_scaled_over(const DecodeParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+  const RescaleLookup r = stage_rescale_tables<false>(lds_raw, p, 0, 0, 0);
+  const OverLookup ov = stage_over_lin(lds_raw, p, p.table_linear_bytes + p.table_encode_bytes);
+  __syncthreads();
+  BT709_SCALED_WALK(true, OVER, ov);
+}
+#undef BT709_SCALED_WALK
 
 // ---------------------------------------------------------------------------
 // Pass 2 ALONE: -[MetalScaleRenderContext renderScaled:...] + samplingShader
@@ -221,9 +243,12 @@ int scaled_taps(const DecodeParams &p, uint32_t in_align) {
 }
 
 // the by-wave forms run one workgroup per item (dispatched by the hardware), the per-lane forms persistent workgroups
-const void *scaled_kernel(int taps, bool has_alpha) {
-#define BT709_PICK_SCALED(T, P) \
-  case T: return has_alpha ? reinterpret_cast<const void *>(&decode_nv12_scaled<T, true, P>) : reinterpret_cast<const void *>(&decode_nv12_scaled<T, false, P>)
+const void *scaled_kernel(int taps, bool has_alpha, uint32_t over = kOverOff) {
+#define BT709_PICK_SCALED(T, P)                                                                                                            \
+  case T:                                                                                                                                  \
+    if (over == kOverDestination) return reinterpret_cast<const void *>(&decode_nv12_scaled_over<T, P, kOverDestination>);                 \
+    if (over != kOverOff) return reinterpret_cast<const void *>(&decode_nv12_scaled_over<T, P, kOverColour>);                              \
+    return has_alpha ? reinterpret_cast<const void *>(&decode_nv12_scaled<T, true, P>) : reinterpret_cast<const void *>(&decode_nv12_scaled<T, false, P>)
   switch (taps) {
     BT709_PICK_SCALED(TAPS_ONCE, false);
     BT709_PICK_SCALED(TAPS_SHARED, false);
@@ -319,8 +344,11 @@ const char *launch_decode_scaled(const DecodeParams &p_in, int frames, bool has_
   if (by_wave && rows > static_cast<uint32_t>(kScaledAheadWave + 1)) rows -= rows % static_cast<uint32_t>(kScaledAheadWave + 1);
   const size_t lds = f16 ? scaled_f16_lds(p) : static_cast<size_t>(p.table_linear_bytes) + p.table_encode_bytes;
   const dim3 block(kBlockThreads);
-  const void *fn = f16 ? scaled_f16_kernel(taps, has_alpha, p.half_table_bytes != 0) : scaled_kernel(taps, has_alpha);
-  const uint64_t resident = resident_workgroups(fn, lds, cus);
+  // BT709HIP_OPT_SCALED_OVER: the *_over kernels (the one launched is the one whose occupancy sizes the grid), lin[256] behind their tables
+  const uint32_t over = has_alpha ? p.over_mode : kOverOff;
+  const size_t lds_launch = lds + (over != kOverOff ? kOverLinBytes : 0u);
+  const void *fn = f16 ? scaled_f16_kernel(taps, has_alpha, p.half_table_bytes != 0, over) : scaled_kernel(taps, has_alpha, over);
+  const uint64_t resident = resident_workgroups(fn, lds_launch, cus);
   const uint32_t balanced_rows = one_generation_rows(cols, p.out_height, nframes, resident, max_rows, by_wave);
   if (balanced_rows) rows = balanced_rows;
   p.scaled_rows = rows;
@@ -336,7 +364,9 @@ const char *launch_decode_scaled(const DecodeParams &p_in, int frames, bool has_
   record_scaled_launch(ScaledLaunchRecord{{grid.x, grid.y, grid.z}, {block.x, block.y, block.z}, static_cast<uint32_t>(taps), rows, persistent ? 1u : 0u,
                                           balanced_rows ? 1u : 0u, static_cast<uint32_t>(resident), 0, items});
   void *args[] = {&p};
-  (void)hipLaunchKernel(fn, grid, block, args, lds, stream);  // a failure is picked up by the caller's hipGetLastError
+  (void)hipLaunchKernel(fn, grid, block, args, lds_launch, stream);  // a failure is picked up by the caller's hipGetLastError
+  if (over == kOverDestination) return f16 ? "decode_nv12_scaled_f16<alpha,over>" : "decode_nv12_scaled<alpha,over>";
+  if (over != kOverOff) return f16 ? "decode_nv12_scaled_f16<alpha,over-colour>" : "decode_nv12_scaled<alpha,over-colour>";
   if (f16) return has_alpha ? "decode_nv12_scaled_f16<alpha>" : "decode_nv12_scaled_f16";
   return has_alpha ? "decode_nv12_scaled<alpha>" : "decode_nv12_scaled";
 }
@@ -347,6 +377,10 @@ hipError_t prepare_scaled_kernels() {
       scaled_kernel(TAPS_SHARED, false), scaled_kernel(TAPS_ONCE, false),
       scaled_kernel(TAPS_BYTES, true), scaled_kernel(TAPS_PAIRS, true), scaled_kernel(TAPS_WIDE, true),
       scaled_kernel(TAPS_SHARED, true), scaled_kernel(TAPS_ONCE, true),
+      scaled_kernel(TAPS_BYTES, true, kOverDestination), scaled_kernel(TAPS_PAIRS, true, kOverDestination), scaled_kernel(TAPS_WIDE, true, kOverDestination),
+      scaled_kernel(TAPS_SHARED, true, kOverDestination), scaled_kernel(TAPS_ONCE, true, kOverDestination),
+      scaled_kernel(TAPS_BYTES, true, kOverColour), scaled_kernel(TAPS_PAIRS, true, kOverColour), scaled_kernel(TAPS_WIDE, true, kOverColour),
+      scaled_kernel(TAPS_SHARED, true, kOverColour), scaled_kernel(TAPS_ONCE, true, kOverColour),
       reinterpret_cast<const void *>(&render_scaled<true>),
       reinterpret_cast<const void *>(&render_scaled<false>),
   };

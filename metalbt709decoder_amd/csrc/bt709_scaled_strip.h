@@ -3,6 +3,7 @@
 // row_taps), the row cache and the filter (RowCache), the strip walk (walk_strip) and the fused kernels' strip (scaled_strip:
 // fetch, tap forms, store) -- one copy of each, so the kernels agree bit for bit on taps, weights and summation order.
 #pragma once
+#include "bt709_over.h"
 #include "bt709_rescale.h"
 
 namespace bt709 {
@@ -223,6 +224,15 @@ __device__ __forceinline__ void walk_strip(const StripTaps &vt, uint32_t oy0, ui
   }
 }
 
+// lin[256] of the blend (DecodeParams::over_table_lin, 1 KiB) into LDS at byte `at` of the dynamic segment; the caller synchronises
+__device__ __forceinline__ OverLookup stage_over_lin(unsigned char *lds_raw, const DecodeParams &p, uint32_t at) {
+  const u32x4 *l = reinterpret_cast<const u32x4 *>(p.over_table_lin);
+  stage_batched(reinterpret_cast<u32x4 *>(lds_raw + at), kOverLinBytes / 16, threadIdx.x, blockDim.x, [&](uint32_t i) { return l[i]; });
+  OverLookup ov = {};  // the encode side is the kernel's own table (TapLight::encode_unit)
+  ov.lin_off = lds_address(lds_raw) + at;
+  return ov;
+}
+
 // The 8-bit sRGB intermediate: a tap is decoded to its byte and linearised as the sRGB8 sampler does (one lookup, times 2^-40:
 // bt709_rescale.h), an alpha tap is byteNorm of its decoded byte, the sums go to the encode table as they are (edges staged in
 // the sums' domain), and a decoder without an alpha channel writes its alpha fill.
@@ -247,6 +257,11 @@ struct Srgb8Light {
     }
   }
   __device__ __forceinline__ uint32_t encode(float sum) const { return encode_byte(r, sum); }
+  // the blend's unit-range v (the over form of scaled_strip): into the sums' domain, where this table's edges are staged -- times
+  // 2^-40, exact on both sides of the comparison, and the index fma's product gives v back
+  __device__ __forceinline__ uint32_t encode_unit(float v) const {
+    return encode_byte(r, __fmul_rn(v, __uint_as_float(static_cast<uint32_t>(127 + kLinearScaleLog2) << 23)));
+  }
   __device__ __forceinline__ uint32_t opaque_word(const DecodeParams &p) const { return p.alpha_word; }
 };
 
@@ -271,9 +286,16 @@ struct Srgb8Light {
 //     call; `live` masks the store.
 //   TapLight: what a decoded tap is when the filter sees it, and what becomes of the filter's sums -- Srgb8Light below (the 8-bit
 //     sRGB intermediate of decode_nv12_scaled) or HalfLight (bt709_rescale_f16.hip: the RGBA16Float intermediate).
-template <int TAPS, bool HAS_ALPHA, typename TapLight>
-__device__ __forceinline__ void scaled_strip(const DecodeParams &p, const TapLight &light,
-                                             const FramePlanes &f, uint32_t ox_raw, uint32_t oy0, uint32_t oy1, const StripTaps &vt) {
+//   OVER (kOverDestination / kOverColour; alpha decoders: BT709HIP_OPT_SCALED_OVER): the row's word -- the BYTES the
+//     plain form stores -- goes through bt709_over.h over_blend before the store, `ov` locating lin[256] in LDS.  The epilogue sees
+//     bytes only, so it is the same for both intermediates; its encode is the TapLight's own table (encode_unit).  Destination
+//     mode: the lane loads the word it is about to overwrite at the top of output_row (the row's conversion and filter hide the
+//     latency; the wait also covers the rows fetched ahead, issued before it -- vmcnt is in order).  A by-wave lane past the row's
+//     end loads the last column's word again (in bounds) and drops it with its store.
+template <int TAPS, bool HAS_ALPHA, int OVER = kOverOff, typename TapLight>
+__device__ __forceinline__ void scaled_strip(const DecodeParams &p, const TapLight &light, const FramePlanes &f, uint32_t ox_raw, uint32_t oy0,
+                                             uint32_t oy1, const StripTaps &vt, const OverLookup &ov = OverLookup{}) {
+  static_assert(OVER == kOverOff || HAS_ALPHA, "there is nothing to composite without an alpha channel");
   // TAPS_SHARED / TAPS_ONCE: every lane of the wave stays alive; one past the row's end works on the last column again and does not store
   constexpr bool BY_WAVE = TAPS == TAPS_SHARED || TAPS == TAPS_ONCE;
   constexpr int N = HAS_ALPHA ? 4 : 3;  // R, G, B and the byteNorm of the alpha tap (alpha decoders)
@@ -430,12 +452,20 @@ __device__ __forceinline__ void scaled_strip(const DecodeParams &p, const TapLig
   RowCache<N> cache;
   // one output row from the fetched bytes of its two source rows
   auto output_row = [&](uint32_t oy, const RowTaps &rt, const Fetched1 &f0, const Fetched1 &f1) {
+    uint32_t bg = 0u;  // what the output holds: read once, by the lane that writes it
+    if constexpr (OVER == kOverDestination) bg = __builtin_amdgcn_raw_buffer_load_b32(ro, ox * 4u, oy * p.out_stride, kScaledStoreAux);
     float acc[N];
     cache.filter(ct, rt, f0, f1, decode_row, acc);
     const uint32_t R = light.encode(acc[0]);
     const uint32_t G = light.encode(acc[1]);
     const uint32_t B = light.encode(acc[2]);
     const uint32_t aw = HAS_ALPHA ? alpha_word_of(acc[N - 1]) : light.opaque_word(p);
+    if constexpr (OVER != kOverOff) {
+      if (!BY_WAVE || live)
+        __builtin_amdgcn_raw_buffer_store_b32(over_blend<OVER>(ov, p.over_lin, R, G, B, aw >> 24, bg, [&](float v) { return light.encode_unit(v); }), ro,
+                                              ox * 4u, oy * p.out_stride, kScaledStoreAux);
+      return;
+    }
     if (!BY_WAVE || live)
       __builtin_amdgcn_raw_buffer_store_b32(pack_bgra(R, G, B, aw), ro, ox * 4u, oy * p.out_stride, kScaledStoreAux);
   };

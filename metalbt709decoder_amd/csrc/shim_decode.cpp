@@ -89,8 +89,8 @@ int ensure_half_table(bt709hip_decoder *dec, void *stream) {
   return BT709HIP_OK;
 }
 
-// lin[256] of the composite-over kernels (BT709HIP_OPT_COMPOSITE_OVER), built by the first setup or decode that finds the
-// option on; not while recording a graph.  dec->setup_mutex held.
+// lin[256] of the composite-over kernels (BT709HIP_OPT_COMPOSITE_OVER, BT709HIP_OPT_SCALED_OVER), built by the first setup or
+// decode that finds one of the options on; not while recording a graph.  dec->setup_mutex held.
 static int build_over_table(bt709hip_decoder *dec, void *stream) {
   if (dec->d_over_lin.load(std::memory_order_acquire) != nullptr) return BT709HIP_OK;
   if (capturing(static_cast<hipStream_t>(stream))) return BT709HIP_ERR_NOT_SETUP;
@@ -106,6 +106,16 @@ int ensure_over_table(bt709hip_decoder *dec, void *stream) {
   if (dec->d_over_lin.load(std::memory_order_acquire) != nullptr) return BT709HIP_OK;
   std::lock_guard<std::mutex> lock(dec->setup_mutex);
   return build_over_table(dec, stream);
+}
+
+// The blend's fields of a launch (`over`: BT709HIP_OVER_DESTINATION or a colour): the table, the mode, the colour's linear values
+static int set_over(DecodeParams *p, bt709hip_decoder *dec, int over, void *stream) {
+  if (int rc = ensure_over_table(dec, stream)) return rc;
+  p->over_table_lin = dec->d_over_lin.load(std::memory_order_acquire);
+  p->over_mode = over == BT709HIP_OVER_DESTINATION ? kOverDestination : kOverColour;
+  if (over >= 0)  // the entries of the kernels' own table
+    for (int c = 0; c < 3; ++c) p->over_lin[c] = srgb_to_linear(static_cast<float>((over >> (16 - 8 * c)) & 0xff) * (1.0f / 255.0f));
+  return BT709HIP_OK;
 }
 
 // Table pointers and lookup constants of a launch.
@@ -238,6 +248,11 @@ int bt709hip_decoder_set_option(bt709hip_decoder *dec, int option, int value) {
       if (!dec->has_alpha) return BT709HIP_ERR_UNSUPPORTED;  // nothing to composite
       dec->composite_over = value;
       return BT709HIP_OK;
+    case BT709HIP_OPT_SCALED_OVER:  // the same domain and refusals, a value of its own
+      if (value != BT709HIP_OVER_OFF && value != BT709HIP_OVER_DESTINATION && (value < 0 || value > 0xFFFFFF)) return BT709HIP_ERR_INVALID_ARG;
+      if (!dec->has_alpha) return BT709HIP_ERR_UNSUPPORTED;
+      dec->scaled_over = value;
+      return BT709HIP_OK;
     default: return BT709HIP_ERR_INVALID_ARG;
   }
 }
@@ -254,6 +269,7 @@ int bt709hip_decoder_get_option(const bt709hip_decoder *dec, int option, int *va
     case BT709HIP_OPT_COALESCE_MAX_AGE_US: *value = dec->coalesce_max_age_us; return BT709HIP_OK;
     case BT709HIP_OPT_SCALE_INTERMEDIATE: *value = dec->scale_intermediate; return BT709HIP_OK;
     case BT709HIP_OPT_COMPOSITE_OVER: *value = dec->composite_over; return BT709HIP_OK;
+    case BT709HIP_OPT_SCALED_OVER: *value = dec->scaled_over; return BT709HIP_OK;
     default: return BT709HIP_ERR_INVALID_ARG;
   }
 }
@@ -262,7 +278,7 @@ int bt709hip_decoder_setup(bt709hip_decoder *dec) {
   if (dec == nullptr) return BT709HIP_ERR_INVALID_ARG;
   std::lock_guard<std::mutex> lock(dec->setup_mutex);
   if (dec->ctx == nullptr) return BT709HIP_ERR_NOT_SETUP;  // MetalBT709Decoder.m:48-54
-  const bool over = dec->composite_over != BT709HIP_OVER_OFF;  // its table rides along, also on a decoder set up before the option was
+  const bool over = dec->composite_over != BT709HIP_OVER_OFF || dec->scaled_over != BT709HIP_OVER_OFF;  // their table rides along, also on a decoder set up before the option was
   if (dec->ready) {                                        // second call is a nop (.m:66-70)
     if (!over || dec->d_over_lin.load(std::memory_order_acquire) != nullptr) return BT709HIP_OK;
     if (int rc = bind(dec->ctx)) return rc;
@@ -413,13 +429,8 @@ int decode_batch_now(bt709hip_decoder *dec, int count, const bt709hip_frame *fra
   if (over != BT709HIP_OVER_OFF && info.format == BT709HIP_FORMAT_RGBA16F) return BT709HIP_ERR_UNSUPPORTED;
   if (p.width == 0) return BT709HIP_OK;
   hipStream_t s = pick(dec->ctx, stream);
-  if (over != BT709HIP_OVER_OFF) {
-    if (int rc = ensure_over_table(dec, stream)) return rc;
-    p.over_table_lin = dec->d_over_lin.load(std::memory_order_acquire);
-    p.over_mode = over == BT709HIP_OVER_DESTINATION ? kOverDestination : kOverColour;
-    if (over >= 0)  // the colour's linear values: the entries of the kernels' own table
-      for (int c = 0; c < 3; ++c) p.over_lin[c] = srgb_to_linear(static_cast<float>((over >> (16 - 8 * c)) & 0xff) * (1.0f / 255.0f));
-  }
+  if (over != BT709HIP_OVER_OFF)
+    if (int rc = set_over(&p, dec, over, stream)) return rc;
   if (info.format == BT709HIP_FORMAT_RGBA16F) {  // the reference's pre-10.14 intermediate: linear-light halves
     if (int rc = ensure_half_table(dec, stream)) return rc;
     last_launch_shape() = LaunchShape{};
@@ -439,9 +450,12 @@ int decode_batch_now(bt709hip_decoder *dec, int count, const bt709hip_frame *fra
 }
 
 // The any-ratio launch of a gathered batch (p.out_width x p.out_height set): bt709hip_decode_scaled_batch, and
-// bt709hip_decode_half_batch when the rescale goes through the RGBA16Float intermediate (BT709HIP_OPT_SCALE_INTERMEDIATE)
-static int launch_scaled(bt709hip_decoder *dec, DecodeParams &p, const BatchInfo &info, int count, void *stream, int wait_until_completed) {
+// bt709hip_decode_half_batch when the rescale goes through the RGBA16Float intermediate (BT709HIP_OPT_SCALE_INTERMEDIATE) or blends
+// (`over`: the value of BT709HIP_OPT_SCALED_OVER the call read)
+static int launch_scaled(bt709hip_decoder *dec, DecodeParams &p, const BatchInfo &info, int count, int over, void *stream, int wait_until_completed) {
   if (p.out_height > static_cast<uint32_t>(kMaxGridYZ)) return BT709HIP_ERR_UNSUPPORTED;
+  if (over != BT709HIP_OVER_OFF)
+    if (int rc = set_over(&p, dec, over, stream)) return rc;
   p.scale_x = static_cast<float>(p.width) / static_cast<float>(p.out_width);
   p.scale_y = static_cast<float>(p.height) / static_cast<float>(p.out_height);
   if (dec->scale_intermediate == BT709HIP_FORMAT_RGBA16F) {
@@ -496,10 +510,12 @@ int bt709hip_decode_half_batch(bt709hip_decoder *dec, int count, const bt709hip_
   BatchInfo info;
   if (dec != nullptr) FLUSH_STREAM(dec->ctx, stream);
   if (int rc = gather_batch(dec, count, frames, alphas, outs, OutShape::kHalf, stream, &p, &info)) return rc;
-  if (dec->composite_over != BT709HIP_OVER_OFF) return BT709HIP_ERR_UNSUPPORTED;  // BT709HIP_OPT_COMPOSITE_OVER: the 1:1 path only
+  // BT709HIP_OPT_SCALED_OVER blends here; without it BT709HIP_OPT_COMPOSITE_OVER (the 1:1 path only) refuses
+  const int over = dec->scaled_over;
+  if (over == BT709HIP_OVER_OFF && dec->composite_over != BT709HIP_OVER_OFF) return BT709HIP_ERR_UNSUPPORTED;
   if (p.width == 0) return BT709HIP_OK;
-  // through the RGBA16Float intermediate: the any-ratio kernel at ratio 2.0 (no persistent 2:1 variant; the half-kernel options are not read)
-  if (dec->scale_intermediate == BT709HIP_FORMAT_RGBA16F) return launch_scaled(dec, p, info, count, stream, wait_until_completed);
+  // through the RGBA16Float intermediate, or blended: the any-ratio kernel at ratio 2.0 (no persistent 2:1 variant; the half-kernel options are not read)
+  if (dec->scale_intermediate == BT709HIP_FORMAT_RGBA16F || over != BT709HIP_OVER_OFF) return launch_scaled(dec, p, info, count, over, stream, wait_until_completed);
   hipStream_t s = pick(dec->ctx, stream);
   // wide: same tiling as the 1:1 kernel over the source width; narrow: 256 output pixels per workgroup
   const bool wide = info.in_align >= 4 && info.out_align >= 8;
@@ -534,9 +550,10 @@ int bt709hip_decode_scaled_batch(bt709hip_decoder *dec, int count, const bt709hi
   // the frames are validated like any decode input; the surfaces may have any (common) size
   if (dec != nullptr) FLUSH_STREAM(dec->ctx, stream);
   if (int rc = gather_batch(dec, count, frames, alphas, outs, OutShape::kAny, stream, &p, &info)) return rc;
-  if (dec->composite_over != BT709HIP_OVER_OFF) return BT709HIP_ERR_UNSUPPORTED;  // BT709HIP_OPT_COMPOSITE_OVER: the 1:1 path only
+  const int over = dec->scaled_over;  // BT709HIP_OPT_SCALED_OVER blends here; without it BT709HIP_OPT_COMPOSITE_OVER (the 1:1 path only) refuses
+  if (over == BT709HIP_OVER_OFF && dec->composite_over != BT709HIP_OVER_OFF) return BT709HIP_ERR_UNSUPPORTED;
   if (p.width == 0) return BT709HIP_OK;
-  return launch_scaled(dec, p, info, count, stream, wait_until_completed);
+  return launch_scaled(dec, p, info, count, over, stream, wait_until_completed);
 }
 
 int bt709hip_decode_scaled(bt709hip_decoder *dec, const bt709hip_frame *frame, const bt709hip_frame *alpha,

@@ -79,6 +79,7 @@ struct bt709hip_decoder {
   std::atomic<int> coalesce_max_age_us{0};  // BT709HIP_OPT_COALESCE_MAX_AGE_US: 0 = no age limit
   std::atomic<int> scale_intermediate{BT709HIP_FORMAT_BGRA8_SRGB};  // BT709HIP_OPT_SCALE_INTERMEDIATE: what the fused rescales filter
   std::atomic<int> composite_over{BT709HIP_OVER_OFF};  // BT709HIP_OPT_COMPOSITE_OVER: off, the destination, or an sRGB colour R<<16 | G<<8 | B
+  std::atomic<int> scaled_over{BT709HIP_OVER_OFF};     // BT709HIP_OPT_SCALED_OVER: the same three forms, read by the rescale paths alone
   std::mutex queue_mutex;   // guards queues
   std::vector<PendingQueue> queues;  // one per stream that has (had) queued frames
   std::mutex setup_mutex;
@@ -101,7 +102,7 @@ struct bt709hip_decoder {
   // first use under setup_mutex; half.table_bytes == 0 with half_ready: the gamma has no curve
   bool half_ready = false;  // under setup_mutex
   HalfParams half = {};
-  // BT709HIP_OPT_COMPOSITE_OVER: lin[256] = sRGB_nonLinearNormToLinear(byteNorm(b)), built by the first setup or decode that
+  // BT709HIP_OPT_COMPOSITE_OVER / BT709HIP_OPT_SCALED_OVER: lin[256] = sRGB_nonLinearNormToLinear(byteNorm(b)), built by the first setup or decode that
   // finds the option on (under setup_mutex; release-stored last, acquire-loaded by the decode)
   std::atomic<void *> d_over_lin{nullptr};
 };

@@ -826,28 +826,46 @@ class MetalBT709Decoder:
         reference's non-opaque MTKView over a pattern image, AAPLViewController.m:30-66: tile the pattern into the texture
         first) or an (r, g, b) tuple of sRGB bytes (its black / white backgrounds: (0, 0, 0) / (255, 255, 255)).  The colour frame
         holds premultiplied colour; the blend runs in linear light.  BGRA8 targets of decodeBT709 only."""
-        v = self._options.get(_capi.OPT_COMPOSITE_OVER, _capi.OVER_OFF)
+        return self._over_get(_capi.OPT_COMPOSITE_OVER)
+
+    @compositeOver.setter
+    def compositeOver(self, background):
+        self._over_set(_capi.OPT_COMPOSITE_OVER, "compositeOver", background)
+
+    @property
+    def scaledCompositeOver(self):
+        """What the fused rescales of an alpha decoder (decode_scaled / decode_half, a ring created with half_scale) are blended
+        over, inside the rescale kernel (_capi.OPT_SCALED_OVER): the forms of compositeOver -- None, "destination" or an (r, g, b)
+        tuple -- held separately from it.  The alpha clip played view-fit over the app's background: bit for bit "rescale, then
+        blend the 8-bit result" (DESIGN.md 3.6), in whichever intermediate resizeTexturePixelFormat selects."""
+        return self._over_get(_capi.OPT_SCALED_OVER)
+
+    @scaledCompositeOver.setter
+    def scaledCompositeOver(self, background):
+        self._over_set(_capi.OPT_SCALED_OVER, "scaledCompositeOver", background)
+
+    def _over_get(self, option):
+        v = self._options.get(option, _capi.OVER_OFF)
         if v == _capi.OVER_OFF:
             return None
         return "destination" if v == _capi.OVER_DESTINATION else ((v >> 16) & 0xFF, (v >> 8) & 0xFF, v & 0xFF)
 
-    @compositeOver.setter
-    def compositeOver(self, background):
+    def _over_set(self, option, name, background):
         if background is None:
             value = _capi.OVER_OFF
             if not self._handle and not self.hasAlphaChannel:  # nothing to switch off: the option is an alpha decoder's
-                self._options.pop(_capi.OPT_COMPOSITE_OVER, None)
+                self._options.pop(option, None)
                 return
         elif isinstance(background, str):
             if background != "destination":
-                raise ValueError('compositeOver: None, "destination" or an (r, g, b) tuple of bytes')
+                raise ValueError('%s: None, "destination" or an (r, g, b) tuple of bytes' % name)
             value = _capi.OVER_DESTINATION
         else:
             r, g, b = (int(c) for c in background)
             if not all(0 <= c <= 255 for c in (r, g, b)):
-                raise ValueError('compositeOver: None, "destination" or an (r, g, b) tuple of bytes')
+                raise ValueError('%s: None, "destination" or an (r, g, b) tuple of bytes' % name)
             value = r << 16 | g << 8 | b
-        self.setOption(_capi.OPT_COMPOSITE_OVER, value)
+        self.setOption(option, value)
 
     def flush(self, commandBuffer=None, allStreams=False):
         """Coalescing submit (setOption(_capi.OPT_COALESCE, n)): issue the frames queued for the command buffer's stream (or

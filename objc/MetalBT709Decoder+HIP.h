@@ -31,6 +31,10 @@
 // property reads BT709HIPCompositeOverOff until it is set.  Set before -setupMetal or at any time after.
 enum { BT709HIPCompositeOverOff = -1, BT709HIPCompositeOverDestination = -2 };  // BT709HIP_OVER_OFF, BT709HIP_OVER_DESTINATION
 @property (nonatomic, assign) int hipCompositeOver;
+// The same for the FUSED rescales (bt709hip_decode_scaled / _decode_half through hipDecoderHandle; BT709HIP_OPT_SCALED_OVER): the
+// alpha clip played view-fit over the app's background, blended inside the rescale kernel.  The same values, held separately from
+// hipCompositeOver; reads BT709HIPCompositeOverOff until it is set.
+@property (nonatomic, assign) int hipScaledCompositeOver;
 // The bt709hip_decoder behind this object (NULL before -setupMetal), as a void * so that this header needs no bt709hip.h.
 - (void *) hipDecoderHandle;
 // Completes every frame still in flight: their pixels are copied into the textures passed with them.  Same thread

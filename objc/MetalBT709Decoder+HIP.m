@@ -27,6 +27,7 @@ enum { BT709HIPMaxInFlight = 3 };  // MaxBuffersInFlight, AAPLRenderer.m:34
   id<MTLTexture> _pendingTexture[BT709HIPMaxInFlight];   // nil = the slot owes nothing
   int _nextSlot;                   // the slot bt709hip_pool_acquire hands out next (follows every acquire)
   BOOL _hipCompositeOverSet;       // hipCompositeOver has been assigned (an int property starts at 0, which is "over black")
+  BOOL _hipScaledCompositeOverSet; // the same for hipScaledCompositeOver
 }
 - (BOOL) finishHIPSlot:(int)slot;
 - (void) applyHIPCoalescing;
@@ -82,6 +83,8 @@ static void BT709HIPCopyPlane(void *dst, size_t dstStride, CVPixelBufferRef pb, 
                               self.hipResizeTexturePixelFormat == MTLPixelFormatRGBA16Float ? BT709HIP_FORMAT_RGBA16F : BT709HIP_FORMAT_BGRA8_SRGB);
   // hipCompositeOver: what an alpha decoder's 1:1 decode is blended over inside the kernel (refused without hasAlphaChannel)
   if (self.hasAlphaChannel) bt709hip_decoder_set_option(_hipDecoder, BT709HIP_OPT_COMPOSITE_OVER, self.hipCompositeOver);
+  // hipScaledCompositeOver: the same for its fused rescales
+  if (self.hasAlphaChannel) bt709hip_decoder_set_option(_hipDecoder, BT709HIP_OPT_SCALED_OVER, self.hipScaledCompositeOver);
 }
 - (void) setHipCoalesceFrames:(int)n { _hipCoalesceFrames = n; [self applyHIPCoalescing]; }
 - (void) setHipCoalesceMaxAgeMicroseconds:(int)us { _hipCoalesceMaxAgeMicroseconds = us; [self applyHIPCoalescing]; }
@@ -89,6 +92,9 @@ static void BT709HIPCopyPlane(void *dst, size_t dstStride, CVPixelBufferRef pb, 
 @synthesize hipCompositeOver = _hipCompositeOver;
 - (int) hipCompositeOver { return _hipCompositeOverSet ? _hipCompositeOver : BT709HIP_OVER_OFF; }
 - (void) setHipCompositeOver:(int)background { _hipCompositeOver = background; _hipCompositeOverSet = YES; [self applyHIPCoalescing]; }
+@synthesize hipScaledCompositeOver = _hipScaledCompositeOver;
+- (int) hipScaledCompositeOver { return _hipScaledCompositeOverSet ? _hipScaledCompositeOver : BT709HIP_OVER_OFF; }
+- (void) setHipScaledCompositeOver:(int)background { _hipScaledCompositeOver = background; _hipScaledCompositeOverSet = YES; [self applyHIPCoalescing]; }
 - (void *) hipDecoderHandle { return _hipDecoder; }
 
 // Copies a finished slot's pinned BGRA rows into the texture the caller passed for that frame: its top-left
