@@ -416,6 +416,12 @@ class MetalBT709Decoder {
     return background;
   }
 
+  // How decodeBT709 reads the caller's colour buffers (include/bt709hip_ext.h BT709HIP_OPT_CHROMA_LAYOUT): BT709HIP_CHROMA_NV12 (the
+  // default) or BT709HIP_CHROMA_I420 -- cbcr is the U plane at pitch cbcr_stride >= W/2, V the same shape (height/2) * cbcr_stride
+  // behind it: a YUV4MPEG2 FRAME payload as uploaded.  BGRA8 targets of decodeBT709 only; rings and pools stay NV12.
+  static constexpr int kChromaLayoutOption = BT709HIP_OPT_CHROMA_LAYOUT;
+  static constexpr int kChromaNV12 = BT709HIP_CHROMA_NV12, kChromaI420 = BT709HIP_CHROMA_I420;
+
   // The coalescing submit (include/bt709hip_ext.h BT709HIP_OPT_COALESCE): keep the reference's one-decodeBT709-call-per-frame cadence
   // on device-resident frames and let `frames` (2..32; 0 = off) queued calls go out as one launch; maxAgeMicroseconds > 0: a queue
   // older than that is issued by the context's next call on ANY stream (BT709HIP_OPT_COALESCE_MAX_AGE_US), so an idle caller's

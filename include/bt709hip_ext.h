@@ -98,6 +98,7 @@ typedef enum {
   BT709HIP_OPT_COALESCE_MAX_AGE_US = 7, /* 0 (default): queued frames wait for their stream's next call, however long; t > 0: a queue whose oldest frame was queued more than t microseconds ago is issued by the next bt709hip_* call that touches ANY stream of the context (or any decode of any decoder of it) */
   BT709HIP_OPT_COMPOSITE_OVER = 9,   /* alpha decoders: BT709HIP_OVER_OFF (default), BT709HIP_OVER_DESTINATION, or an sRGB colour R<<16 | G<<8 | B; see below */
   BT709HIP_OPT_SCALED_OVER = 10,     /* alpha decoders, the rescale paths: the values of BT709HIP_OPT_COMPOSITE_OVER, held separately; see below */
+  BT709HIP_OPT_CHROMA_LAYOUT = 11,   /* BT709HIP_CHROMA_NV12 (default) or BT709HIP_CHROMA_I420: how the 1:1 decode reads the caller's colour frames; see below */
   BT709HIP_OPT_SCALE_INTERMEDIATE = 8  /* the intermediate the FUSED rescales filter, a bt709hip_format: BT709HIP_FORMAT_BGRA8_SRGB (default) or BT709HIP_FORMAT_RGBA16F; any other value: BT709HIP_ERR_INVALID_ARG, option unchanged.  See below */
 } bt709hip_decoder_option;
 int bt709hip_decoder_set_option(bt709hip_decoder *dec, int option, int value);
@@ -156,6 +157,33 @@ int bt709hip_decoder_get_option(const bt709hip_decoder *dec, int option, int *va
  * "decode_nv12_scaled<alpha,over-colour>", "decode_nv12_scaled_f16<alpha,over>" / "decode_nv12_scaled_f16<alpha,over-colour>". */
 #define BT709HIP_OVER_OFF (-1)
 #define BT709HIP_OVER_DESTINATION (-2)
+/* BT709HIP_OPT_CHROMA_LAYOUT.  The reference's on-disk format is PLANAR 4:2:0 -- a YUV4MPEG2 C420jpeg FRAME is Y, then U, then V
+ * (Renderer/y4m_writer.h:194-241) -- and so is every software decoder's yuv420p.  With the option at BT709HIP_CHROMA_I420 the
+ * colour bt709hip_frame of bt709hip_decode and bt709hip_decode_batch (pointer table or evenly spaced frames, the coalescing
+ * submit included) is read as three planes, with no interleave pass and no staging buffer:
+ *   y, y_stride   as before;
+ *   cbcr          the U (Cb) plane: (W/2) x (H/2) bytes, rows cbcr_stride bytes apart, cbcr_stride >= W/2;
+ *   the V (Cr) plane has the same pitch and starts at cbcr + (height/2) * cbcr_stride.
+ * A tight Y4M FRAME payload uploaded as one blob is y = base, y_stride = W, cbcr = base + W*H, cbcr_stride = W/2.  Pixel (x, y)
+ * takes Y[y][x], U[y/2][x/2], V[y/2][x/2]; the output is byte for byte what the NV12 decode of the interleaved twin of the planes
+ * writes -- BGRA8_SRGB targets, every gamma, decoders with and without an alpha channel (alpha frames are Y-only and do not
+ * change), BT709HIP_OPT_COMPOSITE_OVER in both modes.  Validation: cbcr_stride < W/2 is BT709HIP_ERR_STRIDE (NV12: < W); the
+ * other checks and limits are NV12's, applied to the U plane's extent and the V plane's; an evenly spaced batch is one whose U
+ * planes are (V follows from cbcr).  Fast kernels need W % 4 == 0, luma / alpha planes 4-byte aligned, the U pointer and
+ * cbcr_stride 2-byte aligned and the output 16-byte aligned; any other frame takes the general kernel.
+ * bt709hip_last_kernel_name: the NV12 names with "decode_i420_" for "decode_nv12_" ("decode_i420_quads<nt>",
+ * "decode_i420_quads<alpha>", "decode_i420_blocks", ...).  Any value but the two: BT709HIP_ERR_INVALID_ARG, the option keeps
+ * its value.  Setting it never touches the device and needs no device table (it works inside a graph capture); frames a
+ * coalescing decoder has queued go out first, under the layout they were queued with, and frames of two layouts never share a
+ * launch.  NOT covered:
+ *   - RGBA16F targets, bt709hip_decode_half[_batch] and bt709hip_decode_scaled[_batch] return BT709HIP_ERR_UNSUPPORTED after
+ *     their usual validation and write nothing while the option is BT709HIP_CHROMA_I420 (their strip loaders read NV12);
+ *   - objects that allocate their own frames -- ring, ring set, pool, shard -- stay NV12 whatever the option holds (their
+ *     launches pass the layout instead of reading the option; bt709hip_ring_frame keeps describing NV12 planes);
+ *   - bt709hip_unconvert, bt709hip_render_scaled and the encoder have no chroma plane to lay out and are unchanged;
+ *   - YV12 (V before U), and planar frames whose V plane is anywhere but (height/2) * cbcr_stride behind U. */
+#define BT709HIP_CHROMA_NV12 0
+#define BT709HIP_CHROMA_I420 1
 
 /* COALESCING SUBMIT (extension, opt-in: bt709hip_decoder_set_option(dec, BT709HIP_OPT_COALESCE, n), n = 2..32).
  * The reference's cadence is one -decodeBT709: call per frame (MetalBT709Decoder.h:65-72, AAPLRenderer.m:914-957), each call

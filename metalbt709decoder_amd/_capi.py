@@ -44,6 +44,9 @@ OPT_COMPOSITE_OVER = 9  # alpha decoders: OVER_OFF (default), OVER_DESTINATION, 
 OPT_SCALED_OVER = 10  # alpha decoders, the rescale paths (decode_scaled / decode_half): the same three forms, held separately
 OVER_OFF = -1
 OVER_DESTINATION = -2
+OPT_CHROMA_LAYOUT = 11  # how the 1:1 decode reads the caller's colour frames: CHROMA_NV12 (default) or CHROMA_I420 (planar: U, then V)
+CHROMA_NV12 = 0
+CHROMA_I420 = 1
 CTX_OPT_GRID_MULT = 1
 CTX_OPT_ENCODE_ROW_PAIRS = 2
 CTX_OPT_ENCODE_THREADS = 3

@@ -105,7 +105,14 @@ struct DecodeParams {
   uint32_t over_mode;  // kOverOff / kOverDestination / kOverColour
   float over_lin[3];
   const void *over_table_lin;
+  // BT709HIP_OPT_CHROMA_LAYOUT (the 1:1 kernels of the caller's frames): kChromaI420 = frames[i].cbcr is the U (Cb) plane, W/2 x
+  // H/2 bytes at pitch cbcr_stride, and the V (Cr) plane the same shape v_offset = (H/2) * cbcr_stride bytes behind it;
+  // launch_decode then runs the decode_i420_* kernels (bt709_planar.hip).  Every other launcher reads NV12 whatever this holds.
+  uint32_t chroma_layout;  // kChromaNV12 / kChromaI420
+  uint32_t chroma_reserved;
+  uint64_t v_offset;
 };
+enum : uint32_t { kChromaNV12 = 0, kChromaI420 = 1 };  // == BT709HIP_CHROMA_*
 enum : uint32_t { kOverOff = 0, kOverDestination = 1, kOverColour = 2 };
 constexpr uint32_t kOverLinBytes = 256 * sizeof(float);
 

@@ -6,7 +6,8 @@
 // after the other by one process run the same launch at 0.74-0.82 of the HBM roofline, each keeping its rate; the output
 // slab carries most of it, the pairing with the input slab a further 1-2 %).  Rounds 2-3 hunted for a good pairing inside
 // bench.py; this file is that hunt as product behaviour: bt709hip_ring_create allocates `tries` candidates per slab, times
-// the decoder's OWN launch over the pairings and keeps the fastest.  Written on top of the public C ABI only.
+// the decoder's OWN launch over the pairings and keeps the fastest.  Written on top of the public C ABI, but
+// for its two launches (below).
 #include "../../include/bt709hip_ext.h"
 
 #include <algorithm>
@@ -16,6 +17,16 @@
 #include <new>
 #include <utility>
 #include <vector>
+
+// The ring's frames are its own and NV12 (bt709hip_ring_frame describes them): its launches go through the two batch entry points
+// under that layout, whatever BT709HIP_OPT_CHROMA_LAYOUT says about the frames the decoder's caller brings (shim_internal.h).
+// The two declarations repeat shim_internal.h's (that header's helpers share names with this file's own): change them together.
+namespace bt709shim __attribute__((visibility("hidden"))) {
+int decode_batch_layout(bt709hip_decoder *dec, int layout, int count, const bt709hip_frame *frames, const bt709hip_frame *alphas,
+                        const bt709hip_surface *outs, void *stream, int wait_until_completed);
+int decode_half_batch_layout(bt709hip_decoder *dec, int layout, int count, const bt709hip_frame *frames, const bt709hip_frame *alphas,
+                             const bt709hip_surface *outs, void *stream, int wait_until_completed);
+}  // namespace bt709shim
 
 struct bt709hip_ring {
   bt709hip_decoder *dec = nullptr;
@@ -95,8 +106,8 @@ int launch(bt709hip_ring *r, int first, int count, void *stream, int wait) {
   const bt709hip_frame *f = r->f.data() + first;
   const bt709hip_frame *a = r->has_alpha ? r->a.data() + first : nullptr;
   const bt709hip_surface *o = r->o.data() + first;
-  return r->half ? bt709hip_decode_half_batch(r->dec, count, f, a, o, stream, wait)
-                 : bt709hip_decode_batch(r->dec, count, f, a, o, stream, wait);
+  return r->half ? bt709shim::decode_half_batch_layout(r->dec, BT709HIP_CHROMA_NV12, count, f, a, o, stream, wait)
+                 : bt709shim::decode_batch_layout(r->dec, BT709HIP_CHROMA_NV12, count, f, a, o, stream, wait);
 }
 
 double now_s() {

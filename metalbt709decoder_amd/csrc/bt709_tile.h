@@ -95,5 +95,61 @@ struct TileIn {
   }
 };
 
+// The same tile over PLANAR chroma (DecodeParams::chroma_layout == kChromaI420; bt709_planar.hip): f.cbcr is the U plane, rows
+// cbcr_stride apart, and V the same plane v_offset bytes on.  A quad's chroma is 2 bytes of U and 2 of V where NV12 holds one
+// dword: two 2-byte loads, and after the pin one v_perm_b32 builds the NV12 word cw = {Cb0, Cr0, Cb1, Cr1} the shared arithmetic
+// takes.  Everything else is TileIn's, the straight-line rule included.  Alignment: U pointer, pitch and v_offset even.
+// BOUND: q <= quads - 1 = W/4 - 1, so a lane reads bytes [2q, 2q + 1] <= W/2 - 1 of a chroma row of W/2 bytes, and rp <=
+// row_pairs - 1 = H/2 - 1 is a row of each plane: no load leaves a row's W/2 bytes, in either plane, whatever the pitch.
+template <bool NT>
+__device__ __forceinline__ uint32_t load16(const uint8_t *p) {
+  if (NT) return __builtin_nontemporal_load(reinterpret_cast<const uint16_t *>(p));
+  return *reinterpret_cast<const uint16_t *>(p);
+}
+
+template <int N, bool HAS_ALPHA, bool DEST = false>
+struct TileInI420 {
+  uint32_t ya[N], yb[N], cu[N], cv[N], cw[N], aa[N], ab[N];
+  TileWord16 da[DEST ? N : 1], db[DEST ? N : 1];
+
+  template <bool NT>
+  __device__ __forceinline__ void load(const FramePlanes &f, const DecodeParams &p, uint32_t rp, uint32_t row_pairs, uint32_t q0, uint32_t quads) {
+    rp = min(rp, row_pairs - 1);
+    const uint8_t *y0 = f.y + static_cast<size_t>(2 * rp) * p.y_stride;
+    const uint8_t *y1 = y0 + p.y_stride;
+    const uint8_t *uu = f.cbcr + static_cast<size_t>(rp) * p.cbcr_stride;
+    const uint8_t *vv = uu + p.v_offset;
+    const uint8_t *a0 = HAS_ALPHA ? f.alpha + static_cast<size_t>(2 * rp) * p.alpha_stride : nullptr;
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      const uint32_t q = min(q0 + j * blockDim.x, quads - 1);
+      ya[j] = load32<NT>(y0 + 4 * q);
+      yb[j] = load32<NT>(y1 + 4 * q);
+      cu[j] = load16<NT>(uu + 2 * q);
+      cv[j] = load16<NT>(vv + 2 * q);
+      if (HAS_ALPHA) {
+        aa[j] = load32<NT>(a0 + 4 * q);
+        ab[j] = load32<NT>(a0 + p.alpha_stride + 4 * q);
+      }
+      if (DEST) {
+        const uint8_t *o0 = f.out + static_cast<size_t>(2 * rp) * p.out_stride + 16 * static_cast<size_t>(q);
+        da[DEST ? j : 0] = __builtin_nontemporal_load(reinterpret_cast<const TileWord16 *>(o0));
+        db[DEST ? j : 0] = __builtin_nontemporal_load(reinterpret_cast<const TileWord16 *>(o0 + p.out_stride));
+      }
+    }
+  }
+
+  __device__ __forceinline__ void pin() {
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      asm volatile("" : "+v"(ya[j]), "+v"(yb[j]), "+v"(cu[j]), "+v"(cv[j]));
+      if (HAS_ALPHA) asm volatile("" : "+v"(aa[j]), "+v"(ab[j]));
+      if (DEST) asm volatile("" : "+v"(da[DEST ? j : 0]), "+v"(db[DEST ? j : 0]));
+      // selector bytes, LSB first: U byte 0, V byte 0, U byte 1, V byte 1 (0-3: the second operand, 4-7: the first)
+      cw[j] = __builtin_amdgcn_perm(cv[j], cu[j], 0x05010400u);
+    }
+  }
+};
+
 }  // namespace
 }  // namespace bt709

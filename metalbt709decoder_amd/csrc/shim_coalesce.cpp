@@ -13,7 +13,7 @@ int issue_queue(bt709hip_decoder *dec, PendingQueue &q) {
   frames.swap(q.frames);
   alphas.swap(q.alphas);
   outs.swap(q.outs);
-  return decode_batch_now(dec, static_cast<int>(frames.size()), frames.data(), q.with_alphas ? alphas.data() : nullptr, outs.data(),
+  return decode_batch_now(dec, q.layout, static_cast<int>(frames.size()), frames.data(), q.with_alphas ? alphas.data() : nullptr, outs.data(),
                           q.stream, 0);
 }
 
@@ -96,9 +96,9 @@ bool same_shape(const bt709hip_frame &a, const bt709hip_frame &b) {
 }  // namespace
 
 // BT709HIP_OPT_COALESCE (include/bt709hip_ext.h, COALESCING SUBMIT): validate now, launch later.
-int coalescing_submit(bt709hip_decoder *dec, int count, const bt709hip_frame *frames, const bt709hip_frame *alphas,
+int coalescing_submit(bt709hip_decoder *dec, int layout, int count, const bt709hip_frame *frames, const bt709hip_frame *alphas,
                       const bt709hip_surface *outs, void *stream, int wait_until_completed) {
-  if (dec->ctx == nullptr) return decode_batch_now(dec, count, frames, alphas, outs, stream, wait_until_completed);
+  if (dec->ctx == nullptr) return decode_batch_now(dec, layout, count, frames, alphas, outs, stream, wait_until_completed);
   hipStream_t s = pick(dec->ctx, stream);
   // what the context's OTHER coalescing decoders have queued for this stream was submitted before this call: it goes first.
   // Done before this decoder's own queue_mutex is taken (lock order: the context's coalescing_mutex, then a queue_mutex).
@@ -119,12 +119,13 @@ int coalescing_submit(bt709hip_decoder *dec, int count, const bt709hip_frame *fr
   if (!eligible) {  // in stream order: what is queued goes first
     if (q != nullptr)
       if (int rc = issue_queue(dec, *q)) return rc;
-    return decode_batch_now(dec, count, frames, alphas, outs, stream, wait_until_completed);
+    return decode_batch_now(dec, layout, count, frames, alphas, outs, stream, wait_until_completed);
   }
   {  // the call's own status: everything -decodeBT709: checks, now
     DecodeParams p;
     BatchInfo info;
-    if (int rc = gather_batch(dec, count, frames, alphas, outs, OutShape::kSame, stream, &p, &info)) return rc;
+    if (int rc = gather_batch(dec, count, frames, alphas, outs, OutShape::kSame, layout, stream, &p, &info)) return rc;
+    if (layout == BT709HIP_CHROMA_I420 && info.format == BT709HIP_FORMAT_RGBA16F) return BT709HIP_ERR_UNSUPPORTED;  // decode_batch_now's refusal, now
     if (p.width == 0) return BT709HIP_OK;  // empty frames: nothing to launch
   }
   if (q == nullptr) {
@@ -135,12 +136,13 @@ int coalescing_submit(bt709hip_decoder *dec, int count, const bt709hip_frame *fr
   if (!q->frames.empty()) {
     const bool fits = q->frames.size() + static_cast<size_t>(count) <= static_cast<size_t>(n) &&
                       same_shape(q->frames[0], frames[0]) && q->frames[0].transfer == frames[0].transfer &&
-                      q->outs[0].stride == outs[0].stride && q->outs[0].format == outs[0].format &&
+                      q->outs[0].stride == outs[0].stride && q->outs[0].format == outs[0].format && q->layout == layout &&
                       q->with_alphas == (alphas != nullptr) && (alphas == nullptr || q->alphas[0].y_stride == alphas[0].y_stride);
     if (!fits)
       if (int rc = issue_queue(dec, *q)) return rc;
   }
   q->with_alphas = alphas != nullptr;
+  q->layout = layout;
   if (q->frames.empty()) q->oldest_us = now_us();
   q->frames.insert(q->frames.end(), frames, frames + count);
   if (alphas != nullptr) q->alphas.insert(q->alphas.end(), alphas, alphas + count);

@@ -16,7 +16,7 @@ int required_transfer(int gamma) {
 
 // Validation of one frame/alpha/surface triple in the reference's order
 // (MetalBT709Decoder.m:265-368), then the checks the texture wrappers imply.
-int validate(const bt709hip_decoder *dec, const bt709hip_frame *f, const bt709hip_frame *a,
+int validate(const bt709hip_decoder *dec, int layout, const bt709hip_frame *f, const bt709hip_frame *a,
              const bt709hip_surface *o, int out_w, int out_h, int render_w, int render_h) {
   if (f == nullptr || o == nullptr) return BT709HIP_ERR_INVALID_ARG;
   if (f->width < 0 || f->height < 0) return BT709HIP_ERR_INVALID_ARG;
@@ -31,8 +31,9 @@ int validate(const bt709hip_decoder *dec, const bt709hip_frame *f, const bt709hi
   if (f->width == 0 || f->height == 0) return BT709HIP_OK;
   if (f->y == nullptr || f->cbcr == nullptr || o->bgra == nullptr) return BT709HIP_ERR_INVALID_ARG;
   if (dec->has_alpha && a->y == nullptr) return BT709HIP_ERR_INVALID_ARG;
-  if (f->y_stride < static_cast<size_t>(f->width) || f->cbcr_stride < static_cast<size_t>(f->width))
-    return BT709HIP_ERR_STRIDE;
+  // a chroma row: W bytes of Cb,Cr pairs, or W/2 bytes of each planar plane (BT709HIP_OPT_CHROMA_LAYOUT)
+  const size_t chroma_row = static_cast<size_t>(layout == BT709HIP_CHROMA_I420 ? f->width / 2 : f->width);
+  if (f->y_stride < static_cast<size_t>(f->width) || f->cbcr_stride < chroma_row) return BT709HIP_ERR_STRIDE;
   if (dec->has_alpha && a->y_stride < static_cast<size_t>(a->width)) return BT709HIP_ERR_STRIDE;
   if ((o->format != BT709HIP_FORMAT_BGRA8_SRGB && o->format != BT709HIP_FORMAT_RGBA16F) || o->reserved != 0)
     return BT709HIP_ERR_INVALID_ARG;
@@ -248,6 +249,10 @@ int bt709hip_decoder_set_option(bt709hip_decoder *dec, int option, int value) {
       if (!dec->has_alpha) return BT709HIP_ERR_UNSUPPORTED;  // nothing to composite
       dec->composite_over = value;
       return BT709HIP_OK;
+    case BT709HIP_OPT_CHROMA_LAYOUT:
+      if (value != BT709HIP_CHROMA_NV12 && value != BT709HIP_CHROMA_I420) return BT709HIP_ERR_INVALID_ARG;
+      dec->chroma_layout = value;
+      return BT709HIP_OK;
     case BT709HIP_OPT_SCALED_OVER:  // the same domain and refusals, a value of its own
       if (value != BT709HIP_OVER_OFF && value != BT709HIP_OVER_DESTINATION && (value < 0 || value > 0xFFFFFF)) return BT709HIP_ERR_INVALID_ARG;
       if (!dec->has_alpha) return BT709HIP_ERR_UNSUPPORTED;
@@ -270,6 +275,7 @@ int bt709hip_decoder_get_option(const bt709hip_decoder *dec, int option, int *va
     case BT709HIP_OPT_SCALE_INTERMEDIATE: *value = dec->scale_intermediate; return BT709HIP_OK;
     case BT709HIP_OPT_COMPOSITE_OVER: *value = dec->composite_over; return BT709HIP_OK;
     case BT709HIP_OPT_SCALED_OVER: *value = dec->scaled_over; return BT709HIP_OK;
+    case BT709HIP_OPT_CHROMA_LAYOUT: *value = dec->chroma_layout; return BT709HIP_OK;
     default: return BT709HIP_ERR_INVALID_ARG;
   }
 }
@@ -343,7 +349,7 @@ static void fold_align(uint32_t *a, uintptr_t v) {
 // (MetalBT709Decoder.m:265-368), checks that the batch shares one geometry, and fills the pointer
 // table, pitches and frame spacing of `p`.  Returns BT709HIP_OK with p->width == 0 for empty frames.
 int gather_batch(bt709hip_decoder *dec, int count, const bt709hip_frame *frames, const bt709hip_frame *alphas,
-                 const bt709hip_surface *outs, OutShape shape, void *stream, DecodeParams *p, BatchInfo *info) {
+                 const bt709hip_surface *outs, OutShape shape, int layout, void *stream, DecodeParams *p, BatchInfo *info) {
   if (dec == nullptr || frames == nullptr || outs == nullptr || count < 0) return BT709HIP_ERR_INVALID_ARG;
   // an alpha buffer handed to an opaque decoder is validated (.m:294-306, 357-368) but not read
   const bt709hip_frame *planes_a = dec->has_alpha ? alphas : nullptr;
@@ -365,7 +371,7 @@ int gather_batch(bt709hip_decoder *dec, int count, const bt709hip_frame *frames,
     const int want_w = shape == OutShape::kSame ? f.width : (shape == OutShape::kHalf ? f.width / 2 : o.width);
     const int want_h = shape == OutShape::kSame ? f.height : (shape == OutShape::kHalf ? f.height / 2 : o.height);
     if (shape == OutShape::kAny && (o.width < 0 || o.height < 0)) return BT709HIP_ERR_INVALID_ARG;
-    if (int rc = validate(dec, &f, a, &o, want_w, want_h, o.width, o.height)) return rc;
+    if (int rc = validate(dec, layout, &f, a, &o, want_w, want_h, o.width, o.height)) return rc;
     if (o.format != BT709HIP_FORMAT_BGRA8_SRGB && (shape != OutShape::kSame || o.format != BT709HIP_FORMAT_RGBA16F))
       return BT709HIP_ERR_UNSUPPORTED;
     if (f.width != f0.width || f.height != f0.height || f.y_stride != f0.y_stride || f.cbcr_stride != f0.cbcr_stride ||
@@ -379,12 +385,14 @@ int gather_batch(bt709hip_decoder *dec, int count, const bt709hip_frame *frames,
       p->frames[i].out = static_cast<uint8_t *>(o.bgra);
     }
     fold_align(&info->in_align, reinterpret_cast<uintptr_t>(f.y));
-    fold_align(&info->in_align, reinterpret_cast<uintptr_t>(f.cbcr));
+    if (layout != BT709HIP_CHROMA_I420) fold_align(&info->in_align, reinterpret_cast<uintptr_t>(f.cbcr));
+    fold_align(&info->chroma_align, reinterpret_cast<uintptr_t>(f.cbcr));
     if (planes_a) fold_align(&info->in_align, reinterpret_cast<uintptr_t>(a->y));
     fold_align(&info->out_align, reinterpret_cast<uintptr_t>(o.bgra));
   }
   fold_align(&info->in_align, f0.y_stride);
-  fold_align(&info->in_align, f0.cbcr_stride);
+  if (layout != BT709HIP_CHROMA_I420) fold_align(&info->in_align, f0.cbcr_stride);
+  fold_align(&info->chroma_align, f0.cbcr_stride);
   if (planes_a) fold_align(&info->in_align, alphas[0].y_stride);
   fold_align(&info->out_align, o0.stride);
   // the row-pair dimension of the 1:1 and 2:1 kernels is gridDim.y; the any-ratio kernel walks strips of OUTPUT rows
@@ -409,6 +417,10 @@ int gather_batch(bt709hip_decoder *dec, int count, const bt709hip_frame *frames,
   p->out_width = static_cast<uint32_t>(o0.width);
   p->out_height = static_cast<uint32_t>(o0.height);
   p->alpha_word = dec->alpha_fill << 24;
+  if (layout == BT709HIP_CHROMA_I420) {  // the V plane: H/2 rows of the U plane's pitch behind it
+    p->chroma_layout = kChromaI420;
+    p->v_offset = static_cast<uint64_t>(f0.height / 2) * f0.cbcr_stride;
+  }
   return BT709HIP_OK;
 }
 
@@ -420,13 +432,14 @@ int gather_batch(bt709hip_decoder *dec, int count, const bt709hip_frame *frames,
 namespace bt709shim __attribute__((visibility("hidden"))) {
 
 // the launch itself (no queueing)
-int decode_batch_now(bt709hip_decoder *dec, int count, const bt709hip_frame *frames, const bt709hip_frame *alphas,
+int decode_batch_now(bt709hip_decoder *dec, int layout, int count, const bt709hip_frame *frames, const bt709hip_frame *alphas,
                      const bt709hip_surface *outs, void *stream, int wait_until_completed) {
   DecodeParams p;
   BatchInfo info;
-  if (int rc = gather_batch(dec, count, frames, alphas, outs, OutShape::kSame, stream, &p, &info)) return rc;
+  if (int rc = gather_batch(dec, count, frames, alphas, outs, OutShape::kSame, layout, stream, &p, &info)) return rc;
   const int over = dec->composite_over;  // BT709HIP_OPT_COMPOSITE_OVER: into BGRA8_SRGB targets only
   if (over != BT709HIP_OVER_OFF && info.format == BT709HIP_FORMAT_RGBA16F) return BT709HIP_ERR_UNSUPPORTED;
+  if (layout == BT709HIP_CHROMA_I420 && info.format == BT709HIP_FORMAT_RGBA16F) return BT709HIP_ERR_UNSUPPORTED;  // planar chroma: BGRA8_SRGB targets only
   if (p.width == 0) return BT709HIP_OK;
   hipStream_t s = pick(dec->ctx, stream);
   if (over != BT709HIP_OVER_OFF)
@@ -440,7 +453,8 @@ int decode_batch_now(bt709hip_decoder *dec, int count, const bt709hip_frame *fra
   }
   // Fast path: one short-lived workgroup per tile of a row pair, dispatched in address order
   // (see the kernel file's header).  General path keeps the grid-strided shape.
-  const bool fast = (p.width % 4) == 0 && info.in_align >= 4 && info.out_align >= 16;
+  // Planar chroma: the luma and alpha planes as NV12's, the chroma folded on its own -- a quad's chroma is a 2-byte load per plane
+  const bool fast = (p.width % 4) == 0 && info.in_align >= 4 && info.out_align >= 16 && (layout != BT709HIP_CHROMA_I420 || info.chroma_align >= 2);
   const uint32_t gx = fast ? quads_tiles(p.width) : grid_x_for(dec->ctx, p.height / 2, count);
   const uint32_t threads = quads_block_threads(p.width);
   last_launch_shape() = LaunchShape{};
@@ -475,41 +489,26 @@ static int launch_scaled(bt709hip_decoder *dec, DecodeParams &p, const BatchInfo
   return finish_launch(s, wait_until_completed);
 }
 
-}  // namespace bt709shim
-
-extern "C" {
-
-int bt709hip_decode_batch(bt709hip_decoder *dec, int count, const bt709hip_frame *frames,
-                          const bt709hip_frame *alphas, const bt709hip_surface *outs, void *stream,
-                          int wait_until_completed) {
-  if (dec != nullptr && dec->coalesce > 1) return coalescing_submit(dec, count, frames, alphas, outs, stream, wait_until_completed);
+// bt709hip_decode_batch under an explicit chroma layout (also declared in bt709_ring.cpp, which includes the public header only)
+int decode_batch_layout(bt709hip_decoder *dec, int layout, int count, const bt709hip_frame *frames, const bt709hip_frame *alphas,
+                        const bt709hip_surface *outs, void *stream, int wait_until_completed) {
+  if (dec != nullptr && dec->coalesce > 1) return coalescing_submit(dec, layout, count, frames, alphas, outs, stream, wait_until_completed);
   // frames another (coalescing) decoder of the context queued on this stream were submitted first: they are issued first
   if (dec != nullptr && dec->ctx != nullptr && dec->ctx->n_coalescing.load(std::memory_order_acquire) != 0) {
     if (int rc = bind(dec->ctx)) return rc;
     FLUSH_STREAM(dec->ctx, stream);
   }
-  return decode_batch_now(dec, count, frames, alphas, outs, stream, wait_until_completed);
+  return decode_batch_now(dec, layout, count, frames, alphas, outs, stream, wait_until_completed);
 }
 
-int bt709hip_decode(bt709hip_decoder *dec, const bt709hip_frame *frame, const bt709hip_frame *alpha,
-                    const bt709hip_surface *out, int render_width, int render_height, void *stream,
-                    int wait_until_completed) {
-  if (dec == nullptr) return BT709HIP_ERR_INVALID_ARG;
-  if (int rc = ensure_setup(dec, stream)) return rc;
-  // render size is a property of this call only; check it here, the rest in the batch path
-  if (int rc = validate(dec, frame, alpha, out, frame ? frame->width : 0, frame ? frame->height : 0, render_width,
-                        render_height))
-    return rc;
-  return bt709hip_decode_batch(dec, 1, frame, alpha, out, stream, wait_until_completed);
-}
-
-int bt709hip_decode_half_batch(bt709hip_decoder *dec, int count, const bt709hip_frame *frames,
-                               const bt709hip_frame *alphas, const bt709hip_surface *outs, void *stream,
-                               int wait_until_completed) {
+// bt709hip_decode_half_batch under an explicit chroma layout (also declared in bt709_ring.cpp)
+int decode_half_batch_layout(bt709hip_decoder *dec, int layout, int count, const bt709hip_frame *frames, const bt709hip_frame *alphas,
+                             const bt709hip_surface *outs, void *stream, int wait_until_completed) {
   DecodeParams p;
   BatchInfo info;
   if (dec != nullptr) FLUSH_STREAM(dec->ctx, stream);
-  if (int rc = gather_batch(dec, count, frames, alphas, outs, OutShape::kHalf, stream, &p, &info)) return rc;
+  if (int rc = gather_batch(dec, count, frames, alphas, outs, OutShape::kHalf, layout, stream, &p, &info)) return rc;
+  if (layout == BT709HIP_CHROMA_I420) return BT709HIP_ERR_UNSUPPORTED;  // the rescale kernels' strip loaders read NV12
   // BT709HIP_OPT_SCALED_OVER blends here; without it BT709HIP_OPT_COMPOSITE_OVER (the 1:1 path only) refuses
   const int over = dec->scaled_over;
   if (over == BT709HIP_OVER_OFF && dec->composite_over != BT709HIP_OVER_OFF) return BT709HIP_ERR_UNSUPPORTED;
@@ -536,6 +535,35 @@ int bt709hip_decode_half_batch(bt709hip_decoder *dec, int count, const bt709hip_
   return finish_launch(s, wait_until_completed);
 }
 
+}  // namespace bt709shim
+
+extern "C" {
+
+int bt709hip_decode_batch(bt709hip_decoder *dec, int count, const bt709hip_frame *frames,
+                          const bt709hip_frame *alphas, const bt709hip_surface *outs, void *stream,
+                          int wait_until_completed) {
+  return decode_batch_layout(dec, dec != nullptr ? dec->chroma_layout.load() : BT709HIP_CHROMA_NV12, count, frames, alphas, outs, stream, wait_until_completed);
+}
+
+int bt709hip_decode(bt709hip_decoder *dec, const bt709hip_frame *frame, const bt709hip_frame *alpha,
+                    const bt709hip_surface *out, int render_width, int render_height, void *stream,
+                    int wait_until_completed) {
+  if (dec == nullptr) return BT709HIP_ERR_INVALID_ARG;
+  if (int rc = ensure_setup(dec, stream)) return rc;
+  // render size is a property of this call only; check it here, the rest in the batch path
+  const int layout = dec->chroma_layout;  // read once: the call runs with what it read
+  if (int rc = validate(dec, layout, frame, alpha, out, frame ? frame->width : 0, frame ? frame->height : 0, render_width,
+                        render_height))
+    return rc;
+  return decode_batch_layout(dec, layout, 1, frame, alpha, out, stream, wait_until_completed);
+}
+
+int bt709hip_decode_half_batch(bt709hip_decoder *dec, int count, const bt709hip_frame *frames,
+                               const bt709hip_frame *alphas, const bt709hip_surface *outs, void *stream,
+                               int wait_until_completed) {
+  return decode_half_batch_layout(dec, dec != nullptr ? dec->chroma_layout.load() : BT709HIP_CHROMA_NV12, count, frames, alphas, outs, stream, wait_until_completed);
+}
+
 int bt709hip_decode_half(bt709hip_decoder *dec, const bt709hip_frame *frame, const bt709hip_frame *alpha,
                          const bt709hip_surface *out, void *stream, int wait_until_completed) {
   if (frame == nullptr || out == nullptr) return BT709HIP_ERR_INVALID_ARG;
@@ -549,7 +577,9 @@ int bt709hip_decode_scaled_batch(bt709hip_decoder *dec, int count, const bt709hi
   BatchInfo info;
   // the frames are validated like any decode input; the surfaces may have any (common) size
   if (dec != nullptr) FLUSH_STREAM(dec->ctx, stream);
-  if (int rc = gather_batch(dec, count, frames, alphas, outs, OutShape::kAny, stream, &p, &info)) return rc;
+  const int layout = dec != nullptr ? dec->chroma_layout.load() : BT709HIP_CHROMA_NV12;
+  if (int rc = gather_batch(dec, count, frames, alphas, outs, OutShape::kAny, layout, stream, &p, &info)) return rc;
+  if (layout == BT709HIP_CHROMA_I420) return BT709HIP_ERR_UNSUPPORTED;  // the rescale kernels' strip loaders read NV12
   const int over = dec->scaled_over;  // BT709HIP_OPT_SCALED_OVER blends here; without it BT709HIP_OPT_COMPOSITE_OVER (the 1:1 path only) refuses
   if (over == BT709HIP_OVER_OFF && dec->composite_over != BT709HIP_OVER_OFF) return BT709HIP_ERR_UNSUPPORTED;
   if (p.width == 0) return BT709HIP_OK;

@@ -58,6 +58,7 @@ struct bt709hip_context {
 struct PendingQueue {
   hipStream_t stream = nullptr;
   bool with_alphas = false;  // the calls passed alpha descriptors
+  int layout = BT709HIP_CHROMA_NV12;  // the chroma layout its frames were submitted under (BT709HIP_OPT_CHROMA_LAYOUT)
   int64_t oldest_us = 0;     // steady-clock time at which the oldest frame it holds was queued (BT709HIP_OPT_COALESCE_MAX_AGE_US)
   std::vector<bt709hip_frame> frames, alphas;
   std::vector<bt709hip_surface> outs;
@@ -80,6 +81,7 @@ struct bt709hip_decoder {
   std::atomic<int> scale_intermediate{BT709HIP_FORMAT_BGRA8_SRGB};  // BT709HIP_OPT_SCALE_INTERMEDIATE: what the fused rescales filter
   std::atomic<int> composite_over{BT709HIP_OVER_OFF};  // BT709HIP_OPT_COMPOSITE_OVER: off, the destination, or an sRGB colour R<<16 | G<<8 | B
   std::atomic<int> scaled_over{BT709HIP_OVER_OFF};     // BT709HIP_OPT_SCALED_OVER: the same three forms, read by the rescale paths alone
+  std::atomic<int> chroma_layout{BT709HIP_CHROMA_NV12};  // BT709HIP_OPT_CHROMA_LAYOUT: how bt709hip_decode[_batch] read the CALLER's colour frames
   std::mutex queue_mutex;   // guards queues
   std::vector<PendingQueue> queues;  // one per stream that has (had) queued frames
   std::mutex setup_mutex;
@@ -158,7 +160,9 @@ int finish_launch(hipStream_t s, int wait_until_completed);
 
 // shim_decode.cpp
 int required_transfer(int gamma);
-int validate(const bt709hip_decoder *dec, const bt709hip_frame *f, const bt709hip_frame *a, const bt709hip_surface *o, int out_w,
+// `layout` (here and below): BT709HIP_CHROMA_* of the colour frames.  The public entry points pass the decoder's option; the
+// objects that allocate their own (NV12) frames -- ring, ring set, pool, shard -- pass BT709HIP_CHROMA_NV12 whatever it holds.
+int validate(const bt709hip_decoder *dec, int layout, const bt709hip_frame *f, const bt709hip_frame *a, const bt709hip_surface *o, int out_w,
              int out_h, int render_w, int render_h);
 int ensure_setup(bt709hip_decoder *dec, void *stream);
 int ensure_half_table(bt709hip_decoder *dec, void *stream);
@@ -171,15 +175,22 @@ enum class OutShape { kSame, kHalf, kAny };  // output size relative to the fram
 
 struct BatchInfo {
   bool uniform = false;    // frames evenly spaced in memory (no pointer table needed)
-  uint32_t in_align = 16;  // largest power of two <= 16 dividing every input plane pointer and pitch
+  uint32_t in_align = 16;  // largest power of two <= 16 dividing every input plane pointer and pitch (I420: the luma and alpha planes')
+  uint32_t chroma_align = 16;  // the same over the chroma pointers and pitch alone (I420: the U plane's; V sits a whole number of rows behind it)
   uint32_t out_align = 16; // same for the outputs
   int format = BT709HIP_FORMAT_BGRA8_SRGB;
 };
 // validation of a batch in the reference's order + the launch parameters it implies
 int gather_batch(bt709hip_decoder *dec, int count, const bt709hip_frame *frames, const bt709hip_frame *alphas,
-                 const bt709hip_surface *outs, OutShape shape, void *stream, DecodeParams *p, BatchInfo *info);
-int decode_batch_now(bt709hip_decoder *dec, int count, const bt709hip_frame *frames, const bt709hip_frame *alphas,
+                 const bt709hip_surface *outs, OutShape shape, int layout, void *stream, DecodeParams *p, BatchInfo *info);
+int decode_batch_now(bt709hip_decoder *dec, int layout, int count, const bt709hip_frame *frames, const bt709hip_frame *alphas,
                      const bt709hip_surface *outs, void *stream, int wait_until_completed);
+// bt709hip_decode_batch / bt709hip_decode_half_batch under an explicit layout (they pass the option's value).  bt709_ring.cpp, which
+// includes the public header only, repeats these two declarations: change them together
+int decode_batch_layout(bt709hip_decoder *dec, int layout, int count, const bt709hip_frame *frames, const bt709hip_frame *alphas,
+                        const bt709hip_surface *outs, void *stream, int wait_until_completed);
+int decode_half_batch_layout(bt709hip_decoder *dec, int layout, int count, const bt709hip_frame *frames, const bt709hip_frame *alphas,
+                             const bt709hip_surface *outs, void *stream, int wait_until_completed);
 
 // shim_convert.cpp
 int encoder_tables(bt709hip_context *ctx, int input_gamma, int output_gamma, hipStream_t s);
@@ -190,7 +201,7 @@ int issue_queue(bt709hip_decoder *dec, PendingQueue &q);
 int flush_decoder(bt709hip_decoder *dec, hipStream_t s, bool all, bool aged_only = false);
 int flush_stream(bt709hip_context *ctx, hipStream_t s, const bt709hip_decoder *skip = nullptr);
 int set_coalescing(bt709hip_decoder *dec, int n);
-int coalescing_submit(bt709hip_decoder *dec, int count, const bt709hip_frame *frames, const bt709hip_frame *alphas,
+int coalescing_submit(bt709hip_decoder *dec, int layout, int count, const bt709hip_frame *frames, const bt709hip_frame *alphas,
                       const bt709hip_surface *outs, void *stream, int wait_until_completed);
 
 // every entry point that takes a stream issues what coalescing decoders have queued for it first

@@ -144,7 +144,8 @@ int bt709hip_pool_submit(bt709hip_pool *pool, int slot) {
   // slot that can be neither submitted nor acquired again.
   s.acquired = false;
   s.busy = true;
-  if (int rc = bt709hip_decode(pool->dec, &f, pool->dec->has_alpha ? &a : nullptr, &o, w, h, s.stream, 0)) return rc;
+  // the slot's staging IS NV12 (the acquire call hands out Y and CbCr planes): the layout is passed, the decoder's option not read
+  if (int rc = decode_batch_layout(pool->dec, BT709HIP_CHROMA_NV12, 1, &f, pool->dec->has_alpha ? &a : nullptr, &o, s.stream, 0)) return rc;
   if (int rc = bt709hip_decoder_flush(pool->dec, s.stream)) return rc;  // the raw copy below must follow the decode
   HIP_TRY(hipMemcpyAsync(s.h_out, s.d_out, pool->out_bytes, hipMemcpyDeviceToHost, s.stream));
   return BT709HIP_OK;

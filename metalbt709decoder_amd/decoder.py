@@ -437,17 +437,22 @@ class CVPixelBuffer:
     """kCVPixelFormatType_420YpCbCr8BiPlanarVideoRange buffer in device memory plus the
     attachments -processBT709ToSRGB: validates (MetalBT709Decoder.m:311-368)."""
 
-    def __init__(self, ctx, width, height, y_stride=None, cbcr_stride=None, planes=None):
+    def __init__(self, ctx, width, height, y_stride=None, cbcr_stride=None, planes=None, planar=False):
         """planes: (y, cbcr) device pointers somebody else owns; cbcr may be None for an ALPHA buffer (a decoder reads only
-        the Y plane of one, and convertAlphaIntoCoreVideoBuffer then writes only that)."""
+        the Y plane of one, and convertAlphaIntoCoreVideoBuffer then writes only that).
+        planar: the chroma is two planes (I420, the YUV4MPEG2 layout; _capi.CHROMA_I420) -- cbcr_ptr is the U plane, W/2 x H/2
+        bytes at pitch cbcr_stride (default W/2 rounded up to 16), and V the same shape (H/2) * cbcr_stride behind it: W/2 x H
+        bytes in all.  decodeBT709 reads such a buffer in place (it sets _capi.OPT_CHROMA_LAYOUT from this flag on every call,
+        whatever setOption was given); the rescales, RGBA16F targets and the encoder do not take one."""
         self.ctx, self.width, self.height = ctx, int(width), int(height)
+        self.planar = bool(planar)
         self.y_stride = int(y_stride) if y_stride else _align_up(self.width, 16)
-        self.cbcr_stride = int(cbcr_stride) if cbcr_stride else _align_up(self.width, 16)
+        self.cbcr_stride = int(cbcr_stride) if cbcr_stride else _align_up(self.width // 2 if self.planar else self.width, 16)
         self.attachments = {}
         self._buf = None
         if planes is None:
             ysz = _align_up(self.y_stride * self.height, 256)
-            csz = self.cbcr_stride * (self.height // 2)
+            csz = self.cbcr_stride * (self.height // 2) * (2 if self.planar else 1)
             self._buf = DeviceBuffer(ctx, max(ysz + csz, 16))
             self.y_ptr, self.cbcr_ptr = self._buf.ptr, self._buf.ptr + ysz
         else:
@@ -464,8 +469,45 @@ class CVPixelBuffer:
         return Frame(self.y_ptr, self.y_stride, self.cbcr_ptr, self.cbcr_stride, self.width, self.height,
                      self.getAttachment("YCbCrMatrix"), self.getAttachment("TransferFunction"))
 
+    @property
+    def chroma_layout(self):
+        return _capi.CHROMA_I420 if self.planar else _capi.CHROMA_NV12
+
+    @property
+    def v_ptr(self):
+        """The V plane of a planar buffer."""
+        return self.cbcr_ptr + (self.height // 2) * self.cbcr_stride
+
+    def planes(self):
+        """Device pointers and pitches of the buffer's planes: [(Y, pitch), (CbCr, pitch)], or [(Y, pitch), (U, pitch), (V, pitch)]
+        for a planar buffer."""
+        if not self.planar:
+            return [(self.y_ptr, self.y_stride), (self.cbcr_ptr, self.cbcr_stride)]
+        return [(self.y_ptr, self.y_stride), (self.cbcr_ptr, self.cbcr_stride), (self.v_ptr, self.cbcr_stride)]
+
+    def upload_yuv(self, y, u, v, commandBuffer=None):
+        """Planar buffers: the three planes as they are, no kernel."""
+        assert self.planar
+        y, u, v = (np.ascontiguousarray(a, dtype=np.uint8) for a in (y, u, v))
+        assert y.shape == (self.height, self.width) and u.shape == v.shape == (self.height // 2, self.width // 2)
+        for (ptr, pitch), plane in zip(self.planes(), (y, u, v)):
+            self.ctx._upload(ptr, pitch, plane, commandBuffer)
+        self.ctx._sync(commandBuffer)
+
+    def download_yuv(self, commandBuffer=None):
+        """Planar buffers: tight (H, W), (H/2, W/2), (H/2, W/2) arrays read back, no kernel."""
+        assert self.planar
+        out = [np.empty((self.height, self.width), np.uint8)] + [np.empty((self.height // 2, self.width // 2), np.uint8) for _ in range(2)]
+        if self.width and self.height:
+            stream = commandBuffer.stream if commandBuffer else None
+            for (ptr, pitch), a in zip(self.planes(), out):
+                _capi.check(self.ctx.lib.bt709hip_download(self.ctx.handle, a.ctypes.data, a.shape[1], ptr, pitch, a.shape[1], a.shape[0], stream), "download plane")
+            self.ctx._sync(commandBuffer)
+        return tuple(out)
+
     # plane upload/download (CVPixelBufferLockBaseAddress + memcpy in the reference)
     def upload_planes(self, y, cbcr, commandBuffer=None):
+        assert not self.planar, "a planar buffer takes upload_yuv"
         y = np.ascontiguousarray(y, dtype=np.uint8)
         cbcr = np.ascontiguousarray(cbcr, dtype=np.uint8)
         assert y.shape == (self.height, self.width) and cbcr.shape == (self.height // 2, self.width)
@@ -628,9 +670,9 @@ class BGRAToBT709Converter:
     """Buffer helpers of Renderer/BGRAToBT709Converter.{h,m} that the decode tests use."""
 
     @staticmethod
-    def createCoreVideoYCbCrBuffer(ctx, size, y_stride=None, cbcr_stride=None):
+    def createCoreVideoYCbCrBuffer(ctx, size, y_stride=None, cbcr_stride=None, planar=False):
         w, h = size  # BGRAToBT709Converter.m:471-494
-        return CVPixelBuffer(ctx, w, h, y_stride, cbcr_stride)
+        return CVPixelBuffer(ctx, w, h, y_stride, cbcr_stride, planar=planar)
 
     @staticmethod
     def setBT709Attributes(buf):
@@ -797,7 +839,8 @@ class MetalBT709Decoder:
         self._options = {}  # bt709hip_decoder_option -> value, applied at setup and on change
 
     def setOption(self, option, value):
-        """Kernel-selection knob (bt709hip_decoder_set_option; _capi.OPT_*): tuning and test hook."""
+        """Kernel-selection knob (bt709hip_decoder_set_option; _capi.OPT_*): tuning and test hook.  Not OPT_CHROMA_LAYOUT: the decode
+        calls set that one from the buffers they are handed (CVPixelBuffer.planar)."""
         self._options[int(option)] = int(value)
         if self._handle:
             _capi.check(self.metalRenderContext.lib.bt709hip_decoder_set_option(self._handle, int(option), int(value)),
@@ -911,6 +954,20 @@ class MetalBT709Decoder:
         self.lastStatus = _capi.OK
         return True
 
+    def _set_layout(self, pixelBuffers, what):
+        """The chroma layout option (_capi.OPT_CHROMA_LAYOUT) from the buffers a call was handed: a planar CVPixelBuffer is read in
+        place by decodeBT709 / decodeBT709Batch; the rescales and RGBA16F targets then fail with ERR_UNSUPPORTED.  Cheap: the
+        setter never touches the device.  The buffer's `planar` flag is AUTHORITATIVE in this mirror: every decode call sets the
+        option from it, so a value given to setOption(_capi.OPT_CHROMA_LAYOUT, ...) by hand lasts until the next decode call --
+        planar memory is described by CVPixelBuffer(..., planes=(y, u), planar=True), not by the option."""
+        layouts = {getattr(b, "chroma_layout", _capi.CHROMA_NV12) for b in pixelBuffers}
+        if len(layouts) > 1:
+            return self._fail(_capi.ERR_INVALID_ARG, what + ": planar and NV12 buffers in one call")
+        layout = layouts.pop() if layouts else _capi.CHROMA_NV12
+        if self._options.get(_capi.OPT_CHROMA_LAYOUT, _capi.CHROMA_NV12) != layout:
+            self.setOption(_capi.OPT_CHROMA_LAYOUT, layout)
+        return True
+
     def decodeBT709(self, yCbCrInputTexture, alphaPixelBuffer=None, bgraSRGBTexture=None, commandBuffer=None,
                     renderPassDescriptor=None, renderWidth=0, renderHeight=0, waitUntilCompleted=False):
         """Returns True on success, False on any validation or launch failure
@@ -926,6 +983,8 @@ class MetalBT709Decoder:
         if yCbCrInputTexture is None or target is None:
             return self._fail(_capi.ERR_INVALID_ARG, "decodeBT709")
         lib = self.metalRenderContext.lib
+        if not self._set_layout([yCbCrInputTexture], "decodeBT709"):
+            return False
         frame = yCbCrInputTexture.frame()
         alpha = alphaPixelBuffer.frame() if alphaPixelBuffer is not None else None
         surf = target.surface()
@@ -949,6 +1008,8 @@ class MetalBT709Decoder:
         if not self.setupMetal():
             return False
         n = len(pixelBuffers)
+        if not self._set_layout(pixelBuffers, "decodeBT709Batch"):
+            return False
         frames = (Frame * n)(*[b.frame() for b in pixelBuffers])
         surfs = (Surface * n)(*[t.surface() for t in textures])
         alphas = (Frame * n)(*[b.frame() for b in alphaPixelBuffers]) if alphaPixelBuffers else None
@@ -965,7 +1026,7 @@ class MetalBT709Decoder:
         """-decodeBT709 into an intermediate + MetalScaleRenderContext -renderScaled:
         (AAPLRenderer.m:940-977), fused: the tuned kernel for the exact 2:1 ratio, the general
         bilinear kernel for any other view size (bit-identical where both apply)."""
-        if not self.setupMetal():
+        if not self.setupMetal() or not self._set_layout([yCbCrInputTexture], "decodeBT709Scaled"):
             return False
         frame, surf = yCbCrInputTexture.frame(), bgraSRGBTexture.surface()
         alpha = alphaPixelBuffer.frame() if alphaPixelBuffer is not None else None
@@ -986,7 +1047,7 @@ class MetalBT709Decoder:
         """Fused decode + rescale of `count` same-geometry frames into same-sized outputs in one launch
         (no reference twin): the 2:1 kernels when every output is exactly half the frame (large launches
         run the persistent conflict-free kernel), the general bilinear kernel otherwise."""
-        if not self.setupMetal():
+        if not self.setupMetal() or not self._set_layout(pixelBuffers, "decodeBT709ScaledBatch"):
             return False
         n = len(pixelBuffers)
         frames = (Frame * n)(*[b.frame() for b in pixelBuffers])

@@ -133,13 +133,18 @@ class Y4MReader:
 
 # ------------------------------------------------------------------ GPU hops
 
-def i420_to_pixel_buffer(ctx, y, u, v, tag_bt709=True):
-    """Upload planar Y,U,V and interleave the chroma on the device into a new 420v CVPixelBuffer."""
+def i420_to_pixel_buffer(ctx, y, u, v, tag_bt709=True, planar=False):
+    """Upload planar Y,U,V and interleave the chroma on the device into a new 420v CVPixelBuffer.
+    planar=True: a PLANAR buffer instead (CVPixelBuffer(planar=True)) -- the three planes are uploaded as they are and nothing is
+    launched; decodeBT709 reads it in place (_capi.OPT_CHROMA_LAYOUT)."""
     y, u, v = (np.ascontiguousarray(a, dtype=np.uint8) for a in (y, u, v))
     h, w = y.shape
-    buf = BGRAToBT709Converter.createCoreVideoYCbCrBuffer(ctx, (w, h))
+    buf = BGRAToBT709Converter.createCoreVideoYCbCrBuffer(ctx, (w, h), planar=planar)
     if tag_bt709:
         BGRAToBT709Converter.setBT709Attributes(buf)
+    if planar:
+        buf.upload_yuv(y, u, v)
+        return buf
     cw, ch = w // 2, h // 2
     pitch = (cw + 15) // 16 * 16
     stage = DeviceBuffer(ctx, max(2 * pitch * ch, 16))
@@ -153,7 +158,9 @@ def i420_to_pixel_buffer(ctx, y, u, v, tag_bt709=True):
 
 
 def pixel_buffer_to_i420(buf):
-    """De-interleave a device CVPixelBuffer's chroma on the GPU and read Y,U,V back."""
+    """De-interleave a device CVPixelBuffer's chroma on the GPU and read Y,U,V back (a planar buffer: a plain download)."""
+    if getattr(buf, "planar", False):
+        return buf.download_yuv()
     ctx = buf.ctx
     w, h = buf.width, buf.height
     cw, ch = w // 2, h // 2

@@ -35,6 +35,7 @@ Gates (macro -> what it does; profiles/ file it produced):
   BT709_LAB_SCALED_PAIR_DPP            the same with the copy taken from the next lane by a DPP move (lane-pair exchange)      r06_ab_scaled_share.txt
   BT709_LAB_SCALED_ONCE_LDS            wave-decodes-once form exchanging through a wave-private LDS tile (same bytes out)      r06_ab_scaled_share.txt
   BT709_LAB_SCALED_NO_FETCH / _NO_DECODE / _NO_ENCODE / _NO_STORE  any-ratio kernel, WRONG OUTPUT: one part deleted each      r06_ab_scaled_parts.txt
+  BT709_LAB_I420_PAIRED                planar 1:1 fast kernels: ONE chroma dword per quad, shared by lane pairs over DPP, instead of two 2-byte loads (same bytes out; frames without W % 8 == 0, 4-byte aligned chroma planes and V less than 4 GiB behind U take the general kernel)   r12_planar.txt
   BT709_LAB_HUNT_TRACE                 bt709hip_ring_create prints where its hunt's wall-clock time went (stderr; same ring)   r06_hunt_default.txt
 """
 import os
@@ -60,7 +61,7 @@ GATES = [
       cw[j] = load32<NT>(cc + 4 * q);
 #endif
 """),
-    ("bt709_kernels.hip",
+    ("bt709_decode_body.h",
      """  if (!QUANT) {  // the sRGB mode needs no table (decode_quad)
     stage_table(lds_raw, p.table_unit, p.table_unit_bytes);  // after the tile's loads are in flight
     __syncthreads();
@@ -73,7 +74,7 @@ GATES = [
   }
 #endif
 """),
-    ("bt709_kernels.hip",
+    ("bt709_decode_body.h",
      """    decode_quad<HAS_ALPHA, QUANT, LOGIDX>(ul, in.ya[u], in.yb[u], in.cw[u], HAS_ALPHA ? in.aa[u] : 0u, HAS_ALPHA ? in.ab[u] : 0u, p.alpha_word, top, bot);
     if (q < quads && rp_raw < row_pairs) {
 """,
@@ -741,7 +742,7 @@ double *lab_trace() {  // seconds: malloc, free, mem_info, warm-up, probe
 """),
 ]
 
-MACROS = ["BT709_LAB_NO_ARITH", "BT709_LAB_NO_LOADS", "BT709_LAB_NO_STORES", "BT709_LAB_NO_TABLE", "BT709_NO_FMA_CENTRE",
+MACROS = ["BT709_LAB_I420_PAIRED", "BT709_LAB_NO_ARITH", "BT709_LAB_NO_LOADS", "BT709_LAB_NO_STORES", "BT709_LAB_NO_TABLE", "BT709_NO_FMA_CENTRE",
           "BT709_INDEX_RTZ", "BT709_UNIFORM_INDEX_TWO_STEP", "BT709_REP_SPLIT_ENCODE", "BT709_LAB_BOUND_SHARED_INDEX",
           "BT709_LAB_BOUND_ONE_ENCODE", "BT709_LAB_HALF_TABLE", "BT709_LAB_F16_NO_ARITH", "BT709_LAB_F16_NO_TABLE",
           "BT709_LAB_F16_CVT_ONLY", "BT709_LAB_F16_NO_CAND_GATHER", "BT709_LAB_F16_NO_T_GATHER", "BT709_LAB_F16_NO_INDEX_SCALE", "BT709_LAB_F16_DMA_STAGING", "BT709_LAB_ENC_NO_ARITH", "BT709_LAB_UNC_NO_ARITH", "BT709_LAB_SCALED_QUARTER_FEWER_TAPS", "BT709_LAB_HALF_ENCODE_B32",
@@ -749,6 +750,46 @@ MACROS = ["BT709_LAB_NO_ARITH", "BT709_LAB_NO_LOADS", "BT709_LAB_NO_STORES", "BT
 
 
 RESCALE_FILES = ("bt709_rescale.h", "bt709_rescale_half.hip", "bt709_rescale_scaled.hip", "bt709_scaled_strip.h")  # round 6 split bt709_rescale.hip; the strip shared with bt709_rescale_f16.hip moved to a header
+
+
+GATES += [
+    # round 12: the planar front end's other chroma-fetch design (profiles/LAB.md, "Round 12").  A lane whose quad q
+    # is even loads the U dword of quads q, q + 1, its odd neighbour the V dword; quad_perm:[1,0,3,2] hands each the other's, and one
+    # v_perm_b32 with a per-lane selector picks the lane's two U and two V bytes.  As many VMEM instructions as NV12.  In bounds only
+    # while quads is even (the last even lane's dword ends at the row's last byte), the chroma planes are 4-byte aligned and V sits
+    # less than 4 GiB behind U: the third gate below makes the shim send every other frame to the general kernel.
+    ("bt709_tile.h",
+     """      cu[j] = load16<NT>(uu + 2 * q);
+      cv[j] = load16<NT>(vv + 2 * q);
+""",
+     """#if defined(BT709_LAB_I420_PAIRED)
+      cu[j] = load32<NT>(uu + (4 * (q >> 1) + ((q & 1) ? static_cast<uint32_t>(p.v_offset) : 0u)));
+      cv[j] = (q & 1) ? 0x07030602u : 0x01050004u;  // the perm's selector: bytes 0-3 the partner's dword, 4-7 the lane's own
+#else
+      cu[j] = load16<NT>(uu + 2 * q);
+      cv[j] = load16<NT>(vv + 2 * q);
+#endif
+"""),
+    ("bt709_tile.h",
+     """      cw[j] = __builtin_amdgcn_perm(cv[j], cu[j], 0x05010400u);
+""",
+     """#if defined(BT709_LAB_I420_PAIRED)
+      cw[j] = __builtin_amdgcn_perm(cu[j], static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(cu[j]), 0xB1, 0xF, 0xF, false)), cv[j]);
+#else
+      cw[j] = __builtin_amdgcn_perm(cv[j], cu[j], 0x05010400u);
+#endif
+"""),
+    ("shim_decode.cpp",
+     """  const bool fast = (p.width % 4) == 0 && info.in_align >= 4 && info.out_align >= 16 && (layout != BT709HIP_CHROMA_I420 || info.chroma_align >= 2);
+""",
+     """#if defined(BT709_LAB_I420_PAIRED)  // the paired fetch is in bounds for these frames only; the others take the general kernel
+  const bool fast = (p.width % 4) == 0 && info.in_align >= 4 && info.out_align >= 16 &&
+                    (layout != BT709HIP_CHROMA_I420 || ((p.width % 8) == 0 && info.chroma_align >= 4 && p.v_offset + p.width / 2 <= 0xffffffffull));
+#else
+  const bool fast = (p.width % 4) == 0 && info.in_align >= 4 && info.out_align >= 16 && (layout != BT709HIP_CHROMA_I420 || info.chroma_align >= 2);
+#endif
+"""),
+]
 
 
 def resolve(csrc, name, product):
