@@ -220,7 +220,15 @@ int bt709hip_decoder_flush_all(bt709hip_decoder *dec);
  * - item 0) in every plane.  No reference twin (the reference converts, rescales and encodes one frame per call: a 4K frame
  * is a 12-22 us kernel, too short to fill the chip; one 4K +unconvert: per call runs at 0.58 of the roofline).  Differing sizes,
  * strides or formats: BT709HIP_ERR_SIZE_MISMATCH.  bt709hip_render_scaled_batch takes evenly spaced surfaces only
- * (BT709HIP_ERR_UNSUPPORTED otherwise).  bt709hip_encode_batch with BT709HIP_FORMAT_BGRA8_ALPHA input (alpha frames, bt709hip.h):
+ * (BT709HIP_ERR_UNSUPPORTED otherwise), each base a multiple of its texel size (BT709HIP_ERR_STRIDE, as the single call).
+ * THE UNIFORM RULE, for every batched entry point (bt709hip_decode_batch and the coalescing queue included): a batch is evenly
+ * spaced when, plane by plane (Y, CbCr, alpha, target; the encoder's BGRA, Y, CbCr), item i's pointer is item 0's + i * step, the
+ * step being item 1's pointer - item 0's as a signed 64-bit byte count.  ANY TWO items are evenly spaced: a batch of two always
+ * launches this way, whatever its pointers.  A step may be negative (items in descending order), 4 GiB or more, another for
+ * every plane and of another sign, and 0 on the input side (one frame, one alpha plane, decoded into several targets).  It is
+ * folded into the alignment the fast kernels need: a step off that alignment selects the general kernel, same bytes out.
+ * Output items that overlap one another (an output step smaller than a target's extent, 0 included) are the caller's error:
+ * the result is undefined and nothing checks for it.  bt709hip_encode_batch with BT709HIP_FORMAT_BGRA8_ALPHA input (alpha frames, bt709hip.h):
  * every out[i].cbcr NULL or none (else BT709HIP_ERR_INVALID_ARG); bt709hip_encoder_prepare(ctx, LINEAR, LINEAR) also builds its table. */
 int bt709hip_unconvert_batch(bt709hip_decoder *dec, int count, const void *const *ycbcr_words, size_t in_stride, int width, int height,
                              const bt709hip_surface *outs, void *stream, int wait_until_completed);

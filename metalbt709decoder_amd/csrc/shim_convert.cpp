@@ -191,6 +191,10 @@ static int render_scaled_launch(bt709hip_context *ctx, int count, const bt709hip
       out->stride < static_cast<size_t>(out->width) * 4 || (out->stride & 3) || !aligned(out->bgra, 4) ||
       in->stride > 0xffffffffu || out->stride > 0xffffffffu)
     return BT709HIP_ERR_STRIDE;
+  // the other surfaces of a batch share surface 0's geometry; their bases are checked as its base was (a step that is no
+  // multiple of the texel size misaligns surface 1 onwards)
+  for (int i = 1; i < count; ++i)
+    if (!aligned(in[i].bgra, ipx) || !aligned(out[i].bgra, 4)) return BT709HIP_ERR_STRIDE;
   if (out->height > kMaxGridYZ) return BT709HIP_ERR_UNSUPPORTED;
   if (int rc = bind(ctx)) return rc;
   FLUSH_STREAM(ctx, stream);

@@ -1,0 +1,365 @@
+"""Where the frames of a batched call lie (tests/test_batch_spacing_cpu.py, tests/test_batch_spacing_gpu.py; numpy and ctypes only).
+
+Every batched entry point finds frame i of a launch either in a pointer table (32 entries) or, when the caller's pointers are
+evenly spaced, as frame 0 + i * step with one signed 64-bit step per plane -- and ANY two frames are evenly spaced.  The rest
+of the suite carves its frames in ascending order at one positive pitch from one slab.  build(route, cls) lays the planes of a
+ROUTE (an entry point and a kernel form: its planes, sizes, decoder options and the kernel it must report) out in one input and
+one output slab under a SPACING CLASS:
+
+    descending-2 / -3 / -33   every step negative; 33 frames are past the pointer table
+    crossed-up-down / -down-up  inputs ascending and outputs descending, and the reverse
+    fan-out                   every input step 0 (one frame, one alpha plane), the outputs ascending
+    plane-skew                each plane evenly spaced at a step of its own: input plane j steps by j + 1 slots of its size, output
+                              plane j by j + 2, every second plane of a side downwards
+    far / far-descending      two frames 2^32 + d bytes apart on every plane (d small, a multiple of 16), the high one second / first
+    bands-tail-descending     70 frames, all steps negative: 64 under the XCD-band map, 6 behind advance_frames
+    skewed-step-2 / -1        frame 0 16-byte aligned, the step of every byte-addressed plane = 2 (mod 4) / odd
+    table-twin                the descending-3 frames with the middle one moved: no step reaches every frame, the table is used
+
+The slabs are the two of 4 GiB + 1 MiB the far classes need; the other classes lie 1 GiB inside them (an address that is off by
+less than that is still memory of the test's own).  A layout names WINDOWS: the byte ranges the test uploads, downloads and
+checks.  Below 2^32 + 1 MiB of slab only the windows are ever touched by the host: the small classes have one window (their
+whole span), the far classes one per frame and plane -- the samples with a guard band either side -- and one ALIAS window per
+plane where a step cut to its low 32 bits would land: frame 0 + d (far: zero- or sign-extended alike), frame 0 - d
+(far-descending, sign-extended; zero-extended it leaves the slab, which is why that class is never run against a variant that
+cuts the step).  Layout.check() asserts, on the CPU, that all of them lie inside their slab, apart from one another by at least
+a guard band."""
+import ctypes as C
+
+import numpy as np
+
+from metalbt709decoder_amd import _capi
+from metalbt709decoder_amd._capi import Frame, Surface
+
+CANARY = 0x5A
+GUARD = 256
+FAR = 1 << 32
+SLAB_BYTES = FAR + (1 << 20)
+NEAR_ORIGIN = 1 << 30
+MATRIX_709, TRANSFER_709, TRANSFER_SRGB, TRANSFER_LINEAR = 1, 1, 2, 3  # the frame tags (kCVImageBuffer...: metalbt709decoder_amd)
+GAMMA_APPLE, GAMMA_SRGB, GAMMA_LINEAR = 0, 1, 2
+F16, SRGB8, ALPHA8 = _capi.FORMAT_RGBA16F, _capi.FORMAT_BGRA8_SRGB, _capi.FORMAT_BGRA8_ALPHA
+
+# class -> (kind, frames)
+CLASSES = {
+    "descending-2": ("descending", 2), "descending-3": ("descending", 3), "descending-33": ("descending", 33),
+    "crossed-up-down": ("crossed-up-down", 3), "crossed-down-up": ("crossed-down-up", 3),
+    "fan-out": ("fan-out", 3), "plane-skew": ("plane-skew", 3),
+    "far": ("far", 2), "far-descending": ("far-descending", 2),
+    "bands-tail-descending": ("descending", 70),
+    "skewed-step-2": ("skewed", 3), "skewed-step-1": ("skewed", 3),
+    "table-twin": ("table-twin", 3),
+}
+SKEW = {"skewed-step-2": 2, "skewed-step-1": 1}
+TWIN_SLOTS = [2, 3, 0]
+
+
+def _up(v, a):
+    return (v + a - 1) // a * a
+
+
+class Plane:
+    """rows x row_bytes samples at pitch `stride`; unit: what the entry point requires a base pointer to be a multiple of (1: any
+    address is accepted, so the skewed classes apply)."""
+
+    def __init__(self, name, row_bytes, rows, stride, unit=1):
+        assert stride >= row_bytes
+        self.name, self.row_bytes, self.rows, self.stride, self.unit = name, row_bytes, rows, stride, unit
+        self.extent = stride * (rows - 1) + row_bytes
+
+    def index(self, off):
+        """Indices of the samples, (rows, row_bytes), in an array whose element 0 is `off` bytes before the plane."""
+        return off + np.arange(self.rows)[:, None] * self.stride + np.arange(self.row_bytes)[None, :]
+
+
+class Route:
+    """entry: "decode" | "half" | "scaled" | "render" | "unconvert" | "encode".  size / out_size: (w, h) of a frame and of its
+    target.  kernel: what bt709hip_last_kernel_name must report; taps: (tap form, persistent) of bt709hip_last_scaled_launch_info;
+    skew: skew residue -> (kernel, taps) of the demoted launch; bands: the launch splits under bands-tail-descending."""
+
+    def __init__(self, name, entry, size, out_size, ins, outs, kernel, gamma=GAMMA_APPLE, alpha=False, options=(), over=None, fmt=SRGB8,
+                 in_fmt=SRGB8, taps=None, skew=None, bands=False, reads_destination=False, pair=None, no_skew=None):
+        self.name, self.entry, self.size, self.out_size, self.ins, self.outs, self.kernel = name, entry, size, out_size, ins, outs, kernel
+        self.gamma, self.alpha, self.options, self.over, self.fmt, self.in_fmt = gamma, alpha, tuple(options), over, fmt, in_fmt
+        self.taps, self.skew, self.bands, self.reads_destination, self.pair, self.no_skew = taps, skew, bands, reads_destination, pair, no_skew
+
+    def plane(self, name):
+        return next(p for p in self.ins + self.outs if p.name == name)
+
+    def classes(self):
+        """The classes that apply (see CLASSES_NOT_RUN for the others)."""
+        out = ["descending-2", "descending-3", "descending-33", "crossed-up-down", "crossed-down-up", "fan-out"]
+        if len(self.ins) > 1 or len(self.outs) > 1:
+            out.append("plane-skew")
+        out += ["far", "far-descending"]
+        if self.bands:
+            out.append("bands-tail-descending")
+        if self.skew:
+            out += [c for c in SKEW if SKEW[c] in self.skew]
+        out.append("table-twin")
+        return out
+
+
+def _nv12(w, h, sy, sc, sa=None):
+    planes = [Plane("y", w, h, sy), Plane("cbcr", w, h // 2, sc)]
+    return planes + ([Plane("alpha", w, h, sa)] if sa else [])
+
+
+def _out(ow, oh, pad, px=4):
+    return [Plane("out", px * ow, oh, px * ow + pad, unit=px)]
+
+
+W, H = 64, 16
+HALF_REP = ((_capi.OPT_HALF_KERNEL, 1), (_capi.OPT_HALF_WORKGROUPS, 3))  # three persistent workgroups: the cursor wraps from frame to frame
+ONCE, WIDE, PAIRS, BYTES = _capi.SCALED_TAPS_ONCE, _capi.SCALED_TAPS_WIDE, _capi.SCALED_TAPS_PAIRS, _capi.SCALED_TAPS_BYTES
+DOWN = dict(size=(W, H), out_size=(40, 10))  # 1.6 : 1 both ways, the per-lane (persistent) forms
+_scaled_skew = lambda kernel: {2: (kernel, (PAIRS, 1)), 1: (kernel, (BYTES, 1))}
+
+ROUTES = [
+    # ---- bt709hip_decode_batch
+    Route("quads", "decode", (W, H), (W, H), _nv12(W, H, 80, 80), _out(W, H, 16), b"decode_nv12_quads<nt>", bands=True,
+          skew={2: (b"decode_nv12_blocks", None), 1: (b"decode_nv12_blocks", None)}),
+    Route("blocks", "decode", (W, H), (W, H), _nv12(W, H, 65, 67), _out(W, H, 4), b"decode_nv12_blocks",
+          no_skew="variant_cases.LAUNCH_CASES step-40 / bands-72 (step_pad (1, 4)) pin the general kernel at an odd step"),
+    Route("quads-over", "decode", (W, H), (W, H), _nv12(W, H, 80, 80, 96), _out(W, H, 16), b"decode_nv12_quads<alpha,over>", gamma=GAMMA_SRGB, alpha=True,
+          over=_capi.OVER_DESTINATION, reads_destination=True, bands=True,
+          skew={2: (b"decode_nv12_blocks<alpha,over>", None), 1: (b"decode_nv12_blocks<alpha,over>", None)}),
+    # planar chroma: the "cbcr" plane is U's H/2 rows, then V's, at one pitch -- V follows each frame's own U
+    Route("i420", "decode", (W, H), (W, H), [Plane("y", W, H, 80), Plane("cbcr", W // 2, H, 48)], _out(W, H, 16), b"decode_i420_quads<nt>",
+          options=((_capi.OPT_CHROMA_LAYOUT, _capi.CHROMA_I420),), bands=True,
+          skew={2: (b"decode_i420_blocks", None), 1: (b"decode_i420_blocks", None)}),
+    Route("rgba16f-alpha", "decode", (W, H), (W, H), _nv12(W, H, 80, 80, 96), _out(W, H, 16, px=8), b"decode_nv12_rgba16f<alpha>", gamma=GAMMA_SRGB,
+          alpha=True, fmt=F16, bands=True, skew={2: (b"decode_nv12_rgba16f<alpha>", None), 1: (b"decode_nv12_rgba16f<alpha>", None)}),
+    # ---- bt709hip_decode_half_batch
+    Route("half-wide", "half", (W, H), (W // 2, H // 2), _nv12(W, H, 80, 80), _out(W // 2, H // 2, 16), b"decode_nv12_half<wide>",
+          skew={2: (b"decode_nv12_half<narrow>", None), 1: (b"decode_nv12_half<narrow>", None)}),
+    Route("half-narrow", "half", (W, H), (W // 2, H // 2), _nv12(W, H, 65, 67), _out(W // 2, H // 2, 4), b"decode_nv12_half<narrow>",
+          no_skew="already the kernel a skewed step demotes to (the half-wide route runs the class)"),
+    Route("half-rep-alpha", "half", (W, H), (W // 2, H // 2), _nv12(W, H, 80, 80, 96), _out(W // 2, H // 2, 16), b"decode_nv12_half_rep<alpha>",
+          gamma=GAMMA_SRGB, alpha=True, options=HALF_REP,
+          skew={2: (b"decode_nv12_half<narrow,alpha>", None), 1: (b"decode_nv12_half<narrow,alpha>", None)}),
+    # ---- bt709hip_decode_scaled_batch
+    Route("scaled-once", "scaled", (32, 8), (64, 16), _nv12(32, 8, 48, 48), _out(64, 16, 16), b"decode_nv12_scaled", taps=(ONCE, 0),
+          skew={2: (b"decode_nv12_scaled", (ONCE, 0)), 1: (b"decode_nv12_scaled", (BYTES, 1))}),
+    Route("scaled-wide", "scaled", ins=_nv12(W, H, 80, 80), outs=_out(40, 10, 16), kernel=b"decode_nv12_scaled", taps=(WIDE, 1),
+          skew=_scaled_skew(b"decode_nv12_scaled"), **DOWN),
+    Route("scaled-f16", "scaled", ins=_nv12(W, H, 80, 80), outs=_out(40, 10, 16), kernel=b"decode_nv12_scaled_f16", taps=(WIDE, 1),
+          options=((_capi.OPT_SCALE_INTERMEDIATE, F16),), skew=_scaled_skew(b"decode_nv12_scaled_f16"), **DOWN),
+    Route("scaled-over", "scaled", ins=_nv12(W, H, 80, 80, 96), outs=_out(40, 10, 16), kernel=b"decode_nv12_scaled<alpha,over>", taps=(WIDE, 1),
+          gamma=GAMMA_SRGB, alpha=True, options=((_capi.OPT_SCALED_OVER, _capi.OVER_DESTINATION),), reads_destination=True,
+          skew=_scaled_skew(b"decode_nv12_scaled<alpha,over>"), **DOWN),
+    # ---- bt709hip_render_scaled_batch (no pointer table: surfaces that are not evenly spaced are refused)
+    Route("render-bgra8", "render", (W, H), (40, 10), [Plane("in", 4 * W, H, 4 * W + 16, unit=4)], _out(40, 10, 16), b"render_scaled<bgra8>",
+          no_skew="every surface base must be a multiple of the texel size (BT709HIP_ERR_STRIDE: tests/test_batch_spacing_cpu.py)"),
+    Route("render-rgba16f", "render", (W, H), (40, 10), [Plane("in", 8 * W, H, 8 * W + 16, unit=8)], _out(40, 10, 16), b"render_scaled<rgba16f>",
+          in_fmt=F16, no_skew="every surface base must be a multiple of the texel size (BT709HIP_ERR_STRIDE: tests/test_batch_spacing_cpu.py)"),
+    # ---- bt709hip_unconvert_batch
+    Route("unconvert-vec", "unconvert", (W, 8), (W, 8), [Plane("in", 4 * W, 8, 4 * W + 16, unit=4)], _out(W, 8, 16), b"unconvert_packed444<vec>",
+          no_skew="words and texels must be 4-byte aligned"),
+    Route("unconvert-pixel", "unconvert", (30, 6), (30, 6), [Plane("in", 120, 6, 124, unit=4)], _out(30, 6, 8), b"unconvert_packed444",
+          no_skew="words and texels must be 4-byte aligned"),
+    # ---- bt709hip_encode_batch
+    Route("encode-fast", "encode", (W, H), (W, H), [Plane("bgra", 4 * W, H, 4 * W + 16, unit=4)], _nv12(W, H, 80, 80), b"encode_bgra_nv12",
+          pair=(GAMMA_SRGB, GAMMA_APPLE), bands=True, skew={2: (b"encode_bgra_nv12_blocks", None), 1: (b"encode_bgra_nv12_blocks", None)}),
+    Route("encode-blocks", "encode", (W, H), (W, H), [Plane("bgra", 4 * W, H, 4 * W + 4, unit=4)], _nv12(W, H, 65, 67), b"encode_bgra_nv12_blocks",
+          pair=(GAMMA_SRGB, GAMMA_APPLE), no_skew="already the kernel a skewed step demotes to (the encode-fast route runs the class)"),
+    # an alpha clip's luma with cbcr == NULL in every frame: the split launch's tail passes advance_frames' `if (cbcr)`
+    Route("encode-alpha-y", "encode", (W, H), (W, H), [Plane("bgra", 4 * W, H, 4 * W + 16, unit=4)], [Plane("y", W, H, 80)], b"encode_alpha_y",
+          pair=(GAMMA_LINEAR, GAMMA_LINEAR), in_fmt=ALPHA8, bands=True, skew={2: (b"encode_alpha_y_blocks", None), 1: (b"encode_alpha_y_blocks", None)}),
+]
+ROUTE = {r.name: r for r in ROUTES}
+PAIRS_RUN = [(r.name, c) for r in ROUTES for c in r.classes()]
+# what is not run, and why: (route, class) -> reason
+CLASSES_NOT_RUN = {(r.name, c): r.no_skew for r in ROUTES if r.no_skew for c in SKEW}
+CLASSES_NOT_RUN.update({(r.name, "plane-skew"): "one input plane and one output plane" for r in ROUTES if len(r.ins) == 1 and len(r.outs) == 1})
+CLASSES_NOT_RUN.update({(r.name, "bands-tail-descending"): "the launch is never split (no XCD-band map for this kernel)" for r in ROUTES if not r.bands})
+
+
+class Layout:
+    """in_off / out_off: plane name -> byte offset of every frame's plane in its slab; steps: plane name -> step, None under
+    table-twin; source[i]: which frame's samples frame i reads (fan-out: all read frame 0's); *_windows: [(lo, hi)] the host
+    touches; *_alias: [(lo, hi)] among them that hold no frame."""
+
+    def __init__(self, route, cls):
+        self.route, self.cls = route, cls
+        self.kind, self.n = CLASSES[cls]
+        self.uniform = self.kind != "table-twin"
+        self.in_off, self.out_off, self.steps = {}, {}, {}
+        self.in_windows, self.out_windows, self.in_alias, self.out_alias = [], [], [], []
+        self.source = [0] * self.n if self.kind == "fan-out" else list(range(self.n))
+
+    def side(self, which):
+        return (self.route.ins, self.in_off, self.in_windows, self.in_alias) if which == "in" else (self.route.outs, self.out_off, self.out_windows, self.out_alias)
+
+    def extents(self, which):
+        """The byte ranges that hold samples or are an alias window, each once."""
+        planes, off, _, alias = self.side(which)
+        return sorted({(o, o + p.extent) for p in planes for o in off[p.name]} | set(alias))
+
+    def check(self):
+        r, n = self.route, self.n
+        for which in ("in", "out"):
+            planes, off, windows, alias = self.side(which)
+            ext = self.extents(which)
+            assert all(0 <= lo < hi <= SLAB_BYTES for lo, hi in ext), (r.name, self.cls, which, "outside the slab")
+            # pairwise disjoint and not adjacent: a guard band between any two
+            assert all(b[0] - a[1] >= GUARD for a, b in zip(ext, ext[1:])), (r.name, self.cls, which, "overlapping or adjacent")
+            # every one of them, with its guard bands, lies in exactly one window; the windows are disjoint and inside the slab
+            assert all(0 <= lo < hi <= SLAB_BYTES for lo, hi in windows)
+            ws = sorted(windows)
+            assert all(a[1] <= b[0] for a, b in zip(ws, ws[1:]))
+            for lo, hi in ext:
+                g = 0 if (lo, hi) in alias else GUARD
+                assert sum(1 for wl, wh in windows if wl <= lo - g and hi + g <= wh) == 1, (r.name, self.cls, which, lo, hi)
+            for p in planes:
+                o, step = off[p.name], self.steps[p.name]
+                assert len(o) == n and all(v % p.unit == 0 for v in o) and o[0] % 16 == 0
+                if self.uniform:
+                    assert all(o[i] == o[0] + i * step for i in range(n)), (r.name, self.cls, p.name)
+                else:
+                    assert step is None and n > 2 and any(o[i] - o[0] != i * (o[1] - o[0]) for i in range(n)), (r.name, self.cls, p.name)
+        steps = [self.steps[p.name] for p in r.ins + r.outs]
+        ins, outs = [self.steps[p.name] for p in r.ins], [self.steps[p.name] for p in r.outs]
+        if self.kind == "descending":
+            assert all(s < 0 for s in steps)
+        elif self.kind in ("crossed-up-down", "crossed-down-up"):
+            up = self.kind == "crossed-up-down"
+            assert all((s > 0) == up for s in ins) and all((s < 0) == up for s in outs)
+        elif self.kind == "fan-out":
+            assert all(s == 0 for s in ins) and all(s > 0 for s in outs)
+        elif self.kind == "plane-skew":
+            assert len(set(steps)) == len(steps) and any(s < 0 for s in steps) and any(s > 0 for s in steps)
+        elif self.kind in ("far", "far-descending"):
+            sign = 1 if self.kind == "far" else -1
+            for which in ("in", "out"):
+                planes, off, _, alias = self.side(which)
+                assert len(alias) == len(planes)
+                for p in planes:
+                    o, d = off[p.name], sign * self.steps[p.name] - FAR
+                    assert 0 < d < (1 << 20) and d % 16 == 0 and max(o) >= FAR and min(o) < (1 << 20)
+                    cut = self.steps[p.name] & 0xFFFFFFFF  # the step's low 32 bits: zero-extended as they are, sign-extended below
+                    landed = o[0] + (cut if sign > 0 else cut - FAR)
+                    assert (landed, landed + p.extent) in alias, (r.name, self.cls, p.name)
+        elif self.kind == "skewed":
+            k = SKEW[self.cls]
+            for p in r.ins + r.outs:
+                s = self.steps[p.name]
+                assert s > 0 and (s % 4 == 2 if k == 2 else s % 2 == 1) if p.unit == 1 else s % 16 == 0
+            assert any(p.unit == 1 for p in r.ins + r.outs)
+        return self
+
+
+def _slots(kind, n, which, j):
+    """Which slot of plane j's region frame i lies in."""
+    up, down = list(range(n)), list(range(n - 1, -1, -1))
+    if kind == "descending":
+        return down
+    if kind in ("crossed-up-down", "crossed-down-up"):
+        return up if (which == "in") == (kind == "crossed-up-down") else down
+    if kind == "fan-out":
+        return [0] * n if which == "in" else up
+    if kind == "plane-skew":  # outputs a slot more than inputs: an output plane as large as an input plane still steps differently
+        return [k * (j + (1 if which == "in" else 2)) for k in (down if j % 2 else up)]
+    if kind == "table-twin":
+        return TWIN_SLOTS
+    return up  # skewed
+
+
+def build(route, cls):
+    L = Layout(route, cls)
+    kind, n = L.kind, L.n
+    for which in ("in", "out"):
+        planes, off, windows, alias = L.side(which)
+        if kind in ("far", "far-descending"):
+            cursor = 0
+            for p in planes:
+                d = _up(p.extent + 2 * GUARD + 16, 16)
+                low = cursor + GUARD
+                high = low + FAR + d
+                off[p.name] = [low, high] if kind == "far" else [high, low]
+                L.steps[p.name] = off[p.name][1] - off[p.name][0]
+                a = low + d if kind == "far" else low + FAR  # frame 0 + the step's low 32 bits
+                alias.append((a, a + p.extent))
+                windows += [(low - GUARD, low + p.extent + GUARD), (high - GUARD, high + p.extent + GUARD), (a, a + p.extent)]
+                cursor += _up(2 * GUARD + d + p.extent, 256)
+            assert cursor <= (1 << 20) - GUARD
+        else:
+            cursor = NEAR_ORIGIN
+            for j, p in enumerate(planes):
+                pitch = _up(p.extent + 2 * GUARD, 256) + (SKEW.get(cls, 0) if p.unit == 1 else 0)
+                slots = _slots(kind, n, which, j)
+                off[p.name] = [cursor + GUARD + k * pitch for k in slots]
+                L.steps[p.name] = off[p.name][1] - off[p.name][0] if L.uniform else None
+                cursor = _up(cursor + GUARD + max(max(slots) + 1, 4) * pitch + GUARD, 256)  # at least table-twin's four slots: its frames 0 and 2 are descending-3's
+            windows.append((NEAR_ORIGIN, cursor))
+    return L.check()
+
+
+# ------------------------------------------------------------------ descriptors and calls (the product library or the fake-runtime build)
+
+class Call:
+    """The descriptor arrays of one batched call over `layout` with the slabs at in_base / out_base."""
+
+    def __init__(self, route, layout, in_base, out_base):
+        r, L, n = route, layout, layout.n
+        self.route, self.n = r, n
+        w, h = r.size
+        ow, oh = r.out_size
+        i_ptr = lambda name, i: in_base + L.in_off[name][i]
+        o_ptr = lambda name, i: out_base + L.out_off[name][i]
+        transfer = {GAMMA_APPLE: TRANSFER_709, GAMMA_SRGB: TRANSFER_SRGB, GAMMA_LINEAR: TRANSFER_LINEAR}[r.gamma]
+        if r.entry in ("decode", "half", "scaled"):
+            y, c = r.plane("y"), r.plane("cbcr")
+            self.frames = (Frame * n)(*[Frame(i_ptr("y", i), y.stride, i_ptr("cbcr", i), c.stride, w, h, MATRIX_709, transfer) for i in range(n)])
+            self.alphas = None
+            if r.alpha:
+                a = r.plane("alpha")
+                self.alphas = (Frame * n)(*[Frame(i_ptr("alpha", i), a.stride, None, a.stride, w, h, MATRIX_709, TRANSFER_LINEAR) for i in range(n)])
+            self.surfs = (Surface * n)(*[Surface(o_ptr("out", i), r.plane("out").stride, ow, oh, r.fmt, 0) for i in range(n)])
+        elif r.entry == "render":
+            self.ins = (Surface * n)(*[Surface(i_ptr("in", i), r.plane("in").stride, w, h, r.in_fmt, 0) for i in range(n)])
+            self.surfs = (Surface * n)(*[Surface(o_ptr("out", i), r.plane("out").stride, ow, oh, SRGB8, 0) for i in range(n)])
+        elif r.entry == "unconvert":
+            self.ptrs = (C.c_void_p * n)(*[i_ptr("in", i) for i in range(n)])
+            self.surfs = (Surface * n)(*[Surface(o_ptr("out", i), r.plane("out").stride, w, h, SRGB8, 0) for i in range(n)])
+        else:
+            cbcr = len(r.outs) > 1
+            self.ins = (Surface * n)(*[Surface(i_ptr("bgra", i), r.plane("bgra").stride, w, h, r.in_fmt, 0) for i in range(n)])
+            self.frames = (Frame * n)(*[Frame(o_ptr("y", i), r.plane("y").stride, o_ptr("cbcr", i) if cbcr else None, r.plane("cbcr").stride if cbcr else 0,
+                                              w, h, 0, 0) for i in range(n)])
+
+    def batch(self, lib, ctx, dec, stream=None, wait=1, count=None):
+        r, n = self.route, self.n if count is None else count
+        if r.entry == "decode":
+            return lib.bt709hip_decode_batch(dec, n, self.frames, self.alphas, self.surfs, stream, wait)
+        if r.entry == "half":
+            return lib.bt709hip_decode_half_batch(dec, n, self.frames, self.alphas, self.surfs, stream, wait)
+        if r.entry == "scaled":
+            return lib.bt709hip_decode_scaled_batch(dec, n, self.frames, self.alphas, self.surfs, stream, wait)
+        if r.entry == "render":
+            return lib.bt709hip_render_scaled_batch(ctx, n, self.ins, self.surfs, stream, wait)
+        if r.entry == "unconvert":
+            return lib.bt709hip_unconvert_batch(dec, n, self.ptrs, r.plane("in").stride, r.size[0], r.size[1], self.surfs, stream, wait)
+        return lib.bt709hip_encode_batch(ctx, n, self.ins, self.frames, r.pair[0], r.pair[1], stream, wait)
+
+    def single(self, lib, ctx, dec, i, stream=None, wait=1):
+        r = self.route
+        if r.entry in ("decode", "half", "scaled"):
+            f, a, s = C.byref(self.frames[i]), C.byref(self.alphas[i]) if self.alphas is not None else None, C.byref(self.surfs[i])
+            if r.entry == "decode":
+                return lib.bt709hip_decode(dec, f, a, s, r.size[0], r.size[1], stream, wait)
+            return (lib.bt709hip_decode_half if r.entry == "half" else lib.bt709hip_decode_scaled)(dec, f, a, s, stream, wait)
+        if r.entry == "render":
+            return lib.bt709hip_render_scaled(ctx, C.byref(self.ins[i]), C.byref(self.surfs[i]), stream, wait)
+        if r.entry == "unconvert":
+            return lib.bt709hip_unconvert(dec, self.ptrs[i], r.plane("in").stride, r.size[0], r.size[1], C.byref(self.surfs[i]), stream, wait)
+        return lib.bt709hip_encode(ctx, C.byref(self.ins[i]), C.byref(self.frames[i]), r.pair[0], r.pair[1], stream, wait)
+
+    def expected_steps(self, layout):
+        """What the launch's step fields must hold, in the order the fake runtime reports them (fake_hip.h fake_hip_addressing)."""
+        r, s = self.route, layout.steps
+        if r.entry in ("decode", "half", "scaled"):
+            return [s["y"], s["cbcr"], s["alpha"] if r.alpha else 0, s["out"]]
+        if r.entry in ("render", "unconvert"):
+            return [s["in"], s["out"], 0, 0]
+        return [s["bgra"], s["y"], s["cbcr"] if len(r.outs) > 1 else 0, 0]

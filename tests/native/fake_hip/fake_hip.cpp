@@ -518,6 +518,18 @@ hipError_t hipGraphLaunch(hipGraphExec_t g, hipStream_t s) {
 
 namespace bt709 {
 
+// what fake_hip_last_addressing reports: filled by every launcher below
+static thread_local fake_hip_addressing tl_addressing = {-1, 0, {0, 0, 0, 0}};
+static void note_addressing(bool uniform, int frames, int64_t s0, int64_t s1, int64_t s2 = 0, int64_t s3 = 0) {
+  tl_addressing = fake_hip_addressing{uniform ? 1 : 0, frames, {s0, s1, s2, s3}};
+}
+static void note_addressing(const DecodeParams &p, int frames) { note_addressing(p.uniform != 0, frames, p.step_y, p.step_cbcr, p.step_alpha, p.step_out); }
+int last_addressing(fake_hip_addressing *out) {
+  if (out == nullptr || tl_addressing.uniform < 0) return -1;
+  *out = tl_addressing;
+  return 0;
+}
+
 LaunchShape &last_launch_shape() {
   static thread_local LaunchShape shape = {};
   return shape;
@@ -529,6 +541,7 @@ static double frame_bytes(const DecodeParams &p, double out_px_bytes) {
 
 const char *launch_decode(const DecodeParams &p, int frames, int variant, bool has_alpha, bool quantiser, bool nontemporal, int xcd_bands,
                           uint32_t grid_x, uint32_t block_threads, hipStream_t stream) {
+  note_addressing(p, frames);
   LaunchShape &shape = last_launch_shape();
   if (shape.launches++ == 0) {
     shape.grid[0] = grid_x, shape.grid[1] = p.height / 2, shape.grid[2] = static_cast<uint32_t>(frames);
@@ -540,10 +553,12 @@ const char *launch_decode(const DecodeParams &p, int frames, int variant, bool h
   return launch(stream, name, frames, p.frames[0].y, p.frames[0].out, frames * frame_bytes(p, 4.0));
 }
 const char *launch_decode_rgba16f(const DecodeParams &p, const HalfParams &, int frames, bool, uint32_t, uint32_t, uint32_t, bool, hipStream_t stream) {
+  note_addressing(p, frames);
   return launch(stream, "decode_nv12_rgba16f", frames, p.frames[0].y, p.frames[0].out, frames * frame_bytes(p, 8.0));
 }
 const char *launch_unconvert(const DecodeParams &, const UnconvertBatch &b, size_t, size_t, uint32_t width, uint32_t height, bool, bool,
                              hipStream_t stream) {
+  note_addressing(b.uniform, b.count, b.in_step, b.out_step);
   return launch(stream, "unconvert_packed444", b.count, b.in[0], b.out[0], 8.0 * width * height * b.count);
 }
 // the two 2:1 launchers record a plausible plan: one workgroup per tile and output row / the persistent grid
@@ -556,10 +571,12 @@ static void fill_half_record(uint32_t gx, uint32_t gy, uint32_t gz, uint32_t thr
   }
 }
 const char *launch_decode_half(const DecodeParams &p, int frames, bool, bool, bool, uint32_t grid_x, uint32_t block_threads, hipStream_t stream) {
+  note_addressing(p, frames);
   fill_half_record(grid_x, p.height / 2, static_cast<uint32_t>(frames), block_threads);
   return launch(stream, "decode_nv12_half", frames, p.frames[0].y, p.frames[0].out, frames * frame_bytes(p, 4.0));
 }
 const char *launch_decode_half_rep(const DecodeParams &p, int frames, bool, bool, uint32_t workgroups, uint32_t, hipStream_t stream) {
+  note_addressing(p, frames);
   fill_half_record(workgroups ? workgroups : 1, 1, 1, kRepBlockThreads);
   return launch(stream, "decode_nv12_half_rep", frames, p.frames[0].y, p.frames[0].out, frames * frame_bytes(p, 4.0));
 }
@@ -570,14 +587,17 @@ static void fill_scaled_record(uint32_t out_width, uint32_t out_height, int fram
                                           static_cast<uint64_t>(cols) * strips * static_cast<uint32_t>(frames)});
 }
 const char *launch_decode_scaled(const DecodeParams &p, int frames, bool, uint32_t, uint32_t, hipStream_t stream) {
+  note_addressing(p, frames);
   fill_scaled_record(p.out_width, p.out_height, frames, TAPS_BYTES);
   return launch(stream, "decode_nv12_scaled", frames, p.frames[0].y, p.frames[0].out, frames * frame_bytes(p, 4.0));
 }
 const char *launch_render_scaled(const RenderParams &p, int frames, bool, uint32_t, hipStream_t stream) {
+  note_addressing(frames > 1, frames, p.in_step, p.out_step);
   fill_scaled_record(p.out_width, p.out_height, frames, 0);
   return launch(stream, "render_scaled", frames, p.in, p.out, frames * 4.0 * (static_cast<double>(p.width) * p.height + static_cast<double>(p.out_width) * p.out_height));
 }
 const char *launch_encode(const EncodeParams &p, int frames, bool fast, bool xcd_bands, hipStream_t stream) {
+  note_addressing(p.uniform != 0, frames, p.step_bgra, p.step_y, p.step_cbcr);
   // the plan the real launcher would record for a plain (single-launch) call: tiles x row-pair groups x pictures
   LaunchShape &shape = last_launch_shape();
   if (shape.launches++ == 0) {
@@ -626,6 +646,7 @@ void fake_hip_set_device_memory(uint64_t total) {
     d.total = total;
   }
 }
+int fake_hip_last_addressing(fake_hip_addressing *out) { return bt709::last_addressing(out); }
 uint64_t fake_hip_log_size(void) { return rt().ops.load(); }
 int fake_hip_log_get(uint64_t index, fake_hip_op *out) {
   Runtime &r = rt();

@@ -36,6 +36,7 @@ Gates (macro -> what it does; profiles/ file it produced):
   BT709_LAB_SCALED_ONCE_LDS            wave-decodes-once form exchanging through a wave-private LDS tile (same bytes out)      r06_ab_scaled_share.txt
   BT709_LAB_SCALED_NO_FETCH / _NO_DECODE / _NO_ENCODE / _NO_STORE  any-ratio kernel, WRONG OUTPUT: one part deleted each      r06_ab_scaled_parts.txt
   BT709_LAB_I420_PAIRED                planar 1:1 fast kernels: ONE chroma dword per quad, shared by lane pairs over DPP, instead of two 2-byte loads (same bytes out; frames without W % 8 == 0, 4-byte aligned chroma planes and V less than 4 GiB behind U take the general kernel)   r12_planar.txt
+  BT709_LAB_STEP32                     frame_planes, WRONG ADDRESSES: every step of a uniform batch cut to its low 32 bits, zero-extended.  Shows that tests/test_batch_spacing_gpu.py bites: run ONLY -k "far and not descending" against it (frames 2^32 + d apart: the cut step lands on the alias windows inside the test's own slabs); with a NEGATIVE step the cut address leaves the allocation
   BT709_LAB_HUNT_TRACE                 bt709hip_ring_create prints where its hunt's wall-clock time went (stderr; same ring)   r06_hunt_default.txt
 """
 import os
@@ -746,8 +747,29 @@ MACROS = ["BT709_LAB_I420_PAIRED", "BT709_LAB_NO_ARITH", "BT709_LAB_NO_LOADS", "
           "BT709_INDEX_RTZ", "BT709_UNIFORM_INDEX_TWO_STEP", "BT709_REP_SPLIT_ENCODE", "BT709_LAB_BOUND_SHARED_INDEX",
           "BT709_LAB_BOUND_ONE_ENCODE", "BT709_LAB_HALF_TABLE", "BT709_LAB_F16_NO_ARITH", "BT709_LAB_F16_NO_TABLE",
           "BT709_LAB_F16_CVT_ONLY", "BT709_LAB_F16_NO_CAND_GATHER", "BT709_LAB_F16_NO_T_GATHER", "BT709_LAB_F16_NO_INDEX_SCALE", "BT709_LAB_F16_DMA_STAGING", "BT709_LAB_ENC_NO_ARITH", "BT709_LAB_UNC_NO_ARITH", "BT709_LAB_SCALED_QUARTER_FEWER_TAPS", "BT709_LAB_HALF_ENCODE_B32",
-          "BT709_LAB_SCALED_HALF_FEWER_TAPS", "BT709_LAB_SCALED_PAIR_DPP", "BT709_LAB_SCALED_ONCE_LDS", "BT709_LAB_HUNT_TRACE", "BT709_LAB_SCALED_NO_FETCH", "BT709_LAB_SCALED_NO_DECODE", "BT709_LAB_SCALED_NO_ENCODE", "BT709_LAB_SCALED_NO_STORE", "BT709_LAB_SCALED_STORE_ONE_LINE", "BT709_LAB_ANY_ORDER", "BT709_LAB_HALF_NO_FETCH", "BT709_LAB_HALF_NO_STORE", "BT709_LAB_BAND_ROT", "BT709_LAB_BAND_XOR"]
+          "BT709_LAB_SCALED_HALF_FEWER_TAPS", "BT709_LAB_SCALED_PAIR_DPP", "BT709_LAB_SCALED_ONCE_LDS", "BT709_LAB_HUNT_TRACE", "BT709_LAB_SCALED_NO_FETCH", "BT709_LAB_SCALED_NO_DECODE", "BT709_LAB_SCALED_NO_ENCODE", "BT709_LAB_SCALED_NO_STORE", "BT709_LAB_SCALED_STORE_ONE_LINE", "BT709_LAB_ANY_ORDER", "BT709_LAB_HALF_NO_FETCH", "BT709_LAB_HALF_NO_STORE", "BT709_LAB_BAND_ROT", "BT709_LAB_BAND_XOR", "BT709_LAB_STEP32"]
 
+
+GATES += [
+    ("bt709_device.h",
+     """  f.y += static_cast<int64_t>(i) * p.step_y;
+  f.cbcr += static_cast<int64_t>(i) * p.step_cbcr;
+  if (f.alpha) f.alpha += static_cast<int64_t>(i) * p.step_alpha;
+  f.out += static_cast<int64_t>(i) * p.step_out;
+""",
+     """#if defined(BT709_LAB_STEP32)  // WRONG ADDRESSES: the steps' low 32 bits, zero-extended
+  f.y += static_cast<int64_t>(i) * static_cast<int64_t>(static_cast<uint32_t>(p.step_y));
+  f.cbcr += static_cast<int64_t>(i) * static_cast<int64_t>(static_cast<uint32_t>(p.step_cbcr));
+  if (f.alpha) f.alpha += static_cast<int64_t>(i) * static_cast<int64_t>(static_cast<uint32_t>(p.step_alpha));
+  f.out += static_cast<int64_t>(i) * static_cast<int64_t>(static_cast<uint32_t>(p.step_out));
+#else
+  f.y += static_cast<int64_t>(i) * p.step_y;
+  f.cbcr += static_cast<int64_t>(i) * p.step_cbcr;
+  if (f.alpha) f.alpha += static_cast<int64_t>(i) * p.step_alpha;
+  f.out += static_cast<int64_t>(i) * p.step_out;
+#endif
+"""),
+]
 
 RESCALE_FILES = ("bt709_rescale.h", "bt709_rescale_half.hip", "bt709_rescale_scaled.hip", "bt709_scaled_strip.h")  # round 6 split bt709_rescale.hip; the strip shared with bt709_rescale_f16.hip moved to a header
 
