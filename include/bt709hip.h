@@ -24,6 +24,12 @@
  * passed as void* (NULL = the context's default stream); sizes and strides are bytes.  Every function returns a
  * bt709hip_status (0 = success) unless noted; the reference's BOOL is ok = (status == 0).
  *
+ * The pitch rule, for every pitch of every entry point (Y, CbCr, the alpha frame's Y, a surface's stride, the packed words'
+ * in_stride, the plane shuffles' three): at least a row, at most 2^32 - 1 -- the kernels form row x pitch in 64 bits, so a plane
+ * may span any number of bytes -- else BT709HIP_ERR_STRIDE.  bt709hip_decode_scaled[_batch], bt709hip_render_scaled[_batch] and the
+ * calls of bt709hip_decode_half[_batch] that go through them additionally need rows x pitch < 2^31 for every plane and the output
+ * (they form row offsets in 32 bits) and otherwise return BT709HIP_ERR_UNSUPPORTED.
+ *
  * Ownership (differs from the reference on purpose): the caller owns every buffer and stream; a decoder
  * holds only its lookup tables, keeps no per-frame state and may be used from several streams and threads at once.
  * Buffers must stay alive until the stream has passed the call that uses them.
@@ -54,7 +60,7 @@ typedef enum {
   BT709HIP_ERR_MATRIX = -5,         /* YCbCr matrix tag is not ITU_R_709_2 (.m:311-318) */
   BT709HIP_ERR_TRANSFER = -6,       /* transfer tag does not match the decoder's gamma (.m:320-353) */
   BT709HIP_ERR_ALPHA_TRANSFER = -7, /* alpha buffer is not tagged linear (.m:357-368) */
-  BT709HIP_ERR_STRIDE = -8,         /* stride smaller than a row / misaligned output */
+  BT709HIP_ERR_STRIDE = -8,         /* stride smaller than a row or above 2^32 - 1 / misaligned output */
   BT709HIP_ERR_HIP = -9,            /* a HIP call failed: see bt709hip_last_hip_error */
   BT709HIP_ERR_NO_DEVICE = -10,     /* no such GPU */
   BT709HIP_ERR_UNSUPPORTED = -11    /* e.g. batch larger than BT709HIP_MAX_BATCH */

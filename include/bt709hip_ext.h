@@ -229,7 +229,10 @@ int bt709hip_decoder_flush_all(bt709hip_decoder *dec);
  * folded into the alignment the fast kernels need: a step off that alignment selects the general kernel, same bytes out.
  * Output items that overlap one another (an output step smaller than a target's extent, 0 included) are the caller's error:
  * the result is undefined and nothing checks for it.  bt709hip_encode_batch with BT709HIP_FORMAT_BGRA8_ALPHA input (alpha frames, bt709hip.h):
- * every out[i].cbcr NULL or none (else BT709HIP_ERR_INVALID_ARG); bt709hip_encoder_prepare(ctx, LINEAR, LINEAR) also builds its table. */
+ * every out[i].cbcr NULL or none (else BT709HIP_ERR_INVALID_ARG); bt709hip_encoder_prepare(ctx, LINEAR, LINEAR) also builds its table.
+ * Pitches follow bt709hip.h's rule in every batched form: each at most 2^32 - 1, the alpha frames' included (BT709HIP_ERR_STRIDE);
+ * bt709hip_decode_scaled_batch and bt709hip_render_scaled_batch additionally need rows x pitch < 2^31 for every plane and the
+ * output (BT709HIP_ERR_UNSUPPORTED). */
 int bt709hip_unconvert_batch(bt709hip_decoder *dec, int count, const void *const *ycbcr_words, size_t in_stride, int width, int height,
                              const bt709hip_surface *outs, void *stream, int wait_until_completed);
 int bt709hip_decode_half_batch(bt709hip_decoder *dec, int count, const bt709hip_frame *frames, const bt709hip_frame *alphas,

@@ -165,6 +165,14 @@ struct ScaledLaunchRecord {
 // The two rescale launchers hand the plan of every launch they make to the host shim, which keeps it per thread next to the kernel
 // name (shim_core.cpp defines this).  A call and not an out-parameter: the launchers' signatures stay what test doubles link against.
 void record_scaled_launch(const ScaledLaunchRecord &record);
+// The any-ratio kernels and pass 2 alone form row offsets in 32 bits (the scalar offset of a raw buffer resource of 2^31 - 1
+// records): a plane of `rows` rows must end below 2 GiB.  What the two launchers refuse with nullptr (and their test doubles with them).
+inline bool plane_fits(uint64_t rows, uint64_t stride) { return rows * stride < (1ull << 31); }
+inline bool scaled_planes_fit(const DecodeParams &p, bool has_alpha) {
+  return plane_fits(p.height, p.y_stride) && plane_fits(p.height / 2, p.cbcr_stride) && (!has_alpha || plane_fits(p.height, p.alpha_stride)) &&
+         plane_fits(p.out_height, p.out_stride);
+}
+inline bool render_planes_fit(const RenderParams &p) { return plane_fits(p.height, p.in_stride) && plane_fits(p.out_height, p.out_stride); }
 // grid = (column tiles, strips of `rows` output rows, frames)
 const char *launch_render_scaled(const RenderParams &p, int frames, bool in_rgba16f, uint32_t compute_units, hipStream_t stream);
 

@@ -215,11 +215,6 @@ render_scaled(const RenderParams p) {
 
 namespace {
 
-// the kernels form row offsets in 32 bits: a plane of `rows` rows must end below 2 GiB
-bool plane_fits(uint64_t rows, uint64_t stride) {
-  return rows * stride < (1ull << 31);
-}
-
 // rows per strip: as many as still leave `want` workgroups in the launch (table staging is per workgroup), 1 ... max_rows
 uint32_t rows_per_strip(uint32_t cols, uint32_t out_height, uint32_t frames, uint64_t want, uint32_t max_rows) {
   const uint32_t rows = static_cast<uint32_t>(static_cast<uint64_t>(cols) * out_height * frames / want);
@@ -311,7 +306,7 @@ const char *launch_render_scaled(const RenderParams &p_in, int frames, bool in_r
   const uint32_t cols = (p.out_width + kBlockThreads - 1) / kBlockThreads;
   const uint32_t rows = rows_per_strip(cols, p.out_height, static_cast<uint32_t>(frames), 8ull * (compute_units ? compute_units : 256u), 16);
   p.rows = rows;
-  if (!plane_fits(p.height, p.in_stride) || !plane_fits(p.out_height, p.out_stride)) return nullptr;
+  if (!render_planes_fit(p)) return nullptr;  // row offsets are formed in 32 bits (bt709_kernels.h)
   const dim3 grid(cols, (p.out_height + rows - 1) / rows, static_cast<uint32_t>(frames));
   const size_t lds = static_cast<size_t>(p.table_encode_bytes) + 1024;
   record_scaled_launch(ScaledLaunchRecord{{grid.x, grid.y, grid.z}, {kBlockThreads, 1, 1}, 0, rows, 0, 0, 0, 0, static_cast<uint64_t>(grid.x) * grid.y * grid.z});
@@ -324,9 +319,7 @@ const char *launch_decode_scaled(const DecodeParams &p_in, int frames, bool has_
                                  uint32_t compute_units, hipStream_t stream) {
   DecodeParams p = p_in;
   const uint32_t cus = compute_units ? compute_units : 256u, nframes = static_cast<uint32_t>(frames);
-  if (!plane_fits(p.height, p.y_stride) || !plane_fits(p.height / 2, p.cbcr_stride) || (has_alpha && !plane_fits(p.height, p.alpha_stride)) ||
-      !plane_fits(p.out_height, p.out_stride))
-    return nullptr;
+  if (!scaled_planes_fit(p, has_alpha)) return nullptr;  // row offsets are formed in 32 bits (bt709_kernels.h)
   const int taps = scaled_taps(p, in_align);
   // through the RGBA16Float intermediate (bt709_rescale_f16.hip): the same plan, every tap form persistent
   const bool f16 = p.scale_f16 != 0;

@@ -42,6 +42,7 @@ int validate(const bt709hip_decoder *dec, int layout, const bt709hip_frame *f, c
     return BT709HIP_ERR_STRIDE;
   if (f->y_stride > 0xffffffffu || f->cbcr_stride > 0xffffffffu || o->stride > 0xffffffffu)
     return BT709HIP_ERR_STRIDE;
+  if (dec->has_alpha && a->y_stride > 0xffffffffu) return BT709HIP_ERR_STRIDE;  // the launch carries every pitch in 32 bits
   return BT709HIP_OK;
 }
 

@@ -25,6 +25,7 @@ plane where a step cut to its low 32 bits would land: frame 0 + d (far: zero- or
 cuts the step).  Layout.check() asserts, on the CPU, that all of them lie inside their slab, apart from one another by at least
 a guard band."""
 import ctypes as C
+import zlib
 
 import numpy as np
 
@@ -363,3 +364,167 @@ class Call:
         if r.entry in ("render", "unconvert"):
             return [s["in"], s["out"], 0, 0]
         return [s["bgra"], s["y"], s["cbcr"] if len(r.outs) > 1 else 0, 0]
+
+
+# ------------------------------------------------------------------ samples, backgrounds and what they must become
+# (shared by tests/test_batch_spacing_gpu.py and tests/test_row_pitch_gpu.py, which lays the same routes out at other pitches:
+# a route is looked up by NAME, so both modules draw the same samples and compute each reference once)
+
+_data, _want = {}, {}
+
+
+def _route_seed(route):
+    names = [r.name for r in ROUTES]
+    return names.index(route.name) if route.name in names else 500 + zlib.crc32(route.name.encode()) % 400
+
+
+def frame_data(route, k):
+    """plane name -> (rows, row_bytes) bytes of frame k: random, another for every frame and route."""
+    key = (route.name, k)
+    if key not in _data:
+        rng = np.random.default_rng(100000 + 1000 * _route_seed(route) + k)
+        w, h = route.size
+        d = {}
+        for p in route.ins:
+            if route.entry == "render" and route.in_fmt == F16:  # finite halves, some above 1.0
+                d[p.name] = (rng.random((h, w, 4)) * 1.25).astype(np.float16).view(np.uint8).reshape(h, 8 * w)
+            elif route.entry == "unconvert":  # Y | Cb << 8 | Cr << 16
+                d[p.name] = rng.integers(0, 1 << 24, (h, w), dtype=np.uint32).view(np.uint8).reshape(h, 4 * w)
+            else:
+                d[p.name] = rng.integers(0, 256, (p.rows, p.row_bytes), dtype=np.uint8)
+        _data[key] = d
+    return _data[key]
+
+
+def background(route, i):
+    ow, oh = route.out_size
+    return np.random.default_rng(7000 + i).integers(0, 256, (oh, 4 * ow), dtype=np.uint8)
+
+
+def interleave(uv_planes):
+    """The NV12 twin of an I420 "cbcr" plane (U's rows, then V's)."""
+    half = uv_planes.shape[0] // 2
+    c = np.empty((half, 2 * uv_planes.shape[1]), np.uint8)
+    c[:, 0::2], c[:, 1::2] = uv_planes[:half], uv_planes[half:]
+    return c
+
+
+def want(route, oracle, tabs, T, k, bg_index):
+    """plane name -> (rows, row_bytes) bytes frame k's samples must become (over the background of target bg_index, where the
+    route reads its destination): the oracle call the route's own tests use.  tabs: over_cases.tables(oracle); T: the alpha
+    luma table (tests/golden/alpha_luma.json)."""
+    key = (route.name, k, bg_index if route.reads_destination else None)
+    if key in _want:
+        return _want[key]
+    d = frame_data(route, k)
+    w, h = route.size
+    ow, oh = route.out_size
+    g = route.gamma
+    if route.entry in ("decode", "half", "scaled"):
+        y, a = d["y"], d.get("alpha")
+        c = interleave(d["cbcr"]) if route.name == "i420" else d["cbcr"]
+        if route.entry == "decode":
+            out = oracle.decode_nv12_rgba16f(g, y, c, a).view(np.uint8).reshape(h, 8 * w) if route.fmt == F16 else oracle.decode_nv12(g, y, c, alpha=a)
+        elif route.entry == "half":
+            out = oracle.decode_nv12_half(g, y, c, alpha=a)
+        elif dict(route.options).get(_capi.OPT_SCALE_INTERMEDIATE) == F16:
+            out = oracle.render_scaled(oracle.decode_nv12_rgba16f(g, y, c, a), ow, oh)
+        else:
+            out = oracle.decode_nv12_scaled(g, y, c, ow, oh, alpha=a)
+        assert out is not None
+        if route.reads_destination:
+            import over_cases as oc
+            out = oc.composite_over(out.reshape(oh, ow, 4), background(route, bg_index).reshape(oh, ow, 4), *tabs).reshape(oh, 4 * ow)
+        res = {"out": out}
+    elif route.entry == "render":
+        src = d["in"].view(np.float16).reshape(h, w, 4) if route.in_fmt == F16 else d["in"]
+        res = {"out": oracle.render_scaled(src, ow, oh)}
+    elif route.entry == "unconvert":
+        res = {"out": oracle.unconvert_packed(g, d["in"].view(np.uint32).reshape(h, w), w, h).view(np.uint8).reshape(h, 4 * w)}
+    elif route.entry == "interleave":  # numpy's interleave
+        c = np.empty((d["u"].shape[0], 2 * d["u"].shape[1]), np.uint8)
+        c[:, 0::2], c[:, 1::2] = d["u"], d["v"]
+        res = {"cbcr": c}
+    elif route.entry == "deinterleave":
+        res = {"u": d["cbcr"][:, 0::2], "v": d["cbcr"][:, 1::2]}
+    elif route.in_fmt == ALPHA8:
+        res = {"y": T[d["bgra"].reshape(h, w, 4)[:, :, 3]]}
+    else:
+        y, c = oracle.encode_nv12(d["bgra"].view(np.uint32).reshape(h, w), w, h, route.pair[0], route.pair[1])
+        res = {"y": y, "cbcr": c}
+    for name, arr in res.items():
+        p = route.plane(name)
+        res[name] = np.ascontiguousarray(arr).reshape(p.rows, p.row_bytes)
+    _want[key] = res
+    return res
+
+
+# ------------------------------------------------------------------ the slabs' windows (rig: variant_cases.Rig; a window may hold
+# whole planes -- the layouts above -- or single rows: tests/row_pitch_cases.py)
+
+def _rows_in(planes, off, n, lo, hi):
+    """(plane, frame, row, offset in the window) of every row of samples that lies in window lo..hi."""
+    for p in planes:
+        for i in range(n):
+            first = off[p.name][i]
+            if first + p.extent <= lo or first >= hi:
+                continue
+            for r in range(p.rows):
+                a = first + r * p.stride
+                if lo <= a and a + p.row_bytes <= hi:
+                    yield p, i, r, a - lo
+
+
+def upload_inputs(rig, d_in, L, fill):
+    """Every input window: `fill` in every byte that is no sample (row padding, guard bands, the alias windows)."""
+    for lo, hi in L.in_windows:
+        host = np.full(hi - lo, fill, np.uint8)
+        for p, i, r, at in _rows_in(L.route.ins, L.in_off, L.n, lo, hi):
+            host[at:at + p.row_bytes] = frame_data(L.route, L.source[i])[p.name][r]
+        rig.upload(d_in + lo, host)
+
+
+def reset_outputs(rig, d_out, L):
+    """Every output window: the canary, and where the route reads its destination background i in the pixels of target i.
+    -> the windows' bytes as uploaded."""
+    before = []
+    for lo, hi in L.out_windows:
+        host = np.full(hi - lo, CANARY, np.uint8)
+        if L.route.reads_destination:
+            for p, i, r, at in _rows_in(L.route.outs, L.out_off, L.n, lo, hi):
+                host[at:at + p.row_bytes] = background(L.route, i)[r]
+        rig.upload(d_out + lo, host)
+        before.append(host)
+    return before
+
+
+def collect(rig, d_out, L, before, label):
+    """-> {(plane name, frame): (rows, row_bytes)} of every output window; every byte outside the pixels must be what it was."""
+    got = {(p.name, i): np.empty((p.rows, p.row_bytes), np.uint8) for p in L.route.outs for i in range(L.n)}
+    seen = 0
+    for (lo, hi), was in zip(L.out_windows, before):
+        raw = rig.download(d_out + lo, hi - lo)
+        outside = np.ones(raw.size, bool)
+        for p, i, r, at in _rows_in(L.route.outs, L.out_off, L.n, lo, hi):
+            got[(p.name, i)][r] = raw[at:at + p.row_bytes]
+            outside[at:at + p.row_bytes] = False
+            seen += 1
+        stray = np.flatnonzero(outside & (raw != was))
+        assert stray.size == 0, "%s: %d bytes written outside the pixels, first at slab offset %d (window %d..%d%s)" % (
+            label, stray.size, lo + stray[0], lo, hi, ", an alias window" if (lo, hi) in L.out_alias else "")
+    assert seen == L.n * sum(p.rows for p in L.route.outs)  # every row of every frame lay in exactly one window
+    return got
+
+
+def assert_plane(got, wanted, label):
+    if not np.array_equal(got, wanted):
+        bad = np.argwhere(got != wanted)
+        r, x = bad[0]
+        raise AssertionError("%s: differs first at row %d, byte %d (got %d, want %d); %d of %d bytes differ"
+                             % (label, r, x, got[r, x], wanted[r, x], len(bad), got.size))
+
+
+def scaled_record(lib):
+    info = _capi.ScaledLaunchInfo()
+    _capi.check(lib.bt709hip_last_scaled_launch_info(C.byref(info)))
+    return info.taps, info.persistent

@@ -586,12 +586,14 @@ static void fill_scaled_record(uint32_t out_width, uint32_t out_height, int fram
   record_scaled_launch(ScaledLaunchRecord{{cols, strips, static_cast<uint32_t>(frames)}, {kBlockThreads, 1, 1}, taps, 4, 0, 0, 0, 0,
                                           static_cast<uint64_t>(cols) * strips * static_cast<uint32_t>(frames)});
 }
-const char *launch_decode_scaled(const DecodeParams &p, int frames, bool, uint32_t, uint32_t, hipStream_t stream) {
+const char *launch_decode_scaled(const DecodeParams &p, int frames, bool has_alpha, uint32_t, uint32_t, hipStream_t stream) {
+  if (!scaled_planes_fit(p, has_alpha)) return nullptr;  // the real launcher's refusal (bt709_kernels.h), before anything is recorded
   note_addressing(p, frames);
   fill_scaled_record(p.out_width, p.out_height, frames, TAPS_BYTES);
   return launch(stream, "decode_nv12_scaled", frames, p.frames[0].y, p.frames[0].out, frames * frame_bytes(p, 4.0));
 }
 const char *launch_render_scaled(const RenderParams &p, int frames, bool, uint32_t, hipStream_t stream) {
+  if (!render_planes_fit(p)) return nullptr;
   note_addressing(frames > 1, frames, p.in_step, p.out_step);
   fill_scaled_record(p.out_width, p.out_height, frames, 0);
   return launch(stream, "render_scaled", frames, p.in, p.out, frames * 4.0 * (static_cast<double>(p.width) * p.height + static_cast<double>(p.out_width) * p.out_height));

@@ -100,145 +100,24 @@ def decoders(rig):
     return get
 
 
-# ------------------------------------------------------------------ samples, backgrounds and what they must become
+# samples, backgrounds, what they must become and the slabs' windows: batch_spacing_cases (shared with tests/test_row_pitch_gpu.py)
+want, assert_plane = bs.want, bs.assert_plane
 
-_data, _want = {}, {}
-
-
-def frame_data(route, k):
-    """plane name -> (rows, row_bytes) bytes of frame k: random, another for every frame and route."""
-    key = (route.name, k)
-    if key not in _data:
-        rng = np.random.default_rng(100000 + 1000 * bs.ROUTES.index(route) + k)
-        w, h = route.size
-        d = {}
-        for p in route.ins:
-            if route.entry == "render" and route.in_fmt == bs.F16:  # finite halves, some above 1.0
-                d[p.name] = (rng.random((h, w, 4)) * 1.25).astype(np.float16).view(np.uint8).reshape(h, 8 * w)
-            elif route.entry == "unconvert":  # Y | Cb << 8 | Cr << 16
-                d[p.name] = rng.integers(0, 1 << 24, (h, w), dtype=np.uint32).view(np.uint8).reshape(h, 4 * w)
-            else:
-                d[p.name] = rng.integers(0, 256, (p.rows, p.row_bytes), dtype=np.uint8)
-        _data[key] = d
-    return _data[key]
-
-
-def background(route, i):
-    ow, oh = route.out_size
-    return np.random.default_rng(7000 + i).integers(0, 256, (oh, 4 * ow), dtype=np.uint8)
-
-
-def _interleave(uv_planes):
-    """The NV12 twin of an I420 "cbcr" plane (U's rows, then V's)."""
-    half = uv_planes.shape[0] // 2
-    c = np.empty((half, 2 * uv_planes.shape[1]), np.uint8)
-    c[:, 0::2], c[:, 1::2] = uv_planes[:half], uv_planes[half:]
-    return c
-
-
-def want(route, oracle, tabs, T, k, bg_index):
-    """plane name -> (rows, row_bytes) bytes frame k's samples must become (over the background of target bg_index, where the
-    route reads its destination): the oracle call the route's own tests use."""
-    key = (route.name, k, bg_index if route.reads_destination else None)
-    if key in _want:
-        return _want[key]
-    d = frame_data(route, k)
-    w, h = route.size
-    ow, oh = route.out_size
-    g = route.gamma
-    if route.entry in ("decode", "half", "scaled"):
-        y, a = d["y"], d.get("alpha")
-        c = _interleave(d["cbcr"]) if route.name == "i420" else d["cbcr"]
-        if route.entry == "decode":
-            out = oracle.decode_nv12_rgba16f(g, y, c, a).view(np.uint8).reshape(h, 8 * w) if route.fmt == bs.F16 else oracle.decode_nv12(g, y, c, alpha=a)
-        elif route.entry == "half":
-            out = oracle.decode_nv12_half(g, y, c, alpha=a)
-        elif dict(route.options).get(_capi.OPT_SCALE_INTERMEDIATE) == bs.F16:
-            out = oracle.render_scaled(oracle.decode_nv12_rgba16f(g, y, c, a), ow, oh)
-        else:
-            out = oracle.decode_nv12_scaled(g, y, c, ow, oh, alpha=a)
-        assert out is not None
-        if route.reads_destination:
-            out = oc.composite_over(out.reshape(oh, ow, 4), background(route, bg_index).reshape(oh, ow, 4), *tabs).reshape(oh, 4 * ow)
-        res = {"out": out}
-    elif route.entry == "render":
-        src = d["in"].view(np.float16).reshape(h, w, 4) if route.in_fmt == bs.F16 else d["in"]
-        res = {"out": oracle.render_scaled(src, ow, oh)}
-    elif route.entry == "unconvert":
-        res = {"out": oracle.unconvert_packed(g, d["in"].view(np.uint32).reshape(h, w), w, h).view(np.uint8).reshape(h, 4 * w)}
-    elif route.in_fmt == bs.ALPHA8:
-        res = {"y": T[d["bgra"].reshape(h, w, 4)[:, :, 3]]}
-    else:
-        y, c = oracle.encode_nv12(d["bgra"].view(np.uint32).reshape(h, w), w, h, route.pair[0], route.pair[1])
-        res = {"y": y, "cbcr": c}
-    for name, arr in res.items():
-        p = route.plane(name)
-        res[name] = np.ascontiguousarray(arr).reshape(p.rows, p.row_bytes)
-    _want[key] = res
-    return res
-
-
-# ------------------------------------------------------------------ the slabs' windows
 
 def upload_inputs(rig, slabs, L, fill):
-    """Every input window: `fill` in every byte that is no sample (row padding, guard bands, the alias windows)."""
-    for lo, hi in L.in_windows:
-        host = np.full(hi - lo, fill, np.uint8)
-        for p in L.route.ins:
-            for i in range(L.n):
-                off = L.in_off[p.name][i]
-                if lo <= off < hi:
-                    host[p.index(off - lo)] = frame_data(L.route, L.source[i])[p.name]
-        rig.upload(slabs.d_in + lo, host)
+    bs.upload_inputs(rig, slabs.d_in, L, fill)
 
 
 def reset_outputs(rig, slabs, L):
-    """Every output window: the canary, and where the route reads its destination background i in the pixels of target i.
-    -> the windows' bytes as uploaded."""
-    before = []
-    for lo, hi in L.out_windows:
-        host = np.full(hi - lo, bs.CANARY, np.uint8)
-        if L.route.reads_destination:
-            p = L.route.plane("out")
-            for i, off in enumerate(L.out_off["out"]):
-                if lo <= off < hi:
-                    host[p.index(off - lo)] = background(L.route, i)
-        rig.upload(slabs.d_out + lo, host)
-        before.append(host)
-    return before
+    return bs.reset_outputs(rig, slabs.d_out, L)
 
 
 def collect(rig, slabs, L, before, label):
-    """-> {(plane name, frame): (rows, row_bytes)} of every output window; every byte outside the pixels must be what it was."""
-    got = {}
-    for (lo, hi), was in zip(L.out_windows, before):
-        raw = rig.download(slabs.d_out + lo, hi - lo)
-        outside = np.ones(raw.size, bool)
-        for p in L.route.outs:
-            for i, off in enumerate(L.out_off[p.name]):
-                if lo <= off < hi:
-                    idx = p.index(off - lo)
-                    got[(p.name, i)] = raw[idx]
-                    outside[idx] = False
-        stray = np.flatnonzero(outside & (raw != was))
-        assert stray.size == 0, "%s: %d bytes written outside the pixels, first at slab offset %d (window %d..%d%s)" % (
-            label, stray.size, lo + stray[0], lo, hi, ", an alias window" if (lo, hi) in L.out_alias else "")
-    assert len(got) == L.n * len(L.route.outs)
-    return got
-
-
-def assert_plane(got, wanted, label):
-    if not np.array_equal(got, wanted):
-        bad = np.argwhere(got != wanted)
-        r, x = bad[0]
-        raise AssertionError("%s: differs first at row %d, byte %d (got %d, want %d); %d of %d bytes differ"
-                             % (label, r, x, got[r, x], wanted[r, x], len(bad), got.size))
+    return bs.collect(rig, slabs.d_out, L, before, label)
 
 
 def scaled_record(rig):
-    info = _capi.ScaledLaunchInfo()
-    _capi.check(rig.lib.bt709hip_last_scaled_launch_info(C.byref(info)))
-    return info.taps, info.persistent
+    return bs.scaled_record(rig.lib)
 
 
 # ------------------------------------------------------------------ the tests

@@ -37,6 +37,7 @@ Gates (macro -> what it does; profiles/ file it produced):
   BT709_LAB_SCALED_NO_FETCH / _NO_DECODE / _NO_ENCODE / _NO_STORE  any-ratio kernel, WRONG OUTPUT: one part deleted each      r06_ab_scaled_parts.txt
   BT709_LAB_I420_PAIRED                planar 1:1 fast kernels: ONE chroma dword per quad, shared by lane pairs over DPP, instead of two 2-byte loads (same bytes out; frames without W % 8 == 0, 4-byte aligned chroma planes and V less than 4 GiB behind U take the general kernel)   r12_planar.txt
   BT709_LAB_STEP32                     frame_planes, WRONG ADDRESSES: every step of a uniform batch cut to its low 32 bits, zero-extended.  Shows that tests/test_batch_spacing_gpu.py bites: run ONLY -k "far and not descending" against it (frames 2^32 + d apart: the cut step lands on the alias windows inside the test's own slabs); with a NEGATIVE step the cut address leaves the allocation
+  BT709_LAB_ROW32                      TileIn::load, decode_nv12_half<wide>'s target row, encode_bgra_nv12's CbCr row, WRONG ADDRESSES: row x pitch cut to its low 32 bits, zero-extended.  Shows that tests/test_row_pitch_gpu.py bites: run ONLY the past-2^32 ids (-k "past and 32": `^` is no character of a -k expression; the cut offset lands on the alias windows inside the test's own slabs) and the past-2^31 ids (-k "past and 31"; must pass: zero-extension is right below 2^32).  There is no sign-extending twin: under past-2^32 it would leave the allocation
   BT709_LAB_HUNT_TRACE                 bt709hip_ring_create prints where its hunt's wall-clock time went (stderr; same ring)   r06_hunt_default.txt
 """
 import os
@@ -747,7 +748,7 @@ MACROS = ["BT709_LAB_I420_PAIRED", "BT709_LAB_NO_ARITH", "BT709_LAB_NO_LOADS", "
           "BT709_INDEX_RTZ", "BT709_UNIFORM_INDEX_TWO_STEP", "BT709_REP_SPLIT_ENCODE", "BT709_LAB_BOUND_SHARED_INDEX",
           "BT709_LAB_BOUND_ONE_ENCODE", "BT709_LAB_HALF_TABLE", "BT709_LAB_F16_NO_ARITH", "BT709_LAB_F16_NO_TABLE",
           "BT709_LAB_F16_CVT_ONLY", "BT709_LAB_F16_NO_CAND_GATHER", "BT709_LAB_F16_NO_T_GATHER", "BT709_LAB_F16_NO_INDEX_SCALE", "BT709_LAB_F16_DMA_STAGING", "BT709_LAB_ENC_NO_ARITH", "BT709_LAB_UNC_NO_ARITH", "BT709_LAB_SCALED_QUARTER_FEWER_TAPS", "BT709_LAB_HALF_ENCODE_B32",
-          "BT709_LAB_SCALED_HALF_FEWER_TAPS", "BT709_LAB_SCALED_PAIR_DPP", "BT709_LAB_SCALED_ONCE_LDS", "BT709_LAB_HUNT_TRACE", "BT709_LAB_SCALED_NO_FETCH", "BT709_LAB_SCALED_NO_DECODE", "BT709_LAB_SCALED_NO_ENCODE", "BT709_LAB_SCALED_NO_STORE", "BT709_LAB_SCALED_STORE_ONE_LINE", "BT709_LAB_ANY_ORDER", "BT709_LAB_HALF_NO_FETCH", "BT709_LAB_HALF_NO_STORE", "BT709_LAB_BAND_ROT", "BT709_LAB_BAND_XOR", "BT709_LAB_STEP32"]
+          "BT709_LAB_SCALED_HALF_FEWER_TAPS", "BT709_LAB_SCALED_PAIR_DPP", "BT709_LAB_SCALED_ONCE_LDS", "BT709_LAB_HUNT_TRACE", "BT709_LAB_SCALED_NO_FETCH", "BT709_LAB_SCALED_NO_DECODE", "BT709_LAB_SCALED_NO_ENCODE", "BT709_LAB_SCALED_NO_STORE", "BT709_LAB_SCALED_STORE_ONE_LINE", "BT709_LAB_ANY_ORDER", "BT709_LAB_HALF_NO_FETCH", "BT709_LAB_HALF_NO_STORE", "BT709_LAB_BAND_ROT", "BT709_LAB_BAND_XOR", "BT709_LAB_STEP32", "BT709_LAB_ROW32"]
 
 
 GATES += [
@@ -767,6 +768,49 @@ GATES += [
   f.cbcr += static_cast<int64_t>(i) * p.step_cbcr;
   if (f.alpha) f.alpha += static_cast<int64_t>(i) * p.step_alpha;
   f.out += static_cast<int64_t>(i) * p.step_out;
+#endif
+"""),
+]
+
+GATES += [
+    # the row products of three kernels cut to 32 bits (tests/test_row_pitch_gpu.py, past-2^32: the last chroma row / target row lies above 2^32)
+    ("bt709_tile.h",
+     """    const uint8_t *y0 = f.y + static_cast<size_t>(2 * rp) * p.y_stride;
+    const uint8_t *y1 = y0 + p.y_stride;
+    const uint8_t *cc = f.cbcr + static_cast<size_t>(rp) * p.cbcr_stride;
+    const uint8_t *a0 = HAS_ALPHA ? f.alpha + static_cast<size_t>(2 * rp) * p.alpha_stride : nullptr;
+""",
+     """#if defined(BT709_LAB_ROW32)  // WRONG ADDRESSES: the products' low 32 bits, zero-extended
+    const uint8_t *y0 = f.y + static_cast<size_t>(static_cast<uint32_t>(2 * rp * p.y_stride));
+    const uint8_t *y1 = y0 + p.y_stride;
+    const uint8_t *cc = f.cbcr + static_cast<size_t>(static_cast<uint32_t>(rp * p.cbcr_stride));
+    const uint8_t *a0 = HAS_ALPHA ? f.alpha + static_cast<size_t>(static_cast<uint32_t>(2 * rp * p.alpha_stride)) : nullptr;
+#else
+    const uint8_t *y0 = f.y + static_cast<size_t>(2 * rp) * p.y_stride;
+    const uint8_t *y1 = y0 + p.y_stride;
+    const uint8_t *cc = f.cbcr + static_cast<size_t>(rp) * p.cbcr_stride;
+    const uint8_t *a0 = HAS_ALPHA ? f.alpha + static_cast<size_t>(2 * rp) * p.alpha_stride : nullptr;
+#endif
+"""),
+    ("bt709_rescale_half.hip",
+     """  uint8_t *o = f.out + static_cast<size_t>(orow) * p.out_stride;
+""",
+     """#if defined(BT709_LAB_ROW32)  // the wide form only
+  uint8_t *o = f.out + (WIDE ? static_cast<size_t>(static_cast<uint32_t>(orow * p.out_stride)) : static_cast<size_t>(orow) * p.out_stride);
+#else
+  uint8_t *o = f.out + static_cast<size_t>(orow) * p.out_stride;
+#endif
+"""),
+    ("bt709_encode.hip",
+     """      __builtin_nontemporal_store(
+          cbcr, reinterpret_cast<uint32_t *>(f.cbcr + static_cast<size_t>(rp) * p.cbcr_stride + 4u * q));
+""",
+     """#if defined(BT709_LAB_ROW32)
+      __builtin_nontemporal_store(
+          cbcr, reinterpret_cast<uint32_t *>(f.cbcr + static_cast<size_t>(static_cast<uint32_t>(rp * p.cbcr_stride)) + 4u * q));
+#else
+      __builtin_nontemporal_store(
+          cbcr, reinterpret_cast<uint32_t *>(f.cbcr + static_cast<size_t>(rp) * p.cbcr_stride + 4u * q));
 #endif
 """),
 ]
