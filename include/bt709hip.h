@@ -176,20 +176,22 @@ int bt709hip_decoder_setup(bt709hip_decoder *dec);
 /* -decodeBT709:... (MetalBT709Decoder.h:65-72).  Enqueues ONE fused kernel (chroma replicate + YCbCr->RGB matrix +
  * exact transfer + 8-bit pack) on `stream`.  `alpha` is NULL unless the decoder has an alpha channel.
  * render_width / height must equal the frame size (pass 1 never scales: .m:284-290).  wait_until_completed != 0
- * synchronises the stream before returning (.m:486-489). */
+ * synchronises the stream before returning (.m:486-489).  Row pairs are counted in gridDim.y: height / 2 <= 65535, i.e. up
+ * to 131070 rows (BT709HIP_ERR_UNSUPPORTED past it); no limit on the width. */
 int bt709hip_decode(bt709hip_decoder *dec, const bt709hip_frame *frame, const bt709hip_frame *alpha,
                     const bt709hip_surface *out, int render_width, int render_height, void *stream, int wait_until_completed);
 /* The same operator over `count` independent frames of one geometry (same size, strides, tags) in ONE launch -- how a
  * stream of frames stays off the launch-latency floor (a 4K frame is a ~7.6 us kernel).  count <= BT709HIP_MAX_BATCH
  * in general (the plane pointers travel in the kernel arguments); when frames, alphas and outputs are EVENLY SPACED
  * in memory -- frame i at frame 0 + i * (frame 1 - frame 0), as in a ring carved from one allocation -- any count
- * up to 65535.  alphas may be NULL. */
+ * up to 65535 (BT709HIP_ERR_UNSUPPORTED past it).  alphas may be NULL. */
 int bt709hip_decode_batch(bt709hip_decoder *dec, int count, const bt709hip_frame *frames, const bt709hip_frame *alphas,
                           const bt709hip_surface *outs, void *stream, int wait_until_completed);
 
 /* Pass 1 + pass 2 (-renderScaled:, bilinear) fused for the exact 2:1 ratio: out is (W/2) x (H/2); W, H multiples of 4.
  * Two-pass-equivalent arithmetic: each output channel is the linear-light mean of the four decoded 8-bit sRGB values,
- * re-encoded to sRGB; the alpha channel of an alpha decoder is filtered as a plain unorm. */
+ * re-encoded to sRGB; the alpha channel of an alpha decoder is filtered as a plain unorm.  height / 2 <= 65535 as
+ * for bt709hip_decode: with H a multiple of 4 up to 131068 rows (BT709HIP_ERR_UNSUPPORTED past it). */
 int bt709hip_decode_half(bt709hip_decoder *dec, const bt709hip_frame *frame, const bt709hip_frame *alpha,
                          const bt709hip_surface *out, void *stream, int wait_until_completed);
 /* Pass 1 + pass 2 fused for ANY output size (view-fit, down or up): bilinear in linear light over the decoded 8-bit
@@ -210,7 +212,7 @@ int bt709hip_render_scaled(bt709hip_context *ctx, const bt709hip_surface *in, co
  * Software type, .m:61-85 -> unconvertSoftware .m:146-198): `ycbcr_words` are PACKED 4:4:4 pixels, one 32-bit word
  * Y | Cb << 8 | Cr << 16 each, rows in_stride bytes apart; `out` receives (A<<24)|(R<<16)|(G<<8)|B with the decoder's
  * gamma and A = the decoder's alpha fill.  Odd width or height: BT709HIP_ERR_ODD_DIMENSIONS (.m:69-74); a decoder
- * with an alpha channel: BT709HIP_ERR_UNSUPPORTED. */
+ * with an alpha channel: BT709HIP_ERR_UNSUPPORTED.  height <= 65535, i.e. up to 65534 rows (BT709HIP_ERR_UNSUPPORTED past it). */
 int bt709hip_unconvert(bt709hip_decoder *dec, const void *ycbcr_words, size_t in_stride, int width, int height,
                        const bt709hip_surface *out, void *stream, int wait_until_completed);
 /* The step before the decode, on the GPU: 8-bit BGRA -> NV12 BT.709 video range with the reference's linear-light 2x2
@@ -221,12 +223,14 @@ int bt709hip_unconvert(bt709hip_decoder *dec, const void *ycbcr_words, size_t in
  * `out` points to are written (its tags are ignored).  Even, equal sizes on both sides.
  * in->format BGRA8_ALPHA: the ALPHA frame of `in` -- Y = the reference's luma of the grey (A,A,A), every Cb, Cr = 128.
  * Both gammas must be LINEAR (else BT709HIP_ERR_ALPHA_TRANSFER); out->cbcr may be NULL: only Y is written then (a
- * decoder reads nothing else of an alpha frame).  R, G, B are not read and not premultiplied (.m:805-841). */
+ * decoder reads nothing else of an alpha frame).  R, G, B are not read and not premultiplied (.m:805-841).
+ * height / 2 <= 65535, i.e. up to 131070 rows (BT709HIP_ERR_UNSUPPORTED past it). */
 int bt709hip_encode(bt709hip_context *ctx, const bt709hip_surface *in, const bt709hip_frame *out, int input_gamma,
                     int output_gamma, void *stream, int wait_until_completed);
 /* The reference's on-disk 4:2:0 format is YUV4MPEG2 "C420jpeg": planar Y, U (Cb), V (Cr) per frame
  * (Renderer/y4m_writer.h:194-241).  These move the two chroma planes to / from NV12's interleaved CbCr plane on the
- * device (the Y plane is the same in both layouts).  chroma_width x chroma_height = (W/2) x (H/2). */
+ * device (the Y plane is the same in both layouts).  chroma_width x chroma_height = (W/2) x (H/2); chroma_height <= 65535
+ * (BT709HIP_ERR_UNSUPPORTED past it). */
 int bt709hip_interleave_cbcr(bt709hip_context *ctx, const void *u, size_t u_stride, const void *v, size_t v_stride,
                              void *cbcr, size_t cbcr_stride, int chroma_width, int chroma_height, void *stream,
                              int wait_until_completed);

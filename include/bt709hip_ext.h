@@ -219,7 +219,9 @@ int bt709hip_decoder_flush_all(bt709hip_decoder *dec);
  * its limits: up to BT709HIP_MAX_BATCH arbitrary buffers, or any number up to 65535 when item i sits at item 0 + i * (item 1
  * - item 0) in every plane.  No reference twin (the reference converts, rescales and encodes one frame per call: a 4K frame
  * is a 12-22 us kernel, too short to fill the chip; one 4K +unconvert: per call runs at 0.58 of the roofline).  Differing sizes,
- * strides or formats: BT709HIP_ERR_SIZE_MISMATCH.  bt709hip_render_scaled_batch takes evenly spaced surfaces only
+ * strides or formats: BT709HIP_ERR_SIZE_MISMATCH.  More than 65535 evenly spaced items: BT709HIP_ERR_UNSUPPORTED, but from
+ * bt709hip_render_scaled_batch, which checks count with its other arguments, BT709HIP_ERR_INVALID_ARG.  The single calls' row
+ * limits (bt709hip.h) hold for every item.  bt709hip_render_scaled_batch takes evenly spaced surfaces only
  * (BT709HIP_ERR_UNSUPPORTED otherwise), each base a multiple of its texel size (BT709HIP_ERR_STRIDE, as the single call).
  * THE UNIFORM RULE, for every batched entry point (bt709hip_decode_batch and the coalescing queue included): a batch is evenly
  * spaced when, plane by plane (Y, CbCr, alpha, target; the encoder's BGRA, Y, CbCr), item i's pointer is item 0's + i * step, the
@@ -432,10 +434,11 @@ int bt709hip_half_thresholds(int gamma, float *thresholds, int capacity);
 int bt709hip_half_lookup(int gamma, float x, int candidate_offset, int *table_entries);
 /* Name of the kernel the last decode on this thread launched (for profiling). */
 const char *bt709hip_last_kernel_name(void);
-/* Launch shape of the last decode or encode this thread issued -- bt709hip_decode / _decode_batch (1:1, BGRA8 or RGBA16F target),
+/* Launch shape of the last decode, encode or plane shuffle this thread issued -- bt709hip_decode / _decode_batch (1:1, BGRA8 or RGBA16F target),
  * bt709hip_decode_half / _decode_half_batch (the short-lived 2:1 kernel: grid = tiles, groups of output rows, frames; the persistent one:
  * grid = (workgroups, 1, 1), block = the lanes of a tile row; launches 1, xcd_bands 0) or
- * bt709hip_encode / _encode_batch (grid = tiles [x 8 under the XCD-aware map], row-pair groups, pictures [per band]): grid and block of its
+ * bt709hip_encode / _encode_batch (grid = tiles [x 8 under the XCD-aware map], row-pair groups, pictures [per band]) or
+ * bt709hip_interleave_cbcr / _deinterleave_cbcr (grid = 256-lane groups, chroma rows, 1): grid and block of its
  * first kernel launch, the number of launches it took (2: the XCD-aware map over a multiple of 8 frames plus the plain map
  * over the rest) and the work map of the first (bt709hip_decoder_option BT709HIP_OPT_XCD_BANDS value actually used; 0 plain). */
 typedef struct {

@@ -10,6 +10,7 @@
 #include <cstdint>
 
 #include "bt709_kernels.h"
+#include "bt709_launch.h"
 
 namespace bt709 {
 namespace {
@@ -105,6 +106,7 @@ const char *launch_planes(const PlaneParams &p, bool interleave, hipStream_t str
   uint32_t gx = (items + kBlockThreads - 1) / kBlockThreads;
   if (gx < 1) gx = 1;
   const dim3 grid(gx, p.chroma_height, 1);
+  record_launch(grid, dim3(kBlockThreads), 0);
   if (interleave) {
     hipLaunchKernelGGL(interleave_cbcr, grid, dim3(kBlockThreads), 0, stream, p);
     return "interleave_cbcr";

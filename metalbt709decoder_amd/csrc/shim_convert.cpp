@@ -356,6 +356,7 @@ static int planes_call(bt709hip_context *ctx, const void *u, size_t u_stride, co
   p.wide = (cw % 8) == 0 && (u_stride % 8) == 0 && (v_stride % 8) == 0 && (cbcr_stride % 16) == 0 && aligned(u, 8) &&
            aligned(v, 8) && aligned(cbcr, 16);
   hipStream_t s = pick(ctx, stream);
+  last_launch_shape() = LaunchShape{};
   set_kernel_name(launch_planes(p, interleave, s));
   HIP_TRY(hipGetLastError());
   if (wait) HIP_TRY(hipStreamSynchronize(s));

@@ -83,6 +83,7 @@ class Route:
         self.name, self.entry, self.size, self.out_size, self.ins, self.outs, self.kernel = name, entry, size, out_size, ins, outs, kernel
         self.gamma, self.alpha, self.options, self.over, self.fmt, self.in_fmt = gamma, alpha, tuple(options), over, fmt, in_fmt
         self.taps, self.skew, self.bands, self.reads_destination, self.pair, self.no_skew = taps, skew, bands, reads_destination, pair, no_skew
+        self.key = name  # what frame_data / want remember a route's frames under: a resized copy (tests/extent_cases.py) takes its own
 
     def plane(self, name):
         return next(p for p in self.ins + self.outs if p.name == name)
@@ -380,7 +381,7 @@ def _route_seed(route):
 
 def frame_data(route, k):
     """plane name -> (rows, row_bytes) bytes of frame k: random, another for every frame and route."""
-    key = (route.name, k)
+    key = (route.key, k)
     if key not in _data:
         rng = np.random.default_rng(100000 + 1000 * _route_seed(route) + k)
         w, h = route.size
@@ -413,7 +414,7 @@ def want(route, oracle, tabs, T, k, bg_index):
     """plane name -> (rows, row_bytes) bytes frame k's samples must become (over the background of target bg_index, where the
     route reads its destination): the oracle call the route's own tests use.  tabs: over_cases.tables(oracle); T: the alpha
     luma table (tests/golden/alpha_luma.json)."""
-    key = (route.name, k, bg_index if route.reads_destination else None)
+    key = (route.key, k, bg_index if route.reads_destination else None)
     if key in _want:
         return _want[key]
     d = frame_data(route, k)
