@@ -421,6 +421,9 @@ class MetalBT709Decoder {
   // behind it: a YUV4MPEG2 FRAME payload as uploaded.  BGRA8 targets of decodeBT709 only; rings and pools stay NV12.
   static constexpr int kChromaLayoutOption = BT709HIP_OPT_CHROMA_LAYOUT;
   static constexpr int kChromaNV12 = BT709HIP_CHROMA_NV12, kChromaI420 = BT709HIP_CHROMA_I420;
+  // The encoder's twin is an option of the CONTEXT (bt709hip_context_set_option; BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT = 6): the same
+  // two values select the planes bt709hip_encode[_batch] writes.  This mirror has no encoder; a caller of the C ABI sets it there.
+  static constexpr int kEncodeChromaLayoutOption = BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT;
 
   // The coalescing submit (include/bt709hip_ext.h BT709HIP_OPT_COALESCE): keep the reference's one-decodeBT709-call-per-frame cadence
   // on device-resident frames and let `frames` (2..32; 0 = off) queued calls go out as one launch; maxAgeMicroseconds > 0: a queue

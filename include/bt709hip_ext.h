@@ -41,15 +41,37 @@ typedef struct {
 int bt709hip_context_info(const bt709hip_context *ctx, bt709hip_device_info *info);
 
 /* Launch-shape knobs of a context (tuning and test hooks; no reference twin).  Values are
- * clamped to their valid range; 0 restores the default. */
+ * clamped to their valid range; 0 restores the default.  BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT is no knob and is NOT clamped:
+ * see below. */
 typedef enum {
   BT709HIP_CTX_OPT_GRID_MULT = 1,       /* general (unaligned-layout) kernels: workgroups per launch = CUs x 8 x this; default 2 */
   BT709HIP_CTX_OPT_ENCODE_ROW_PAIRS = 2,/* encoder: consecutive row pairs per workgroup; default 0 = sized per launch */
   BT709HIP_CTX_OPT_ENCODE_THREADS = 3,  /* encoder: lanes per workgroup (rounded down to whole waves); default 0 = from the width */
   BT709HIP_CTX_OPT_XCD_BANDS = 4,       /* encoder: 1 (default) XCD-aware work map for launches of a multiple of 8 pictures; 0 plain order */
-  BT709HIP_CTX_OPT_STREAMING_TRIES = 5  /* device buffers of 256 MB or more that the library allocates itself (in-flight pool slots, the sharder's lanes) go through bt709hip_malloc_streaming with this many candidates; default 4, 1 = plain allocation */
+  BT709HIP_CTX_OPT_STREAMING_TRIES = 5, /* device buffers of 256 MB or more that the library allocates itself (in-flight pool slots, the sharder's lanes) go through bt709hip_malloc_streaming with this many candidates; default 4, 1 = plain allocation */
+  BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT = 6 /* BT709HIP_CHROMA_NV12 (default) or BT709HIP_CHROMA_I420: the planes bt709hip_encode[_batch] writes; any other value is refused */
 } bt709hip_context_option;
 int bt709hip_context_set_option(bt709hip_context *ctx, int option, int value);
+/* BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT.  The reference's encoder exists to write YUV4MPEG2 files, whose FRAME is planar: Y, then
+ * U, then V (Renderer/y4m_writer.h:194-241).  With the option at BT709HIP_CHROMA_I420 (the values are BT709HIP_OPT_CHROMA_LAYOUT's,
+ * defined below) the bt709hip_frame that bt709hip_encode and bt709hip_encode_batch WRITE is three planes, in the convention of
+ * the decode side, with no de-interleave pass and no scratch plane:
+ *   y, y_stride   as before;
+ *   cbcr          the U (Cb) plane: (W/2) x (H/2) bytes, rows cbcr_stride bytes apart, cbcr_stride >= W/2;
+ *   the V (Cr) plane has the same pitch and starts at cbcr + (height/2) * cbcr_stride (a 64-bit product).
+ * U[r][c] and V[r][c] are bytes 2c and 2c+1 of row r of the CbCr plane the NV12 encode of the same picture writes, Y is that
+ * encode's Y; nothing outside the three planes' samples is written (row padding, a gap between U's last row and V's first, bytes
+ * behind V).  A tight FRAME payload is y = base, y_stride = W, cbcr = base + W*H, cbcr_stride = W/2: one contiguous download of
+ * W*H*3/2 bytes is the payload.  Validation: cbcr_stride < W/2 is BT709HIP_ERR_STRIDE (NV12: < W); every other check and limit
+ * is NV12's; an evenly spaced batch is one whose BGRA, Y and U pointers are (V follows from U).  The fast kernel needs
+ * W % 4 == 0, the BGRA pointer and pitch 16-byte aligned, Y 4-byte, the U pointer and cbcr_stride 2-byte; any other call takes
+ * the general kernel.  Launch plans (bt709hip_last_launch_info) are the NV12 encoder's for the same size and count, and
+ * BT709HIP_CTX_OPT_ENCODE_ROW_PAIRS, _ENCODE_THREADS and _XCD_BANDS apply as they do there.  bt709hip_last_kernel_name:
+ * "encode_bgra_i420", "encode_bgra_i420_blocks".  BGRA8_ALPHA input with chroma planes: every U and V byte is 128
+ * ("encode_alpha_y<i420>", "encode_alpha_y_blocks<i420>"); with cbcr == NULL only Y is written, by the same kernels under the
+ * same names as under NV12.  The call reads the option once, on entry.  Any value but the two: BT709HIP_ERR_INVALID_ARG, the
+ * option keeps its value (the other context options clamp; this one does not).  Setting it never touches the device and needs
+ * no table: it works while a stream is being captured.  Under BT709HIP_CHROMA_NV12 nothing changes. */
 
 /* A stream with a scheduling priority (hipStreamCreateWithPriority): 0 = normal, negative = higher, positive = lower; clamped
  * to the device's range.  (MTLCommandQueue has no twin; a renderer that decodes ahead of what it presents puts the look-ahead
@@ -180,7 +202,8 @@ int bt709hip_decoder_get_option(const bt709hip_decoder *dec, int option, int *va
  *     their usual validation and write nothing while the option is BT709HIP_CHROMA_I420 (their strip loaders read NV12);
  *   - objects that allocate their own frames -- ring, ring set, pool, shard -- stay NV12 whatever the option holds (their
  *     launches pass the layout instead of reading the option; bt709hip_ring_frame keeps describing NV12 planes);
- *   - bt709hip_unconvert, bt709hip_render_scaled and the encoder have no chroma plane to lay out and are unchanged;
+ *   - bt709hip_unconvert and bt709hip_render_scaled have no chroma plane to lay out and are unchanged; the encoder WRITES one,
+ *     and its layout is the context's own option, BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT (above), not this one;
  *   - YV12 (V before U), and planar frames whose V plane is anywhere but (height/2) * cbcr_stride behind U. */
 #define BT709HIP_CHROMA_NV12 0
 #define BT709HIP_CHROMA_I420 1

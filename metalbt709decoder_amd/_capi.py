@@ -52,6 +52,7 @@ CTX_OPT_ENCODE_ROW_PAIRS = 2
 CTX_OPT_ENCODE_THREADS = 3
 CTX_OPT_XCD_BANDS = 4
 CTX_OPT_STREAMING_TRIES = 5
+CTX_OPT_ENCODE_CHROMA_LAYOUT = 6  # the planes bt709hip_encode[_batch] writes: CHROMA_NV12 (default) or CHROMA_I420; any other value is refused
 
 
 class RingPlacement(C.Structure):  # bt709hip_ring_placement

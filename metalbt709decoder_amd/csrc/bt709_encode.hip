@@ -37,6 +37,9 @@
 // A lane owns a 4x2-pixel quad (two blocks): two 16-byte loads, three 4-byte stores; lanes
 // of a wave are consecutive quads of one row pair; grid = (tiles, row-pair groups, frames).  LDS holds
 // the 2 KiB per-byte table and the two-resolution BT709_from_linear table.
+//
+// The same pictures as three planes (I420: Y, U, V -- the YUV4MPEG2 FRAME payload) come from the planar twins below: one body
+// per kernel shape, templated on the layout; only the placement of a quad's four chroma bytes and their stores differ.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -127,23 +130,33 @@ __device__ __forceinline__ void encode_block(const EncodeLds &t, float fl_quarte
   v[5] = quant_arg(er, static_cast<float>(kCMax - kCMin), 128.0f);                     // BT709.h:235, 246
 }
 
-// Truncate the twelve values of a quad (two blocks) and place them: Y rows top / bottom, CbCr with
-// Cb in the low byte (CVPixelBufferUtils.h:358-361).  One asm statement: the conversions must not
-// be separated from the mode switch around them.
-__device__ __forceinline__ void quantize_quad(const float a[6], const float b[6], uint32_t &ytop, uint32_t &ybot,
+// Truncate the twelve values of a quad (two blocks) and place them: Y rows top / bottom, and the four chroma bytes in one word,
+// Cr of the first block in byte lane CR0 and Cb of the second in lane CB1 (quantize_quad below).  One asm statement: the
+// conversions must not be separated from the mode switch around them.
+template <int CR0, int CB1>
+__device__ __forceinline__ void quantize_quad_lanes(const float a[6], const float b[6], uint32_t &ytop, uint32_t &ybot,
                                               uint32_t &cbcr) {
   ytop = ybot = cbcr = 0;
   asm("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 0, 2), 3\n\t"
       "v_cvt_pk_u8_f32 %0, %3, 0, %0\n\tv_cvt_pk_u8_f32 %0, %4, 1, %0\n\t"
       "v_cvt_pk_u8_f32 %1, %5, 0, %1\n\tv_cvt_pk_u8_f32 %1, %6, 1, %1\n\t"
-      "v_cvt_pk_u8_f32 %2, %7, 0, %2\n\tv_cvt_pk_u8_f32 %2, %8, 1, %2\n\t"
+      "v_cvt_pk_u8_f32 %2, %7, 0, %2\n\tv_cvt_pk_u8_f32 %2, %8, %15, %2\n\t"
       "v_cvt_pk_u8_f32 %0, %9, 2, %0\n\tv_cvt_pk_u8_f32 %0, %10, 3, %0\n\t"
       "v_cvt_pk_u8_f32 %1, %11, 2, %1\n\tv_cvt_pk_u8_f32 %1, %12, 3, %1\n\t"
-      "v_cvt_pk_u8_f32 %2, %13, 2, %2\n\tv_cvt_pk_u8_f32 %2, %14, 3, %2\n\t"
+      "v_cvt_pk_u8_f32 %2, %13, %16, %2\n\tv_cvt_pk_u8_f32 %2, %14, 3, %2\n\t"
       "s_setreg_imm32_b32 hwreg(HW_REG_MODE, 0, 2), 0"
       : "+v"(ytop), "+v"(ybot), "+v"(cbcr)
       : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(a[4]), "v"(a[5]), "v"(b[0]), "v"(b[1]), "v"(b[2]), "v"(b[3]),
-        "v"(b[4]), "v"(b[5]));
+        "v"(b[4]), "v"(b[5]), "n"(CR0), "n"(CB1));
+}
+
+// NV12: Cb0 Cr0 Cb1 Cr1, Cb in the low byte (CVPixelBufferUtils.h:358-361) -- the CbCr plane's dword.
+// I420: Cb0 Cb1 Cr0 Cr1 -- the low half is the U plane's two bytes, the high half the V plane's.  v_cvt_pk_u8_f32 takes the byte
+// lane as an operand, so either placement costs the same twelve instructions.
+template <uint32_t LAYOUT>
+__device__ __forceinline__ void quantize_quad(const float a[6], const float b[6], uint32_t &ytop, uint32_t &ybot, uint32_t &cbcr) {
+  if (LAYOUT == kChromaI420) quantize_quad_lanes<2, 1>(a, b, ytop, ybot, cbcr);
+  else quantize_quad_lanes<1, 2>(a, b, ytop, ybot, cbcr);
 }
 
 // one block (general kernel): bytes 0,1 of each word
@@ -187,94 +200,44 @@ __device__ __forceinline__ EncodeFrame encode_frame(const EncodeParams &p, uint3
   return f;
 }
 
+// Where a quad's / block's chroma goes.  LAYOUT is EncodeParams::chroma_layout, uniform over the launch:
+//   kChromaNV12: `row` of the CbCr plane, Cb Cr pairs -- one dword per quad;
+//   kChromaI420: `row` of the U plane and the same row of the V plane (H/2) x cbcr_stride bytes behind it (v_plane_offset: 64 bits) -- the
+//                word quantize_quad<kChromaI420> packed, low half to U, high half to V: a wave writes 128 contiguous bytes to each.
+__device__ __forceinline__ uint64_t v_plane_offset(const EncodeParams &p) {
+  return static_cast<uint64_t>(p.height >> 1) * p.cbcr_stride;  // uniform: two scalar multiplies
+}
+template <uint32_t LAYOUT>
+__device__ __forceinline__ void store_quad_chroma(const EncodeParams &p, uint8_t *row, uint32_t q, uint32_t word) {
+  if (LAYOUT == kChromaI420) {
+    __builtin_nontemporal_store(static_cast<uint16_t>(word), reinterpret_cast<uint16_t *>(row + 2u * q));
+    __builtin_nontemporal_store(static_cast<uint16_t>(word >> 16), reinterpret_cast<uint16_t *>(row + v_plane_offset(p) + 2u * q));
+  } else {
+    __builtin_nontemporal_store(word, reinterpret_cast<uint32_t *>(row + 4u * q));
+  }
+}
+// general kernels: bytes, any alignment
+// Byte 1 of a word quantize_block packed, for the byte store beside byte 0's.  The NV12 kernel's compiler merges the two into one
+// 2-byte store at whatever address the row has (legal on gfx950); the planar twin keeps the value opaque so that every store of
+// it stays a byte store, as its contract (any alignment, byte stores) reads.
+template <uint32_t LAYOUT>
+__device__ __forceinline__ uint8_t second_byte(uint32_t word) {
+  uint32_t b = word >> 8;
+  if (LAYOUT == kChromaI420) asm("" : "+v"(b));
+  return static_cast<uint8_t>(b);
+}
+template <uint32_t LAYOUT>
+__device__ __forceinline__ void store_block_chroma(const EncodeParams &p, uint8_t *row, uint32_t bx, uint8_t cb, uint8_t cr) {
+  if (LAYOUT == kChromaI420) {
+    row[bx] = cb;
+    (row + v_plane_offset(p))[bx] = cr;
+  } else {
+    row[2 * bx] = cb;
+    row[2 * bx + 1] = cr;
+  }
+}
+
 }  // namespace
-
-// grid = (tiles, row-pair groups, frames); a workgroup walks row_pairs_per_block consecutive row
-// pairs of one frame, prefetching the next pair while it encodes the current one.
-__global__ void __launch_bounds__(kMaxBlockThreads)
-encode_bgra_nv12(const EncodeParams p) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-  const BandedWork work = banded_work(p.xcd_bands, p.frames_per_band);  // XCD-aware work map: bt709_tile.h
-  const EncodeFrame f = encode_frame(p, work.frame);
-  const uint32_t quads = p.width >> 2;
-  const uint32_t row_pairs = p.height >> 1;
-  const uint32_t q_raw = work.tile * blockDim.x + threadIdx.x;
-  const uint32_t q = min(q_raw, quads - 1);
-  const uint32_t rp0 = blockIdx.y * p.row_pairs_per_block;
-  const uint32_t rp_end = min(rp0 + p.row_pairs_per_block, row_pairs);
-
-  // row pointers are uniform (SGPR base), the lane adds a 32-bit offset: no 64-bit VALU address arithmetic
-  const uint8_t *s0 = f.bgra + static_cast<size_t>(2 * rp0) * p.bgra_stride;
-  u32x4 top = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(s0 + 16u * q));
-  u32x4 bot = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(s0 + p.bgra_stride + 16u * q));
-
-  const EncodeLds t = stage_encode_tables(lds_raw, p);  // after the first loads are in flight
-  __syncthreads();
-  const float quarter_n = __fmul_rn(0.25f, p.from_linear_scale);
-
-  for (uint32_t rp = rp0; rp < rp_end; ++rp) {
-    // prefetch the next row pair before the arithmetic; nothing on the workgroup's last pair (a
-    // clamped re-read of the own rows cost 8 % extra HBM reads at 9 row pairs per workgroup:
-    // non-temporal loads do not stay in L2)
-    u32x4 ntop = top, nbot = bot;
-    if (rp + 1 < rp_end) {
-      const uint8_t *s1 = f.bgra + static_cast<size_t>(2 * (rp + 1)) * p.bgra_stride;
-      ntop = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(s1 + 16u * q));
-      nbot = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(s1 + p.bgra_stride + 16u * q));
-    }
-
-    float va[6], vb[6];
-    {
-      const uint32_t blk[4] = {top.x, top.y, bot.x, bot.y};
-      encode_block(t, quarter_n, blk, va);
-    }
-    {
-      const uint32_t blk[4] = {top.z, top.w, bot.z, bot.w};
-      encode_block(t, quarter_n, blk, vb);
-    }
-    uint32_t ytop, ybot, cbcr;
-    quantize_quad(va, vb, ytop, ybot, cbcr);
-    if (q_raw < quads) {
-      uint8_t *y0 = f.y + static_cast<size_t>(2 * rp) * p.y_stride;
-      __builtin_nontemporal_store(ytop, reinterpret_cast<uint32_t *>(y0 + 4u * q));
-      __builtin_nontemporal_store(ybot, reinterpret_cast<uint32_t *>(y0 + p.y_stride + 4u * q));
-      __builtin_nontemporal_store(
-          cbcr, reinterpret_cast<uint32_t *>(f.cbcr + static_cast<size_t>(rp) * p.cbcr_stride + 4u * q));
-    }
-    top = ntop;
-    bot = nbot;
-  }
-}
-
-// General layout: one lane per 2x2 block, scalar loads/stores, any alignment.
-__global__ void __launch_bounds__(kBlockThreads)
-encode_bgra_nv12_blocks(const EncodeParams p) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-  const EncodeLds t = stage_encode_tables(lds_raw, p);
-  __syncthreads();
-  const EncodeFrame f = encode_frame(p, blockIdx.z);
-  const float quarter_n = __fmul_rn(0.25f, p.from_linear_scale);
-  const uint32_t bw = p.width >> 1;
-  const uint32_t rp = blockIdx.y;
-  for (uint32_t bx = blockIdx.x * blockDim.x + threadIdx.x; bx < bw; bx += gridDim.x * blockDim.x) {
-    const uint32_t *r0 = reinterpret_cast<const uint32_t *>(f.bgra + static_cast<size_t>(2 * rp) * p.bgra_stride);
-    const uint32_t *r1 = reinterpret_cast<const uint32_t *>(f.bgra + static_cast<size_t>(2 * rp + 1) * p.bgra_stride);
-    const uint32_t blk[4] = {r0[2 * bx], r0[2 * bx + 1], r1[2 * bx], r1[2 * bx + 1]};
-    float v[6];
-    encode_block(t, quarter_n, blk, v);
-    uint32_t ytop, ybot, cbcr;
-    quantize_block(v, ytop, ybot, cbcr);
-    uint8_t *y0 = f.y + static_cast<size_t>(2 * rp) * p.y_stride;
-    uint8_t *y1 = y0 + p.y_stride;
-    uint8_t *c = f.cbcr + static_cast<size_t>(rp) * p.cbcr_stride;
-    y0[2 * bx] = static_cast<uint8_t>(ytop);
-    y0[2 * bx + 1] = static_cast<uint8_t>(ytop >> 8);
-    y1[2 * bx] = static_cast<uint8_t>(ybot);
-    y1[2 * bx + 1] = static_cast<uint8_t>(ybot >> 8);
-    c[2 * bx] = static_cast<uint8_t>(cbcr);
-    c[2 * bx + 1] = static_cast<uint8_t>(cbcr >> 8);
-  }
-}
 
 // ---------------------------------------------------------------- alpha frames (BT709HIP_FORMAT_BGRA8_ALPHA)
 // The reference's alpha clip is the ordinary encode of the grey picture (A,A,A) under (Linear, Linear)
@@ -300,75 +263,35 @@ __device__ __forceinline__ uint32_t alpha_luma4(const uint32_t *lut, const u32x4
 
 }  // namespace
 
-// grid = (tiles, row-pair groups, frames), as encode_bgra_nv12
-__global__ void __launch_bounds__(kMaxBlockThreads)
-encode_alpha_y(const EncodeParams p) {
-  __shared__ uint32_t lut[64];
-  const BandedWork work = banded_work(p.xcd_bands, p.frames_per_band);
-  const EncodeFrame f = encode_frame(p, work.frame);
-  const uint32_t quads = p.width >> 2;
-  const uint32_t row_pairs = p.height >> 1;
-  const uint32_t q_raw = work.tile * blockDim.x + threadIdx.x;
-  const uint32_t q = min(q_raw, quads - 1);
-  const uint32_t rp0 = blockIdx.y * p.row_pairs_per_block;
-  const uint32_t rp_end = min(rp0 + p.row_pairs_per_block, row_pairs);
-  const bool with_cbcr = p.frames[0].cbcr != nullptr;  // uniform over the launch
+// NV12: the CbCr plane
+#define BT709_ENCODE_LAYOUT kChromaNV12
+#define BT709_ENCODE_KERNEL encode_bgra_nv12
+#define BT709_ENCODE_KERNEL_BLOCKS encode_bgra_nv12_blocks
+#define BT709_ENCODE_ALPHA_KERNEL encode_alpha_y
+#define BT709_ENCODE_ALPHA_KERNEL_BLOCKS encode_alpha_y_blocks
+#include "bt709_encode_kernels.inc"
+#undef BT709_ENCODE_LAYOUT
+#undef BT709_ENCODE_KERNEL
+#undef BT709_ENCODE_KERNEL_BLOCKS
+#undef BT709_ENCODE_ALPHA_KERNEL
+#undef BT709_ENCODE_ALPHA_KERNEL_BLOCKS
 
-  const uint8_t *s0 = f.bgra + static_cast<size_t>(2 * rp0) * p.bgra_stride;
-  u32x4 top = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(s0 + 16u * q));
-  u32x4 bot = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(s0 + p.bgra_stride + 16u * q));
-
-  stage_alpha_luma(lut, p);  // after the first loads are in flight
-  __syncthreads();
-
-  for (uint32_t rp = rp0; rp < rp_end; ++rp) {
-    u32x4 ntop = top, nbot = bot;
-    if (rp + 1 < rp_end) {  // nothing on the workgroup's last pair, as encode_bgra_nv12
-      const uint8_t *s1 = f.bgra + static_cast<size_t>(2 * (rp + 1)) * p.bgra_stride;
-      ntop = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(s1 + 16u * q));
-      nbot = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(s1 + p.bgra_stride + 16u * q));
-    }
-    const uint32_t ytop = alpha_luma4(lut, top), ybot = alpha_luma4(lut, bot);
-    if (q_raw < quads) {
-      uint8_t *y0 = f.y + static_cast<size_t>(2 * rp) * p.y_stride;
-      __builtin_nontemporal_store(ytop, reinterpret_cast<uint32_t *>(y0 + 4u * q));
-      __builtin_nontemporal_store(ybot, reinterpret_cast<uint32_t *>(y0 + p.y_stride + 4u * q));
-      if (with_cbcr)
-        __builtin_nontemporal_store(
-            0x80808080u, reinterpret_cast<uint32_t *>(f.cbcr + static_cast<size_t>(rp) * p.cbcr_stride + 4u * q));
-    }
-    top = ntop;
-    bot = nbot;
-  }
-}
-
-// General layout: one lane per 2x2 block, byte loads of the four A's and byte stores, any alignment.
-__global__ void __launch_bounds__(kBlockThreads)
-encode_alpha_y_blocks(const EncodeParams p) {
-  __shared__ uint32_t lut[64];
-  stage_alpha_luma(lut, p);
-  __syncthreads();
-  const uint8_t *t = reinterpret_cast<const uint8_t *>(lut);
-  const EncodeFrame f = encode_frame(p, blockIdx.z);
-  const bool with_cbcr = p.frames[0].cbcr != nullptr;
-  const uint32_t bw = p.width >> 1;
-  const uint32_t rp = blockIdx.y;
-  for (uint32_t bx = blockIdx.x * blockDim.x + threadIdx.x; bx < bw; bx += gridDim.x * blockDim.x) {
-    const uint8_t *r0 = f.bgra + static_cast<size_t>(2 * rp) * p.bgra_stride + 8u * bx;
-    const uint8_t *r1 = r0 + p.bgra_stride;
-    uint8_t *y0 = f.y + static_cast<size_t>(2 * rp) * p.y_stride + 2u * bx;
-    uint8_t *y1 = y0 + p.y_stride;
-    y0[0] = t[r0[3]];
-    y0[1] = t[r0[7]];
-    y1[0] = t[r1[3]];
-    y1[1] = t[r1[7]];
-    if (with_cbcr) {
-      uint8_t *c = f.cbcr + static_cast<size_t>(rp) * p.cbcr_stride + 2u * bx;
-      c[0] = 128;
-      c[1] = 128;
-    }
-  }
-}
+// BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT = BT709HIP_CHROMA_I420: the planar twins -- three planes, Y then U then V, the
+// YUV4MPEG2 FRAME payload (Renderer/y4m_writer.h:194-241).  Preconditions of the fast ones (checked by the host shim): width
+// % 4 == 0; BGRA pointer and pitch 16-byte aligned, Y 4-byte, the U pointer and the chroma pitch 2-byte (the V plane then is, too).
+// The alpha twins ("encode_alpha_y<i420>", "encode_alpha_y_blocks<i420>") write 128 to every U and every V byte; they are only
+// launched with chroma planes: an alpha frame without them has nothing to lay out and takes the kernels above.
+#define BT709_ENCODE_LAYOUT kChromaI420
+#define BT709_ENCODE_KERNEL encode_bgra_i420
+#define BT709_ENCODE_KERNEL_BLOCKS encode_bgra_i420_blocks
+#define BT709_ENCODE_ALPHA_KERNEL encode_alpha_y_i420
+#define BT709_ENCODE_ALPHA_KERNEL_BLOCKS encode_alpha_y_blocks_i420
+#include "bt709_encode_kernels.inc"
+#undef BT709_ENCODE_LAYOUT
+#undef BT709_ENCODE_KERNEL
+#undef BT709_ENCODE_KERNEL_BLOCKS
+#undef BT709_ENCODE_ALPHA_KERNEL
+#undef BT709_ENCODE_ALPHA_KERNEL_BLOCKS
 
 const char *launch_encode(const EncodeParams &params, int frames, bool fast, bool xcd_bands, hipStream_t stream) {
   const BandPlan plan = plan_bands(frames, fast && xcd_bands, params.uniform, kXcdBandMinFrames);
@@ -381,6 +304,8 @@ const char *launch_encode(const EncodeParams &params, int frames, bool fast, boo
   EncodeParams p = params;
   if (p.row_pairs_per_block == 0) p.row_pairs_per_block = encode_row_pairs_per_block(p.width, p.height, frames);
   const bool alpha = p.alpha_luma != nullptr;  // BT709HIP_FORMAT_BGRA8_ALPHA: same plan, the alpha kernels (static LDS)
+  // the plan does not depend on the layout, only the kernel does (an alpha frame without chroma planes arrives as kChromaNV12)
+  const bool planar = p.chroma_layout == kChromaI420;
   const size_t lds = alpha ? 0 : 256 * sizeof(EncodeByteEntry) + p.from_linear_bytes;
   if (fast) {
     const uint32_t quads = p.width / 4;
@@ -398,25 +323,42 @@ const char *launch_encode(const EncodeParams &params, int frames, bool fast, boo
               (p.height / 2 + p.row_pairs_per_block - 1) / p.row_pairs_per_block, frames);
     if (plan.banded) grid = band_grid(p, 1, grid);
     record_launch(grid, dim3(threads), p.xcd_bands);
+    if (alpha && planar) {
+      hipLaunchKernelGGL(encode_alpha_y_i420, grid, dim3(threads), lds, stream, p);
+      return "encode_alpha_y<i420>";
+    }
     if (alpha) {
       hipLaunchKernelGGL(encode_alpha_y, grid, dim3(threads), lds, stream, p);
       return "encode_alpha_y";
+    }
+    if (planar) {
+      hipLaunchKernelGGL(encode_bgra_i420, grid, dim3(threads), lds, stream, p);
+      return "encode_bgra_i420";
     }
     hipLaunchKernelGGL(encode_bgra_nv12, grid, dim3(threads), lds, stream, p);
     return "encode_bgra_nv12";
   }
   const dim3 grid((p.width / 2 + kBlockThreads - 1) / kBlockThreads, p.height / 2, frames);
   record_launch(grid, dim3(kBlockThreads), 0);
+  if (alpha && planar) {
+    hipLaunchKernelGGL(encode_alpha_y_blocks_i420, grid, dim3(kBlockThreads), lds, stream, p);
+    return "encode_alpha_y_blocks<i420>";
+  }
   if (alpha) {
     hipLaunchKernelGGL(encode_alpha_y_blocks, grid, dim3(kBlockThreads), lds, stream, p);
     return "encode_alpha_y_blocks";
+  }
+  if (planar) {
+    hipLaunchKernelGGL(encode_bgra_i420_blocks, grid, dim3(kBlockThreads), lds, stream, p);
+    return "encode_bgra_i420_blocks";
   }
   hipLaunchKernelGGL(encode_bgra_nv12_blocks, grid, dim3(kBlockThreads), lds, stream, p);
   return "encode_bgra_nv12_blocks";
 }
 
 hipError_t prepare_encode_kernels() {
-  const void *fns[] = {reinterpret_cast<const void *>(&encode_bgra_nv12), reinterpret_cast<const void *>(&encode_bgra_nv12_blocks)};
+  const void *fns[] = {reinterpret_cast<const void *>(&encode_bgra_nv12), reinterpret_cast<const void *>(&encode_bgra_nv12_blocks),
+                       reinterpret_cast<const void *>(&encode_bgra_i420), reinterpret_cast<const void *>(&encode_bgra_i420_blocks)};
   return raise_lds_cap(fns, kRepLdsBytes);
 }
 

@@ -176,7 +176,7 @@ inline bool render_planes_fit(const RenderParams &p) { return plane_fits(p.heigh
 // grid = (column tiles, strips of `rows` output rows, frames)
 const char *launch_render_scaled(const RenderParams &p, int frames, bool in_rgba16f, uint32_t compute_units, hipStream_t stream);
 
-// BGRA -> NV12 encoder (bt709_encode.hip).  One frame per launch.
+// BGRA -> NV12 / I420 encoder (bt709_encode.hip).
 struct EncodeFrame {
   const uint8_t *bgra;  // W x H words (A<<24)|(R<<16)|(G<<8)|B, alpha ignored
   uint8_t *y;
@@ -186,6 +186,11 @@ struct EncodeParams {
   EncodeFrame frames[kMaxBatch];
   // uniform != 0: frame i = frames[0] + i * step_* (bytes), as in DecodeParams
   uint32_t uniform;
+  // BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT: kChromaI420 = frames[i].cbcr is the U (Cb) plane, W/2 x H/2 bytes at pitch cbcr_stride,
+  // and the V (Cr) plane the same shape (H/2) * cbcr_stride bytes (a 64-bit product, formed by the kernels) behind it;
+  // launch_encode then runs the encode_*_i420 kernels.  kChromaNV12 whenever the frames carry no chroma plane (alpha frames).
+  // (It sits in what was padding: the kernarg block and every other field's offset are what they were.)
+  uint32_t chroma_layout;  // kChromaNV12 / kChromaI420
   int64_t step_bgra, step_y, step_cbcr;
   const EncodeByteEntry *per_byte;  // 256 entries for the (input gamma, output gamma) pair
   const TransferBucket *from_linear;  // two-resolution BT709_from_linear(., output gamma) table (SplitTable)

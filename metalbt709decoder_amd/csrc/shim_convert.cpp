@@ -1,6 +1,6 @@
 // C-ABI shim, the converters either side of the decode (include/bt709hip.h): +unconvert: on packed 4:4:4 words
 // (Renderer/BGRAToBT709Converter.h:34-46), pass 2 alone (-renderScaled:, Renderer/MetalScaleRenderContext.h:34-40), the
-// BGRA -> NV12 encoder (+convertIntoCoreVideoBuffer:, BGRAToBT709Converter.h:73-76) and the planar <-> NV12 chroma layouts
+// BGRA -> NV12 / I420 encoder (+convertIntoCoreVideoBuffer:, BGRAToBT709Converter.h:73-76) and the planar <-> NV12 chroma layouts
 // of the reference's Y4M files (Renderer/y4m_writer.h:194-241).
 #include "shim_internal.h"
 
@@ -239,8 +239,12 @@ int bt709hip_encode_batch(bt709hip_context *ctx, int count, const bt709hip_surfa
   // so cbcr may be NULL -- in every frame of the call or in none -- and cbcr_stride is not looked at then
   const bool alpha = in0.format == BT709HIP_FORMAT_BGRA8_ALPHA;
   const bool no_cbcr = alpha && out0.cbcr == nullptr;
+  // BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT, read once: cbcr is the U plane, W/2 bytes a row, V (H/2) x cbcr_stride bytes behind it.
+  // Without a chroma plane there is nothing to lay out: such a call is what it was, whatever the option holds.
+  const bool planar = ctx->encode_chroma_layout == BT709HIP_CHROMA_I420 && !no_cbcr;
+  const size_t chroma_align = planar ? 2 : 4;  // the fast kernels' chroma store: a 2-byte half per plane, or the CbCr dword
   bool uniform = count > 1;
-  bool fast = (in0.width % 4) == 0 && (in0.stride % 16) == 0 && (out0.y_stride % 4) == 0 && (no_cbcr || (out0.cbcr_stride % 4) == 0);
+  bool fast = (in0.width % 4) == 0 && (in0.stride % 16) == 0 && (out0.y_stride % 4) == 0 && (no_cbcr || (out0.cbcr_stride % chroma_align) == 0);
   EncodeParams p;
   std::memset(&p, 0, sizeof p);
   for (int i = 0; i < count; ++i) {
@@ -260,10 +264,10 @@ int bt709hip_encode_batch(bt709hip_context *ctx, int count, const bt709hip_surfa
     if (in.width == 0 || in.height == 0) continue;
     if (in.bgra == nullptr || out.y == nullptr || (out.cbcr == nullptr) != no_cbcr) return BT709HIP_ERR_INVALID_ARG;
     const size_t w = static_cast<size_t>(in.width);
-    if (in.stride < 4 * w || (in.stride & 3) || !aligned(in.bgra, 4) || out.y_stride < w || (!no_cbcr && out.cbcr_stride < w))
+    if (in.stride < 4 * w || (in.stride & 3) || !aligned(in.bgra, 4) || out.y_stride < w || (!no_cbcr && out.cbcr_stride < (planar ? w / 2 : w)))
       return BT709HIP_ERR_STRIDE;
     if (in.stride > 0xffffffffu || out.y_stride > 0xffffffffu || (!no_cbcr && out.cbcr_stride > 0xffffffffu)) return BT709HIP_ERR_STRIDE;
-    fast = fast && aligned(in.bgra, 16) && aligned(out.y, 4) && aligned(out.cbcr, 4);
+    fast = fast && aligned(in.bgra, 16) && aligned(out.y, 4) && aligned(out.cbcr, chroma_align);
     if (i >= 2)
       uniform = uniform && byte_step(ins[0].bgra, in.bgra) == byte_step(ins[0].bgra, ins[1].bgra) * i &&
                 byte_step(outs[0].y, out.y) == byte_step(outs[0].y, outs[1].y) * i &&
@@ -308,6 +312,7 @@ int bt709hip_encode_batch(bt709hip_context *ctx, int count, const bt709hip_surfa
   p.bgra_stride = static_cast<uint32_t>(in0.stride);
   p.y_stride = static_cast<uint32_t>(out0.y_stride);
   p.cbcr_stride = no_cbcr ? 0u : static_cast<uint32_t>(out0.cbcr_stride);
+  p.chroma_layout = planar ? kChromaI420 : kChromaNV12;
   last_launch_shape() = LaunchShape{};
   set_kernel_name(launch_encode(p, count, fast, ctx->xcd_bands != 0, s));
   HIP_TRY(hipGetLastError());

@@ -133,6 +133,10 @@ int bt709hip_context_set_option(bt709hip_context *ctx, int option, int value) {
     case BT709HIP_CTX_OPT_XCD_BANDS:
       ctx->xcd_bands = value != 0;
       return BT709HIP_OK;
+    case BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT:  // a plain property: no device, no table; refused, not clamped
+      if (value != BT709HIP_CHROMA_NV12 && value != BT709HIP_CHROMA_I420) return BT709HIP_ERR_INVALID_ARG;
+      ctx->encode_chroma_layout = value;
+      return BT709HIP_OK;
     case BT709HIP_CTX_OPT_STREAMING_TRIES:
       ctx->streaming_tries = value <= 0 ? 4 : clamp_int(value, 1, 32);
       return BT709HIP_OK;

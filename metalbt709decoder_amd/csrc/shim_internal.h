@@ -39,6 +39,7 @@ struct bt709hip_context {
   int grid_blocks = 0;  // workgroups a general-path launch aims for (all frames together)
   int encode_row_pairs = 0, encode_threads = 0;  // BT709HIP_CTX_OPT_ENCODE_*: 0 = sized per launch
   int xcd_bands = 1;                             // BT709HIP_CTX_OPT_XCD_BANDS: XCD-aware work map of batched encoder launches
+  int encode_chroma_layout = BT709HIP_CHROMA_NV12;  // BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT: the planes bt709hip_encode[_batch] writes
   int streaming_tries = 4;                       // BT709HIP_CTX_OPT_STREAMING_TRIES: placement candidates for buffers of 256 MB and more that the library allocates itself
   std::mutex encoder_mutex;
   EncoderTables encoders[3][3];  // [input gamma][output gamma], built on first use

@@ -443,7 +443,8 @@ class CVPixelBuffer:
         planar: the chroma is two planes (I420, the YUV4MPEG2 layout; _capi.CHROMA_I420) -- cbcr_ptr is the U plane, W/2 x H/2
         bytes at pitch cbcr_stride (default W/2 rounded up to 16), and V the same shape (H/2) * cbcr_stride behind it: W/2 x H
         bytes in all.  decodeBT709 reads such a buffer in place (it sets _capi.OPT_CHROMA_LAYOUT from this flag on every call,
-        whatever setOption was given); the rescales, RGBA16F targets and the encoder do not take one."""
+        whatever setOption was given), and convertIntoCoreVideoBuffer[s] / convertAlphaIntoCoreVideoBuffer[s] write one in place
+        (they set the context's _capi.CTX_OPT_ENCODE_CHROMA_LAYOUT from it); the rescales and RGBA16F targets do not take one."""
         self.ctx, self.width, self.height = ctx, int(width), int(height)
         self.planar = bool(planar)
         self.y_stride = int(y_stride) if y_stride else _align_up(self.width, 16)
@@ -540,6 +541,29 @@ class MetalRenderContext:
         self.handle = None
         self.lib = None
         self.commandQueue = None
+        self._encode_layout = _capi.CHROMA_NV12  # the CTX_OPT_ENCODE_CHROMA_LAYOUT this object last set (the library's default)
+
+    def setEncodeChromaLayout(self, layout):
+        """bt709hip_context_set_option(CTX_OPT_ENCODE_CHROMA_LAYOUT): the planes bt709hip_encode[_batch] writes on this context,
+        _capi.CHROMA_NV12 or _capi.CHROMA_I420.  The convert calls set it from the buffers they are handed; a caller of the C ABI
+        on this context's handle sets it here, so that this object's memory of the value stays true.  Returns True/False."""
+        rc = self.lib.bt709hip_context_set_option(self.handle, _capi.CTX_OPT_ENCODE_CHROMA_LAYOUT, int(layout))
+        if rc != _capi.OK:
+            log.error("setEncodeChromaLayout(%d): %s", layout, _capi.strerror(rc))
+            return False
+        self._encode_layout = int(layout)
+        return True
+
+    def _set_encode_layout(self, pixelBuffers, what):
+        """The encoder's chroma layout from the buffers an encode call was handed: a planar CVPixelBuffer is written in place.  As
+        MetalBT709Decoder._set_layout: the buffer's `planar` flag is authoritative, planar and NV12 buffers in one call are
+        refused before anything is launched, and the setter -- which never touches the device -- is only called on a change."""
+        layouts = {getattr(b, "chroma_layout", _capi.CHROMA_NV12) for b in pixelBuffers}
+        if len(layouts) > 1:
+            log.error("%s: planar and NV12 buffers in one call", what)
+            return False
+        layout = layouts.pop() if layouts else _capi.CHROMA_NV12
+        return self._encode_layout == layout or self.setEncodeChromaLayout(layout)
 
     def setupMetal(self):
         """Idempotent (MetalRenderContext.m:36-74).  Returns False when there is no GPU."""
@@ -686,8 +710,11 @@ class BGRAToBT709Converter:
         """+convertIntoCoreVideoBuffer:cvPixelBuffer:inputGamma:outputGamma: (BGRAToBT709Converter.h:73-76)
         -> cvpbu_ycbcr_subsample: BGRA pixels -> NV12 with linear-light 2x2 chroma averaging, on the GPU.
         The source is a BGRATexture (device memory) instead of a CGImage.  Gammas are MetalBT709Gamma*
-        values Apple / SRGB / Linear.  Returns True/False like the reference."""
+        values Apple / SRGB / Linear.  Returns True/False like the reference.  A planar buffer
+        (createCoreVideoYCbCrBuffer(..., planar=True)) is written as Y, U, V -- the Y4M FRAME payload -- by the same launch."""
         ctx = bgraTexture.ctx
+        if not ctx._set_encode_layout([cvPixelBuffer], "convertIntoCoreVideoBuffer"):
+            return False
         surf, frame = bgraTexture.surface(), cvPixelBuffer.frame()
         stream = commandBuffer.stream if commandBuffer is not None else None
         rc = ctx.lib.bt709hip_encode(ctx.handle, C.byref(surf), C.byref(frame), int(inputGamma), int(outputGamma),
@@ -708,6 +735,8 @@ class BGRAToBT709Converter:
         if n == 0:
             return True
         ctx = bgraTextures[0].ctx
+        if not ctx._set_encode_layout(cvPixelBuffers, "convertIntoCoreVideoBuffers"):
+            return False
         surfs = (Surface * n)(*[t.surface() for t in bgraTextures])
         frames = (Frame * n)(*[b.frame() for b in cvPixelBuffers])
         stream = commandBuffer.stream if commandBuffer is not None else None
@@ -742,6 +771,8 @@ class BGRAToBT709Converter:
         if n == 0:
             return True
         ctx = bgraTextures[0].ctx
+        if not ctx._set_encode_layout(cvPixelBuffers, "convertAlphaIntoCoreVideoBuffers"):
+            return False
         surfs = (Surface * n)(*[t.surface() for t in bgraTextures])
         for s in surfs:
             if s.format != _capi.FORMAT_BGRA8_SRGB:

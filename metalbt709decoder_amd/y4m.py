@@ -12,6 +12,10 @@ An ALPHA clip is the same container (srgb_to_bt709/srgb_to_bt709.m:1120-1183 wri
 are what BGRAToBT709Converter.convertAlphaIntoCoreVideoBuffer leaves in a buffer that HAS a CbCr plane (Y = the luma of the
 grey (A,A,A), every U and V byte 128), and write_pixel_buffer writes them like any other frame.
 
+A frame encoded into a PLANAR buffer -- convertIntoCoreVideoBuffer into createCoreVideoYCbCrBuffer(..., planar=True), which
+sets the encoder's chroma layout (_capi.CTX_OPT_ENCODE_CHROMA_LAYOUT) to I420 -- already lies on the device as the FRAME payload:
+write_pixel_buffer downloads its three planes and needs no GPU hop.  An NV12 buffer still takes the de-interleave pass.
+
 The writer reproduces those bytes exactly; the reader also accepts files without the XYSCSS
 line and with other header tags (as long as the chroma tag is a 4:2:0 one).
 """
@@ -54,7 +58,7 @@ class Y4MWriter:
         self.write_frame(y, cbcr[:, 0::2], cbcr[:, 1::2])
 
     def write_pixel_buffer(self, buf):
-        """A device CVPixelBuffer: chroma is de-interleaved on the GPU, then read back."""
+        """A device CVPixelBuffer: a planar one is read back as it is; an NV12 one has its chroma de-interleaved on the GPU first."""
         y, u, v = pixel_buffer_to_i420(buf)
         self.write_frame(y, u, v)
 

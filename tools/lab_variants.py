@@ -36,6 +36,8 @@ Gates (macro -> what it does; profiles/ file it produced):
   BT709_LAB_SCALED_ONCE_LDS            wave-decodes-once form exchanging through a wave-private LDS tile (same bytes out)      r06_ab_scaled_share.txt
   BT709_LAB_SCALED_NO_FETCH / _NO_DECODE / _NO_ENCODE / _NO_STORE  any-ratio kernel, WRONG OUTPUT: one part deleted each      r06_ab_scaled_parts.txt
   BT709_LAB_I420_PAIRED                planar 1:1 fast kernels: ONE chroma dword per quad, shared by lane pairs over DPP, instead of two 2-byte loads (same bytes out; frames without W % 8 == 0, 4-byte aligned chroma planes and V less than 4 GiB behind U take the general kernel)   r12_planar.txt
+  BT709_LAB_ENC_I420_PAIRED            planar encode, fast kernels: lane pairs exchange the packed chroma word over DPP; the even lane stores ONE U dword, the odd lane ONE V dword, instead of two 2-byte stores a lane (same bytes out for W % 8 == 0 and 4-byte aligned chroma planes ONLY: no shim gate sends the other frames elsewhere -- bench sizes only)   r13_encode_planar.txt
+  BT709_LAB_ENC_I420_WIDE              planar encode, fast colour kernel: a lane owns 8x2 pixels (two quads): four 16-byte loads, two 8-byte luma stores, one U and one V dword a row pair; half the lanes a row (same bytes out for W % 8 == 0, 8-byte aligned luma and 4-byte aligned chroma ONLY -- bench sizes only)   r13_encode_planar.txt
   BT709_LAB_STEP32                     frame_planes, WRONG ADDRESSES: every step of a uniform batch cut to its low 32 bits, zero-extended.  Shows that tests/test_batch_spacing_gpu.py bites: run ONLY -k "far and not descending" against it (frames 2^32 + d apart: the cut step lands on the alias windows inside the test's own slabs); with a NEGATIVE step the cut address leaves the allocation
   BT709_LAB_ROW32                      TileIn::load, decode_nv12_half<wide>'s target row, encode_bgra_nv12's CbCr row, WRONG ADDRESSES: row x pitch cut to its low 32 bits, zero-extended.  Shows that tests/test_row_pitch_gpu.py bites: run ONLY the past-2^32 ids (-k "past and 32": `^` is no character of a -k expression; the cut offset lands on the alias windows inside the test's own slabs) and the past-2^31 ids (-k "past and 31"; must pass: zero-extension is right below 2^32).  There is no sign-extending twin: under past-2^32 it would leave the allocation
   BT709_LAB_HUNT_TRACE                 bt709hip_ring_create prints where its hunt's wall-clock time went (stderr; same ring)   r06_hunt_default.txt
@@ -692,19 +694,19 @@ double *lab_trace() {  // seconds: malloc, free, mem_info, warm-up, probe
      """  uint32_t scaled_rows;  // output rows of a strip (filled by launch_decode_scaled)""",
      """  uint32_t lab_tile_off;  // BT709_LAB_SCALED_ONCE_LDS
   uint32_t scaled_rows;"""),
-    ("bt709_encode.hip",
+    ("bt709_encode_kernels.inc",  # the encoder's kernel text, compiled once per chroma layout: a gate reaches the NV12 and the I420 kernel
      """    uint32_t ytop, ybot, cbcr;
-    quantize_quad(va, vb, ytop, ybot, cbcr);
+    quantize_quad<BT709_ENCODE_LAYOUT>(va, vb, ytop, ybot, cbcr);
     if (q_raw < quads) {""",
      """    uint32_t ytop, ybot, cbcr;
 #if defined(BT709_LAB_ENC_NO_ARITH)  // WRONG OUTPUT: the launch's loads and stores with no table lookups and no arithmetic
     ytop = top.x ^ top.y ^ top.z ^ top.w, ybot = bot.x ^ bot.y ^ bot.z ^ bot.w, cbcr = ytop + ybot;
     (void)va, (void)vb;
 #else
-    quantize_quad(va, vb, ytop, ybot, cbcr);
+    quantize_quad<BT709_ENCODE_LAYOUT>(va, vb, ytop, ybot, cbcr);
 #endif
     if (q_raw < quads) {"""),
-    ("bt709_encode.hip",
+    ("bt709_encode_kernels.inc",
      """    {
       const uint32_t blk[4] = {top.x, top.y, bot.x, bot.y};
       encode_block(t, quarter_n, blk, va);
@@ -744,7 +746,7 @@ double *lab_trace() {  // seconds: malloc, free, mem_info, warm-up, probe
 """),
 ]
 
-MACROS = ["BT709_LAB_I420_PAIRED", "BT709_LAB_NO_ARITH", "BT709_LAB_NO_LOADS", "BT709_LAB_NO_STORES", "BT709_LAB_NO_TABLE", "BT709_NO_FMA_CENTRE",
+MACROS = ["BT709_LAB_ENC_I420_PAIRED", "BT709_LAB_ENC_I420_WIDE", "BT709_LAB_I420_PAIRED", "BT709_LAB_NO_ARITH", "BT709_LAB_NO_LOADS", "BT709_LAB_NO_STORES", "BT709_LAB_NO_TABLE", "BT709_NO_FMA_CENTRE",
           "BT709_INDEX_RTZ", "BT709_UNIFORM_INDEX_TWO_STEP", "BT709_REP_SPLIT_ENCODE", "BT709_LAB_BOUND_SHARED_INDEX",
           "BT709_LAB_BOUND_ONE_ENCODE", "BT709_LAB_HALF_TABLE", "BT709_LAB_F16_NO_ARITH", "BT709_LAB_F16_NO_TABLE",
           "BT709_LAB_F16_CVT_ONLY", "BT709_LAB_F16_NO_CAND_GATHER", "BT709_LAB_F16_NO_T_GATHER", "BT709_LAB_F16_NO_INDEX_SCALE", "BT709_LAB_F16_DMA_STAGING", "BT709_LAB_ENC_NO_ARITH", "BT709_LAB_UNC_NO_ARITH", "BT709_LAB_SCALED_QUARTER_FEWER_TAPS", "BT709_LAB_HALF_ENCODE_B32",
@@ -801,16 +803,13 @@ GATES += [
   uint8_t *o = f.out + static_cast<size_t>(orow) * p.out_stride;
 #endif
 """),
-    ("bt709_encode.hip",
-     """      __builtin_nontemporal_store(
-          cbcr, reinterpret_cast<uint32_t *>(f.cbcr + static_cast<size_t>(rp) * p.cbcr_stride + 4u * q));
+    ("bt709_encode_kernels.inc",
+     """      store_quad_chroma<BT709_ENCODE_LAYOUT>(p, f.cbcr + static_cast<size_t>(rp) * p.cbcr_stride, q, cbcr);
 """,
      """#if defined(BT709_LAB_ROW32)
-      __builtin_nontemporal_store(
-          cbcr, reinterpret_cast<uint32_t *>(f.cbcr + static_cast<size_t>(static_cast<uint32_t>(rp * p.cbcr_stride)) + 4u * q));
+      store_quad_chroma<BT709_ENCODE_LAYOUT>(p, f.cbcr + static_cast<size_t>(static_cast<uint32_t>(rp * p.cbcr_stride)), q, cbcr);
 #else
-      __builtin_nontemporal_store(
-          cbcr, reinterpret_cast<uint32_t *>(f.cbcr + static_cast<size_t>(rp) * p.cbcr_stride + 4u * q));
+      store_quad_chroma<BT709_ENCODE_LAYOUT>(p, f.cbcr + static_cast<size_t>(rp) * p.cbcr_stride, q, cbcr);
 #endif
 """),
 ]
@@ -853,6 +852,119 @@ GATES += [
                     (layout != BT709HIP_CHROMA_I420 || ((p.width % 8) == 0 && info.chroma_align >= 4 && p.v_offset + p.width / 2 <= 0xffffffffull));
 #else
   const bool fast = (p.width % 4) == 0 && info.in_align >= 4 && info.out_align >= 16 && (layout != BT709HIP_CHROMA_I420 || info.chroma_align >= 2);
+#endif
+"""),
+]
+
+GATES += [
+    # round 13: the planar ENCODER's two other chroma-store designs (profiles/LAB.md, "Round 13").  The shipped one packs Cb0 Cb1
+    # in the low half and Cr0 Cr1 in the high half of a quad's chroma word and issues two 2-byte stores a lane.
+    # PAIRED: quad_perm:[1,0,3,2] hands each lane its neighbour's word; one v_perm_b32 builds U0..U3 in the even lane and V0..V3 in
+    # the odd one, and each stores one dword -- as many VMEM instructions as NV12.
+    ("bt709_encode.hip",
+     """    __builtin_nontemporal_store(static_cast<uint16_t>(word), reinterpret_cast<uint16_t *>(row + 2u * q));
+    __builtin_nontemporal_store(static_cast<uint16_t>(word >> 16), reinterpret_cast<uint16_t *>(row + v_plane_offset(p) + 2u * q));
+""",
+     """#if defined(BT709_LAB_ENC_I420_PAIRED)
+    const uint32_t other = static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(word), 0xB1, 0xF, 0xF, false));
+    const bool odd = (q & 1u) != 0u;
+    const uint32_t both = odd ? __builtin_amdgcn_perm(word, other, 0x07060302u) : __builtin_amdgcn_perm(other, word, 0x05040100u);
+    __builtin_nontemporal_store(both, reinterpret_cast<uint32_t *>(row + (odd ? v_plane_offset(p) : 0ull) + 4u * (q >> 1)));
+#else
+    __builtin_nontemporal_store(static_cast<uint16_t>(word), reinterpret_cast<uint16_t *>(row + 2u * q));
+    __builtin_nontemporal_store(static_cast<uint16_t>(word >> 16), reinterpret_cast<uint16_t *>(row + v_plane_offset(p) + 2u * q));
+#endif
+"""),
+    # WIDE: the kernel text is compiled once per layout; this marks the planar pass so that the body below replaces the I420 colour
+    # kernel alone, and the launcher gives it tiles of lane PAIRS of quads.
+    ("bt709_encode.hip",
+     """#define BT709_ENCODE_LAYOUT kChromaI420
+""",
+     """#define BT709_ENCODE_LAYOUT kChromaI420
+#define BT709_LAB_ENC_PLANAR_TEXT 1
+"""),
+    ("bt709_encode_kernels.inc",
+     """BT709_ENCODE_KERNEL(const EncodeParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+""",
+     """BT709_ENCODE_KERNEL(const EncodeParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+#if defined(BT709_LAB_ENC_I420_WIDE) && defined(BT709_LAB_ENC_PLANAR_TEXT)
+  {
+    const BandedWork work = banded_work(p.xcd_bands, p.frames_per_band);
+    const EncodeFrame f = encode_frame(p, work.frame);
+    const uint32_t pairs = p.width >> 3;
+    const uint32_t row_pairs = p.height >> 1;
+    const uint32_t l_raw = work.tile * blockDim.x + threadIdx.x;
+    const uint32_t l = min(l_raw, pairs - 1);
+    const uint32_t rp0 = blockIdx.y * p.row_pairs_per_block;
+    const uint32_t rp_end = min(rp0 + p.row_pairs_per_block, row_pairs);
+    const uint8_t *s0 = f.bgra + static_cast<size_t>(2 * rp0) * p.bgra_stride;
+    u32x4 top[2], bot[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      top[j] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(s0 + 32u * l + 16u * j));
+      bot[j] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(s0 + p.bgra_stride + 32u * l + 16u * j));
+    }
+    const EncodeLds t = stage_encode_tables(lds_raw, p);
+    __syncthreads();
+    const float quarter_n = __fmul_rn(0.25f, p.from_linear_scale);
+    for (uint32_t rp = rp0; rp < rp_end; ++rp) {
+      u32x4 ntop[2] = {top[0], top[1]}, nbot[2] = {bot[0], bot[1]};
+      if (rp + 1 < rp_end) {
+        const uint8_t *s1 = f.bgra + static_cast<size_t>(2 * (rp + 1)) * p.bgra_stride;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          ntop[j] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(s1 + 32u * l + 16u * j));
+          nbot[j] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(s1 + p.bgra_stride + 32u * l + 16u * j));
+        }
+      }
+      uint32_t yt[2], yb[2], cc[2];
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        float va[6], vb[6];
+        const uint32_t blk0[4] = {top[j].x, top[j].y, bot[j].x, bot[j].y};
+        encode_block(t, quarter_n, blk0, va);
+        const uint32_t blk1[4] = {top[j].z, top[j].w, bot[j].z, bot[j].w};
+        encode_block(t, quarter_n, blk1, vb);
+        quantize_quad<kChromaI420>(va, vb, yt[j], yb[j], cc[j]);
+      }
+      if (l_raw < pairs) {
+        uint8_t *y0 = f.y + static_cast<size_t>(2 * rp) * p.y_stride;
+        __builtin_nontemporal_store(u32x2{yt[0], yt[1]}, reinterpret_cast<u32x2 *>(y0 + 8u * l));
+        __builtin_nontemporal_store(u32x2{yb[0], yb[1]}, reinterpret_cast<u32x2 *>(y0 + p.y_stride + 8u * l));
+        uint8_t *row = f.cbcr + static_cast<size_t>(rp) * p.cbcr_stride;
+        __builtin_nontemporal_store(__builtin_amdgcn_perm(cc[1], cc[0], 0x05040100u), reinterpret_cast<uint32_t *>(row + 4u * l));
+        __builtin_nontemporal_store(__builtin_amdgcn_perm(cc[1], cc[0], 0x07060302u), reinterpret_cast<uint32_t *>(row + v_plane_offset(p) + 4u * l));
+      }
+#pragma unroll
+      for (int j = 0; j < 2; ++j) top[j] = ntop[j], bot[j] = nbot[j];
+    }
+    return;
+  }
+#endif
+"""),
+    ("bt709_encode.hip",
+     """    dim3 grid((quads + threads - 1) / threads,
+              (p.height / 2 + p.row_pairs_per_block - 1) / p.row_pairs_per_block, frames);
+""",
+     """#if defined(BT709_LAB_ENC_I420_WIDE)
+    uint32_t units = quads;
+    if (planar && !alpha) {  // a lane owns two quads: the NV12 plan's rules over half as many lanes
+      units = quads / 2;
+      threads = p.block_threads ? p.block_threads : encode_block_threads(p.width / 2);
+      if (p.block_threads == 0 && frames == 1) {
+        const uint32_t tiles = (units + 511) / 512;
+        threads = ((units + tiles - 1) / tiles + 63) / 64 * 64;
+        if (threads < 64) threads = 64;
+      }
+      if (threads > static_cast<uint32_t>(kMaxBlockThreads)) threads = kMaxBlockThreads;
+    }
+    dim3 grid((units + threads - 1) / threads,
+              (p.height / 2 + p.row_pairs_per_block - 1) / p.row_pairs_per_block, frames);
+#else
+    dim3 grid((quads + threads - 1) / threads,
+              (p.height / 2 + p.row_pairs_per_block - 1) / p.row_pairs_per_block, frames);
 #endif
 """),
 ]
