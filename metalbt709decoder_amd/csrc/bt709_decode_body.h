@@ -1,6 +1,6 @@
-// Device code shared by the 1:1 decode kernels of both chroma layouts (bt709_kernels.hip: NV12; bt709_planar.hip: planar I420):
-// the per-quad and per-block arithmetic, the composite-over staging and the body of the fast kernels.  Only the tile front end
-// -- which chroma bytes reach which quad -- differs between the layouts (bt709_tile.h TileIn / TileInI420).
+// Device code of the 1:1 decode kernels (bt709_kernels.hip), shared by both chroma layouts (NV12, planar I420): the per-quad and
+// per-block arithmetic, the composite-over staging and the body of the fast kernels.  Only the tile front end -- which chroma
+// bytes reach which quad -- depends on the layout (bt709_tile.h TileIn<LAYOUT, ...>).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -129,11 +129,11 @@ __device__ __forceinline__ void over_quad(const OverLookup &o, const DecodeParam
 // aligned.  grid = (tiles, H/2, frames); a tile is blockDim * kQuadsPerLane quads.
 // ---------------------------------------------------------------------------
 // LOGIDX: the table is in log-bucket form (one shift more per channel).  (The body once covered 2 or 4 row pairs per workgroup: that
-// served the LINEAR mode's 33 KiB uniform table until its log-bucket form made it 5 KiB, decode_nv12_quads_log below.)
+// served the LINEAR mode's 33 KiB uniform table until its log-bucket form made it 5 KiB, decode_quads_log.)
 // OVER (kOverDestination / kOverColour; alpha decoders): the composite-over form -- the tile's front end also loads what the
 // output held (destination mode), both of its tables are staged behind the loads, and the quads go through over_quad.
-// IN: the tile front end -- TileIn (NV12) or TileInI420 (planar chroma: bt709_planar.hip); both leave cw = {Cb0, Cr0, Cb1, Cr1} per quad.
-template <bool HAS_ALPHA, bool NT, bool QUANT, bool LOGIDX = false, int OVER = kOverOff, template <int, bool, bool> class IN = TileIn>
+// LAYOUT: the chroma layout, handed to the tile front end, which leaves cw = {Cb0, Cr0, Cb1, Cr1} per quad for either.
+template <uint32_t LAYOUT, bool HAS_ALPHA, bool NT, bool QUANT, bool LOGIDX = false, int OVER = kOverOff>
 __device__ __forceinline__ void quads_body(const DecodeParams &p, unsigned char *lds_raw) {
   constexpr int UNROLL = kQuadsPerLane;
   const BandedWork work = banded_work<true>(p.xcd_bands, p.frames_per_band);  // XCD-aware work map: bt709_tile.h
@@ -150,7 +150,7 @@ __device__ __forceinline__ void quads_body(const DecodeParams &p, unsigned char 
 
   // straight-line: loads, table, pin, arithmetic, predicated stores (bt709_tile.h TileIn)
   static_assert(OVER == kOverOff || HAS_ALPHA, "there is nothing to composite without an alpha channel");
-  IN<UNROLL, HAS_ALPHA, OVER == kOverDestination> in;
+  TileIn<LAYOUT, UNROLL, HAS_ALPHA, OVER == kOverDestination> in;
   in.template load<NT>(f, p, rp_raw, row_pairs, q0, quads);
   OverLookup ol = {};
   if constexpr (OVER != kOverOff) {

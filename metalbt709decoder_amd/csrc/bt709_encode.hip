@@ -38,8 +38,8 @@
 // of a wave are consecutive quads of one row pair; grid = (tiles, row-pair groups, frames).  LDS holds
 // the 2 KiB per-byte table and the two-resolution BT709_from_linear table.
 //
-// The same pictures as three planes (I420: Y, U, V -- the YUV4MPEG2 FRAME payload) come from the planar twins below: one body
-// per kernel shape, templated on the layout; only the placement of a quad's four chroma bytes and their stores differ.
+// The same pictures as three planes (I420: Y, U, V -- the YUV4MPEG2 FRAME payload) come from the same kernels: each is a template
+// on the layout; only the placement of a quad's four chroma bytes and their stores differ.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -239,10 +239,103 @@ __device__ __forceinline__ void store_block_chroma(const EncodeParams &p, uint8_
 
 }  // namespace
 
+// The four kernels, each written once over the chroma layout (EncodeParams::chroma_layout, uniform over the launch): LAYOUT
+// reaches quantize_quad, store_quad_chroma, store_block_chroma and second_byte, nothing else.  kChromaI420
+// (BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT = BT709HIP_CHROMA_I420) writes three planes, Y then U then V, the YUV4MPEG2 FRAME
+// payload (Renderer/y4m_writer.h:194-241).  Preconditions of its fast kernels (checked by the host shim): width % 4 == 0; BGRA
+// pointer and pitch 16-byte aligned, Y 4-byte, the U pointer and the chroma pitch 2-byte (the V plane then is, too).  The layout
+// is a parameter of the __global__ kernels themselves and not of a body inlined under them: that layer changed the NV12 kernels'
+// code (profiles/r14_layout_template_isa.txt).
+// grid = (tiles, row-pair groups, frames); a workgroup walks row_pairs_per_block consecutive row
+// pairs of one frame, prefetching the next pair while it encodes the current one.
+template <uint32_t LAYOUT>
+__global__ void __launch_bounds__(kMaxBlockThreads)
+encode_bgra(const EncodeParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+  const BandedWork work = banded_work(p.xcd_bands, p.frames_per_band);  // XCD-aware work map: bt709_tile.h
+  const EncodeFrame f = encode_frame(p, work.frame);
+  const uint32_t quads = p.width >> 2;
+  const uint32_t row_pairs = p.height >> 1;
+  const uint32_t q_raw = work.tile * blockDim.x + threadIdx.x;
+  const uint32_t q = min(q_raw, quads - 1);
+  const uint32_t rp0 = blockIdx.y * p.row_pairs_per_block;
+  const uint32_t rp_end = min(rp0 + p.row_pairs_per_block, row_pairs);
+
+  // row pointers are uniform (SGPR base), the lane adds a 32-bit offset: no 64-bit VALU address arithmetic
+  const uint8_t *s0 = f.bgra + static_cast<size_t>(2 * rp0) * p.bgra_stride;
+  u32x4 top = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(s0 + 16u * q));
+  u32x4 bot = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(s0 + p.bgra_stride + 16u * q));
+
+  const EncodeLds t = stage_encode_tables(lds_raw, p);  // after the first loads are in flight
+  __syncthreads();
+  const float quarter_n = __fmul_rn(0.25f, p.from_linear_scale);
+
+  for (uint32_t rp = rp0; rp < rp_end; ++rp) {
+    // prefetch the next row pair before the arithmetic; nothing on the workgroup's last pair (a
+    // clamped re-read of the own rows cost 8 % extra HBM reads at 9 row pairs per workgroup:
+    // non-temporal loads do not stay in L2)
+    u32x4 ntop = top, nbot = bot;
+    if (rp + 1 < rp_end) {
+      const uint8_t *s1 = f.bgra + static_cast<size_t>(2 * (rp + 1)) * p.bgra_stride;
+      ntop = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(s1 + 16u * q));
+      nbot = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(s1 + p.bgra_stride + 16u * q));
+    }
+
+    float va[6], vb[6];
+    {
+      const uint32_t blk[4] = {top.x, top.y, bot.x, bot.y};
+      encode_block(t, quarter_n, blk, va);
+    }
+    {
+      const uint32_t blk[4] = {top.z, top.w, bot.z, bot.w};
+      encode_block(t, quarter_n, blk, vb);
+    }
+    uint32_t ytop, ybot, cbcr;
+    quantize_quad<LAYOUT>(va, vb, ytop, ybot, cbcr);
+    if (q_raw < quads) {
+      uint8_t *y0 = f.y + static_cast<size_t>(2 * rp) * p.y_stride;
+      __builtin_nontemporal_store(ytop, reinterpret_cast<uint32_t *>(y0 + 4u * q));
+      __builtin_nontemporal_store(ybot, reinterpret_cast<uint32_t *>(y0 + p.y_stride + 4u * q));
+      store_quad_chroma<LAYOUT>(p, f.cbcr + static_cast<size_t>(rp) * p.cbcr_stride, q, cbcr);
+    }
+    top = ntop;
+    bot = nbot;
+  }
+}
+
+// General layout: one lane per 2x2 block, scalar loads/stores, any alignment.
+template <uint32_t LAYOUT>
+__global__ void __launch_bounds__(kBlockThreads)
+encode_bgra_blocks(const EncodeParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+  const EncodeLds t = stage_encode_tables(lds_raw, p);
+  __syncthreads();
+  const EncodeFrame f = encode_frame(p, blockIdx.z);
+  const float quarter_n = __fmul_rn(0.25f, p.from_linear_scale);
+  const uint32_t bw = p.width >> 1;
+  const uint32_t rp = blockIdx.y;
+  for (uint32_t bx = blockIdx.x * blockDim.x + threadIdx.x; bx < bw; bx += gridDim.x * blockDim.x) {
+    const uint32_t *r0 = reinterpret_cast<const uint32_t *>(f.bgra + static_cast<size_t>(2 * rp) * p.bgra_stride);
+    const uint32_t *r1 = reinterpret_cast<const uint32_t *>(f.bgra + static_cast<size_t>(2 * rp + 1) * p.bgra_stride);
+    const uint32_t blk[4] = {r0[2 * bx], r0[2 * bx + 1], r1[2 * bx], r1[2 * bx + 1]};
+    float v[6];
+    encode_block(t, quarter_n, blk, v);
+    uint32_t ytop, ybot, cbcr;
+    quantize_block(v, ytop, ybot, cbcr);
+    uint8_t *y0 = f.y + static_cast<size_t>(2 * rp) * p.y_stride;
+    uint8_t *y1 = y0 + p.y_stride;
+    y0[2 * bx] = static_cast<uint8_t>(ytop);
+    y0[2 * bx + 1] = second_byte<LAYOUT>(ytop);
+    y1[2 * bx] = static_cast<uint8_t>(ybot);
+    y1[2 * bx + 1] = second_byte<LAYOUT>(ybot);
+    store_block_chroma<LAYOUT>(p, f.cbcr + static_cast<size_t>(rp) * p.cbcr_stride, bx, static_cast<uint8_t>(cbcr), static_cast<uint8_t>(cbcr >> 8));
+  }
+}
+
 // ---------------------------------------------------------------- alpha frames (BT709HIP_FORMAT_BGRA8_ALPHA)
 // The reference's alpha clip is the ordinary encode of the grey picture (A,A,A) under (Linear, Linear)
 // (srgb_to_bt709/srgb_to_bt709.m:842-954), which is Y = T[A] per pixel and Cb = Cr = 128 (bt709_alpha_luma.h).  Same tile
-// shape, work map, prefetch and clamps as encode_bgra_nv12; the arithmetic is one byte lookup per pixel.
+// shape, work map, prefetch and clamps as encode_bgra; the arithmetic is one byte lookup per pixel.
 // TABLE, not arithmetic: the float expression costs a conversion, four multiplies, three adds and a converting pack per pixel
 // (9 VALU, 4 of them 4-cycle); the lookup is a shift, a ds_read_u8 and a share of three v_perm/v_lshl_or per word.  The 256
 // bytes are 64 dwords = one per LDS bank: lanes that hit the same dword broadcast, different dwords never conflict.
@@ -263,35 +356,97 @@ __device__ __forceinline__ uint32_t alpha_luma4(const uint32_t *lut, const u32x4
 
 }  // namespace
 
-// NV12: the CbCr plane
-#define BT709_ENCODE_LAYOUT kChromaNV12
-#define BT709_ENCODE_KERNEL encode_bgra_nv12
-#define BT709_ENCODE_KERNEL_BLOCKS encode_bgra_nv12_blocks
-#define BT709_ENCODE_ALPHA_KERNEL encode_alpha_y
-#define BT709_ENCODE_ALPHA_KERNEL_BLOCKS encode_alpha_y_blocks
-#include "bt709_encode_kernels.inc"
-#undef BT709_ENCODE_LAYOUT
-#undef BT709_ENCODE_KERNEL
-#undef BT709_ENCODE_KERNEL_BLOCKS
-#undef BT709_ENCODE_ALPHA_KERNEL
-#undef BT709_ENCODE_ALPHA_KERNEL_BLOCKS
+// grid = (tiles, row-pair groups, frames), as encode_bgra
+template <uint32_t LAYOUT>
+__global__ void __launch_bounds__(kMaxBlockThreads)
+encode_alpha_y(const EncodeParams p) {
+  __shared__ uint32_t lut[64];
+  const BandedWork work = banded_work(p.xcd_bands, p.frames_per_band);
+  const EncodeFrame f = encode_frame(p, work.frame);
+  const uint32_t quads = p.width >> 2;
+  const uint32_t row_pairs = p.height >> 1;
+  const uint32_t q_raw = work.tile * blockDim.x + threadIdx.x;
+  const uint32_t q = min(q_raw, quads - 1);
+  const uint32_t rp0 = blockIdx.y * p.row_pairs_per_block;
+  const uint32_t rp_end = min(rp0 + p.row_pairs_per_block, row_pairs);
+  const bool with_cbcr = p.frames[0].cbcr != nullptr;  // uniform over the launch
 
-// BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT = BT709HIP_CHROMA_I420: the planar twins -- three planes, Y then U then V, the
-// YUV4MPEG2 FRAME payload (Renderer/y4m_writer.h:194-241).  Preconditions of the fast ones (checked by the host shim): width
-// % 4 == 0; BGRA pointer and pitch 16-byte aligned, Y 4-byte, the U pointer and the chroma pitch 2-byte (the V plane then is, too).
-// The alpha twins ("encode_alpha_y<i420>", "encode_alpha_y_blocks<i420>") write 128 to every U and every V byte; they are only
-// launched with chroma planes: an alpha frame without them has nothing to lay out and takes the kernels above.
-#define BT709_ENCODE_LAYOUT kChromaI420
-#define BT709_ENCODE_KERNEL encode_bgra_i420
-#define BT709_ENCODE_KERNEL_BLOCKS encode_bgra_i420_blocks
-#define BT709_ENCODE_ALPHA_KERNEL encode_alpha_y_i420
-#define BT709_ENCODE_ALPHA_KERNEL_BLOCKS encode_alpha_y_blocks_i420
-#include "bt709_encode_kernels.inc"
-#undef BT709_ENCODE_LAYOUT
-#undef BT709_ENCODE_KERNEL
-#undef BT709_ENCODE_KERNEL_BLOCKS
-#undef BT709_ENCODE_ALPHA_KERNEL
-#undef BT709_ENCODE_ALPHA_KERNEL_BLOCKS
+  const uint8_t *s0 = f.bgra + static_cast<size_t>(2 * rp0) * p.bgra_stride;
+  u32x4 top = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(s0 + 16u * q));
+  u32x4 bot = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(s0 + p.bgra_stride + 16u * q));
+
+  stage_alpha_luma(lut, p);  // after the first loads are in flight
+  __syncthreads();
+
+  for (uint32_t rp = rp0; rp < rp_end; ++rp) {
+    u32x4 ntop = top, nbot = bot;
+    if (rp + 1 < rp_end) {  // nothing on the workgroup's last pair, as encode_bgra
+      const uint8_t *s1 = f.bgra + static_cast<size_t>(2 * (rp + 1)) * p.bgra_stride;
+      ntop = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(s1 + 16u * q));
+      nbot = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(s1 + p.bgra_stride + 16u * q));
+    }
+    const uint32_t ytop = alpha_luma4(lut, top), ybot = alpha_luma4(lut, bot);
+    if (q_raw < quads) {
+      uint8_t *y0 = f.y + static_cast<size_t>(2 * rp) * p.y_stride;
+      __builtin_nontemporal_store(ytop, reinterpret_cast<uint32_t *>(y0 + 4u * q));
+      __builtin_nontemporal_store(ybot, reinterpret_cast<uint32_t *>(y0 + p.y_stride + 4u * q));
+      if (with_cbcr) store_quad_chroma<LAYOUT>(p, f.cbcr + static_cast<size_t>(rp) * p.cbcr_stride, q, 0x80808080u);
+    }
+    top = ntop;
+    bot = nbot;
+  }
+}
+
+// The planar instantiations write 128 to every U and every V byte; they are only launched with chroma planes: an alpha frame
+// without them has nothing to lay out and arrives as kChromaNV12.
+// General layout: one lane per 2x2 block, byte loads of the four A's and byte stores, any alignment.
+template <uint32_t LAYOUT>
+__global__ void __launch_bounds__(kBlockThreads)
+encode_alpha_y_blocks(const EncodeParams p) {
+  __shared__ uint32_t lut[64];
+  stage_alpha_luma(lut, p);
+  __syncthreads();
+  const uint8_t *t = reinterpret_cast<const uint8_t *>(lut);
+  const EncodeFrame f = encode_frame(p, blockIdx.z);
+  const bool with_cbcr = p.frames[0].cbcr != nullptr;
+  const uint32_t bw = p.width >> 1;
+  const uint32_t rp = blockIdx.y;
+  for (uint32_t bx = blockIdx.x * blockDim.x + threadIdx.x; bx < bw; bx += gridDim.x * blockDim.x) {
+    const uint8_t *r0 = f.bgra + static_cast<size_t>(2 * rp) * p.bgra_stride + 8u * bx;
+    const uint8_t *r1 = r0 + p.bgra_stride;
+    uint8_t *y0 = f.y + static_cast<size_t>(2 * rp) * p.y_stride + 2u * bx;
+    uint8_t *y1 = y0 + p.y_stride;
+    y0[0] = t[r0[3]];
+    y0[1] = t[r0[7]];
+    y1[0] = t[r1[3]];
+    y1[1] = t[r1[7]];
+    if (with_cbcr) store_block_chroma<LAYOUT>(p, f.cbcr + static_cast<size_t>(rp) * p.cbcr_stride, bx, 128, 128);
+  }
+}
+
+namespace {
+
+// The kernel of a launch that launch_encode has planned and recorded; the names are what bt709hip_last_kernel_name reports.
+template <uint32_t LAYOUT>
+const char *launch_encode_kernel(const EncodeParams &p, const dim3 &grid, const dim3 &block, size_t lds, bool fast, bool alpha, hipStream_t stream) {
+  constexpr bool planar = LAYOUT == kChromaI420;
+  if (fast && alpha) {
+    hipLaunchKernelGGL(encode_alpha_y<LAYOUT>, grid, block, lds, stream, p);
+    return planar ? "encode_alpha_y<i420>" : "encode_alpha_y";
+  }
+  if (fast) {
+    hipLaunchKernelGGL(encode_bgra<LAYOUT>, grid, block, lds, stream, p);
+    return planar ? "encode_bgra_i420" : "encode_bgra_nv12";
+  }
+  if (alpha) {
+    hipLaunchKernelGGL(encode_alpha_y_blocks<LAYOUT>, grid, block, lds, stream, p);
+    return planar ? "encode_alpha_y_blocks<i420>" : "encode_alpha_y_blocks";
+  }
+  hipLaunchKernelGGL(encode_bgra_blocks<LAYOUT>, grid, block, lds, stream, p);
+  return planar ? "encode_bgra_i420_blocks" : "encode_bgra_nv12_blocks";
+}
+
+}  // namespace
 
 const char *launch_encode(const EncodeParams &params, int frames, bool fast, bool xcd_bands, hipStream_t stream) {
   const BandPlan plan = plan_bands(frames, fast && xcd_bands, params.uniform, kXcdBandMinFrames);
@@ -304,9 +459,8 @@ const char *launch_encode(const EncodeParams &params, int frames, bool fast, boo
   EncodeParams p = params;
   if (p.row_pairs_per_block == 0) p.row_pairs_per_block = encode_row_pairs_per_block(p.width, p.height, frames);
   const bool alpha = p.alpha_luma != nullptr;  // BT709HIP_FORMAT_BGRA8_ALPHA: same plan, the alpha kernels (static LDS)
-  // the plan does not depend on the layout, only the kernel does (an alpha frame without chroma planes arrives as kChromaNV12)
-  const bool planar = p.chroma_layout == kChromaI420;
   const size_t lds = alpha ? 0 : 256 * sizeof(EncodeByteEntry) + p.from_linear_bytes;
+  dim3 grid((p.width / 2 + kBlockThreads - 1) / kBlockThreads, p.height / 2, frames), block(kBlockThreads);
   if (fast) {
     const uint32_t quads = p.width / 4;
     uint32_t threads = p.block_threads ? p.block_threads : encode_block_threads(p.width);
@@ -319,46 +473,19 @@ const char *launch_encode(const EncodeParams &params, int frames, bool fast, boo
       if (threads < 64) threads = 64;
     }
     if (threads > static_cast<uint32_t>(kMaxBlockThreads)) threads = kMaxBlockThreads;
-    dim3 grid((quads + threads - 1) / threads,
-              (p.height / 2 + p.row_pairs_per_block - 1) / p.row_pairs_per_block, frames);
+    grid = dim3((quads + threads - 1) / threads, (p.height / 2 + p.row_pairs_per_block - 1) / p.row_pairs_per_block, frames);
+    block = dim3(threads);
     if (plan.banded) grid = band_grid(p, 1, grid);
-    record_launch(grid, dim3(threads), p.xcd_bands);
-    if (alpha && planar) {
-      hipLaunchKernelGGL(encode_alpha_y_i420, grid, dim3(threads), lds, stream, p);
-      return "encode_alpha_y<i420>";
-    }
-    if (alpha) {
-      hipLaunchKernelGGL(encode_alpha_y, grid, dim3(threads), lds, stream, p);
-      return "encode_alpha_y";
-    }
-    if (planar) {
-      hipLaunchKernelGGL(encode_bgra_i420, grid, dim3(threads), lds, stream, p);
-      return "encode_bgra_i420";
-    }
-    hipLaunchKernelGGL(encode_bgra_nv12, grid, dim3(threads), lds, stream, p);
-    return "encode_bgra_nv12";
   }
-  const dim3 grid((p.width / 2 + kBlockThreads - 1) / kBlockThreads, p.height / 2, frames);
-  record_launch(grid, dim3(kBlockThreads), 0);
-  if (alpha && planar) {
-    hipLaunchKernelGGL(encode_alpha_y_blocks_i420, grid, dim3(kBlockThreads), lds, stream, p);
-    return "encode_alpha_y_blocks<i420>";
-  }
-  if (alpha) {
-    hipLaunchKernelGGL(encode_alpha_y_blocks, grid, dim3(kBlockThreads), lds, stream, p);
-    return "encode_alpha_y_blocks";
-  }
-  if (planar) {
-    hipLaunchKernelGGL(encode_bgra_i420_blocks, grid, dim3(kBlockThreads), lds, stream, p);
-    return "encode_bgra_i420_blocks";
-  }
-  hipLaunchKernelGGL(encode_bgra_nv12_blocks, grid, dim3(kBlockThreads), lds, stream, p);
-  return "encode_bgra_nv12_blocks";
+  record_launch(grid, block, fast ? p.xcd_bands : 0);
+  // the plan does not depend on the layout, only the kernel does (an alpha frame without chroma planes arrives as kChromaNV12)
+  if (p.chroma_layout == kChromaI420) return launch_encode_kernel<kChromaI420>(p, grid, block, lds, fast, alpha, stream);
+  return launch_encode_kernel<kChromaNV12>(p, grid, block, lds, fast, alpha, stream);
 }
 
 hipError_t prepare_encode_kernels() {
-  const void *fns[] = {reinterpret_cast<const void *>(&encode_bgra_nv12), reinterpret_cast<const void *>(&encode_bgra_nv12_blocks),
-                       reinterpret_cast<const void *>(&encode_bgra_i420), reinterpret_cast<const void *>(&encode_bgra_i420_blocks)};
+  const void *fns[] = {reinterpret_cast<const void *>(&encode_bgra<kChromaNV12>), reinterpret_cast<const void *>(&encode_bgra_blocks<kChromaNV12>),
+                       reinterpret_cast<const void *>(&encode_bgra<kChromaI420>), reinterpret_cast<const void *>(&encode_bgra_blocks<kChromaI420>)};
   return raise_lds_cap(fns, kRepLdsBytes);
 }
 

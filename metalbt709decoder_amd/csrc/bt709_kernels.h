@@ -107,7 +107,7 @@ struct DecodeParams {
   const void *over_table_lin;
   // BT709HIP_OPT_CHROMA_LAYOUT (the 1:1 kernels of the caller's frames): kChromaI420 = frames[i].cbcr is the U (Cb) plane, W/2 x
   // H/2 bytes at pitch cbcr_stride, and the V (Cr) plane the same shape v_offset = (H/2) * cbcr_stride bytes behind it;
-  // launch_decode then runs the decode_i420_* kernels (bt709_planar.hip).  Every other launcher reads NV12 whatever this holds.
+  // launch_decode then runs the kChromaI420 instantiations of its kernels.  Every other launcher reads NV12 whatever this holds.
   uint32_t chroma_layout;  // kChromaNV12 / kChromaI420
   uint32_t chroma_reserved;
   uint64_t v_offset;
@@ -188,7 +188,7 @@ struct EncodeParams {
   uint32_t uniform;
   // BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT: kChromaI420 = frames[i].cbcr is the U (Cb) plane, W/2 x H/2 bytes at pitch cbcr_stride,
   // and the V (Cr) plane the same shape (H/2) * cbcr_stride bytes (a 64-bit product, formed by the kernels) behind it;
-  // launch_encode then runs the encode_*_i420 kernels.  kChromaNV12 whenever the frames carry no chroma plane (alpha frames).
+  // launch_encode then runs the kChromaI420 instantiations of its kernels.  kChromaNV12 whenever the frames carry no chroma plane (alpha frames).
   // (It sits in what was padding: the kernarg block and every other field's offset are what they were.)
   uint32_t chroma_layout;  // kChromaNV12 / kChromaI420
   int64_t step_bgra, step_y, step_cbcr;

@@ -1,4 +1,4 @@
-// CDNA4 (gfx950) kernels of the BT.709 NV12 -> sRGB BGRA decode path.
+// CDNA4 (gfx950) kernels of the BT.709 NV12 / planar I420 -> sRGB BGRA decode path.
 //
 // What the reference does in its first Metal pass -- BT709ToLinearSRGBKernel & friends
 // (Renderer/AAPLShaders.metal:336-407: read Y(gid) and CbCr(gid/2), 3x3 matrix, video-gamma
@@ -32,11 +32,24 @@
 
 namespace bt709 {
 
-template <bool HAS_ALPHA, bool NT, bool QUANT>
+// Every 1:1 kernel is written once over the chroma layout (LAYOUT = DecodeParams::chroma_layout, uniform over the launch;
+// BT709HIP_OPT_CHROMA_LAYOUT).  kChromaI420 is planar 4:2:0 -- the YUV4MPEG2 C420jpeg payload, Y then U then V
+// (Renderer/y4m_writer.h:194-241; a software decoder's yuv420p): pixel (x, y) takes Y[y][x], U[y/2][x/2], V[y/2][x/2], and the
+// output is byte for byte what the NV12 instantiation writes for the interleaved twin of the planes.  Same traffic as NV12,
+// 1.5 B read + 4 B written per pixel, where "interleave the planes, then decode" moves 6.5 B in two launches.  The arithmetic
+// is one text (bt709_decode_body.h); the layout only decides which chroma bytes reach which pixel: the fast kernels' tile front
+// end (bt709_tile.h TileIn) and the general kernels' chroma fetch below.  It is a parameter of the __global__ kernels and of
+// that front end, never of a body inlined under a kernel that had none: that layer changed the NV12 kernels' code
+// (profiles/r14_layout_template_isa.txt).
+//
+// Fast path.  Preconditions (checked by the host shim): width % 4 == 0; y, cbcr and alpha pointers and strides 4-byte aligned
+// (kChromaI420: the U pointer and the chroma pitch 2-byte aligned; v_offset = (H/2) x pitch then is, too); output pointer and
+// stride 16-byte aligned.
+template <uint32_t LAYOUT, bool HAS_ALPHA, bool NT, bool QUANT>
 __global__ void __launch_bounds__(kMaxBlockThreads)
-decode_nv12_quads(const DecodeParams p) {
+decode_quads(const DecodeParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-  quads_body<HAS_ALPHA, NT, QUANT>(p, lds_raw);
+  quads_body<LAYOUT, HAS_ALPHA, NT, QUANT>(p, lds_raw);
 }
 
 // The plain kernel over a LOG-bucket table (DecodeParams::unit1_shift == 16; transfer_tables.h TransferTable::buckets_log):
@@ -45,20 +58,20 @@ decode_nv12_quads(const DecodeParams p) {
 // 33 KiB table (the same body over 2 / 4 row pairs per workgroup, `decode_nv12_quads_rows`, itself 0.706 -> 0.777 over the plain
 // kernel): 256 / 64 / 32 / 8 / 1 frames per launch 0.788 / 0.763 / 0.767 / 0.721 / 0.472 against 0.778 / 0.706 / 0.708 /
 // 0.648 / 0.451.  The rows kernel is gone.
-template <bool NT>
+template <uint32_t LAYOUT, bool NT>
 __global__ void __launch_bounds__(kMaxBlockThreads)
-decode_nv12_quads_log(const DecodeParams p) {
+decode_quads_log(const DecodeParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-  quads_body<false, NT, false, true>(p, lds_raw);
+  quads_body<LAYOUT, false, NT, false, true>(p, lds_raw);
 }
 
 // The alpha decoder's kernel with the composite-over blend (BT709HIP_OPT_COMPOSITE_OVER): LDS- and VALU-bound where the plain
 // kernel is HBM-bound -- 48 to 72 LDS reads per quad.  Streaming accesses throughout.
-template <int OVER>
+template <uint32_t LAYOUT, int OVER>
 __global__ void __launch_bounds__(kMaxBlockThreads)
-decode_nv12_quads_over(const DecodeParams p) {
+decode_quads_over(const DecodeParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-  quads_body<true, true, true, false, OVER>(p, lds_raw);
+  quads_body<LAYOUT, true, true, true, false, OVER>(p, lds_raw);
 }
 
 // ---------------------------------------------------------------------------
@@ -67,10 +80,13 @@ decode_nv12_quads_over(const DecodeParams p) {
 // first; used for ragged or misaligned frames only.  That correctness is pinned by tests/test_decode_variants.py: all 2^24
 // triples through every instantiation below, and the grid-stride loop, both forms of frame_planes and the over kernels at
 // launch shapes computed from the device.
+// Block bx of row pair rp takes its chroma from bytes 2 bx, 2 bx + 1 of the CbCr row (kChromaNV12), or from byte bx of the U row
+// and of the V row v_offset bytes behind it (kChromaI420; bx < W/2: inside the row's W/2 bytes of either plane).
 // ---------------------------------------------------------------------------
-template <bool HAS_ALPHA, bool QUANT>
+template <uint32_t LAYOUT, bool HAS_ALPHA, bool QUANT>
 __global__ void __launch_bounds__(kBlockThreads)
-decode_nv12_blocks(const DecodeParams p) {
+decode_blocks(const DecodeParams p) {
+  constexpr bool PLANAR = LAYOUT == kChromaI420;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   if (!QUANT) {
     stage_table(lds_raw, p.table_unit, p.table_unit_bytes);
@@ -85,7 +101,8 @@ decode_nv12_blocks(const DecodeParams p) {
   for (uint32_t rp = blockIdx.x; rp < row_pairs; rp += gridDim.x) {
     const uint8_t *y0 = f.y + static_cast<size_t>(2 * rp) * p.y_stride;
     const uint8_t *y1 = y0 + p.y_stride;
-    const uint8_t *cc = f.cbcr + static_cast<size_t>(rp) * p.cbcr_stride;
+    const uint8_t *cc = f.cbcr + static_cast<size_t>(rp) * p.cbcr_stride;  // the CbCr row, or the U row
+    const uint8_t *vv = PLANAR ? cc + p.v_offset : nullptr;
     uint32_t *o0 = reinterpret_cast<uint32_t *>(f.out + static_cast<size_t>(2 * rp) * p.out_stride);
     uint32_t *o1 = reinterpret_cast<uint32_t *>(f.out + static_cast<size_t>(2 * rp + 1) * p.out_stride);
     for (uint32_t bx = threadIdx.x; bx < bw; bx += kBlockThreads) {
@@ -101,7 +118,7 @@ decode_nv12_blocks(const DecodeParams p) {
         a[3] = byte_value(a1[2 * bx + 1]);
       }
       uint32_t out[4];
-      decode_block<HAS_ALPHA, QUANT>(ul, y, byte_value(cc[2 * bx]), byte_value(cc[2 * bx + 1]), a, p.alpha_word, out);
+      decode_block<HAS_ALPHA, QUANT>(ul, y, byte_value(PLANAR ? cc[bx] : cc[2 * bx]), byte_value(PLANAR ? vv[bx] : cc[2 * bx + 1]), a, p.alpha_word, out);
       o0[2 * bx] = out[0];
       o0[2 * bx + 1] = out[1];
       o1[2 * bx] = out[2];
@@ -113,9 +130,10 @@ decode_nv12_blocks(const DecodeParams p) {
 // The alpha decoder's general path with the composite-over blend (BT709HIP_OPT_COMPOSITE_OVER): the same walk, each 2x2 block
 // through over_pixel.  A kernel of its own: the plain kernel's code stays what it was.  Each output word is read (destination
 // mode) and written by one lane alone.
-template <int OVER>
+template <uint32_t LAYOUT, int OVER>
 __global__ void __launch_bounds__(kBlockThreads)
-decode_nv12_blocks_over(const DecodeParams p) {
+decode_blocks_over(const DecodeParams p) {
+  constexpr bool PLANAR = LAYOUT == kChromaI420;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   const OverLookup ol = stage_over_tables(lds_raw, p);
   __syncthreads();
@@ -129,7 +147,8 @@ decode_nv12_blocks_over(const DecodeParams p) {
     const uint8_t *y1 = y0 + p.y_stride;
     const uint8_t *a0 = f.alpha + static_cast<size_t>(2 * rp) * p.alpha_stride;
     const uint8_t *a1 = a0 + p.alpha_stride;
-    const uint8_t *cc = f.cbcr + static_cast<size_t>(rp) * p.cbcr_stride;
+    const uint8_t *cc = f.cbcr + static_cast<size_t>(rp) * p.cbcr_stride;  // the CbCr row, or the U row
+    const uint8_t *vv = PLANAR ? cc + p.v_offset : nullptr;
     uint32_t *o0 = reinterpret_cast<uint32_t *>(f.out + static_cast<size_t>(2 * rp) * p.out_stride);
     uint32_t *o1 = reinterpret_cast<uint32_t *>(f.out + static_cast<size_t>(2 * rp + 1) * p.out_stride);
     for (uint32_t bx = threadIdx.x; bx < bw; bx += kBlockThreads) {
@@ -137,7 +156,7 @@ decode_nv12_blocks_over(const DecodeParams p) {
       const float a[4] = {byte_value(a0[2 * bx]), byte_value(a0[2 * bx + 1]), byte_value(a1[2 * bx]), byte_value(a1[2 * bx + 1])};
       uint32_t bg[4] = {0u, 0u, 0u, 0u};
       if (OVER == kOverDestination) bg[0] = o0[2 * bx], bg[1] = o0[2 * bx + 1], bg[2] = o1[2 * bx], bg[3] = o1[2 * bx + 1];
-      const Chroma c = chroma_terms(byte_value(cc[2 * bx]), byte_value(cc[2 * bx + 1]));
+      const Chroma c = chroma_terms(byte_value(PLANAR ? cc[bx] : cc[2 * bx]), byte_value(PLANAR ? vv[bx] : cc[2 * bx + 1]));
       uint32_t out[4];
 #pragma unroll
       for (int px = 0; px < 4; ++px) {
@@ -278,6 +297,69 @@ LaunchShape &last_launch_shape() {
   return shape;
 }
 
+namespace {
+
+// The kernel of a launch that launch_decode has planned and recorded -- its grid, block and LDS bytes, the band map in `p` --
+// for `variant`, `over`, `quant` (the sRGB mode or an alpha decoder) and `nontemporal`.  The names are what
+// bt709hip_last_kernel_name reports.
+template <uint32_t LAYOUT>
+const char *launch_decode_kernel(const DecodeParams &p, const dim3 &grid, const dim3 &block, size_t lds, int variant, uint32_t over,
+                                 bool has_alpha, bool quant, bool nontemporal, hipStream_t stream) {
+  constexpr bool PLANAR = LAYOUT == kChromaI420;
+  if (variant == kVariantQuads) {
+    if (over == kOverDestination) {
+      hipLaunchKernelGGL((decode_quads_over<LAYOUT, kOverDestination>), grid, block, lds, stream, p);
+      return PLANAR ? "decode_i420_quads<alpha,over>" : "decode_nv12_quads<alpha,over>";
+    }
+    if (over != kOverOff) {
+      hipLaunchKernelGGL((decode_quads_over<LAYOUT, kOverColour>), grid, block, lds, stream, p);
+      return PLANAR ? "decode_i420_quads<alpha,over-colour>" : "decode_nv12_quads<alpha,over-colour>";
+    }
+    if (has_alpha) {
+      hipLaunchKernelGGL((decode_quads<LAYOUT, true, true, true>), grid, block, lds, stream, p);
+      return PLANAR ? "decode_i420_quads<alpha>" : "decode_nv12_quads<alpha>";
+    }
+    if (quant) {
+      if (nontemporal) hipLaunchKernelGGL((decode_quads<LAYOUT, false, true, true>), grid, block, lds, stream, p);
+      else hipLaunchKernelGGL((decode_quads<LAYOUT, false, false, true>), grid, block, lds, stream, p);
+      if (nontemporal) return PLANAR ? "decode_i420_quads<nt,quantiser>" : "decode_nv12_quads<nt,quantiser>";
+      return PLANAR ? "decode_i420_quads<quantiser>" : "decode_nv12_quads<quantiser>";
+    }
+    if (p.unit1_shift != 0) {  // log-bucket table (the LINEAR mode)
+      if (nontemporal) hipLaunchKernelGGL((decode_quads_log<LAYOUT, true>), grid, block, lds, stream, p);
+      else hipLaunchKernelGGL((decode_quads_log<LAYOUT, false>), grid, block, lds, stream, p);
+      if (nontemporal) return PLANAR ? "decode_i420_quads_log<nt>" : "decode_nv12_quads_log<nt>";
+      return PLANAR ? "decode_i420_quads_log" : "decode_nv12_quads_log";
+    }
+    if (nontemporal) {
+      hipLaunchKernelGGL((decode_quads<LAYOUT, false, true, false>), grid, block, lds, stream, p);
+      return PLANAR ? "decode_i420_quads<nt>" : "decode_nv12_quads<nt>";
+    }
+    hipLaunchKernelGGL((decode_quads<LAYOUT, false, false, false>), grid, block, lds, stream, p);
+    return PLANAR ? "decode_i420_quads" : "decode_nv12_quads";
+  }
+  if (over == kOverDestination) {
+    hipLaunchKernelGGL((decode_blocks_over<LAYOUT, kOverDestination>), grid, block, lds, stream, p);
+    return PLANAR ? "decode_i420_blocks<alpha,over>" : "decode_nv12_blocks<alpha,over>";
+  }
+  if (over != kOverOff) {
+    hipLaunchKernelGGL((decode_blocks_over<LAYOUT, kOverColour>), grid, block, lds, stream, p);
+    return PLANAR ? "decode_i420_blocks<alpha,over-colour>" : "decode_nv12_blocks<alpha,over-colour>";
+  }
+  if (has_alpha) {
+    hipLaunchKernelGGL((decode_blocks<LAYOUT, true, true>), grid, block, lds, stream, p);
+    return PLANAR ? "decode_i420_blocks<alpha>" : "decode_nv12_blocks<alpha>";
+  }
+  if (quant) {
+    hipLaunchKernelGGL((decode_blocks<LAYOUT, false, true>), grid, block, lds, stream, p);
+    return PLANAR ? "decode_i420_blocks<quantiser>" : "decode_nv12_blocks<quantiser>";
+  }
+  hipLaunchKernelGGL((decode_blocks<LAYOUT, false, false>), grid, block, lds, stream, p);
+  return PLANAR ? "decode_i420_blocks" : "decode_nv12_blocks";
+}
+
+}  // namespace
+
 const char *launch_decode(const DecodeParams &p_in, int frames, int variant, bool has_alpha, bool quantiser, bool nontemporal,
                           int xcd_bands, uint32_t grid_x, uint32_t block_threads, hipStream_t stream) {
   const bool quant = quantiser || has_alpha;  // the sRGB mode: arithmetic, no table
@@ -291,85 +373,43 @@ const char *launch_decode(const DecodeParams &p_in, int frames, int variant, boo
     return launch_decode(tail, plan.tail, variant, has_alpha, quantiser, nontemporal, 0, grid_x, block_threads, stream);
   }
   DecodeParams p = p_in;
+  // general path: grid_x = workgroups per frame, grid-strided over row pairs
+  dim3 grid(grid_x, static_cast<uint32_t>(frames), 1), block(kBlockThreads, 1, 1);
   if (variant == kVariantQuads) {
     // grid_x = tiles per row pair; narrow frames stack row pairs in blockDim.y
     const uint32_t by = quads_rows_per_block(block_threads, grid_x);
-    dim3 grid(grid_x, (p.height / 2 + by - 1) / by, static_cast<uint32_t>(frames));
-    const dim3 block(block_threads, by, 1);
+    grid = dim3(grid_x, (p.height / 2 + by - 1) / by, static_cast<uint32_t>(frames));
+    block = dim3(block_threads, by, 1);
     if (plan.banded) grid = band_grid(p, static_cast<uint32_t>(xcd_bands), grid);
-    record_launch(grid, block, p.xcd_bands);
-    if (p.chroma_layout == kChromaI420) return launch_decode_i420(p, grid, block, lds, variant, over, has_alpha, quant, nontemporal, stream);
-    if (over == kOverDestination) {
-      hipLaunchKernelGGL((decode_nv12_quads_over<kOverDestination>), grid, block, lds, stream, p);
-      return "decode_nv12_quads<alpha,over>";
-    }
-    if (over != kOverOff) {
-      hipLaunchKernelGGL((decode_nv12_quads_over<kOverColour>), grid, block, lds, stream, p);
-      return "decode_nv12_quads<alpha,over-colour>";
-    }
-    if (has_alpha) {
-      hipLaunchKernelGGL((decode_nv12_quads<true, true, true>), grid, block, lds, stream, p);
-      return "decode_nv12_quads<alpha>";
-    }
-    if (quant) {
-      if (nontemporal) hipLaunchKernelGGL((decode_nv12_quads<false, true, true>), grid, block, lds, stream, p);
-      else hipLaunchKernelGGL((decode_nv12_quads<false, false, true>), grid, block, lds, stream, p);
-      return nontemporal ? "decode_nv12_quads<nt,quantiser>" : "decode_nv12_quads<quantiser>";
-    }
-    if (p_in.unit1_shift != 0) {  // log-bucket table (the LINEAR mode)
-      if (nontemporal) hipLaunchKernelGGL((decode_nv12_quads_log<true>), grid, block, lds, stream, p);
-      else hipLaunchKernelGGL((decode_nv12_quads_log<false>), grid, block, lds, stream, p);
-      return nontemporal ? "decode_nv12_quads_log<nt>" : "decode_nv12_quads_log";
-    }
-    if (nontemporal) {
-      hipLaunchKernelGGL((decode_nv12_quads<false, true, false>), grid, block, lds, stream, p);
-      return "decode_nv12_quads<nt>";
-    }
-    hipLaunchKernelGGL((decode_nv12_quads<false, false, false>), grid, block, lds, stream, p);
-    return "decode_nv12_quads";
   }
-  // grid_x = workgroups per frame, grid-strided over row pairs
-  const dim3 grid(grid_x, static_cast<uint32_t>(frames), 1);
-  const dim3 block(kBlockThreads, 1, 1);
-  record_launch(grid, block, 0);
-  if (p.chroma_layout == kChromaI420) return launch_decode_i420(p, grid, block, lds, variant, over, has_alpha, quant, nontemporal, stream);
-  if (over == kOverDestination) {
-    hipLaunchKernelGGL((decode_nv12_blocks_over<kOverDestination>), grid, block, lds, stream, p);
-    return "decode_nv12_blocks<alpha,over>";
-  }
-  if (over != kOverOff) {
-    hipLaunchKernelGGL((decode_nv12_blocks_over<kOverColour>), grid, block, lds, stream, p);
-    return "decode_nv12_blocks<alpha,over-colour>";
-  }
-  if (has_alpha) {
-    hipLaunchKernelGGL((decode_nv12_blocks<true, true>), grid, block, lds, stream, p);
-    return "decode_nv12_blocks<alpha>";
-  }
-  if (quant) {
-    hipLaunchKernelGGL((decode_nv12_blocks<false, true>), grid, block, lds, stream, p);
-    return "decode_nv12_blocks<quantiser>";
-  }
-  hipLaunchKernelGGL((decode_nv12_blocks<false, false>), grid, block, lds, stream, p);
-  return "decode_nv12_blocks";
+  record_launch(grid, block, variant == kVariantQuads ? p.xcd_bands : 0);
+  // the plan does not depend on the chroma layout, only the kernel does
+  if (p.chroma_layout == kChromaI420) return launch_decode_kernel<kChromaI420>(p, grid, block, lds, variant, over, has_alpha, quant, nontemporal, stream);
+  return launch_decode_kernel<kChromaNV12>(p, grid, block, lds, variant, over, has_alpha, quant, nontemporal, stream);
 }
 
+// the table kernels' dynamic-LDS cap
 hipError_t prepare_kernels() {
   const void *fns[] = {
-      reinterpret_cast<const void *>(&decode_nv12_quads<true, true, true>),
-      reinterpret_cast<const void *>(&decode_nv12_quads<false, true, true>),
-      reinterpret_cast<const void *>(&decode_nv12_quads<false, false, true>),
-      reinterpret_cast<const void *>(&decode_nv12_quads<false, true, false>),
-      reinterpret_cast<const void *>(&decode_nv12_quads<false, false, false>),
-      reinterpret_cast<const void *>(&decode_nv12_quads_log<true>),
-      reinterpret_cast<const void *>(&decode_nv12_quads_log<false>),
+      reinterpret_cast<const void *>(&decode_quads<kChromaNV12, true, true, true>),
+      reinterpret_cast<const void *>(&decode_quads<kChromaNV12, false, true, true>),
+      reinterpret_cast<const void *>(&decode_quads<kChromaNV12, false, false, true>),
+      reinterpret_cast<const void *>(&decode_quads<kChromaNV12, false, true, false>),
+      reinterpret_cast<const void *>(&decode_quads<kChromaNV12, false, false, false>),
+      reinterpret_cast<const void *>(&decode_quads_log<kChromaNV12, true>),
+      reinterpret_cast<const void *>(&decode_quads_log<kChromaNV12, false>),
       reinterpret_cast<const void *>(&unconvert_packed444<true, false>),
       reinterpret_cast<const void *>(&unconvert_packed444<false, false>),
-      reinterpret_cast<const void *>(&decode_nv12_blocks<true, true>),
-      reinterpret_cast<const void *>(&decode_nv12_blocks<false, true>),
-      reinterpret_cast<const void *>(&decode_nv12_blocks<false, false>),
+      reinterpret_cast<const void *>(&decode_blocks<kChromaNV12, true, true>),
+      reinterpret_cast<const void *>(&decode_blocks<kChromaNV12, false, true>),
+      reinterpret_cast<const void *>(&decode_blocks<kChromaNV12, false, false>),
+      reinterpret_cast<const void *>(&decode_quads<kChromaI420, false, true, false>),
+      reinterpret_cast<const void *>(&decode_quads<kChromaI420, false, false, false>),
+      reinterpret_cast<const void *>(&decode_quads_log<kChromaI420, true>),
+      reinterpret_cast<const void *>(&decode_quads_log<kChromaI420, false>),
+      reinterpret_cast<const void *>(&decode_blocks<kChromaI420, false, false>),
   };
-  if (const hipError_t e = raise_lds_cap(fns, kRepLdsBytes)) return e;
-  return prepare_planar_kernels();
+  return raise_lds_cap(fns, kRepLdsBytes);
 }
 
 }  // namespace bt709

@@ -55,13 +55,6 @@ inline void record_launch(const dim3 &grid, const dim3 &block, uint32_t xcd_band
   }
 }
 
-// The planar-chroma twins of the 1:1 kernels (bt709_planar.hip; DecodeParams::chroma_layout == kChromaI420): the kernel of a launch
-// launch_decode has planned and recorded -- its grid, block and LDS bytes, the band map in `p` -- under the NV12 launcher's rules
-// for `variant`, `over`, `quant` (the sRGB mode or an alpha decoder) and `nontemporal`.  Returns the kernel's name.
-const char *launch_decode_i420(const DecodeParams &p, const dim3 &grid, const dim3 &block, size_t lds, int variant, uint32_t over,
-                               bool has_alpha, bool quant, bool nontemporal, hipStream_t stream);
-hipError_t prepare_planar_kernels();
-
 // Raise the dynamic-LDS cap of the kernels (tables can exceed the 64 KiB default; gfx950 has 160 KiB per workgroup).
 template <size_t N>
 inline hipError_t raise_lds_cap(const void *const (&kernels)[N], uint32_t bytes) {

@@ -158,7 +158,7 @@ decode_nv12_half(const DecodeParams p) {
     const uint32_t quads = p.width >> 2;
     const uint32_t q0 = blockIdx.x * (blockDim.x * UNROLL) + threadIdx.x;
     // straight-line: loads, tables, pin, arithmetic, predicated stores (bt709_tile.h TileIn)
-    TileIn<UNROLL, HAS_ALPHA> in;
+    TileIn<kChromaNV12, UNROLL, HAS_ALPHA> in;
     in.template load<NT>(f, p, orow_raw, out_rows, q0, quads);
     const RescaleLookup r = stage_rescale_tables(lds_raw, p, 0, 0);  // after the tile's loads are in flight
     __syncthreads();

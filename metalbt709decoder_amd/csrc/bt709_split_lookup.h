@@ -1,6 +1,6 @@
 // Lookup in the two-resolution bucket table (transfer_tables.h SplitTable) -- the encoder's BT709_from_linear
 // (Renderer/BT709.h:1150-1167) -- written ONCE for the device and for the host, as bt709_quantise.h is: hipcc compiles
-// this text into encode_bgra_nv12 / encode_bgra_nv12_blocks, and tests/native/split_table_sweep.cpp compiles the same
+// this text into encode_bgra / encode_bgra_blocks, and tests/native/split_table_sweep.cpp compiles the same
 // text with g++ to replay it over EVERY float in [0, 1] against the oracle's thresholds.
 //
 //   xs   = x * n_fine                          (n_fine a power of two: exact; the kernel folds the 2x2 average's / 4 in)

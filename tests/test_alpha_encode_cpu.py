@@ -300,7 +300,9 @@ def test_alpha_encode_path_is_sanitizer_and_leak_clean(tmp_path):
 # ------------------------------------------------------------------ generated code
 
 def kernel_body(asm, name):
-    m = re.search(r"^_ZN5bt709%d%sENS_12EncodeParamsE:.*?\n(.*?)^\s*\.end_amdhsa_kernel" % (len(name), name), asm, re.S | re.M)
+    sym = "_ZN5bt709%d%sILj0EEEvNS_12EncodeParamsE" % (len(name), name)  # the template's NV12 instantiation
+    assert len(re.findall(r"^%s:" % sym, asm, re.M)) == 1, sym
+    m = re.search(r"^%s:.*?\n(.*?)^\s*\.end_amdhsa_kernel" % sym, asm, re.S | re.M)
     assert m, "%s is not in the generated code" % name
     return m.group(1)
 

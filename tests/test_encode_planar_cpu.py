@@ -258,9 +258,10 @@ def test_setting_the_option_never_touches_the_device_and_works_in_a_capture(fake
 
 # ------------------------------------------------------------------ the generated code
 
-def kernel(asm, name):
-    """-> (instruction lines of the kernel, its metadata block)."""
-    sym = "_ZN5bt709%d%sENS_12EncodeParamsE" % (len(name), name)
+def kernel(asm, name, layout):
+    """-> (instruction lines of the kernel template's instantiation for `layout` (0: NV12, 1: I420), its metadata block)."""
+    sym = "_ZN5bt709%d%sILj%dEEEvNS_12EncodeParamsE" % (len(name), name, layout)
+    assert len(re.findall(r"^%s:" % sym, asm, re.M)) == 1, sym
     m = re.search(r"^%s:[^\n]*\n(.*?)^\.Lfunc_end" % sym, asm, re.S | re.M)
     assert m, "%s is not in the generated code" % name
     lines = [l.split(";")[0].strip() for l in m.group(1).split("\n")]
@@ -285,8 +286,9 @@ def test_isa_of_the_planar_encoder_kernels():
     fast kernel of the same file."""
     from metalbt709decoder_amd import build
     asm = open(build.emit_asm()).read()
-    names = ["encode_bgra_i420", "encode_bgra_i420_blocks", "encode_alpha_y_i420", "encode_alpha_y_blocks_i420"]
-    code = {n: kernel(asm, n) for n in names}
+    names = {"encode_bgra_i420": "encode_bgra", "encode_bgra_i420_blocks": "encode_bgra_blocks", "encode_alpha_y_i420": "encode_alpha_y",
+             "encode_alpha_y_blocks_i420": "encode_alpha_y_blocks"}  # what the kernel is called: the template it instantiates for I420
+    code = {n: kernel(asm, template, 1) for n, template in names.items()}
     for n, (ins, meta) in code.items():
         assert not [i for i in ins if i.startswith("scratch_")], n
         assert meta_int(meta, "private_segment_fixed_size") == 0, n
@@ -300,7 +302,7 @@ def test_isa_of_the_planar_encoder_kernels():
     stores = [i for i in ins if i.startswith("global_store")]
     assert all(re.search(r"\bnt\b", s) for s in stores), stores
     assert sorted(s.split()[0] for s in stores) == ["global_store_dword", "global_store_dword", "global_store_short", "global_store_short_d16_hi"], stores
-    nv12_ops = [i.split()[0] for i in kernel(asm, "encode_bgra_nv12")[0]]
+    nv12_ops = [i.split()[0] for i in kernel(asm, "encode_bgra", 0)[0]]
     for op in ("global_load_dwordx4", "ds_read_b64", "v_lshlrev_b32_sdwa"):  # the NV12 kernel's front end, staging and arithmetic
         assert ops.count(op) == nv12_ops.count(op) > 0, op
     # the fast alpha kernel: two dwords of luma, 0x8080 to each plane
@@ -317,6 +319,6 @@ def test_isa_of_the_planar_encoder_kernels():
     setreg = [k for k, o in enumerate(ops) if o.startswith("s_setreg")]
     assert len(setreg) == 2 and [k for k, o in enumerate(ops) if o == "v_cvt_pk_u8_f32"] == list(range(setreg[0] + 1, setreg[1]))
     # occupancy: not above the VGPR count at which the NV12 fast kernel's waves per SIMD would drop
-    nv12 = meta_int(kernel(asm, "encode_bgra_nv12")[1], "vgpr_count")
+    nv12 = meta_int(kernel(asm, "encode_bgra", 0)[1], "vgpr_count")
     i420 = meta_int(code["encode_bgra_i420"][1], "vgpr_count")
     assert waves_per_simd(i420) >= waves_per_simd(nv12), (i420, nv12)

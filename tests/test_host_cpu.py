@@ -407,7 +407,7 @@ def test_isa_fused_multiply_adds_are_only_the_proven_one(asm):
     instruction has 1/255f (0x3b808081) as its multiplier, and a multiply fused with the float -> half
     conversion (v_fma_mix*: one rounding instead of two) appears nowhere."""
     n = fused = 0
-    for kernel in ("17decode_nv12_quads", "21decode_nv12_quads_log", "18decode_nv12_blocks", "16decode_nv12_half", "20decode_nv12_half_rep",
+    for kernel in ("12decode_quadsILj0E", "16decode_quads_logILj0E", "13decode_blocksILj0E", "16decode_nv12_half", "20decode_nv12_half_rep",
                    "18decode_nv12_scaled", "19decode_nv12_rgba16fILi0E", "19decode_nv12_rgba16fILi1E", "13render_scaled"):
         # RGBA16F curve variant: the half CANDIDATE (bt709_rgba16f.hip half_texels; not reference arithmetic -- the threshold
         # table settles it, and tests/test_rgba16f.py sweeps it over every float) is slope * x + intercept: one fma with three
@@ -456,7 +456,7 @@ def test_isa_fused_multiply_adds_are_only_the_proven_one(asm):
 
 
 def test_isa_memory_shape(asm):
-    body = _kernel_body(asm, "17decode_nv12_quadsILb0ELb1ELb0EE")
+    body = _kernel_body(asm, "12decode_quadsILj0ELb0ELb1ELb0EE")
     assert body.count("global_store_dwordx4") == 4          # 2 quads x 2 rows, 16 B per lane
     assert len(re.findall(r"global_store_dwordx4 .* nt", body)) == 4  # streaming (non-temporal) stores
     assert len(re.findall(r"global_load_dword\s", body)) == 6  # 2 quads x (2 luma rows + 1 CbCr row)
@@ -469,7 +469,7 @@ def test_isa_memory_shape(asm):
     first, last = body.index("global_store_dwordx4"), body.rindex("global_store_dwordx4")
     assert "vmcnt" not in body[first:last]
     assert "scratch_" not in body                           # no spills
-    meta = re.search(r"\.name:\s+_ZN5bt70917decode_nv12_quadsILb0ELb1ELb0EE.*?\.vgpr_count:\s+(\d+)", asm, flags=re.S)
+    meta = re.search(r"\.name:\s+_ZN5bt70912decode_quadsILj0ELb0ELb1ELb0EE.*?\.vgpr_count:\s+(\d+)", asm, flags=re.S)
     assert meta and int(meta.group(1)) <= 64                # 8 waves per SIMD
 
 
@@ -479,18 +479,19 @@ def test_isa_valu_budget_contract(asm):
     from a plain float add (no v_cvt_u32_f32 in the 1:1 kernel), the decode kernels never touch the
     MODE register (round-to-nearest bucket index), and in the encoder every switch of the rounding
     mode is undone inside the same asm statement."""
-    quads = _kernel_body(asm, "17decode_nv12_quadsILb0ELb1ELb0EE")
+    quads = _kernel_body(asm, "12decode_quadsILj0ELb0ELb1ELb0EE")
     assert len(re.findall(r"\bv_cvt_f32_ubyte[0-3]", quads)) == 24          # 16 luma + 8 chroma bytes per 16 pixels
     assert not re.search(r"\bv_cvt_f32_i32|\bv_cvt_u32_f32|\bv_add_u32_sdwa", quads)
     assert len(re.findall(r"v_add_f32_e64 .* clamp", quads)) == 48            # saturation rides on the adds
     n = 0
-    for kernel in ("17decode_nv12_quads", "18decode_nv12_blocks", "16decode_nv12_half", "20decode_nv12_half_rep",
+    for kernel in ("12decode_quadsILj0E", "13decode_blocksILj0E", "16decode_nv12_half", "20decode_nv12_half_rep",
                    "18decode_nv12_scaled"):
         for body in _kernel_bodies(asm, kernel):
             assert "s_setreg" not in body, kernel
             n += 1
     assert n == 27
-    for kernel in ("16encode_bgra_nv12", "23encode_bgra_nv12_blocks"):
+    for kernel in ("11encode_bgraILj0E", "18encode_bgra_blocksILj0E"):  # the NV12 instantiations
+        assert len(_kernel_bodies(asm, kernel)) == 1, kernel
         for body in _kernel_bodies(asm, kernel):
             to_zero = len(re.findall(r"s_setreg_imm32_b32 hwreg\(HW_REG_MODE, 0, 2\), 3", body))
             to_even = len(re.findall(r"s_setreg_imm32_b32 hwreg\(HW_REG_MODE, 0, 2\), 0", body))
@@ -501,7 +502,7 @@ def test_isa_valu_budget_contract(asm):
                 assert ops <= {"v_add_f32", "v_cvt_pk_u8_f32"}, (kernel, ops)
     rep = _kernel_body(asm, "20decode_nv12_half_repILb1E")
     assert "ds_read_b128" in rep and not re.search(r"\bv_cvt_u32_f32\b.*\n.*v_and_or", rep)
-    enc = _kernel_body(asm, "16encode_bgra_nv12E")
+    enc = _kernel_body(asm, "11encode_bgraILj0EE")
     assert enc.count("v_cvt_pk_u8_f32") == 12 and enc.count("v_lshlrev_b32_sdwa") == 24
 
 
@@ -927,7 +928,7 @@ def test_profile_summary_cuts_a_kernel_trace_to_the_sentinel_bracketed_regions(t
     def add(name, grid, dur, did):
         rows.append((name, grid, t[0], t[0] + dur, did, "X", dur))
         t[0] += dur + 10
-    dq = "void bt709::decode_nv12_quads<false, true, false>(bt709::DecodeParams)"
+    dq = "void bt709::decode_quads<0u, false, true, false>(bt709::DecodeParams)"
     did = 0
     for dur in (374, 375):                      # the hunt's probes: outside any region
         did += 1; add(dq, 1 << 20, dur, did)
@@ -944,7 +945,7 @@ def test_profile_summary_cuts_a_kernel_trace_to_the_sentinel_bracketed_regions(t
     import csv
     with open(trace, "w", newline="") as f:
         csv.writer(f).writerows(rows)
-    timed = pmc_summary.timed_dispatches(str(trace), "decode_nv12")
+    timed = pmc_summary.timed_dispatches(str(trace), pmc_summary.DECODE_NV12)
     assert timed["regions"] == 2 and sorted(timed["by_kernel"][dq]) == [412, 413, 414, 415, 416]  # the region that never closed is dropped
     out = tmp_path / "stats.csv"
     pmc_summary.write_timed_stats(str(out), {"regions": 2, "by_kernel": {dq: [413, 414, 415, 412, 416]}})
@@ -958,7 +959,7 @@ def test_profile_summary_cuts_a_kernel_trace_to_the_sentinel_bracketed_regions(t
     plain = tmp_path / "plain.csv"
     with open(plain, "w", newline="") as f:
         csv.writer(f).writerows([rows[0], rows[1], rows[2]])
-    assert pmc_summary.timed_dispatches(str(plain), "decode_nv12") is None
+    assert pmc_summary.timed_dispatches(str(plain), pmc_summary.DECODE_NV12) is None
     assert pmc_summary.timed_dispatch_ids(list(csv.DictReader(open(plain)))) is None
 
 

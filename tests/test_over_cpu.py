@@ -274,9 +274,10 @@ def test_isa_of_the_over_kernels():
     store and the last, and nothing spills.  Per lane (two quads): 48 lin[s] reads, 48 more for lin[d], 48 encode buckets."""
     from metalbt709decoder_amd import build
     asm = open(build.emit_asm()).read()
-    bodies = dict(re.findall(r"^(_ZN5bt709\d+decode_nv12_(?:quads|blocks)_over\w*):[^\n]*\n(.*?)^\.Lfunc_end", asm, flags=re.S | re.M))
-    assert sorted(bodies) == ["_ZN5bt70922decode_nv12_quads_overILi%dEEEvNS_12DecodeParamsE" % m for m in (1, 2)] + \
-        ["_ZN5bt70923decode_nv12_blocks_overILi%dEEEvNS_12DecodeParamsE" % m for m in (1, 2)]
+    # the kChromaNV12 (= 0: the leading ILj0E) instantiations
+    bodies = dict(re.findall(r"^(_ZN5bt709\d+decode_(?:quads|blocks)_overILj0E\w*):[^\n]*\n(.*?)^\.Lfunc_end", asm, flags=re.S | re.M))
+    assert sorted(bodies) == sorted(["_ZN5bt70917decode_quads_overILj0ELi%dEEEvNS_12DecodeParamsE" % m for m in (1, 2)] +
+                                    ["_ZN5bt70918decode_blocks_overILj0ELi%dEEEvNS_12DecodeParamsE" % m for m in (1, 2)])
     for name, body in bodies.items():
         for line in re.findall(r"^\s*(v_(?:pk_)?(?:fma|fmac|fmamk|fmaak|mad|mac|madmk|madak)_(?:f32|f16|legacy|mix)\w*\s[^\n]*)", body, flags=re.M):
             assert re.match(r"v_fmamk_f32 v\d+, v\d+, 0x3b808081, v\d+|v_fmac_f32_e32 v\d+, 0x3b808081, v\d+", line.strip()), (name, line)
@@ -284,7 +285,7 @@ def test_isa_of_the_over_kernels():
         assert "scratch_" not in body, name
         meta = re.search(r"\.name:\s+%s\b.*?\.private_segment_fixed_size:\s+(\d+)" % re.escape(name), asm, flags=re.S)
         assert meta and int(meta.group(1)) == 0, name
-        destination = "ILi1E" in name
+        destination = "ILj0ELi1E" in name  # OVER == kOverDestination
         if "quads" not in name:
             continue
         assert len(re.findall(r"global_load_dwordx4 [^\n]* nt\b", body)) == (4 if destination else 0), name

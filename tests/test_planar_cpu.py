@@ -327,11 +327,12 @@ def test_ring_and_pool_stay_nv12_whatever_the_option_holds(fake, fake_rig):
 
 # ------------------------------------------------------------------ the generated code
 
-I420_KERNELS = ["_ZN5bt70917decode_i420_quadsILb%dELb%dELb%dEEEvNS_12DecodeParamsE" % t for t in ((1, 1, 1), (0, 1, 1), (0, 0, 1), (0, 1, 0), (0, 0, 0))] + \
-    ["_ZN5bt70921decode_i420_quads_logILb%dEEEvNS_12DecodeParamsE" % nt for nt in (1, 0)] + \
-    ["_ZN5bt70922decode_i420_quads_overILi%dEEEvNS_12DecodeParamsE" % m for m in (1, 2)] + \
-    ["_ZN5bt70918decode_i420_blocksILb%dELb%dEEEvNS_12DecodeParamsE" % t for t in ((1, 1), (0, 1), (0, 0))] + \
-    ["_ZN5bt70923decode_i420_blocks_overILi%dEEEvNS_12DecodeParamsE" % m for m in (1, 2)]
+# the kChromaI420 (= 1: the leading ILj1E) instantiations of the five 1:1 kernel shapes
+I420_KERNELS = ["_ZN5bt70912decode_quadsILj1ELb%dELb%dELb%dEEEvNS_12DecodeParamsE" % t for t in ((1, 1, 1), (0, 1, 1), (0, 0, 1), (0, 1, 0), (0, 0, 0))] + \
+    ["_ZN5bt70916decode_quads_logILj1ELb%dEEEvNS_12DecodeParamsE" % nt for nt in (1, 0)] + \
+    ["_ZN5bt70917decode_quads_overILj1ELi%dEEEvNS_12DecodeParamsE" % m for m in (1, 2)] + \
+    ["_ZN5bt70913decode_blocksILj1ELb%dELb%dEEEvNS_12DecodeParamsE" % t for t in ((1, 1), (0, 1), (0, 0))] + \
+    ["_ZN5bt70918decode_blocks_overILj1ELi%dEEEvNS_12DecodeParamsE" % m for m in (1, 2)]
 
 
 def test_isa_of_the_planar_kernels():
@@ -341,8 +342,8 @@ def test_isa_of_the_planar_kernels():
     store shape (four 16-byte non-temporal stores, no wait on memory between the first and the last) and its register budget."""
     from metalbt709decoder_amd import build
     asm = open(build.emit_asm()).read()
-    bodies = dict(re.findall(r"^(_ZN5bt709\d+decode_i420_\w+):[^\n]*\n(.*?)^\.Lfunc_end", asm, flags=re.S | re.M))
-    assert sorted(bodies) == sorted(I420_KERNELS)
+    bodies = dict(re.findall(r"^(_ZN5bt709\d+decode_(?:quads|blocks)(?:_log|_over)?ILj1E\w+):[^\n]*\n(.*?)^\.Lfunc_end", asm, flags=re.S | re.M))
+    assert len(I420_KERNELS) == 14 and sorted(bodies) == sorted(I420_KERNELS)
     for name, body in bodies.items():
         for line in re.findall(r"^\s*(v_(?:pk_)?(?:fma|fmac|fmamk|fmaak|mad|mac|madmk|madak)_(?:f32|f16|legacy|mix)\w*\s[^\n]*)", body, flags=re.M):
             assert re.match(r"v_fmamk_f32 v\d+, v\d+, 0x3b808081, v\d+|v_fmac_f32_e32 v\d+, 0x3b808081, v\d+", line.strip()), (name, line)
@@ -353,9 +354,9 @@ def test_isa_of_the_planar_kernels():
         if "quads" not in name:
             assert "global_load_ushort" not in body and len(re.findall(r"global_load_ubyte\s", body)) >= 6, name  # byte loads: any alignment
             continue
-        alpha = "quadsILb1E" in name or "_over" in name
-        nt = r"[^\n]* nt\b" if ("_over" in name or re.search(r"quads(?:_log)?ILb[01]ELb1E|quads_logILb1E", name)) else r"[^\n]*"
-        if re.search(r"quadsILb0ELb0E|quads_logILb0E", name):
+        alpha = "quadsILj1ELb1E" in name or "_over" in name
+        nt = r"[^\n]* nt\b" if ("_over" in name or re.search(r"quadsILj1ELb[01]ELb1E|quads_logILj1ELb1E", name)) else r"[^\n]*"
+        if re.search(r"quadsILj1ELb0ELb0E|quads_logILj1ELb0E", name):
             assert " nt" not in body, name  # BT709HIP_OPT_NONTEMPORAL = 0: the default cache policy throughout
         assert len(re.findall(r"global_load_ushort " + nt, body)) == 4, name                     # 2 quads x (U, V)
         assert len(re.findall(r"global_load_dword " + nt, body)) == (8 if alpha else 4), name    # 2 quads x (2 luma rows [+ 2 alpha rows])
@@ -365,7 +366,7 @@ def test_isa_of_the_planar_kernels():
             assert max(tile_loads) < body.index("ds_write"), name  # the tile first, then the tables
         first, last = body.index("global_store_dwordx4"), body.rindex("global_store_dwordx4")
         assert "vmcnt" not in body[first:last], name
-    stream = "_ZN5bt70917decode_i420_quadsILb0ELb1ELb0EEEvNS_12DecodeParamsE"  # no alpha, streaming, table
+    stream = "_ZN5bt70912decode_quadsILj1ELb0ELb1ELb0EEEvNS_12DecodeParamsE"  # no alpha, streaming, table
     assert len(re.findall(r"global_store_dwordx4 [^\n]* nt\b", bodies[stream])) == 4
     assert bodies[stream].count("ds_read_b64") == 48  # 16 pixels x 3 channels
     meta = re.search(r"\.name:\s+%s\b.*?\.vgpr_count:\s+(\d+)" % re.escape(stream), asm, flags=re.S)

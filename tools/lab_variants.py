@@ -39,7 +39,7 @@ Gates (macro -> what it does; profiles/ file it produced):
   BT709_LAB_ENC_I420_PAIRED            planar encode, fast kernels: lane pairs exchange the packed chroma word over DPP; the even lane stores ONE U dword, the odd lane ONE V dword, instead of two 2-byte stores a lane (same bytes out for W % 8 == 0 and 4-byte aligned chroma planes ONLY: no shim gate sends the other frames elsewhere -- bench sizes only)   r13_encode_planar.txt
   BT709_LAB_ENC_I420_WIDE              planar encode, fast colour kernel: a lane owns 8x2 pixels (two quads): four 16-byte loads, two 8-byte luma stores, one U and one V dword a row pair; half the lanes a row (same bytes out for W % 8 == 0, 8-byte aligned luma and 4-byte aligned chroma ONLY -- bench sizes only)   r13_encode_planar.txt
   BT709_LAB_STEP32                     frame_planes, WRONG ADDRESSES: every step of a uniform batch cut to its low 32 bits, zero-extended.  Shows that tests/test_batch_spacing_gpu.py bites: run ONLY -k "far and not descending" against it (frames 2^32 + d apart: the cut step lands on the alias windows inside the test's own slabs); with a NEGATIVE step the cut address leaves the allocation
-  BT709_LAB_ROW32                      TileIn::load, decode_nv12_half<wide>'s target row, encode_bgra_nv12's CbCr row, WRONG ADDRESSES: row x pitch cut to its low 32 bits, zero-extended.  Shows that tests/test_row_pitch_gpu.py bites: run ONLY the past-2^32 ids (-k "past and 32": `^` is no character of a -k expression; the cut offset lands on the alias windows inside the test's own slabs) and the past-2^31 ids (-k "past and 31"; must pass: zero-extension is right below 2^32).  There is no sign-extending twin: under past-2^32 it would leave the allocation
+  BT709_LAB_ROW32                      TileIn::load, decode_nv12_half<wide>'s target row, encode_bgra's chroma row, WRONG ADDRESSES: row x pitch cut to its low 32 bits, zero-extended.  Shows that tests/test_row_pitch_gpu.py bites: run ONLY the past-2^32 ids (-k "past and 32": `^` is no character of a -k expression; the cut offset lands on the alias windows inside the test's own slabs) and the past-2^31 ids (-k "past and 31"; must pass: zero-extension is right below 2^32).  There is no sign-extending twin: under past-2^32 it would leave the allocation
   BT709_LAB_HUNT_TRACE                 bt709hip_ring_create prints where its hunt's wall-clock time went (stderr; same ring)   r06_hunt_default.txt
 """
 import os
@@ -55,14 +55,22 @@ GATES = [
     ("bt709_tile.h",  # TileIn::load: the 1:1 kernel and the WIDE branch of the short-lived 2:1 kernel
      """      ya[j] = load32<NT>(y0 + 4 * q);
       yb[j] = load32<NT>(y1 + 4 * q);
-      cw[j] = load32<NT>(cc + 4 * q);
+      if constexpr (PLANAR) {
 """,
-     """#if defined(BT709_LAB_NO_LOADS)  // with BT709_LAB_NO_ARITH: the launch's stores alone
+     """#if defined(BT709_LAB_NO_LOADS)  // with BT709_LAB_NO_ARITH: the launch's stores alone (NV12 launches only: the planar branch below still loads)
       ya[j] = q * 3u, yb[j] = q * 5u, cw[j] = q * 7u + rp;
+      if constexpr (PLANAR) {
 #else
       ya[j] = load32<NT>(y0 + 4 * q);
       yb[j] = load32<NT>(y1 + 4 * q);
-      cw[j] = load32<NT>(cc + 4 * q);
+      if constexpr (PLANAR) {
+#endif
+"""),
+    ("bt709_tile.h",
+     """        cw[j] = load32<NT>(cc + 4 * q);
+""",
+     """#if !defined(BT709_LAB_NO_LOADS)
+        cw[j] = load32<NT>(cc + 4 * q);
 #endif
 """),
     ("bt709_decode_body.h",
@@ -584,12 +592,12 @@ double *lab_trace() {  // seconds: malloc, free, mem_info, warm-up, probe
 """),
     # round 6: consecutive one-frame launches on ONE stream without the in-order barrier between them (hipExtAnyOrderLaunch; the header says "not supported on GFX9xx")
     ("bt709_kernels.hip",
-     """      hipLaunchKernelGGL((decode_nv12_quads<false, true, false>), grid, block, lds, stream, p);
+     """      hipLaunchKernelGGL((decode_quads<LAYOUT, false, true, false>), grid, block, lds, stream, p);
 """,
      """#if defined(BT709_LAB_ANY_ORDER)
-      hipExtLaunchKernelGGL((decode_nv12_quads<false, true, false>), grid, block, lds, stream, nullptr, nullptr, hipExtAnyOrderLaunch, p);
+      hipExtLaunchKernelGGL((decode_quads<LAYOUT, false, true, false>), grid, block, lds, stream, nullptr, nullptr, hipExtAnyOrderLaunch, p);
 #else
-      hipLaunchKernelGGL((decode_nv12_quads<false, true, false>), grid, block, lds, stream, p);
+      hipLaunchKernelGGL((decode_quads<LAYOUT, false, true, false>), grid, block, lds, stream, p);
 #endif
 """),
     ("bt709_kernels.hip",
@@ -694,19 +702,19 @@ double *lab_trace() {  // seconds: malloc, free, mem_info, warm-up, probe
      """  uint32_t scaled_rows;  // output rows of a strip (filled by launch_decode_scaled)""",
      """  uint32_t lab_tile_off;  // BT709_LAB_SCALED_ONCE_LDS
   uint32_t scaled_rows;"""),
-    ("bt709_encode_kernels.inc",  # the encoder's kernel text, compiled once per chroma layout: a gate reaches the NV12 and the I420 kernel
+    ("bt709_encode.hip",  # the encoder's kernels are templates on the chroma layout: a gate reaches the NV12 and the I420 instantiation
      """    uint32_t ytop, ybot, cbcr;
-    quantize_quad<BT709_ENCODE_LAYOUT>(va, vb, ytop, ybot, cbcr);
+    quantize_quad<LAYOUT>(va, vb, ytop, ybot, cbcr);
     if (q_raw < quads) {""",
      """    uint32_t ytop, ybot, cbcr;
 #if defined(BT709_LAB_ENC_NO_ARITH)  // WRONG OUTPUT: the launch's loads and stores with no table lookups and no arithmetic
     ytop = top.x ^ top.y ^ top.z ^ top.w, ybot = bot.x ^ bot.y ^ bot.z ^ bot.w, cbcr = ytop + ybot;
     (void)va, (void)vb;
 #else
-    quantize_quad<BT709_ENCODE_LAYOUT>(va, vb, ytop, ybot, cbcr);
+    quantize_quad<LAYOUT>(va, vb, ytop, ybot, cbcr);
 #endif
     if (q_raw < quads) {"""),
-    ("bt709_encode_kernels.inc",
+    ("bt709_encode.hip",
      """    {
       const uint32_t blk[4] = {top.x, top.y, bot.x, bot.y};
       encode_block(t, quarter_n, blk, va);
@@ -780,17 +788,20 @@ GATES += [
      """    const uint8_t *y0 = f.y + static_cast<size_t>(2 * rp) * p.y_stride;
     const uint8_t *y1 = y0 + p.y_stride;
     const uint8_t *cc = f.cbcr + static_cast<size_t>(rp) * p.cbcr_stride;
+    const uint8_t *vv = PLANAR ? cc + p.v_offset : nullptr;  // cc is the U row then
     const uint8_t *a0 = HAS_ALPHA ? f.alpha + static_cast<size_t>(2 * rp) * p.alpha_stride : nullptr;
 """,
      """#if defined(BT709_LAB_ROW32)  // WRONG ADDRESSES: the products' low 32 bits, zero-extended
     const uint8_t *y0 = f.y + static_cast<size_t>(static_cast<uint32_t>(2 * rp * p.y_stride));
     const uint8_t *y1 = y0 + p.y_stride;
     const uint8_t *cc = f.cbcr + static_cast<size_t>(static_cast<uint32_t>(rp * p.cbcr_stride));
+    const uint8_t *vv = PLANAR ? cc + p.v_offset : nullptr;
     const uint8_t *a0 = HAS_ALPHA ? f.alpha + static_cast<size_t>(static_cast<uint32_t>(2 * rp * p.alpha_stride)) : nullptr;
 #else
     const uint8_t *y0 = f.y + static_cast<size_t>(2 * rp) * p.y_stride;
     const uint8_t *y1 = y0 + p.y_stride;
     const uint8_t *cc = f.cbcr + static_cast<size_t>(rp) * p.cbcr_stride;
+    const uint8_t *vv = PLANAR ? cc + p.v_offset : nullptr;  // cc is the U row then
     const uint8_t *a0 = HAS_ALPHA ? f.alpha + static_cast<size_t>(2 * rp) * p.alpha_stride : nullptr;
 #endif
 """),
@@ -803,13 +814,13 @@ GATES += [
   uint8_t *o = f.out + static_cast<size_t>(orow) * p.out_stride;
 #endif
 """),
-    ("bt709_encode_kernels.inc",
-     """      store_quad_chroma<BT709_ENCODE_LAYOUT>(p, f.cbcr + static_cast<size_t>(rp) * p.cbcr_stride, q, cbcr);
+    ("bt709_encode.hip",
+     """      store_quad_chroma<LAYOUT>(p, f.cbcr + static_cast<size_t>(rp) * p.cbcr_stride, q, cbcr);
 """,
      """#if defined(BT709_LAB_ROW32)
-      store_quad_chroma<BT709_ENCODE_LAYOUT>(p, f.cbcr + static_cast<size_t>(static_cast<uint32_t>(rp * p.cbcr_stride)), q, cbcr);
+      store_quad_chroma<LAYOUT>(p, f.cbcr + static_cast<size_t>(static_cast<uint32_t>(rp * p.cbcr_stride)), q, cbcr);
 #else
-      store_quad_chroma<BT709_ENCODE_LAYOUT>(p, f.cbcr + static_cast<size_t>(rp) * p.cbcr_stride, q, cbcr);
+      store_quad_chroma<LAYOUT>(p, f.cbcr + static_cast<size_t>(rp) * p.cbcr_stride, q, cbcr);
 #endif
 """),
 ]
@@ -824,24 +835,24 @@ GATES += [
     # while quads is even (the last even lane's dword ends at the row's last byte), the chroma planes are 4-byte aligned and V sits
     # less than 4 GiB behind U: the third gate below makes the shim send every other frame to the general kernel.
     ("bt709_tile.h",
-     """      cu[j] = load16<NT>(uu + 2 * q);
-      cv[j] = load16<NT>(vv + 2 * q);
+     """        cu[j] = load16<NT>(cc + 2 * q);
+        cv[j] = load16<NT>(vv + 2 * q);
 """,
      """#if defined(BT709_LAB_I420_PAIRED)
-      cu[j] = load32<NT>(uu + (4 * (q >> 1) + ((q & 1) ? static_cast<uint32_t>(p.v_offset) : 0u)));
-      cv[j] = (q & 1) ? 0x07030602u : 0x01050004u;  // the perm's selector: bytes 0-3 the partner's dword, 4-7 the lane's own
+        cu[j] = load32<NT>(cc + (4 * (q >> 1) + ((q & 1) ? static_cast<uint32_t>(p.v_offset) : 0u)));
+        cv[j] = (q & 1) ? 0x07030602u : 0x01050004u;  // the perm's selector: bytes 0-3 the partner's dword, 4-7 the lane's own
 #else
-      cu[j] = load16<NT>(uu + 2 * q);
-      cv[j] = load16<NT>(vv + 2 * q);
+        cu[j] = load16<NT>(cc + 2 * q);
+        cv[j] = load16<NT>(vv + 2 * q);
 #endif
 """),
     ("bt709_tile.h",
-     """      cw[j] = __builtin_amdgcn_perm(cv[j], cu[j], 0x05010400u);
+     """      if constexpr (PLANAR) cw[j] = __builtin_amdgcn_perm(cv[j], cu[j], 0x05010400u);
 """,
      """#if defined(BT709_LAB_I420_PAIRED)
-      cw[j] = __builtin_amdgcn_perm(cu[j], static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(cu[j]), 0xB1, 0xF, 0xF, false)), cv[j]);
+      if constexpr (PLANAR) cw[j] = __builtin_amdgcn_perm(cu[j], static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(cu[j]), 0xB1, 0xF, 0xF, false)), cv[j]);
 #else
-      cw[j] = __builtin_amdgcn_perm(cv[j], cu[j], 0x05010400u);
+      if constexpr (PLANAR) cw[j] = __builtin_amdgcn_perm(cv[j], cu[j], 0x05010400u);
 #endif
 """),
     ("shim_decode.cpp",
@@ -875,22 +886,16 @@ GATES += [
     __builtin_nontemporal_store(static_cast<uint16_t>(word >> 16), reinterpret_cast<uint16_t *>(row + v_plane_offset(p) + 2u * q));
 #endif
 """),
-    # WIDE: the kernel text is compiled once per layout; this marks the planar pass so that the body below replaces the I420 colour
-    # kernel alone, and the launcher gives it tiles of lane PAIRS of quads.
+    # WIDE: the kernel is a template on the layout; the body below replaces the I420 instantiation of the colour kernel alone, and the
+    # launcher gives it tiles of lane PAIRS of quads.
     ("bt709_encode.hip",
-     """#define BT709_ENCODE_LAYOUT kChromaI420
-""",
-     """#define BT709_ENCODE_LAYOUT kChromaI420
-#define BT709_LAB_ENC_PLANAR_TEXT 1
-"""),
-    ("bt709_encode_kernels.inc",
-     """BT709_ENCODE_KERNEL(const EncodeParams p) {
+     """encode_bgra(const EncodeParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
 """,
-     """BT709_ENCODE_KERNEL(const EncodeParams p) {
+     """encode_bgra(const EncodeParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-#if defined(BT709_LAB_ENC_I420_WIDE) && defined(BT709_LAB_ENC_PLANAR_TEXT)
-  {
+#if defined(BT709_LAB_ENC_I420_WIDE)
+  if constexpr (LAYOUT == kChromaI420) {
     const BandedWork work = banded_work(p.xcd_bands, p.frames_per_band);
     const EncodeFrame f = encode_frame(p, work.frame);
     const uint32_t pairs = p.width >> 3;
@@ -945,12 +950,11 @@ GATES += [
 #endif
 """),
     ("bt709_encode.hip",
-     """    dim3 grid((quads + threads - 1) / threads,
-              (p.height / 2 + p.row_pairs_per_block - 1) / p.row_pairs_per_block, frames);
+     """    grid = dim3((quads + threads - 1) / threads, (p.height / 2 + p.row_pairs_per_block - 1) / p.row_pairs_per_block, frames);
 """,
      """#if defined(BT709_LAB_ENC_I420_WIDE)
     uint32_t units = quads;
-    if (planar && !alpha) {  // a lane owns two quads: the NV12 plan's rules over half as many lanes
+    if (p.chroma_layout == kChromaI420 && !alpha) {  // a lane owns two quads: the NV12 plan's rules over half as many lanes
       units = quads / 2;
       threads = p.block_threads ? p.block_threads : encode_block_threads(p.width / 2);
       if (p.block_threads == 0 && frames == 1) {
@@ -960,11 +964,9 @@ GATES += [
       }
       if (threads > static_cast<uint32_t>(kMaxBlockThreads)) threads = kMaxBlockThreads;
     }
-    dim3 grid((units + threads - 1) / threads,
-              (p.height / 2 + p.row_pairs_per_block - 1) / p.row_pairs_per_block, frames);
+    grid = dim3((units + threads - 1) / threads, (p.height / 2 + p.row_pairs_per_block - 1) / p.row_pairs_per_block, frames);
 #else
-    dim3 grid((quads + threads - 1) / threads,
-              (p.height / 2 + p.row_pairs_per_block - 1) / p.row_pairs_per_block, frames);
+    grid = dim3((quads + threads - 1) / threads, (p.height / 2 + p.row_pairs_per_block - 1) / p.row_pairs_per_block, frames);
 #endif
 """),
 ]

@@ -14,10 +14,10 @@ for P in "TCC_EA0_WRREQ_STALL_sum TCC_EA0_WRREQ_DRAM_CREDIT_STALL_sum TCC_EA0_WR
   echo "== pass $i: $P"
   grep "^SLAB" "$OUT/p$i.log"
   python3 - "$OUT/p$i" $K <<'PY'
-import csv, glob, sys, collections
+import csv, glob, re, sys, collections
 out, K = sys.argv[1], int(sys.argv[2])
 for f in sorted(glob.glob(out + "/**/pmc_counter_collection.csv", recursive=True)):
-    rows = [r for r in csv.DictReader(open(f)) if "decode_nv12_quads" in r["Kernel_Name"]]
+    rows = [r for r in csv.DictReader(open(f)) if re.search(r"decode_quads\w*<0u", r["Kernel_Name"])]  # the NV12 (layout 0) fast 1:1 kernels
     ids = sorted({int(r["Dispatch_Id"]) for r in rows})
     slab_of = {d: i // K for i, d in enumerate(ids)}
     first = {d for i, d in enumerate(ids) if i % K == 0}

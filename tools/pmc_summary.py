@@ -18,14 +18,16 @@ import collections
 import csv
 import json
 import os
+import re
 import shutil
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DECODE_NV12 = r"decode_nv12|decode_(quads|blocks)\w*<0u"
 
 
 def timed_dispatches(kernel_trace_csv, kernel_filter):
-    """Durations (ns) of the `kernel_filter` dispatches between an opening and a closing sentinel of bench.py, by kernel
+    """Durations (ns) of the dispatches whose kernel name the regular expression `kernel_filter` finds, between an opening and a closing sentinel of bench.py, by kernel
     name; None when the trace holds no sentinel pair.  Sentinels: kernel copy_probe with 512 (opening) or 1024 (closing)
     work-items in the launch."""
     rows = list(csv.DictReader(open(kernel_trace_csv)))
@@ -50,7 +52,7 @@ def timed_dispatches(kernel_trace_csv, kernel_filter):
                 regions += 1 if pending else 0
                 pending = []
             continue
-        if inside and kernel_filter in name:
+        if inside and re.search(kernel_filter, name):
             pending.append((name, int(r["End_Timestamp"]) - int(r["Start_Timestamp"])))
     return {"regions": regions, "by_kernel": dict(by_kernel)} if regions else None
 
@@ -94,7 +96,9 @@ def write_timed_stats(path, timed):
 
 def main():
     src, rnd, tag = sys.argv[1], sys.argv[2], sys.argv[3]
-    kernel_filter = sys.argv[4] if len(sys.argv) > 4 else "decode_nv12"
+    # default: every NV12 decode kernel -- the rescale / RGBA16F kernels carry the layout in their name, the 1:1 kernels as their
+    # first template argument (0u = NV12)
+    kernel_filter = sys.argv[4] if len(sys.argv) > 4 else DECODE_NV12
     out_dir = os.path.join(ROOT, "profiles")
     os.makedirs(out_dir, exist_ok=True)
 
@@ -119,7 +123,7 @@ def main():
         durs = [d for v in timed["by_kernel"].values() for d in v]
     elif os.path.exists(kt):
         for r in csv.DictReader(open(kt)):
-            if kernel_filter in r["Kernel_Name"]:
+            if re.search(kernel_filter, r["Kernel_Name"]):
                 durs.append(int(r["End_Timestamp"]) - int(r["Start_Timestamp"]))
     counters = collections.defaultdict(list)
     meta, scope = {}, {}
@@ -130,7 +134,7 @@ def main():
         rows = list(csv.DictReader(open(f)))
         keep = timed_dispatch_ids(rows)  # None: no sentinels in this pass (another program than bench.py): every dispatch counts
         for r in rows:
-            if kernel_filter in r["Kernel_Name"] and (keep is None or r["Dispatch_Id"] in keep):
+            if re.search(kernel_filter, r["Kernel_Name"]) and (keep is None or r["Dispatch_Id"] in keep):
                 counters[r["Counter_Name"]].append(float(r["Counter_Value"]))
                 meta = {k: r[k] for k in ("Kernel_Name", "Grid_Size", "Workgroup_Size", "LDS_Block_Size",
                                           "VGPR_Count", "SGPR_Count")}
