@@ -64,6 +64,12 @@ class MetalRenderContext {
   void releaseRecording(void *recorded) { bt709hip_graph_destroy(ctx_, recorded); }
   bool waitUntilCompleted(void *s) { return bt709hip_stream_synchronize(ctx_, s) == BT709HIP_OK; }
 
+  // The BGRA pictures bt709hip_encode[_batch] is handed on this context hold STRAIGHT alpha: each texel's B, G, R are multiplied by
+  // its A inside the encode kernel, c' = (c * A + 127) / 255 (include/bt709hip_ext.h BT709HIP_CTX_OPT_ENCODE_PREMULTIPLY; DESIGN.md
+  // 3.9).  false (the default): they are encoded as they are.  This mirror has no encoder; a caller of the C ABI encodes on handle().
+  static constexpr int kEncodePremultiplyOption = BT709HIP_CTX_OPT_ENCODE_PREMULTIPLY;
+  bool setEncodePremultiply(bool on) { return (lastStatus_ = bt709hip_context_set_option(ctx_, kEncodePremultiplyOption, on ? 1 : 0)) == BT709HIP_OK; }
+
  private:
   bt709hip_context *ctx_ = nullptr;
   int lastStatus_ = BT709HIP_OK;
@@ -414,6 +420,17 @@ class MetalBT709Decoder {
     int background = BT709HIP_OVER_OFF;
     if (dec_ != nullptr) (void)bt709hip_decoder_get_option(dec_, BT709HIP_OPT_SCALED_OVER, &background);
     return background;
+  }
+
+  // Straight alpha out of the 1:1 decode of an alpha decoder (include/bt709hip_ext.h BT709HIP_OPT_UNPREMULTIPLY): each
+  // pixel's B, G, R divided by its own alpha byte inside the decode kernel, 0 where A = 0.  BGRA8 targets of decodeBT709 only:
+  // while it is on, RGBA16F targets, the rescales and a decode under setCompositeOver fail with BT709HIP_ERR_UNSUPPORTED
+  // (lastStatus).  Refused (false, lastStatus) on a decoder without an alpha channel.
+  bool setStraightAlpha(bool on) { return setOption(BT709HIP_OPT_UNPREMULTIPLY, on ? 1 : 0); }
+  bool straightAlpha() const {
+    int on = 0;
+    if (dec_ != nullptr) (void)bt709hip_decoder_get_option(dec_, BT709HIP_OPT_UNPREMULTIPLY, &on);
+    return on != 0;
   }
 
   // How decodeBT709 reads the caller's colour buffers (include/bt709hip_ext.h BT709HIP_OPT_CHROMA_LAYOUT): BT709HIP_CHROMA_NV12 (the

@@ -219,11 +219,11 @@ int bt709hip_unconvert(bt709hip_decoder *dec, const void *ycbcr_words, size_t in
  * chroma averaging.  Replaces +convertIntoCoreVideoBuffer:cvPixelBuffer:inputGamma:outputGamma:
  * (BGRAToBT709Converter.h:73-76, .m:532-569) -> cvpbu_ycbcr_subsample (CVPixelBufferUtils.h:241-399) ->
  * BT709_average_pixel_values (BT709.h:1349-1509).  Gammas are bt709hip_gamma values APPLE, SRGB or LINEAR; the app
- * encodes with (SRGB, APPLE), (SRGB, SRGB) or (LINEAR, LINEAR) (.m:919-935).  `in` is read (alpha ignored), the planes
- * `out` points to are written (its tags are ignored).  Even, equal sizes on both sides.
- * in->format BGRA8_ALPHA: the ALPHA frame of `in` -- Y = the reference's luma of the grey (A,A,A), every Cb, Cr = 128.
- * Both gammas must be LINEAR (else BT709HIP_ERR_ALPHA_TRANSFER); out->cbcr may be NULL: only Y is written then (a
- * decoder reads nothing else of an alpha frame).  R, G, B are not read and not premultiplied (.m:805-841).
+ * encodes with (SRGB, APPLE), (SRGB, SRGB) or (LINEAR, LINEAR) (.m:919-935).  `in` is read -- B, G, R as they are (a premultiplied
+ * picture, what the reference's tool feeds) and A ignored, unless BT709HIP_CTX_OPT_ENCODE_PREMULTIPLY (bt709hip_ext.h) says `in` is STRAIGHT
+ * alpha: then B, G, R are multiplied by A first -- the planes `out` points to are written (its tags are ignored).  Even, equal sizes.
+ * in->format BGRA8_ALPHA: the ALPHA frame of `in` -- Y = the reference's luma of the grey (A,A,A), every Cb, Cr = 128.  Both gammas must
+ * be LINEAR (else BT709HIP_ERR_ALPHA_TRANSFER); out->cbcr may be NULL: only Y is written then.  R, G, B are not read (.m:805-841), whatever that option holds.
  * height / 2 <= 65535, i.e. up to 131070 rows (BT709HIP_ERR_UNSUPPORTED past it).  BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT
  * (bt709hip_ext.h) at BT709HIP_CHROMA_I420: `out` is written as three planes -- Y, U at out->cbcr, V behind it: a Y4M FRAME. */
 int bt709hip_encode(bt709hip_context *ctx, const bt709hip_surface *in, const bt709hip_frame *out, int input_gamma,

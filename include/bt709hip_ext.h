@@ -41,15 +41,16 @@ typedef struct {
 int bt709hip_context_info(const bt709hip_context *ctx, bt709hip_device_info *info);
 
 /* Launch-shape knobs of a context (tuning and test hooks; no reference twin).  Values are
- * clamped to their valid range; 0 restores the default.  BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT is no knob and is NOT clamped:
- * see below. */
+ * clamped to their valid range; 0 restores the default.  BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT and
+ * BT709HIP_CTX_OPT_ENCODE_PREMULTIPLY are no knobs and are NOT clamped: see below. */
 typedef enum {
   BT709HIP_CTX_OPT_GRID_MULT = 1,       /* general (unaligned-layout) kernels: workgroups per launch = CUs x 8 x this; default 2 */
   BT709HIP_CTX_OPT_ENCODE_ROW_PAIRS = 2,/* encoder: consecutive row pairs per workgroup; default 0 = sized per launch */
   BT709HIP_CTX_OPT_ENCODE_THREADS = 3,  /* encoder: lanes per workgroup (rounded down to whole waves); default 0 = from the width */
   BT709HIP_CTX_OPT_XCD_BANDS = 4,       /* encoder: 1 (default) XCD-aware work map for launches of a multiple of 8 pictures; 0 plain order */
   BT709HIP_CTX_OPT_STREAMING_TRIES = 5, /* device buffers of 256 MB or more that the library allocates itself (in-flight pool slots, the sharder's lanes) go through bt709hip_malloc_streaming with this many candidates; default 4, 1 = plain allocation */
-  BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT = 6 /* BT709HIP_CHROMA_NV12 (default) or BT709HIP_CHROMA_I420: the planes bt709hip_encode[_batch] writes; any other value is refused */
+  BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT = 6, /* BT709HIP_CHROMA_NV12 (default) or BT709HIP_CHROMA_I420: the planes bt709hip_encode[_batch] writes; any other value is refused */
+  BT709HIP_CTX_OPT_ENCODE_PREMULTIPLY = BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT + 2 /* (eight; seven is no option) 0 (default): BGRA8_SRGB input is encoded as it is; 1: it is straight alpha and is premultiplied first; any other value is refused */
 } bt709hip_context_option;
 int bt709hip_context_set_option(bt709hip_context *ctx, int option, int value);
 /* BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT.  The reference's encoder exists to write YUV4MPEG2 files, whose FRAME is planar: Y, then
@@ -72,6 +73,19 @@ int bt709hip_context_set_option(bt709hip_context *ctx, int option, int value);
  * same names as under NV12.  The call reads the option once, on entry.  Any value but the two: BT709HIP_ERR_INVALID_ARG, the
  * option keeps its value (the other context options clamp; this one does not).  Setting it never touches the device and needs
  * no table: it works while a stream is being captured.  Under BT709HIP_CHROMA_NV12 nothing changes. */
+/* BT709HIP_CTX_OPT_ENCODE_PREMULTIPLY.  Every alpha path here works on PREMULTIPLIED colour, because the reference's does: its
+ * encoder tool renders the picture into a kCGImageAlphaPremultipliedFirst bitmap (Renderer/CGFrameBuffer.m:417,
+ * srgb_to_bt709.m:805-811) and CoreGraphics multiplies on the way.  A PNG, an RGBA tensor and a compositor's export hold STRAIGHT
+ * alpha.  With the option at 1, bt709hip_encode and bt709hip_encode_batch replace B, G, R of each BGRA8_SRGB texel by
+ *   c' = (c * A + 127) / 255        c, A in 0..255, integer division; A = 255: c' = c, A = 0: c' = 0
+ * inside the encode kernel, before anything else reads them (definition: DESIGN.md 3.9; CoreGraphics is a closed box, the rounding
+ * is ours): the planes written are bit for bit those of the plain encode of the premultiplied picture, with no pass over it and
+ * no scratch picture.  Covered: every gamma pair, both chroma layouts, fast and general kernels, pointer-table and evenly spaced
+ * batches; validation, limits and launch plans (bt709hip_last_launch_info) are the plain encoder's.  BGRA8_ALPHA input reads A
+ * alone and is unaffected: same kernels, same names, same bytes.  bt709hip_last_kernel_name: "encode_bgra_nv12<premul>",
+ * "encode_bgra_nv12_blocks<premul>", "encode_bgra_i420<premul>", "encode_bgra_i420_blocks<premul>".  The call reads the option
+ * once, on entry.  Any value but 0 and 1: BT709HIP_ERR_INVALID_ARG, the option keeps its value (it is not clamped).  Setting it
+ * never touches the device and needs no table: it works while a stream is being captured.  At 0 nothing changes. */
 
 /* A stream with a scheduling priority (hipStreamCreateWithPriority): 0 = normal, negative = higher, positive = lower; clamped
  * to the device's range.  (MTLCommandQueue has no twin; a renderer that decodes ahead of what it presents puts the look-ahead
@@ -121,6 +135,7 @@ typedef enum {
   BT709HIP_OPT_COMPOSITE_OVER = 9,   /* alpha decoders: BT709HIP_OVER_OFF (default), BT709HIP_OVER_DESTINATION, or an sRGB colour R<<16 | G<<8 | B; see below */
   BT709HIP_OPT_SCALED_OVER = 10,     /* alpha decoders, the rescale paths: the values of BT709HIP_OPT_COMPOSITE_OVER, held separately; see below */
   BT709HIP_OPT_CHROMA_LAYOUT = 11,   /* BT709HIP_CHROMA_NV12 (default) or BT709HIP_CHROMA_I420: how the 1:1 decode reads the caller's colour frames; see below */
+  BT709HIP_OPT_UNPREMULTIPLY = 12,   /* alpha decoders: 0 (default) the 1:1 decode writes premultiplied colour, as the frames hold it; 1: straight alpha; see below */
   BT709HIP_OPT_SCALE_INTERMEDIATE = 8  /* the intermediate the FUSED rescales filter, a bt709hip_format: BT709HIP_FORMAT_BGRA8_SRGB (default) or BT709HIP_FORMAT_RGBA16F; any other value: BT709HIP_ERR_INVALID_ARG, option unchanged.  See below */
 } bt709hip_decoder_option;
 int bt709hip_decoder_set_option(bt709hip_decoder *dec, int option, int value);
@@ -177,6 +192,24 @@ int bt709hip_decoder_get_option(const bt709hip_decoder *dec, int option, int *va
  * 2:1 variant, the half-kernel options ignored) and equals bt709hip_decode_scaled at exactly half.  Validation, limits and
  * bt709hip_last_scaled_launch_info are the plain rescale's.  bt709hip_last_kernel_name: "decode_nv12_scaled<alpha,over>" /
  * "decode_nv12_scaled<alpha,over-colour>", "decode_nv12_scaled_f16<alpha,over>" / "decode_nv12_scaled_f16<alpha,over-colour>". */
+/* BT709HIP_OPT_UNPREMULTIPLY (decoders created with has_alpha != 0).  The colour frame of an alpha clip holds premultiplied
+ * colour, and that is what the decode writes; the reference divides it out again on the CPU where it needs straight alpha
+ * (+[BGRAToBT709Converter unpremultiply:], Renderer/BGRAToBT709Converter.h:129-133 -- a vImage call, a closed box: the rounding
+ * is ours).  With the option at 1, the 1:1 decode into BGRA8_SRGB -- bt709hip_decode, bt709hip_decode_batch and everything that
+ * launches through them: ring, ring set, pool, shard, the coalescing submit; both chroma layouts, fast and general kernels --
+ * writes, for each pixel, the word it writes at 0 with B, G, R replaced by
+ *   c = A == 0 ? 0 : min(255, (255 * c' + A / 2) / A)        c', A in 0..255, integer division
+ * A being that word's own alpha byte, which stays (definition: DESIGN.md 3.9).  A = 255: c = c'; A = 0: the word 0; c' > A -- no
+ * premultiplied value, but a Y, Cb, Cr triple can decode to it -- gives 255.  No round trip with
+ * BT709HIP_CTX_OPT_ENCODE_PREMULTIPLY is promised for small A.  The division happens in the decode kernel's registers: no pass
+ * over the surface, no table.  Any value but 0 and 1: BT709HIP_ERR_INVALID_ARG; on a decoder without an alpha channel:
+ * BT709HIP_ERR_UNSUPPORTED; either way the option keeps its value.  Setting it never touches the device (it works inside a graph
+ * capture); frames a coalescing decoder has queued go out first, under the value they were queued with, and frames of two
+ * values never share a launch.  Refused with BT709HIP_ERR_UNSUPPORTED after the usual validation, writing nothing, while the
+ * option is 1: RGBA16F targets; bt709hip_decode_half[_batch] and bt709hip_decode_scaled[_batch] (a filter wants premultiplied
+ * colour); any 1:1 decode while BT709HIP_OPT_COMPOSITE_OVER is not BT709HIP_OVER_OFF (a blend needs the premultiplied source).
+ * bt709hip_last_kernel_name: "decode_nv12_quads<alpha,straight>", "decode_nv12_blocks<alpha,straight>",
+ * "decode_i420_quads<alpha,straight>", "decode_i420_blocks<alpha,straight>".  At 0 nothing changes. */
 #define BT709HIP_OVER_OFF (-1)
 #define BT709HIP_OVER_DESTINATION (-2)
 /* BT709HIP_OPT_CHROMA_LAYOUT.  The reference's on-disk format is PLANAR 4:2:0 -- a YUV4MPEG2 C420jpeg FRAME is Y, then U, then V

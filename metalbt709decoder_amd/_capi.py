@@ -47,12 +47,14 @@ OVER_DESTINATION = -2
 OPT_CHROMA_LAYOUT = 11  # how the 1:1 decode reads the caller's colour frames: CHROMA_NV12 (default) or CHROMA_I420 (planar: U, then V)
 CHROMA_NV12 = 0
 CHROMA_I420 = 1
+OPT_UNPREMULTIPLY = 12  # alpha decoders: 0 (default) the 1:1 decode writes premultiplied colour; 1: straight alpha
 CTX_OPT_GRID_MULT = 1
 CTX_OPT_ENCODE_ROW_PAIRS = 2
 CTX_OPT_ENCODE_THREADS = 3
 CTX_OPT_XCD_BANDS = 4
 CTX_OPT_STREAMING_TRIES = 5
 CTX_OPT_ENCODE_CHROMA_LAYOUT = 6  # the planes bt709hip_encode[_batch] writes: CHROMA_NV12 (default) or CHROMA_I420; any other value is refused
+CTX_OPT_ENCODE_PREMULTIPLY = 8  # 0 (default): BGRA8_SRGB input is encoded as it is; 1: it is straight alpha, premultiplied in the encode kernel; any other value is refused
 
 
 class RingPlacement(C.Structure):  # bt709hip_ring_placement

@@ -9,9 +9,18 @@
 
 #include "bt709_device.h"
 #include "bt709_over.h"
+#include "bt709_unpremultiply.h"
 
 namespace bt709 {
 namespace {
+
+// BT709HIP_OPT_UNPREMULTIPLY: the pixel an alpha decoder would store, its R, G, B divided by its own alpha byte
+// (bt709_unpremultiply.h: per pixel one reciprocal; per channel a conversion, the division's two fmas and the v_cvt_pk_u8_f32
+// that rounds, saturates and drops the byte into the word -- in registers, no table, no LDS).
+__device__ __forceinline__ uint32_t straight_pixel(uint32_t R, uint32_t G, uint32_t B, uint32_t a) {
+  return unpremultiply_pixel(R, G, B, a, [](float v) { return __builtin_amdgcn_rcpf(v); },
+                             [](float v, uint32_t lane, uint32_t word) { return __builtin_amdgcn_cvt_pk_u8_f32(v, lane, word); });
+}
 
 // One 4x2 quad: 8 pixels x (R, G, B) = 24 lookups.  Pixel p = 0..3 top row, 4..7 bottom row.
 // QUANT: the decoder's mode is sRGB, whose composite is the plain quantiser ("no curve at all", BT709.h:977-983):
@@ -55,14 +64,36 @@ __device__ __forceinline__ void decode_quad(const UnitLookup &u, uint32_t ya, ui
   bot.w = pack_bgra(byte[21], byte[22], byte[23], al[7]);
 }
 
+// decode_quad of an alpha decoder with every pixel through straight_pixel (BT709HIP_OPT_UNPREMULTIPLY)
+__device__ __forceinline__ void straight_quad(uint32_t ya, uint32_t yb, uint32_t cw, uint32_t aa, uint32_t ab, u32x4 &top, u32x4 &bot) {
+  const Chroma c0 = chroma_terms(byte_of(cw, 0), byte_of(cw, 1));
+  const Chroma c1 = chroma_terms(byte_of(cw, 2), byte_of(cw, 3));
+  uint32_t w[8];
+#pragma unroll
+  for (int px = 0; px < 8; ++px) {
+    float x[3];
+    pixel_rgb(byte_of(px < 4 ? ya : yb, px & 3), (px & 2) ? c1 : c0, x[0], x[1], x[2]);
+    w[px] = straight_pixel(quantise_byte(x[0]), quantise_byte(x[1]), quantise_byte(x[2]), quantise_byte(alpha_value(byte_of(px < 4 ? aa : ab, px & 3))));
+  }
+  top.x = w[0], top.y = w[1], top.z = w[2], top.w = w[3];
+  bot.x = w[4], bot.y = w[5], bot.z = w[6], bot.w = w[7];
+}
+
 // One 2x2 block (general path): 4 pixels x (R, G, B); y = {tl, tr, bl, br}
-template <bool HAS_ALPHA, bool QUANT>
+template <bool HAS_ALPHA, bool QUANT, bool STRAIGHT = false>
 __device__ __forceinline__ void decode_block(const UnitLookup &u, const float y[4], float cb, float cr, const float a[4],
                                              uint32_t alpha_word, uint32_t out[4]) {
   const Chroma c = chroma_terms(cb, cr);
   float x[12];
 #pragma unroll
   for (int px = 0; px < 4; ++px) pixel_rgb(y[px], c, x[3 * px], x[3 * px + 1], x[3 * px + 2]);
+  static_assert((HAS_ALPHA && QUANT) || !STRAIGHT, "there is nothing to divide by without an alpha channel");
+  if constexpr (STRAIGHT) {
+#pragma unroll
+    for (int px = 0; px < 4; ++px)
+      out[px] = straight_pixel(quantise_byte(x[3 * px]), quantise_byte(x[3 * px + 1]), quantise_byte(x[3 * px + 2]), quantise_byte(alpha_value(a[px])));
+    return;
+  }
   if (QUANT) {  // sRGB mode: the plain quantiser for every channel (see decode_quad)
 #pragma unroll
     for (int px = 0; px < 4; ++px)
@@ -133,7 +164,8 @@ __device__ __forceinline__ void over_quad(const OverLookup &o, const DecodeParam
 // OVER (kOverDestination / kOverColour; alpha decoders): the composite-over form -- the tile's front end also loads what the
 // output held (destination mode), both of its tables are staged behind the loads, and the quads go through over_quad.
 // LAYOUT: the chroma layout, handed to the tile front end, which leaves cw = {Cb0, Cr0, Cb1, Cr1} per quad for either.
-template <uint32_t LAYOUT, bool HAS_ALPHA, bool NT, bool QUANT, bool LOGIDX = false, int OVER = kOverOff>
+// STRAIGHT (BT709HIP_OPT_UNPREMULTIPLY; alpha decoders, never with OVER): the quads' pixels through straight_pixel.
+template <uint32_t LAYOUT, bool HAS_ALPHA, bool NT, bool QUANT, bool LOGIDX = false, int OVER = kOverOff, bool STRAIGHT = false>
 __device__ __forceinline__ void quads_body(const DecodeParams &p, unsigned char *lds_raw) {
   constexpr int UNROLL = kQuadsPerLane;
   const BandedWork work = banded_work<true>(p.xcd_bands, p.frames_per_band);  // XCD-aware work map: bt709_tile.h
@@ -150,6 +182,8 @@ __device__ __forceinline__ void quads_body(const DecodeParams &p, unsigned char 
 
   // straight-line: loads, table, pin, arithmetic, predicated stores (bt709_tile.h TileIn)
   static_assert(OVER == kOverOff || HAS_ALPHA, "there is nothing to composite without an alpha channel");
+  static_assert(OVER == kOverOff || !STRAIGHT, "a blend needs the premultiplied source");
+  static_assert(HAS_ALPHA || !STRAIGHT, "there is nothing to divide by without an alpha channel");
   TileIn<LAYOUT, UNROLL, HAS_ALPHA, OVER == kOverDestination> in;
   in.template load<NT>(f, p, rp_raw, row_pairs, q0, quads);
   OverLookup ol = {};
@@ -172,6 +206,19 @@ __device__ __forceinline__ void quads_body(const DecodeParams &p, unsigned char 
       const uint32_t q = q0 + u * blockDim.x;
       u32x4 top, bot;
       over_quad<OVER>(ol, p, in.ya[u], in.yb[u], in.cw[u], in.aa[u], in.ab[u], in.da[OVER == kOverDestination ? u : 0], in.db[OVER == kOverDestination ? u : 0], top, bot);
+      if (q < quads && rp_raw < row_pairs) {
+        store16<NT>(o0 + 16 * q, top);
+        store16<NT>(o1 + 16 * q, bot);
+      }
+    }
+    return;
+  }
+  if constexpr (STRAIGHT) {  // the same walk, the quads' pixels through the division
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) {
+      const uint32_t q = q0 + u * blockDim.x;
+      u32x4 top, bot;
+      straight_quad(in.ya[u], in.yb[u], in.cw[u], in.aa[u], in.ab[u], top, bot);
       if (q < quads && rp_raw < row_pairs) {
         store16<NT>(o0 + 16 * q, top);
         store16<NT>(o1 + 16 * q, bot);

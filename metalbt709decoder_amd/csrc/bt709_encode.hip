@@ -46,6 +46,7 @@
 
 #include "bt709_constants.h"
 #include "bt709_launch.h"
+#include "bt709_premultiply.h"
 #include "bt709_split_lookup.h"
 #include "bt709_stage.h"
 #include "bt709_tile.h"
@@ -237,6 +238,18 @@ __device__ __forceinline__ void store_block_chroma(const EncodeParams &p, uint8_
   }
 }
 
+// The BGRA word a kernel of `FORM` encodes for a loaded one: itself, or -- the premultiplying instantiations -- its B, G, R times A
+template <uint32_t FORM>
+__device__ __forceinline__ uint32_t texel(uint32_t word) {
+  if constexpr (form_straight(FORM)) return premultiply_word(word);
+  return word;
+}
+// the four texels of a quad's row premultiplied in place (called from the premultiplying instantiations alone: in the plain ones
+// even a call that does nothing moved the fast kernel's code)
+__device__ __forceinline__ void premultiply_row(u32x4 &row) {
+  row.x = premultiply_word(row.x), row.y = premultiply_word(row.y), row.z = premultiply_word(row.z), row.w = premultiply_word(row.w);
+}
+
 }  // namespace
 
 // The four kernels, each written once over the chroma layout (EncodeParams::chroma_layout, uniform over the launch): LAYOUT
@@ -246,12 +259,19 @@ __device__ __forceinline__ void store_block_chroma(const EncodeParams &p, uint8_
 // pointer and pitch 16-byte aligned, Y 4-byte, the U pointer and the chroma pitch 2-byte (the V plane then is, too).  The layout
 // is a parameter of the __global__ kernels themselves and not of a body inlined under them: that layer changed the NV12 kernels'
 // code (profiles/r14_layout_template_isa.txt).
+// FORM, the template argument of the two colour kernels, is the layout plus kFormStraight for their premultiplying instantiations
+// (BT709HIP_CTX_OPT_ENCODE_PREMULTIPLY): a straight-alpha picture comes in, and each texel's B, G, R are replaced
+// by (c * A + 127) / 255 -- bt709_premultiply.h, integer VALU on the loaded word, the A byte is already in it -- before anything
+// else looks at them, so the planes are those of the plain encode of the premultiplied picture.  One argument and not a second:
+// the instantiations that existed keep their symbols (the ISA tests and profiles name them) and their code
+// (profiles/r15_straight_alpha_isa.txt).
 // grid = (tiles, row-pair groups, frames); a workgroup walks row_pairs_per_block consecutive row
 // pairs of one frame, prefetching the next pair while it encodes the current one.
-template <uint32_t LAYOUT>
+template <uint32_t FORM>
 __global__ void __launch_bounds__(kMaxBlockThreads)
 encode_bgra(const EncodeParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+  constexpr uint32_t LAYOUT = form_layout(FORM);
   const BandedWork work = banded_work(p.xcd_bands, p.frames_per_band);  // XCD-aware work map: bt709_tile.h
   const EncodeFrame f = encode_frame(p, work.frame);
   const uint32_t quads = p.width >> 2;
@@ -281,6 +301,10 @@ encode_bgra(const EncodeParams p) {
       nbot = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(s1 + p.bgra_stride + 16u * q));
     }
 
+    if constexpr (form_straight(FORM)) {  // behind the prefetch, ahead of everything that reads a texel
+      premultiply_row(top);
+      premultiply_row(bot);
+    }
     float va[6], vb[6];
     {
       const uint32_t blk[4] = {top.x, top.y, bot.x, bot.y};
@@ -304,10 +328,11 @@ encode_bgra(const EncodeParams p) {
 }
 
 // General layout: one lane per 2x2 block, scalar loads/stores, any alignment.
-template <uint32_t LAYOUT>
+template <uint32_t FORM>
 __global__ void __launch_bounds__(kBlockThreads)
 encode_bgra_blocks(const EncodeParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+  constexpr uint32_t LAYOUT = form_layout(FORM);
   const EncodeLds t = stage_encode_tables(lds_raw, p);
   __syncthreads();
   const EncodeFrame f = encode_frame(p, blockIdx.z);
@@ -317,7 +342,7 @@ encode_bgra_blocks(const EncodeParams p) {
   for (uint32_t bx = blockIdx.x * blockDim.x + threadIdx.x; bx < bw; bx += gridDim.x * blockDim.x) {
     const uint32_t *r0 = reinterpret_cast<const uint32_t *>(f.bgra + static_cast<size_t>(2 * rp) * p.bgra_stride);
     const uint32_t *r1 = reinterpret_cast<const uint32_t *>(f.bgra + static_cast<size_t>(2 * rp + 1) * p.bgra_stride);
-    const uint32_t blk[4] = {r0[2 * bx], r0[2 * bx + 1], r1[2 * bx], r1[2 * bx + 1]};
+    const uint32_t blk[4] = {texel<FORM>(r0[2 * bx]), texel<FORM>(r0[2 * bx + 1]), texel<FORM>(r1[2 * bx]), texel<FORM>(r1[2 * bx + 1])};
     float v[6];
     encode_block(t, quarter_n, blk, v);
     uint32_t ytop, ybot, cbcr;
@@ -434,6 +459,10 @@ const char *launch_encode_kernel(const EncodeParams &p, const dim3 &grid, const 
     hipLaunchKernelGGL(encode_alpha_y<LAYOUT>, grid, block, lds, stream, p);
     return planar ? "encode_alpha_y<i420>" : "encode_alpha_y";
   }
+  if (fast && p.premultiply) {
+    hipLaunchKernelGGL(encode_bgra<LAYOUT | kFormStraight>, grid, block, lds, stream, p);
+    return planar ? "encode_bgra_i420<premul>" : "encode_bgra_nv12<premul>";
+  }
   if (fast) {
     hipLaunchKernelGGL(encode_bgra<LAYOUT>, grid, block, lds, stream, p);
     return planar ? "encode_bgra_i420" : "encode_bgra_nv12";
@@ -441,6 +470,10 @@ const char *launch_encode_kernel(const EncodeParams &p, const dim3 &grid, const 
   if (alpha) {
     hipLaunchKernelGGL(encode_alpha_y_blocks<LAYOUT>, grid, block, lds, stream, p);
     return planar ? "encode_alpha_y_blocks<i420>" : "encode_alpha_y_blocks";
+  }
+  if (p.premultiply) {
+    hipLaunchKernelGGL(encode_bgra_blocks<LAYOUT | kFormStraight>, grid, block, lds, stream, p);
+    return planar ? "encode_bgra_i420_blocks<premul>" : "encode_bgra_nv12_blocks<premul>";
   }
   hipLaunchKernelGGL(encode_bgra_blocks<LAYOUT>, grid, block, lds, stream, p);
   return planar ? "encode_bgra_i420_blocks" : "encode_bgra_nv12_blocks";
@@ -485,7 +518,9 @@ const char *launch_encode(const EncodeParams &params, int frames, bool fast, boo
 
 hipError_t prepare_encode_kernels() {
   const void *fns[] = {reinterpret_cast<const void *>(&encode_bgra<kChromaNV12>), reinterpret_cast<const void *>(&encode_bgra_blocks<kChromaNV12>),
-                       reinterpret_cast<const void *>(&encode_bgra<kChromaI420>), reinterpret_cast<const void *>(&encode_bgra_blocks<kChromaI420>)};
+                       reinterpret_cast<const void *>(&encode_bgra<kChromaI420>), reinterpret_cast<const void *>(&encode_bgra_blocks<kChromaI420>),
+                       reinterpret_cast<const void *>(&encode_bgra<kChromaNV12 | kFormStraight>), reinterpret_cast<const void *>(&encode_bgra_blocks<kChromaNV12 | kFormStraight>),
+                       reinterpret_cast<const void *>(&encode_bgra<kChromaI420 | kFormStraight>), reinterpret_cast<const void *>(&encode_bgra_blocks<kChromaI420 | kFormStraight>)};
   return raise_lds_cap(fns, kRepLdsBytes);
 }
 

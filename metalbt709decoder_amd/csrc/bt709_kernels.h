@@ -109,10 +109,18 @@ struct DecodeParams {
   // H/2 bytes at pitch cbcr_stride, and the V (Cr) plane the same shape v_offset = (H/2) * cbcr_stride bytes behind it;
   // launch_decode then runs the kChromaI420 instantiations of its kernels.  Every other launcher reads NV12 whatever this holds.
   uint32_t chroma_layout;  // kChromaNV12 / kChromaI420
-  uint32_t chroma_reserved;
+  // BT709HIP_OPT_UNPREMULTIPLY (alpha decoders, the 1:1 kernels into BGRA8_SRGB): != 0 selects the straight-alpha
+  // instantiations in launch_decode; the shim never sets it together with over_mode.  (It sits in what was a reserved word: every
+  // other field's offset is what it was.)
+  uint32_t straight_alpha;
   uint64_t v_offset;
 };
 enum : uint32_t { kChromaNV12 = 0, kChromaI420 = 1 };  // == BT709HIP_CHROMA_*
+// First template argument of the 1:1 decode kernels and the colour encoder's kernels that have a straight-alpha twin: the chroma
+// layout, plus kFormStraight for the twin (decode: R, G, B divided by A behind the arithmetic; encode: multiplied by A ahead of it)
+enum : uint32_t { kFormStraight = 2 };
+constexpr uint32_t form_layout(uint32_t form) { return form & 1u; }
+constexpr bool form_straight(uint32_t form) { return (form & kFormStraight) != 0; }
 enum : uint32_t { kOverOff = 0, kOverDestination = 1, kOverColour = 2 };
 constexpr uint32_t kOverLinBytes = 256 * sizeof(float);
 
@@ -196,8 +204,12 @@ struct EncodeParams {
   const TransferBucket *from_linear;  // two-resolution BT709_from_linear(., output gamma) table (SplitTable)
   uint32_t from_linear_bytes;
   float from_linear_scale;    // its n_fine
-  float from_linear_split;    // fine buckets below this xs ...
-  float from_linear_coarse;   // ... coarse ones above: q = (uint)(xs * coarse) + offset
+  // BT709HIP_CTX_OPT_ENCODE_PREMULTIPLY (BGRA8_SRGB input): != 0 selects the premultiplying instantiations of
+  // encode_bgra / encode_bgra_blocks in launch_encode; no kernel reads it.  (It sits where the split point of the two-resolution
+  // table was carried, which nothing had read since the index became a min(): every other field's offset, and the kernarg
+  // block's size, are what they were.)
+  uint32_t premultiply;
+  float from_linear_coarse;   // fine buckets below the table's split point, coarse ones above: q = (uint)(xs * coarse) + offset
   uint32_t from_linear_offset;
   uint32_t row_pairs_per_block;  // consecutive row pairs a fast-path workgroup walks; 0 = encode_row_pairs_per_block()
   uint32_t block_threads;        // fast-path workgroup size (one quad per lane); 0 = encode_block_threads(width)

@@ -45,11 +45,16 @@ namespace bt709 {
 // Fast path.  Preconditions (checked by the host shim): width % 4 == 0; y, cbcr and alpha pointers and strides 4-byte aligned
 // (kChromaI420: the U pointer and the chroma pitch 2-byte aligned; v_offset = (H/2) x pitch then is, too); output pointer and
 // stride 16-byte aligned.
-template <uint32_t LAYOUT, bool HAS_ALPHA, bool NT, bool QUANT>
+//
+// FORM, the first template argument of decode_quads and decode_blocks, is the layout plus kFormStraight for the straight-alpha
+// instantiations of their alpha forms (BT709HIP_OPT_UNPREMULTIPLY, DESIGN.md 3.9: each pixel's R, G, B divided by its alpha byte
+// before the word is packed -- bt709_unpremultiply.h).  One argument and not a fifth: the instantiations that existed keep their
+// symbols (the ISA tests and profiles name them) and their code (profiles/r15_straight_alpha_isa.txt).
+template <uint32_t FORM, bool HAS_ALPHA, bool NT, bool QUANT>
 __global__ void __launch_bounds__(kMaxBlockThreads)
 decode_quads(const DecodeParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-  quads_body<LAYOUT, HAS_ALPHA, NT, QUANT>(p, lds_raw);
+  quads_body<form_layout(FORM), HAS_ALPHA, NT, QUANT, false, kOverOff, form_straight(FORM)>(p, lds_raw);
 }
 
 // The plain kernel over a LOG-bucket table (DecodeParams::unit1_shift == 16; transfer_tables.h TransferTable::buckets_log):
@@ -83,10 +88,10 @@ decode_quads_over(const DecodeParams p) {
 // Block bx of row pair rp takes its chroma from bytes 2 bx, 2 bx + 1 of the CbCr row (kChromaNV12), or from byte bx of the U row
 // and of the V row v_offset bytes behind it (kChromaI420; bx < W/2: inside the row's W/2 bytes of either plane).
 // ---------------------------------------------------------------------------
-template <uint32_t LAYOUT, bool HAS_ALPHA, bool QUANT>
+template <uint32_t FORM, bool HAS_ALPHA, bool QUANT>
 __global__ void __launch_bounds__(kBlockThreads)
 decode_blocks(const DecodeParams p) {
-  constexpr bool PLANAR = LAYOUT == kChromaI420;
+  constexpr bool PLANAR = form_layout(FORM) == kChromaI420;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   if (!QUANT) {
     stage_table(lds_raw, p.table_unit, p.table_unit_bytes);
@@ -118,7 +123,7 @@ decode_blocks(const DecodeParams p) {
         a[3] = byte_value(a1[2 * bx + 1]);
       }
       uint32_t out[4];
-      decode_block<HAS_ALPHA, QUANT>(ul, y, byte_value(PLANAR ? cc[bx] : cc[2 * bx]), byte_value(PLANAR ? vv[bx] : cc[2 * bx + 1]), a, p.alpha_word, out);
+      decode_block<HAS_ALPHA, QUANT, form_straight(FORM)>(ul, y, byte_value(PLANAR ? cc[bx] : cc[2 * bx]), byte_value(PLANAR ? vv[bx] : cc[2 * bx + 1]), a, p.alpha_word, out);
       o0[2 * bx] = out[0];
       o0[2 * bx + 1] = out[1];
       o1[2 * bx] = out[2];
@@ -315,6 +320,10 @@ const char *launch_decode_kernel(const DecodeParams &p, const dim3 &grid, const 
       hipLaunchKernelGGL((decode_quads_over<LAYOUT, kOverColour>), grid, block, lds, stream, p);
       return PLANAR ? "decode_i420_quads<alpha,over-colour>" : "decode_nv12_quads<alpha,over-colour>";
     }
+    if (has_alpha && p.straight_alpha) {
+      hipLaunchKernelGGL((decode_quads<LAYOUT | kFormStraight, true, true, true>), grid, block, lds, stream, p);
+      return PLANAR ? "decode_i420_quads<alpha,straight>" : "decode_nv12_quads<alpha,straight>";
+    }
     if (has_alpha) {
       hipLaunchKernelGGL((decode_quads<LAYOUT, true, true, true>), grid, block, lds, stream, p);
       return PLANAR ? "decode_i420_quads<alpha>" : "decode_nv12_quads<alpha>";
@@ -345,6 +354,10 @@ const char *launch_decode_kernel(const DecodeParams &p, const dim3 &grid, const 
   if (over != kOverOff) {
     hipLaunchKernelGGL((decode_blocks_over<LAYOUT, kOverColour>), grid, block, lds, stream, p);
     return PLANAR ? "decode_i420_blocks<alpha,over-colour>" : "decode_nv12_blocks<alpha,over-colour>";
+  }
+  if (has_alpha && p.straight_alpha) {
+    hipLaunchKernelGGL((decode_blocks<LAYOUT | kFormStraight, true, true>), grid, block, lds, stream, p);
+    return PLANAR ? "decode_i420_blocks<alpha,straight>" : "decode_nv12_blocks<alpha,straight>";
   }
   if (has_alpha) {
     hipLaunchKernelGGL((decode_blocks<LAYOUT, true, true>), grid, block, lds, stream, p);

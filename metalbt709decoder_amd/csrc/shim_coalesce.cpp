@@ -126,6 +126,7 @@ int coalescing_submit(bt709hip_decoder *dec, int layout, int count, const bt709h
     BatchInfo info;
     if (int rc = gather_batch(dec, count, frames, alphas, outs, OutShape::kSame, layout, stream, &p, &info)) return rc;
     if (layout == BT709HIP_CHROMA_I420 && info.format == BT709HIP_FORMAT_RGBA16F) return BT709HIP_ERR_UNSUPPORTED;  // decode_batch_now's refusal, now
+    if (dec->unpremultiply != 0 && (info.format == BT709HIP_FORMAT_RGBA16F || dec->composite_over != BT709HIP_OVER_OFF)) return BT709HIP_ERR_UNSUPPORTED;  // and BT709HIP_OPT_UNPREMULTIPLY's
     if (p.width == 0) return BT709HIP_OK;  // empty frames: nothing to launch
   }
   if (q == nullptr) {

@@ -242,6 +242,8 @@ int bt709hip_encode_batch(bt709hip_context *ctx, int count, const bt709hip_surfa
   // BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT, read once: cbcr is the U plane, W/2 bytes a row, V (H/2) x cbcr_stride bytes behind it.
   // Without a chroma plane there is nothing to lay out: such a call is what it was, whatever the option holds.
   const bool planar = ctx->encode_chroma_layout == BT709HIP_CHROMA_I420 && !no_cbcr;
+  // BT709HIP_CTX_OPT_ENCODE_PREMULTIPLY, read once: BGRA8_SRGB texels are straight alpha.  BGRA8_ALPHA input reads A alone: unaffected.
+  const bool premultiply = ctx->encode_premultiply != 0 && !alpha;
   const size_t chroma_align = planar ? 2 : 4;  // the fast kernels' chroma store: a 2-byte half per plane, or the CbCr dword
   bool uniform = count > 1;
   bool fast = (in0.width % 4) == 0 && (in0.stride % 16) == 0 && (out0.y_stride % 4) == 0 && (no_cbcr || (out0.cbcr_stride % chroma_align) == 0);
@@ -294,7 +296,6 @@ int bt709hip_encode_batch(bt709hip_context *ctx, int count, const bt709hip_surfa
     p.from_linear = static_cast<const TransferBucket *>(t.d_from_linear);
     p.from_linear_bytes = t.from_linear_bytes;
     p.from_linear_scale = static_cast<float>(t.from_linear_n);
-    p.from_linear_split = t.split;
     p.from_linear_coarse = t.coarse_scale;
     p.from_linear_offset = t.coarse_offset;
   }
@@ -313,6 +314,7 @@ int bt709hip_encode_batch(bt709hip_context *ctx, int count, const bt709hip_surfa
   p.y_stride = static_cast<uint32_t>(out0.y_stride);
   p.cbcr_stride = no_cbcr ? 0u : static_cast<uint32_t>(out0.cbcr_stride);
   p.chroma_layout = planar ? kChromaI420 : kChromaNV12;
+  p.premultiply = premultiply ? 1u : 0u;
   last_launch_shape() = LaunchShape{};
   set_kernel_name(launch_encode(p, count, fast, ctx->xcd_bands != 0, s));
   HIP_TRY(hipGetLastError());

@@ -137,6 +137,10 @@ int bt709hip_context_set_option(bt709hip_context *ctx, int option, int value) {
       if (value != BT709HIP_CHROMA_NV12 && value != BT709HIP_CHROMA_I420) return BT709HIP_ERR_INVALID_ARG;
       ctx->encode_chroma_layout = value;
       return BT709HIP_OK;
+    case BT709HIP_CTX_OPT_ENCODE_PREMULTIPLY:  // the same rule: a plain property, refused and not clamped
+      if (value != 0 && value != 1) return BT709HIP_ERR_INVALID_ARG;
+      ctx->encode_premultiply = value;
+      return BT709HIP_OK;
     case BT709HIP_CTX_OPT_STREAMING_TRIES:
       ctx->streaming_tries = value <= 0 ? 4 : clamp_int(value, 1, 32);
       return BT709HIP_OK;

@@ -259,6 +259,11 @@ int bt709hip_decoder_set_option(bt709hip_decoder *dec, int option, int value) {
       if (!dec->has_alpha) return BT709HIP_ERR_UNSUPPORTED;
       dec->scaled_over = value;
       return BT709HIP_OK;
+    case BT709HIP_OPT_UNPREMULTIPLY:  // COMPOSITE_OVER's refusals; what it excludes is refused by the decode calls, not here
+      if (value != 0 && value != 1) return BT709HIP_ERR_INVALID_ARG;
+      if (!dec->has_alpha) return BT709HIP_ERR_UNSUPPORTED;  // nothing to divide by
+      dec->unpremultiply = value;
+      return BT709HIP_OK;
     default: return BT709HIP_ERR_INVALID_ARG;
   }
 }
@@ -277,6 +282,7 @@ int bt709hip_decoder_get_option(const bt709hip_decoder *dec, int option, int *va
     case BT709HIP_OPT_COMPOSITE_OVER: *value = dec->composite_over; return BT709HIP_OK;
     case BT709HIP_OPT_SCALED_OVER: *value = dec->scaled_over; return BT709HIP_OK;
     case BT709HIP_OPT_CHROMA_LAYOUT: *value = dec->chroma_layout; return BT709HIP_OK;
+    case BT709HIP_OPT_UNPREMULTIPLY: *value = dec->unpremultiply; return BT709HIP_OK;
     default: return BT709HIP_ERR_INVALID_ARG;
   }
 }
@@ -441,7 +447,11 @@ int decode_batch_now(bt709hip_decoder *dec, int layout, int count, const bt709hi
   const int over = dec->composite_over;  // BT709HIP_OPT_COMPOSITE_OVER: into BGRA8_SRGB targets only
   if (over != BT709HIP_OVER_OFF && info.format == BT709HIP_FORMAT_RGBA16F) return BT709HIP_ERR_UNSUPPORTED;
   if (layout == BT709HIP_CHROMA_I420 && info.format == BT709HIP_FORMAT_RGBA16F) return BT709HIP_ERR_UNSUPPORTED;  // planar chroma: BGRA8_SRGB targets only
+  // BT709HIP_OPT_UNPREMULTIPLY: straight alpha into BGRA8_SRGB targets, and never blended (a blend needs the premultiplied source)
+  const bool straight = dec->unpremultiply != 0;
+  if (straight && (info.format == BT709HIP_FORMAT_RGBA16F || over != BT709HIP_OVER_OFF)) return BT709HIP_ERR_UNSUPPORTED;
   if (p.width == 0) return BT709HIP_OK;
+  p.straight_alpha = straight ? 1u : 0u;
   hipStream_t s = pick(dec->ctx, stream);
   if (over != BT709HIP_OVER_OFF)
     if (int rc = set_over(&p, dec, over, stream)) return rc;
@@ -513,6 +523,7 @@ int decode_half_batch_layout(bt709hip_decoder *dec, int layout, int count, const
   // BT709HIP_OPT_SCALED_OVER blends here; without it BT709HIP_OPT_COMPOSITE_OVER (the 1:1 path only) refuses
   const int over = dec->scaled_over;
   if (over == BT709HIP_OVER_OFF && dec->composite_over != BT709HIP_OVER_OFF) return BT709HIP_ERR_UNSUPPORTED;
+  if (dec->unpremultiply != 0) return BT709HIP_ERR_UNSUPPORTED;  // BT709HIP_OPT_UNPREMULTIPLY: the filters want premultiplied colour
   if (p.width == 0) return BT709HIP_OK;
   // through the RGBA16Float intermediate, or blended: the any-ratio kernel at ratio 2.0 (no persistent 2:1 variant; the half-kernel options are not read)
   if (dec->scale_intermediate == BT709HIP_FORMAT_RGBA16F || over != BT709HIP_OVER_OFF) return launch_scaled(dec, p, info, count, over, stream, wait_until_completed);
@@ -583,6 +594,7 @@ int bt709hip_decode_scaled_batch(bt709hip_decoder *dec, int count, const bt709hi
   if (layout == BT709HIP_CHROMA_I420) return BT709HIP_ERR_UNSUPPORTED;  // the rescale kernels' strip loaders read NV12
   const int over = dec->scaled_over;  // BT709HIP_OPT_SCALED_OVER blends here; without it BT709HIP_OPT_COMPOSITE_OVER (the 1:1 path only) refuses
   if (over == BT709HIP_OVER_OFF && dec->composite_over != BT709HIP_OVER_OFF) return BT709HIP_ERR_UNSUPPORTED;
+  if (dec->unpremultiply != 0) return BT709HIP_ERR_UNSUPPORTED;  // BT709HIP_OPT_UNPREMULTIPLY: the filters want premultiplied colour
   if (p.width == 0) return BT709HIP_OK;
   return launch_scaled(dec, p, info, count, over, stream, wait_until_completed);
 }

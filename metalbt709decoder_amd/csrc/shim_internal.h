@@ -40,7 +40,8 @@ struct bt709hip_context {
   int encode_row_pairs = 0, encode_threads = 0;  // BT709HIP_CTX_OPT_ENCODE_*: 0 = sized per launch
   int xcd_bands = 1;                             // BT709HIP_CTX_OPT_XCD_BANDS: XCD-aware work map of batched encoder launches
   int encode_chroma_layout = BT709HIP_CHROMA_NV12;  // BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT: the planes bt709hip_encode[_batch] writes
-  int streaming_tries = 4;                       // BT709HIP_CTX_OPT_STREAMING_TRIES: placement candidates for buffers of 256 MB and more that the library allocates itself
+  int encode_premultiply = 0;                       // BT709HIP_CTX_OPT_ENCODE_PREMULTIPLY: BGRA8_SRGB input is straight alpha, premultiplied by the encode kernels
+  int streaming_tries = 4;                     // BT709HIP_CTX_OPT_STREAMING_TRIES: placement candidates for buffers of 256 MB and more that the library allocates itself
   std::mutex encoder_mutex;
   EncoderTables encoders[3][3];  // [input gamma][output gamma], built on first use
   void *d_alpha_luma = nullptr;  // T[256] of BGRA8_ALPHA input (bt709_alpha_luma.h), built on first use under encoder_mutex
@@ -83,6 +84,7 @@ struct bt709hip_decoder {
   std::atomic<int> composite_over{BT709HIP_OVER_OFF};  // BT709HIP_OPT_COMPOSITE_OVER: off, the destination, or an sRGB colour R<<16 | G<<8 | B
   std::atomic<int> scaled_over{BT709HIP_OVER_OFF};     // BT709HIP_OPT_SCALED_OVER: the same three forms, read by the rescale paths alone
   std::atomic<int> chroma_layout{BT709HIP_CHROMA_NV12};  // BT709HIP_OPT_CHROMA_LAYOUT: how bt709hip_decode[_batch] read the CALLER's colour frames
+  std::atomic<int> unpremultiply{0};                     // BT709HIP_OPT_UNPREMULTIPLY: the 1:1 decode of an alpha decoder writes straight alpha
   std::mutex queue_mutex;   // guards queues
   std::vector<PendingQueue> queues;  // one per stream that has (had) queued frames
   std::mutex setup_mutex;

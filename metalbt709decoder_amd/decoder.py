@@ -554,6 +554,17 @@ class MetalRenderContext:
         self._encode_layout = int(layout)
         return True
 
+    def setEncodePremultiply(self, flag):
+        """bt709hip_context_set_option(CTX_OPT_ENCODE_PREMULTIPLY): True -- the BGRA pictures the convert calls of this context are
+        handed hold STRAIGHT alpha (a PNG, an RGBA tensor) and each texel's B, G, R are multiplied by its A inside the encode
+        kernel, c' = (c * A + 127) / 255; False (the default) -- they are encoded as they are, which is right for
+        premultiplied pictures.  The alpha-frame encode reads A alone either way.  Returns True/False."""
+        rc = self.lib.bt709hip_context_set_option(self.handle, _capi.CTX_OPT_ENCODE_PREMULTIPLY, int(bool(flag)))
+        if rc != _capi.OK:
+            log.error("setEncodePremultiply(%r): %s", flag, _capi.strerror(rc))
+            return False
+        return True
+
     def _set_encode_layout(self, pixelBuffers, what):
         """The encoder's chroma layout from the buffers an encode call was handed: a planar CVPixelBuffer is written in place.  As
         MetalBT709Decoder._set_layout: the buffer's `planar` flag is authoritative, planar and NV12 buffers in one call are
@@ -917,6 +928,36 @@ class MetalBT709Decoder:
     @scaledCompositeOver.setter
     def scaledCompositeOver(self, background):
         self._over_set(_capi.OPT_SCALED_OVER, "scaledCompositeOver", background)
+
+    @property
+    def straightAlpha(self):
+        """True: the 1:1 decode of an alpha decoder (decodeBT709 / decodeBT709Batch into BGRA8 targets, rings and pools included)
+        writes STRAIGHT alpha -- each pixel's B, G, R divided by its own alpha byte inside the decode kernel,
+        c = min(255, (255 c' + A / 2) / A), 0 where A = 0 (_capi.OPT_UNPREMULTIPLY) -- what a PNG writer or an RGBA
+        tensor wants.  False (the default): the premultiplied colour the frames hold.  While it is on, RGBA16Float targets, the
+        rescales and any decode under compositeOver fail with ERR_UNSUPPORTED (lastStatus)."""
+        return bool(self._options.get(_capi.OPT_UNPREMULTIPLY, 0))
+
+    @straightAlpha.setter
+    def straightAlpha(self, flag):
+        self.setStraightAlpha(flag)
+
+    def setStraightAlpha(self, flag):
+        """The straightAlpha property with a status: False and lastStatus = ERR_UNSUPPORTED on a decoder without an alpha channel
+        that is set up already (before setupMetal the value is kept and applied there, like every option)."""
+        value = int(bool(flag))
+        if not self._handle:
+            if not value and not self.hasAlphaChannel:  # nothing to switch off: the option is an alpha decoder's
+                self._options.pop(_capi.OPT_UNPREMULTIPLY, None)
+            else:
+                self._options[_capi.OPT_UNPREMULTIPLY] = value
+            return True
+        rc = self.metalRenderContext.lib.bt709hip_decoder_set_option(self._handle, _capi.OPT_UNPREMULTIPLY, value)
+        if rc != _capi.OK:
+            return self._fail(rc, "straightAlpha")
+        self._options[_capi.OPT_UNPREMULTIPLY] = value
+        self.lastStatus = _capi.OK
+        return True
 
     def _over_get(self, option):
         v = self._options.get(option, _capi.OVER_OFF)

@@ -35,6 +35,12 @@ enum { BT709HIPCompositeOverOff = -1, BT709HIPCompositeOverDestination = -2 };  
 // alpha clip played view-fit over the app's background, blended inside the rescale kernel.  The same values, held separately from
 // hipCompositeOver; reads BT709HIPCompositeOverOff until it is set.
 @property (nonatomic, assign) int hipScaledCompositeOver;
+// YES: the 1:1 decode of a decoder with hasAlphaChannel writes STRAIGHT alpha -- each pixel's B, G, R divided by its own alpha byte
+// inside the decode kernel, the GPU twin of +[BGRAToBT709Converter unpremultiply:] (device-resident frames through
+// hipDecoderHandle; include/bt709hip_ext.h BT709HIP_OPT_UNPREMULTIPLY).  NO (the default): the premultiplied colour the frames hold.
+// While it is YES the rescales, RGBA16Float targets and a decode under hipCompositeOver are refused.  Set before -setupMetal or at
+// any time after.
+@property (nonatomic, assign) BOOL hipStraightAlpha;
 // The bt709hip_decoder behind this object (NULL before -setupMetal), as a void * so that this header needs no bt709hip.h.
 - (void *) hipDecoderHandle;
 // Completes every frame still in flight: their pixels are copied into the textures passed with them.  Same thread

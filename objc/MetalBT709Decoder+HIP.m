@@ -85,6 +85,8 @@ static void BT709HIPCopyPlane(void *dst, size_t dstStride, CVPixelBufferRef pb, 
   if (self.hasAlphaChannel) bt709hip_decoder_set_option(_hipDecoder, BT709HIP_OPT_COMPOSITE_OVER, self.hipCompositeOver);
   // hipScaledCompositeOver: the same for its fused rescales
   if (self.hasAlphaChannel) bt709hip_decoder_set_option(_hipDecoder, BT709HIP_OPT_SCALED_OVER, self.hipScaledCompositeOver);
+  // hipStraightAlpha: its 1:1 decode divides the colour by the alpha byte inside the kernel
+  if (self.hasAlphaChannel) bt709hip_decoder_set_option(_hipDecoder, BT709HIP_OPT_UNPREMULTIPLY, self.hipStraightAlpha ? 1 : 0);
 }
 - (void) setHipCoalesceFrames:(int)n { _hipCoalesceFrames = n; [self applyHIPCoalescing]; }
 - (void) setHipCoalesceMaxAgeMicroseconds:(int)us { _hipCoalesceMaxAgeMicroseconds = us; [self applyHIPCoalescing]; }
@@ -95,6 +97,7 @@ static void BT709HIPCopyPlane(void *dst, size_t dstStride, CVPixelBufferRef pb, 
 @synthesize hipScaledCompositeOver = _hipScaledCompositeOver;
 - (int) hipScaledCompositeOver { return _hipScaledCompositeOverSet ? _hipScaledCompositeOver : BT709HIP_OVER_OFF; }
 - (void) setHipScaledCompositeOver:(int)background { _hipScaledCompositeOver = background; _hipScaledCompositeOverSet = YES; [self applyHIPCoalescing]; }
+- (void) setHipStraightAlpha:(BOOL)on { _hipStraightAlpha = on; [self applyHIPCoalescing]; }
 - (void *) hipDecoderHandle { return _hipDecoder; }
 
 // Copies a finished slot's pinned BGRA rows into the texture the caller passed for that frame: its top-left
