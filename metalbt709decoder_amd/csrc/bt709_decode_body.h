@@ -1,6 +1,7 @@
 // Device code of the 1:1 decode kernels (bt709_kernels.hip), shared by both chroma layouts (NV12, planar I420): the per-quad and
-// per-block arithmetic, the composite-over staging and the body of the fast kernels.  Only the tile front end -- which chroma
-// bytes reach which quad -- depends on the layout (bt709_tile.h TileIn<LAYOUT, ...>).
+// per-block arithmetic, the composite-over staging, the body of the fast kernels (quads_body) and the walk of the general-path
+// kernels (blocks_body).  Only the tile front end -- which chroma bytes reach which quad -- and the general path's chroma fetch
+// depend on the layout (bt709_tile.h TileIn<LAYOUT, ...>).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -200,40 +201,87 @@ __device__ __forceinline__ void quads_body(const DecodeParams &p, unsigned char 
   const UnitLookup ul = unit_lookup(p, lds_raw);
   uint8_t *o0 = f.out + static_cast<size_t>(2 * min(rp_raw, row_pairs - 1)) * p.out_stride;
   uint8_t *o1 = o0 + p.out_stride;
-  if constexpr (OVER != kOverOff) {  // the same walk, the quads through the blend
 #pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {
-      const uint32_t q = q0 + u * blockDim.x;
-      u32x4 top, bot;
-      over_quad<OVER>(ol, p, in.ya[u], in.yb[u], in.cw[u], in.aa[u], in.ab[u], in.da[OVER == kOverDestination ? u : 0], in.db[OVER == kOverDestination ? u : 0], top, bot);
-      if (q < quads && rp_raw < row_pairs) {
-        store16<NT>(o0 + 16 * q, top);
-        store16<NT>(o1 + 16 * q, bot);
-      }
-    }
-    return;
-  }
-  if constexpr (STRAIGHT) {  // the same walk, the quads' pixels through the division
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {
-      const uint32_t q = q0 + u * blockDim.x;
-      u32x4 top, bot;
-      straight_quad(in.ya[u], in.yb[u], in.cw[u], in.aa[u], in.ab[u], top, bot);
-      if (q < quads && rp_raw < row_pairs) {
-        store16<NT>(o0 + 16 * q, top);
-        store16<NT>(o1 + 16 * q, bot);
-      }
-    }
-    return;
-  }
-#pragma unroll
-  for (int u = 0; u < UNROLL; ++u) {
+  for (int u = 0; u < UNROLL; ++u) {  // one walk: the quads through the blend, their pixels through the division, or plain
     const uint32_t q = q0 + u * blockDim.x;
     u32x4 top, bot;
-    decode_quad<HAS_ALPHA, QUANT, LOGIDX>(ul, in.ya[u], in.yb[u], in.cw[u], HAS_ALPHA ? in.aa[u] : 0u, HAS_ALPHA ? in.ab[u] : 0u, p.alpha_word, top, bot);
+    if constexpr (OVER != kOverOff)
+      over_quad<OVER>(ol, p, in.ya[u], in.yb[u], in.cw[u], in.aa[u], in.ab[u], in.da[OVER == kOverDestination ? u : 0], in.db[OVER == kOverDestination ? u : 0], top, bot);
+    else if constexpr (STRAIGHT)
+      straight_quad(in.ya[u], in.yb[u], in.cw[u], in.aa[u], in.ab[u], top, bot);
+    else
+      decode_quad<HAS_ALPHA, QUANT, LOGIDX>(ul, in.ya[u], in.yb[u], in.cw[u], HAS_ALPHA ? in.aa[u] : 0u, HAS_ALPHA ? in.ab[u] : 0u, p.alpha_word, top, bot);
     if (q < quads && rp_raw < row_pairs) {
       store16<NT>(o0 + 16 * q, top);
       store16<NT>(o1 + 16 * q, bot);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// General path: any even width/height, any stride, byte-aligned planes, 4-byte
+// aligned output.  One lane per 2x2 block, grid-strided over row pairs.  Correctness
+// first; used for ragged or misaligned frames only.  That correctness is pinned by tests/test_decode_variants.py: all 2^24
+// triples through every instantiation of decode_blocks and decode_blocks_over, and the grid-stride loop, both forms of
+// frame_planes and the over kernels at launch shapes computed from the device.
+// Block bx of row pair rp takes its chroma from bytes 2 bx, 2 bx + 1 of the CbCr row (kChromaNV12), or from byte bx of the U row
+// and of the V row v_offset bytes behind it (kChromaI420; bx < W/2: inside the row's W/2 bytes of either plane).
+// ---------------------------------------------------------------------------
+// One walk for decode_blocks and decode_blocks_over.  OVER (alpha decoders): each 2x2 block through over_pixel; each output word
+// is read (destination mode) and written by one lane alone.  STRAIGHT (alpha decoders, never with OVER): decode_block's pixels
+// through straight_pixel.
+// The __global__ kernel stages the tables (the unit table unless QUANT; both over tables) and hands in the lookup constants, ul or
+// ol: nothing is in flight ahead of the staging here, and staged from inside this body the kernels gain ten instructions -- this
+// body is simplified as a function of its own before it is inlined, the block count that blockDim.x (the staging) and gridDim.x
+// (the row-pair stride) both read becomes one load with two users, and the compiler's fold of blockDim.x to the uniform workgroup
+// size, which wants one user per load, no longer applies (a global_load_ushort, a compare and a select instead of one packed dword).
+// __restrict__: the parameter block is not written through the plane pointers it holds, so that simplification hoists the loads of
+// the pitches out of the loops together with the arithmetic, in the order the kernels' own text had (profiles/r16_one_walk_isa.txt).
+template <uint32_t LAYOUT, bool HAS_ALPHA, bool QUANT, int OVER = kOverOff, bool STRAIGHT = false>
+__device__ __forceinline__ void blocks_body(const DecodeParams &__restrict__ p, const UnitLookup &ul, const OverLookup &ol) {
+  constexpr bool PLANAR = LAYOUT == kChromaI420;
+  static_assert(OVER == kOverOff || (HAS_ALPHA && QUANT && !STRAIGHT), "a blend needs an alpha decoder's premultiplied source");
+  const FramePlanes f = frame_planes(p, blockIdx.y);
+  const uint32_t bw = p.width >> 1;
+  const uint32_t row_pairs = p.height >> 1;
+
+  for (uint32_t rp = blockIdx.x; rp < row_pairs; rp += gridDim.x) {
+    const uint8_t *y0 = f.y + static_cast<size_t>(2 * rp) * p.y_stride;
+    const uint8_t *y1 = y0 + p.y_stride;
+    const uint8_t *cc = f.cbcr + static_cast<size_t>(rp) * p.cbcr_stride;  // the CbCr row, or the U row
+    const uint8_t *vv = PLANAR ? cc + p.v_offset : nullptr;
+    uint32_t *o0 = reinterpret_cast<uint32_t *>(f.out + static_cast<size_t>(2 * rp) * p.out_stride);
+    uint32_t *o1 = reinterpret_cast<uint32_t *>(f.out + static_cast<size_t>(2 * rp + 1) * p.out_stride);
+    for (uint32_t bx = threadIdx.x; bx < bw; bx += kBlockThreads) {
+      const float y[4] = {byte_value(y0[2 * bx]), byte_value(y0[2 * bx + 1]), byte_value(y1[2 * bx]), byte_value(y1[2 * bx + 1])};
+      float a[4] = {0.f, 0.f, 0.f, 0.f};
+      if (HAS_ALPHA) {
+        const uint8_t *a0 = f.alpha + static_cast<size_t>(2 * rp) * p.alpha_stride;
+        const uint8_t *a1 = a0 + p.alpha_stride;
+        a[0] = byte_value(a0[2 * bx]);
+        a[1] = byte_value(a0[2 * bx + 1]);
+        a[2] = byte_value(a1[2 * bx]);
+        a[3] = byte_value(a1[2 * bx + 1]);
+      }
+      uint32_t bg[4] = {0u, 0u, 0u, 0u};
+      if (OVER == kOverDestination) bg[0] = o0[2 * bx], bg[1] = o0[2 * bx + 1], bg[2] = o1[2 * bx], bg[3] = o1[2 * bx + 1];
+      const float cb = byte_value(PLANAR ? cc[bx] : cc[2 * bx]), cr = byte_value(PLANAR ? vv[bx] : cc[2 * bx + 1]);
+      uint32_t out[4];
+      if constexpr (OVER != kOverOff) {
+        const Chroma c = chroma_terms(cb, cr);
+#pragma unroll
+        for (int px = 0; px < 4; ++px) {
+          float x[3];
+          pixel_rgb(y[px], c, x[0], x[1], x[2]);
+          out[px] = over_pixel<OVER>(ol, p.over_lin, x, a[px], bg[px]);
+        }
+      } else {
+        decode_block<HAS_ALPHA, QUANT, STRAIGHT>(ul, y, cb, cr, a, p.alpha_word, out);
+      }
+      o0[2 * bx] = out[0];
+      o0[2 * bx + 1] = out[1];
+      o1[2 * bx] = out[2];
+      o1[2 * bx + 1] = out[3];
     }
   }
 }

@@ -451,32 +451,41 @@ encode_alpha_y_blocks(const EncodeParams p) {
 
 namespace {
 
-// The kernel of a launch that launch_encode has planned and recorded; the names are what bt709hip_last_kernel_name reports.
-template <uint32_t LAYOUT>
+// One row per selectable kernel: the selector, the kernel for either chroma layout, the two names bt709hip_last_kernel_name
+// reports, and whether the kernel stages its tables in dynamic LDS (the alpha kernels' 256 bytes are static) --
+// prepare_encode_kernels raises the cap of exactly those.  A selector field is a value or kAny; the first matching row is the
+// launch's kernel.
+struct EncodeKernel {
+  int fast, alpha, premultiply;
+  bool stages_table;
+  void (*fn[2])(const EncodeParams);  // [chroma layout]
+  const char *name[2];
+};
+// KERNEL<layout | FORM>; both names from one stem and one suffix: colour kernels spell the layout (encode_bgra_i420<premul>), the
+// alpha kernels' NV12 form names none (encode_alpha_y, encode_alpha_y<i420>)
+#define ENCODE_COLOUR(fast, premultiply, suffix, KERNEL, FORM) \
+  {fast, 0, premultiply, true, {KERNEL<kChromaNV12 | (FORM)>, KERNEL<kChromaI420 | (FORM)>}, {"encode_bgra_nv12" suffix, "encode_bgra_i420" suffix}}
+#define ENCODE_ALPHA(fast, stem, KERNEL) {fast, 1, kAny, false, {KERNEL<kChromaNV12>, KERNEL<kChromaI420>}, {stem, stem "<i420>"}}
+const EncodeKernel kEncodeKernels[] = {
+    ENCODE_ALPHA(1, "encode_alpha_y", encode_alpha_y),
+    ENCODE_COLOUR(1, 1, "<premul>", encode_bgra, kFormStraight),
+    ENCODE_COLOUR(1, 0, "", encode_bgra, 0),
+    ENCODE_ALPHA(0, "encode_alpha_y_blocks", encode_alpha_y_blocks),
+    ENCODE_COLOUR(0, 1, "_blocks<premul>", encode_bgra_blocks, kFormStraight),
+    ENCODE_COLOUR(0, 0, "_blocks", encode_bgra_blocks, 0),
+};
+#undef ENCODE_COLOUR
+#undef ENCODE_ALPHA
+
+// The kernel of a launch that launch_encode has planned and recorded
 const char *launch_encode_kernel(const EncodeParams &p, const dim3 &grid, const dim3 &block, size_t lds, bool fast, bool alpha, hipStream_t stream) {
-  constexpr bool planar = LAYOUT == kChromaI420;
-  if (fast && alpha) {
-    hipLaunchKernelGGL(encode_alpha_y<LAYOUT>, grid, block, lds, stream, p);
-    return planar ? "encode_alpha_y<i420>" : "encode_alpha_y";
+  const uint32_t layout = p.chroma_layout == kChromaI420 ? kChromaI420 : kChromaNV12;
+  for (const EncodeKernel &k : kEncodeKernels) {
+    if (k.fast != fast || k.alpha != alpha || !selects(k.premultiply, p.premultiply != 0)) continue;
+    hipLaunchKernelGGL(k.fn[layout], grid, block, lds, stream, p);
+    return k.name[layout];
   }
-  if (fast && p.premultiply) {
-    hipLaunchKernelGGL(encode_bgra<LAYOUT | kFormStraight>, grid, block, lds, stream, p);
-    return planar ? "encode_bgra_i420<premul>" : "encode_bgra_nv12<premul>";
-  }
-  if (fast) {
-    hipLaunchKernelGGL(encode_bgra<LAYOUT>, grid, block, lds, stream, p);
-    return planar ? "encode_bgra_i420" : "encode_bgra_nv12";
-  }
-  if (alpha) {
-    hipLaunchKernelGGL(encode_alpha_y_blocks<LAYOUT>, grid, block, lds, stream, p);
-    return planar ? "encode_alpha_y_blocks<i420>" : "encode_alpha_y_blocks";
-  }
-  if (p.premultiply) {
-    hipLaunchKernelGGL(encode_bgra_blocks<LAYOUT | kFormStraight>, grid, block, lds, stream, p);
-    return planar ? "encode_bgra_i420_blocks<premul>" : "encode_bgra_nv12_blocks<premul>";
-  }
-  hipLaunchKernelGGL(encode_bgra_blocks<LAYOUT>, grid, block, lds, stream, p);
-  return planar ? "encode_bgra_i420_blocks" : "encode_bgra_nv12_blocks";
+  return nullptr;  // unreachable: the rows cover fast x alpha x premultiply
 }
 
 }  // namespace
@@ -512,16 +521,15 @@ const char *launch_encode(const EncodeParams &params, int frames, bool fast, boo
   }
   record_launch(grid, block, fast ? p.xcd_bands : 0);
   // the plan does not depend on the layout, only the kernel does (an alpha frame without chroma planes arrives as kChromaNV12)
-  if (p.chroma_layout == kChromaI420) return launch_encode_kernel<kChromaI420>(p, grid, block, lds, fast, alpha, stream);
-  return launch_encode_kernel<kChromaNV12>(p, grid, block, lds, fast, alpha, stream);
+  return launch_encode_kernel(p, grid, block, lds, fast, alpha, stream);
 }
 
 hipError_t prepare_encode_kernels() {
-  const void *fns[] = {reinterpret_cast<const void *>(&encode_bgra<kChromaNV12>), reinterpret_cast<const void *>(&encode_bgra_blocks<kChromaNV12>),
-                       reinterpret_cast<const void *>(&encode_bgra<kChromaI420>), reinterpret_cast<const void *>(&encode_bgra_blocks<kChromaI420>),
-                       reinterpret_cast<const void *>(&encode_bgra<kChromaNV12 | kFormStraight>), reinterpret_cast<const void *>(&encode_bgra_blocks<kChromaNV12 | kFormStraight>),
-                       reinterpret_cast<const void *>(&encode_bgra<kChromaI420 | kFormStraight>), reinterpret_cast<const void *>(&encode_bgra_blocks<kChromaI420 | kFormStraight>)};
-  return raise_lds_cap(fns, kRepLdsBytes);
+  for (const EncodeKernel &k : kEncodeKernels) {
+    const void *fns[] = {reinterpret_cast<const void *>(k.fn[0]), reinterpret_cast<const void *>(k.fn[1])};
+    if (const hipError_t e = k.stages_table ? raise_lds_cap(fns, kRepLdsBytes) : hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 }  // namespace bt709

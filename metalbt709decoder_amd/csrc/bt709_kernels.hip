@@ -38,7 +38,7 @@ namespace bt709 {
 // output is byte for byte what the NV12 instantiation writes for the interleaved twin of the planes.  Same traffic as NV12,
 // 1.5 B read + 4 B written per pixel, where "interleave the planes, then decode" moves 6.5 B in two launches.  The arithmetic
 // is one text (bt709_decode_body.h); the layout only decides which chroma bytes reach which pixel: the fast kernels' tile front
-// end (bt709_tile.h TileIn) and the general kernels' chroma fetch below.  It is a parameter of the __global__ kernels and of
+// end (bt709_tile.h TileIn) and the general kernels' chroma fetch (blocks_body).  It is a parameter of the __global__ kernels and of
 // that front end, never of a body inlined under a kernel that had none: that layer changed the NV12 kernels' code
 // (profiles/r14_layout_template_isa.txt).
 //
@@ -79,102 +79,28 @@ decode_quads_over(const DecodeParams p) {
   quads_body<LAYOUT, true, true, true, false, OVER>(p, lds_raw);
 }
 
-// ---------------------------------------------------------------------------
-// General path: any even width/height, any stride, byte-aligned planes, 4-byte
-// aligned output.  One lane per 2x2 block, grid-strided over row pairs.  Correctness
-// first; used for ragged or misaligned frames only.  That correctness is pinned by tests/test_decode_variants.py: all 2^24
-// triples through every instantiation below, and the grid-stride loop, both forms of frame_planes and the over kernels at
-// launch shapes computed from the device.
-// Block bx of row pair rp takes its chroma from bytes 2 bx, 2 bx + 1 of the CbCr row (kChromaNV12), or from byte bx of the U row
-// and of the V row v_offset bytes behind it (kChromaI420; bx < W/2: inside the row's W/2 bytes of either plane).
-// ---------------------------------------------------------------------------
+// General path: ragged or misaligned frames, one lane per 2x2 block.  The walk is bt709_decode_body.h blocks_body (its contract and
+// the tests that pin it are described there); the kernel stages the table ahead of it.  FORM as for decode_quads.
 template <uint32_t FORM, bool HAS_ALPHA, bool QUANT>
 __global__ void __launch_bounds__(kBlockThreads)
 decode_blocks(const DecodeParams p) {
-  constexpr bool PLANAR = form_layout(FORM) == kChromaI420;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   if (!QUANT) {
     stage_table(lds_raw, p.table_unit, p.table_unit_bytes);
     __syncthreads();
   }
-
-  const UnitLookup ul = unit_lookup(p, lds_raw);
-  const FramePlanes f = frame_planes(p, blockIdx.y);
-  const uint32_t bw = p.width >> 1;
-  const uint32_t row_pairs = p.height >> 1;
-
-  for (uint32_t rp = blockIdx.x; rp < row_pairs; rp += gridDim.x) {
-    const uint8_t *y0 = f.y + static_cast<size_t>(2 * rp) * p.y_stride;
-    const uint8_t *y1 = y0 + p.y_stride;
-    const uint8_t *cc = f.cbcr + static_cast<size_t>(rp) * p.cbcr_stride;  // the CbCr row, or the U row
-    const uint8_t *vv = PLANAR ? cc + p.v_offset : nullptr;
-    uint32_t *o0 = reinterpret_cast<uint32_t *>(f.out + static_cast<size_t>(2 * rp) * p.out_stride);
-    uint32_t *o1 = reinterpret_cast<uint32_t *>(f.out + static_cast<size_t>(2 * rp + 1) * p.out_stride);
-    for (uint32_t bx = threadIdx.x; bx < bw; bx += kBlockThreads) {
-      const float y[4] = {byte_value(y0[2 * bx]), byte_value(y0[2 * bx + 1]), byte_value(y1[2 * bx]),
-                          byte_value(y1[2 * bx + 1])};
-      float a[4] = {0.f, 0.f, 0.f, 0.f};
-      if (HAS_ALPHA) {
-        const uint8_t *a0 = f.alpha + static_cast<size_t>(2 * rp) * p.alpha_stride;
-        const uint8_t *a1 = a0 + p.alpha_stride;
-        a[0] = byte_value(a0[2 * bx]);
-        a[1] = byte_value(a0[2 * bx + 1]);
-        a[2] = byte_value(a1[2 * bx]);
-        a[3] = byte_value(a1[2 * bx + 1]);
-      }
-      uint32_t out[4];
-      decode_block<HAS_ALPHA, QUANT, form_straight(FORM)>(ul, y, byte_value(PLANAR ? cc[bx] : cc[2 * bx]), byte_value(PLANAR ? vv[bx] : cc[2 * bx + 1]), a, p.alpha_word, out);
-      o0[2 * bx] = out[0];
-      o0[2 * bx + 1] = out[1];
-      o1[2 * bx] = out[2];
-      o1[2 * bx + 1] = out[3];
-    }
-  }
+  blocks_body<form_layout(FORM), HAS_ALPHA, QUANT, kOverOff, form_straight(FORM)>(p, unit_lookup(p, lds_raw), OverLookup{});
 }
 
 // The alpha decoder's general path with the composite-over blend (BT709HIP_OPT_COMPOSITE_OVER): the same walk, each 2x2 block
-// through over_pixel.  A kernel of its own: the plain kernel's code stays what it was.  Each output word is read (destination
-// mode) and written by one lane alone.
+// through over_pixel.  A kernel of its own: the plain kernel's code stays what it was.
 template <uint32_t LAYOUT, int OVER>
 __global__ void __launch_bounds__(kBlockThreads)
 decode_blocks_over(const DecodeParams p) {
-  constexpr bool PLANAR = LAYOUT == kChromaI420;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   const OverLookup ol = stage_over_tables(lds_raw, p);
   __syncthreads();
-
-  const FramePlanes f = frame_planes(p, blockIdx.y);
-  const uint32_t bw = p.width >> 1;
-  const uint32_t row_pairs = p.height >> 1;
-
-  for (uint32_t rp = blockIdx.x; rp < row_pairs; rp += gridDim.x) {
-    const uint8_t *y0 = f.y + static_cast<size_t>(2 * rp) * p.y_stride;
-    const uint8_t *y1 = y0 + p.y_stride;
-    const uint8_t *a0 = f.alpha + static_cast<size_t>(2 * rp) * p.alpha_stride;
-    const uint8_t *a1 = a0 + p.alpha_stride;
-    const uint8_t *cc = f.cbcr + static_cast<size_t>(rp) * p.cbcr_stride;  // the CbCr row, or the U row
-    const uint8_t *vv = PLANAR ? cc + p.v_offset : nullptr;
-    uint32_t *o0 = reinterpret_cast<uint32_t *>(f.out + static_cast<size_t>(2 * rp) * p.out_stride);
-    uint32_t *o1 = reinterpret_cast<uint32_t *>(f.out + static_cast<size_t>(2 * rp + 1) * p.out_stride);
-    for (uint32_t bx = threadIdx.x; bx < bw; bx += kBlockThreads) {
-      const float y[4] = {byte_value(y0[2 * bx]), byte_value(y0[2 * bx + 1]), byte_value(y1[2 * bx]), byte_value(y1[2 * bx + 1])};
-      const float a[4] = {byte_value(a0[2 * bx]), byte_value(a0[2 * bx + 1]), byte_value(a1[2 * bx]), byte_value(a1[2 * bx + 1])};
-      uint32_t bg[4] = {0u, 0u, 0u, 0u};
-      if (OVER == kOverDestination) bg[0] = o0[2 * bx], bg[1] = o0[2 * bx + 1], bg[2] = o1[2 * bx], bg[3] = o1[2 * bx + 1];
-      const Chroma c = chroma_terms(byte_value(PLANAR ? cc[bx] : cc[2 * bx]), byte_value(PLANAR ? vv[bx] : cc[2 * bx + 1]));
-      uint32_t out[4];
-#pragma unroll
-      for (int px = 0; px < 4; ++px) {
-        float x[3];
-        pixel_rgb(y[px], c, x[0], x[1], x[2]);
-        out[px] = over_pixel<OVER>(ol, p.over_lin, x, a[px], bg[px]);
-      }
-      o0[2 * bx] = out[0];
-      o0[2 * bx + 1] = out[1];
-      o1[2 * bx] = out[2];
-      o1[2 * bx + 1] = out[3];
-    }
-  }
+  blocks_body<LAYOUT, true, true, OVER>(p, UnitLookup{}, ol);
 }
 
 // ---------------------------------------------------------------------------
@@ -260,6 +186,21 @@ unconvert_packed444(const UnconvertParams p) {
   }
 }
 
+namespace {
+// The four instantiations: the selector, the kernel, and whether it stages the table in dynamic LDS (prepare_kernels)
+struct UnconvertKernel {
+  bool vec, quantiser;
+  void (*fn)(const UnconvertParams);
+  bool stages_table;
+};
+const UnconvertKernel kUnconvertKernels[] = {
+    {true, true, unconvert_packed444<true, true>, false},
+    {true, false, unconvert_packed444<true, false>, true},
+    {false, true, unconvert_packed444<false, true>, false},
+    {false, false, unconvert_packed444<false, false>, true},
+};
+}  // namespace
+
 const char *launch_unconvert(const DecodeParams &t, const UnconvertBatch &b, size_t in_stride, size_t out_stride, uint32_t width, uint32_t height,
                              bool vec, bool quantiser, hipStream_t stream) {
   UnconvertParams p;
@@ -284,13 +225,8 @@ const char *launch_unconvert(const DecodeParams &t, const UnconvertBatch &b, siz
   const uint32_t groups = vec ? width / 4 : width;
   const dim3 grid((groups + kBlockThreads - 1) / kBlockThreads, vec ? height / 2 : height, static_cast<uint32_t>(b.count));  // vec: two rows per workgroup row
   const size_t lds = quantiser ? 0 : t.table_unit_bytes;
-  if (vec) {
-    if (quantiser) hipLaunchKernelGGL((unconvert_packed444<true, true>), grid, dim3(kBlockThreads), lds, stream, p);
-    else hipLaunchKernelGGL((unconvert_packed444<true, false>), grid, dim3(kBlockThreads), lds, stream, p);
-  } else {
-    if (quantiser) hipLaunchKernelGGL((unconvert_packed444<false, true>), grid, dim3(kBlockThreads), lds, stream, p);
-    else hipLaunchKernelGGL((unconvert_packed444<false, false>), grid, dim3(kBlockThreads), lds, stream, p);
-  }
+  for (const UnconvertKernel &k : kUnconvertKernels)
+    if (k.vec == vec && k.quantiser == quantiser) hipLaunchKernelGGL(k.fn, grid, dim3(kBlockThreads), lds, stream, p);
   return vec ? "unconvert_packed444<vec>" : "unconvert_packed444";
 }
 
@@ -304,71 +240,55 @@ LaunchShape &last_launch_shape() {
 
 namespace {
 
+// One row per selectable 1:1 kernel: the selector, the kernel for either chroma layout, the two names bt709hip_last_kernel_name
+// reports, and whether the kernel stages a table in dynamic LDS -- prepare_kernels raises the cap of exactly those, so a kernel
+// cannot be launched from here and be missing there.  A selector field is a value or kAny; the FIRST row that matches is the
+// launch's kernel, so the rows of a variant run from the most specific form to the plain one.  `quant`: the sRGB mode or an alpha
+// decoder (arithmetic, no table); `log`: a log-bucket table (the LINEAR mode; the general path takes the shift at run time).
+struct DecodeKernel {
+  int variant, over, alpha, straight, quant, log, nt;
+  bool stages_table;
+  void (*fn[2])(const DecodeParams);  // [chroma layout]
+  const char *name[2];
+};
+// KERNEL<layout | FORM, ...>; both names from one suffix
+#define DECODE_KERNEL(variant, over, alpha, straight, quant, log, nt, stages_table, suffix, KERNEL, FORM, ...)                               \
+  {variant, over, alpha, straight, quant, log, nt, stages_table, {KERNEL<kChromaNV12 | (FORM), __VA_ARGS__>, KERNEL<kChromaI420 | (FORM), __VA_ARGS__>}, \
+   {"decode_nv12_" suffix, "decode_i420_" suffix}}
+const DecodeKernel kDecodeKernels[] = {
+    //            variant         over              alpha straight quant log   nt    stages
+    DECODE_KERNEL(kVariantQuads,  kOverDestination, kAny, kAny,    kAny, kAny, kAny, true,  "quads<alpha,over>", decode_quads_over, 0, kOverDestination),
+    DECODE_KERNEL(kVariantQuads,  kOverColour,      kAny, kAny,    kAny, kAny, kAny, true,  "quads<alpha,over-colour>", decode_quads_over, 0, kOverColour),
+    DECODE_KERNEL(kVariantQuads,  kOverOff,         1,    1,       kAny, kAny, kAny, false, "quads<alpha,straight>", decode_quads, kFormStraight, true, true, true),
+    DECODE_KERNEL(kVariantQuads,  kOverOff,         1,    kAny,    kAny, kAny, kAny, false, "quads<alpha>", decode_quads, 0, true, true, true),
+    DECODE_KERNEL(kVariantQuads,  kOverOff,         0,    kAny,    1,    kAny, 1,    false, "quads<nt,quantiser>", decode_quads, 0, false, true, true),
+    DECODE_KERNEL(kVariantQuads,  kOverOff,         0,    kAny,    1,    kAny, 0,    false, "quads<quantiser>", decode_quads, 0, false, false, true),
+    DECODE_KERNEL(kVariantQuads,  kOverOff,         0,    kAny,    0,    1,    1,    true,  "quads_log<nt>", decode_quads_log, 0, true),
+    DECODE_KERNEL(kVariantQuads,  kOverOff,         0,    kAny,    0,    1,    0,    true,  "quads_log", decode_quads_log, 0, false),
+    DECODE_KERNEL(kVariantQuads,  kOverOff,         0,    kAny,    0,    0,    1,    true,  "quads<nt>", decode_quads, 0, false, true, false),
+    DECODE_KERNEL(kVariantQuads,  kOverOff,         0,    kAny,    0,    0,    0,    true,  "quads", decode_quads, 0, false, false, false),
+    DECODE_KERNEL(kVariantBlocks, kOverDestination, kAny, kAny,    kAny, kAny, kAny, true,  "blocks<alpha,over>", decode_blocks_over, 0, kOverDestination),
+    DECODE_KERNEL(kVariantBlocks, kOverColour,      kAny, kAny,    kAny, kAny, kAny, true,  "blocks<alpha,over-colour>", decode_blocks_over, 0, kOverColour),
+    DECODE_KERNEL(kVariantBlocks, kOverOff,         1,    1,       kAny, kAny, kAny, false, "blocks<alpha,straight>", decode_blocks, kFormStraight, true, true),
+    DECODE_KERNEL(kVariantBlocks, kOverOff,         1,    kAny,    kAny, kAny, kAny, false, "blocks<alpha>", decode_blocks, 0, true, true),
+    DECODE_KERNEL(kVariantBlocks, kOverOff,         0,    kAny,    1,    kAny, kAny, false, "blocks<quantiser>", decode_blocks, 0, false, true),
+    DECODE_KERNEL(kVariantBlocks, kOverOff,         0,    kAny,    0,    kAny, kAny, true,  "blocks", decode_blocks, 0, false, false),
+};
+#undef DECODE_KERNEL
+
 // The kernel of a launch that launch_decode has planned and recorded -- its grid, block and LDS bytes, the band map in `p` --
-// for `variant`, `over`, `quant` (the sRGB mode or an alpha decoder) and `nontemporal`.  The names are what
-// bt709hip_last_kernel_name reports.
-template <uint32_t LAYOUT>
+// for `variant`, `over`, `quant` (the sRGB mode or an alpha decoder) and `nontemporal`.
 const char *launch_decode_kernel(const DecodeParams &p, const dim3 &grid, const dim3 &block, size_t lds, int variant, uint32_t over,
                                  bool has_alpha, bool quant, bool nontemporal, hipStream_t stream) {
-  constexpr bool PLANAR = LAYOUT == kChromaI420;
-  if (variant == kVariantQuads) {
-    if (over == kOverDestination) {
-      hipLaunchKernelGGL((decode_quads_over<LAYOUT, kOverDestination>), grid, block, lds, stream, p);
-      return PLANAR ? "decode_i420_quads<alpha,over>" : "decode_nv12_quads<alpha,over>";
-    }
-    if (over != kOverOff) {
-      hipLaunchKernelGGL((decode_quads_over<LAYOUT, kOverColour>), grid, block, lds, stream, p);
-      return PLANAR ? "decode_i420_quads<alpha,over-colour>" : "decode_nv12_quads<alpha,over-colour>";
-    }
-    if (has_alpha && p.straight_alpha) {
-      hipLaunchKernelGGL((decode_quads<LAYOUT | kFormStraight, true, true, true>), grid, block, lds, stream, p);
-      return PLANAR ? "decode_i420_quads<alpha,straight>" : "decode_nv12_quads<alpha,straight>";
-    }
-    if (has_alpha) {
-      hipLaunchKernelGGL((decode_quads<LAYOUT, true, true, true>), grid, block, lds, stream, p);
-      return PLANAR ? "decode_i420_quads<alpha>" : "decode_nv12_quads<alpha>";
-    }
-    if (quant) {
-      if (nontemporal) hipLaunchKernelGGL((decode_quads<LAYOUT, false, true, true>), grid, block, lds, stream, p);
-      else hipLaunchKernelGGL((decode_quads<LAYOUT, false, false, true>), grid, block, lds, stream, p);
-      if (nontemporal) return PLANAR ? "decode_i420_quads<nt,quantiser>" : "decode_nv12_quads<nt,quantiser>";
-      return PLANAR ? "decode_i420_quads<quantiser>" : "decode_nv12_quads<quantiser>";
-    }
-    if (p.unit1_shift != 0) {  // log-bucket table (the LINEAR mode)
-      if (nontemporal) hipLaunchKernelGGL((decode_quads_log<LAYOUT, true>), grid, block, lds, stream, p);
-      else hipLaunchKernelGGL((decode_quads_log<LAYOUT, false>), grid, block, lds, stream, p);
-      if (nontemporal) return PLANAR ? "decode_i420_quads_log<nt>" : "decode_nv12_quads_log<nt>";
-      return PLANAR ? "decode_i420_quads_log" : "decode_nv12_quads_log";
-    }
-    if (nontemporal) {
-      hipLaunchKernelGGL((decode_quads<LAYOUT, false, true, false>), grid, block, lds, stream, p);
-      return PLANAR ? "decode_i420_quads<nt>" : "decode_nv12_quads<nt>";
-    }
-    hipLaunchKernelGGL((decode_quads<LAYOUT, false, false, false>), grid, block, lds, stream, p);
-    return PLANAR ? "decode_i420_quads" : "decode_nv12_quads";
+  const uint32_t layout = p.chroma_layout == kChromaI420 ? kChromaI420 : kChromaNV12;
+  for (const DecodeKernel &k : kDecodeKernels) {
+    if (k.variant != variant || !selects(k.over, static_cast<int>(over)) || !selects(k.alpha, has_alpha) || !selects(k.straight, p.straight_alpha != 0) ||
+        !selects(k.quant, quant) || !selects(k.log, p.unit1_shift != 0) || !selects(k.nt, nontemporal))
+      continue;
+    hipLaunchKernelGGL(k.fn[layout], grid, block, lds, stream, p);
+    return k.name[layout];
   }
-  if (over == kOverDestination) {
-    hipLaunchKernelGGL((decode_blocks_over<LAYOUT, kOverDestination>), grid, block, lds, stream, p);
-    return PLANAR ? "decode_i420_blocks<alpha,over>" : "decode_nv12_blocks<alpha,over>";
-  }
-  if (over != kOverOff) {
-    hipLaunchKernelGGL((decode_blocks_over<LAYOUT, kOverColour>), grid, block, lds, stream, p);
-    return PLANAR ? "decode_i420_blocks<alpha,over-colour>" : "decode_nv12_blocks<alpha,over-colour>";
-  }
-  if (has_alpha && p.straight_alpha) {
-    hipLaunchKernelGGL((decode_blocks<LAYOUT | kFormStraight, true, true>), grid, block, lds, stream, p);
-    return PLANAR ? "decode_i420_blocks<alpha,straight>" : "decode_nv12_blocks<alpha,straight>";
-  }
-  if (has_alpha) {
-    hipLaunchKernelGGL((decode_blocks<LAYOUT, true, true>), grid, block, lds, stream, p);
-    return PLANAR ? "decode_i420_blocks<alpha>" : "decode_nv12_blocks<alpha>";
-  }
-  if (quant) {
-    hipLaunchKernelGGL((decode_blocks<LAYOUT, false, true>), grid, block, lds, stream, p);
-    return PLANAR ? "decode_i420_blocks<quantiser>" : "decode_nv12_blocks<quantiser>";
-  }
-  hipLaunchKernelGGL((decode_blocks<LAYOUT, false, false>), grid, block, lds, stream, p);
-  return PLANAR ? "decode_i420_blocks" : "decode_nv12_blocks";
+  return nullptr;  // unreachable: the rows of a variant end in one that takes every remaining selector
 }
 
 }  // namespace
@@ -397,32 +317,20 @@ const char *launch_decode(const DecodeParams &p_in, int frames, int variant, boo
   }
   record_launch(grid, block, variant == kVariantQuads ? p.xcd_bands : 0);
   // the plan does not depend on the chroma layout, only the kernel does
-  if (p.chroma_layout == kChromaI420) return launch_decode_kernel<kChromaI420>(p, grid, block, lds, variant, over, has_alpha, quant, nontemporal, stream);
-  return launch_decode_kernel<kChromaNV12>(p, grid, block, lds, variant, over, has_alpha, quant, nontemporal, stream);
+  return launch_decode_kernel(p, grid, block, lds, variant, over, has_alpha, quant, nontemporal, stream);
 }
 
-// the table kernels' dynamic-LDS cap
+// the dynamic-LDS cap of every kernel above that stages a table, both layouts
 hipError_t prepare_kernels() {
-  const void *fns[] = {
-      reinterpret_cast<const void *>(&decode_quads<kChromaNV12, true, true, true>),
-      reinterpret_cast<const void *>(&decode_quads<kChromaNV12, false, true, true>),
-      reinterpret_cast<const void *>(&decode_quads<kChromaNV12, false, false, true>),
-      reinterpret_cast<const void *>(&decode_quads<kChromaNV12, false, true, false>),
-      reinterpret_cast<const void *>(&decode_quads<kChromaNV12, false, false, false>),
-      reinterpret_cast<const void *>(&decode_quads_log<kChromaNV12, true>),
-      reinterpret_cast<const void *>(&decode_quads_log<kChromaNV12, false>),
-      reinterpret_cast<const void *>(&unconvert_packed444<true, false>),
-      reinterpret_cast<const void *>(&unconvert_packed444<false, false>),
-      reinterpret_cast<const void *>(&decode_blocks<kChromaNV12, true, true>),
-      reinterpret_cast<const void *>(&decode_blocks<kChromaNV12, false, true>),
-      reinterpret_cast<const void *>(&decode_blocks<kChromaNV12, false, false>),
-      reinterpret_cast<const void *>(&decode_quads<kChromaI420, false, true, false>),
-      reinterpret_cast<const void *>(&decode_quads<kChromaI420, false, false, false>),
-      reinterpret_cast<const void *>(&decode_quads_log<kChromaI420, true>),
-      reinterpret_cast<const void *>(&decode_quads_log<kChromaI420, false>),
-      reinterpret_cast<const void *>(&decode_blocks<kChromaI420, false, false>),
-  };
-  return raise_lds_cap(fns, kRepLdsBytes);
+  for (const DecodeKernel &k : kDecodeKernels) {
+    const void *fns[] = {reinterpret_cast<const void *>(k.fn[0]), reinterpret_cast<const void *>(k.fn[1])};
+    if (const hipError_t e = k.stages_table ? raise_lds_cap(fns, kRepLdsBytes) : hipSuccess) return e;
+  }
+  for (const UnconvertKernel &k : kUnconvertKernels) {
+    const void *fns[] = {reinterpret_cast<const void *>(k.fn)};
+    if (const hipError_t e = k.stages_table ? raise_lds_cap(fns, kRepLdsBytes) : hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 }  // namespace bt709

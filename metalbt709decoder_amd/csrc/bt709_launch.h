@@ -55,6 +55,10 @@ inline void record_launch(const dim3 &grid, const dim3 &block, uint32_t xcd_band
   }
 }
 
+// A field of a launch table's selector (bt709_kernels.hip, bt709_encode.hip): a value, or kAny
+constexpr int kAny = -1;
+inline bool selects(int want, int have) { return want == kAny || want == have; }
+
 // Raise the dynamic-LDS cap of the kernels (tables can exceed the 64 KiB default; gfx950 has 160 KiB per workgroup).
 template <size_t N>
 inline hipError_t raise_lds_cap(const void *const (&kernels)[N], uint32_t bytes) {

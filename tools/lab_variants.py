@@ -591,14 +591,21 @@ double *lab_trace() {  // seconds: malloc, free, mem_info, warm-up, probe
 #endif
 """),
     # round 6: consecutive one-frame launches on ONE stream without the in-order barrier between them (hipExtAnyOrderLaunch; the header says "not supported on GFX9xx")
+    # (the launch table's one launch line: the experiment's kernel is the row "quads<nt>", decode_quads<layout, false, true, false>)
     ("bt709_kernels.hip",
-     """      hipLaunchKernelGGL((decode_quads<LAYOUT, false, true, false>), grid, block, lds, stream, p);
+     """    hipLaunchKernelGGL(k.fn[layout], grid, block, lds, stream, p);
+    return k.name[layout];
 """,
      """#if defined(BT709_LAB_ANY_ORDER)
-      hipExtLaunchKernelGGL((decode_quads<LAYOUT, false, true, false>), grid, block, lds, stream, nullptr, nullptr, hipExtAnyOrderLaunch, p);
+    if (k.fn[0] == decode_quads<kChromaNV12, false, true, false>) {
+      hipExtLaunchKernelGGL(k.fn[layout], grid, block, lds, stream, nullptr, nullptr, hipExtAnyOrderLaunch, p);
+    } else {
+      hipLaunchKernelGGL(k.fn[layout], grid, block, lds, stream, p);
+    }
 #else
-      hipLaunchKernelGGL((decode_quads<LAYOUT, false, true, false>), grid, block, lds, stream, p);
+    hipLaunchKernelGGL(k.fn[layout], grid, block, lds, stream, p);
 #endif
+    return k.name[layout];
 """),
     ("bt709_kernels.hip",
      """#include <hip/hip_runtime.h>
