@@ -55,7 +55,7 @@ inline void record_launch(const dim3 &grid, const dim3 &block, uint32_t xcd_band
   }
 }
 
-// A field of a launch table's selector (bt709_kernels.hip, bt709_encode.hip): a value, or kAny
+// A field of a launch table's selector (bt709_kernels.hip, bt709_encode.hip, the rescale files): a value, or kAny
 constexpr int kAny = -1;
 inline bool selects(int want, int have) { return want == kAny || want == have; }
 
@@ -67,6 +67,10 @@ inline hipError_t raise_lds_cap(const void *const (&kernels)[N], uint32_t bytes)
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
+}
+template <typename... Params>
+inline hipError_t raise_lds_cap(void (*kernel)(Params...), uint32_t bytes) {  // of one row of a launch table
+  return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
 }
 
 }  // namespace bt709

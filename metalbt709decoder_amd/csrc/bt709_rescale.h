@@ -109,6 +109,15 @@ __device__ __forceinline__ uint32_t encode_byte(const RescaleLookup &r, float a)
   return e.y + (a >= __uint_as_float(e.x) ? 1u : 0u);
 }
 
+// The encode side alone, for UNIT-RANGE values (render_scaled and decode_nv12_scaled_f16: their filters' sums are the table's own
+// domain, so quarter_unscale = 1 and the edges are staged as they are): the log-bucket table in one copy at LDS address enc_off
+__device__ __forceinline__ RescaleLookup unit_encode_lookup(uint32_t enc_off, float log_add, uint32_t log_first) {
+  RescaleLookup r = {};
+  r.enc_shift = 3, r.enc_off = enc_off, r.enc_add = log_add, r.quarter_unscale = 1.0f;
+  r.enc_log_off = enc_off - (log_first << r.enc_shift);
+  return r;
+}
+
 // linear-light values (times 2^-40) of 12 saturated channel values: kLinBatch buckets in flight per wait
 #ifndef BT709_LIN_BATCH
 #define BT709_LIN_BATCH 6
@@ -191,10 +200,28 @@ __device__ __forceinline__ uint32_t half_alpha_arith(float a00, float a01, float
 }  // namespace
 
 hipError_t prepare_scaled_kernels();  // bt709_rescale_scaled.hip; called by prepare_rescale_kernels (bt709_rescale_half.hip)
-// bt709_rescale_f16.hip: the any-ratio kernel through the RGBA16Float intermediate (DecodeParams::scale_f16), launched by
-// launch_decode_scaled under its own plan -- the instantiation for a tap form, the dynamic LDS it needs
-const void *scaled_f16_kernel(int taps, bool has_alpha, bool curve, uint32_t over = 0);  // over: kOverOff, or the *_over form of that mode (alpha decoders)
-size_t scaled_f16_lds(const DecodeParams &p);
-hipError_t prepare_scaled_f16_kernels();  // called by prepare_scaled_kernels
+
+// One row per selectable any-ratio kernel, in the shape of kDecodeKernels (bt709_kernels.hip).  The selector: tap form, alpha plane,
+// `curve` (the decoder's gamma has a half table: the RGBA16Float intermediate only), over mode -- each a value or kAny, the FIRST
+// matching row is the launch's kernel.  `persistent`: the form runs the item loop (launch_decode_scaled plans the grid from it);
+// `name`: what bt709hip_last_kernel_name reports.  launch_decode_scaled looks a row up, prepare_scaled_kernels walks them all.
+struct ScaledKernel {
+  int taps, alpha, curve, over;
+  bool persistent;
+  void (*fn)(const DecodeParams);
+  const char *name;
+};
+struct ScaledKernels {  // the rows of one table
+  const ScaledKernel *first, *last;
+  template <size_t N>
+  ScaledKernels(const ScaledKernel (&rows)[N]) : first(rows), last(rows + N) {}
+  const ScaledKernel *begin() const { return first; }
+  const ScaledKernel *end() const { return last; }
+};
+// bt709_rescale_f16.hip: the rows through the RGBA16Float intermediate (DecodeParams::scale_f16), and the dynamic LDS they need
+ScaledKernels scaled_f16_kernels();
+inline size_t scaled_f16_lds(const DecodeParams &p) {
+  return (p.half_table_bytes ? kHalfPlanLds : 0u) + static_cast<size_t>(p.table_encode_bytes);
+}
 
 }  // namespace bt709

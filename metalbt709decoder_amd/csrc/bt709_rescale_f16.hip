@@ -76,29 +76,13 @@ struct HalfLight {
     if constexpr (OVER != kOverOff) ov = stage_over_lin(lds_raw, p, kEncodeLds + p.table_encode_bytes);                                  \
   }                                                                                                                                      \
   __syncthreads();                                                                                                                       \
-  RescaleLookup r = {};                                                                                                                  \
-  r.enc_shift = 3;                                                                                                                       \
-  r.enc_off = lds_address(lds_raw) + kEncodeLds;                                                                                         \
-  r.enc_add = p.encode_log_add;                                                                                                          \
-  r.enc_log_off = r.enc_off - (p.encode_log_first << r.enc_shift);                                                                       \
+  RescaleLookup r = unit_encode_lookup(lds_address(lds_raw) + kEncodeLds, p.encode_log_add, p.encode_log_first);                         \
   asm volatile("" : "+v"(r.enc_log_off)); /* ONE addend of the v_lshl_add */                                                             \
-  r.quarter_unscale = 1.0f;               /* the sums are unit-range values: the table's own domain */                                   \
   HalfLookup t;                                                                                                                          \
   t.index_scale = p.half_index_scale;                                                                                                    \
   t.below2 = (p.half_h_min - 1u) * 0x10001u;                                                                                             \
   const HalfLight<CURVE> light = {t, r};                                                                                                 \
-  /* the persistent item loop of decode_nv12_scaled: an item = 256 columns x one strip of one frame, column tiles fastest */             \
-  const uint32_t strips = (p.out_height + p.scaled_rows - 1) / p.scaled_rows;                                                            \
-  for (uint32_t item = blockIdx.x; item < p.tile_rows; item += gridDim.x) {                                                              \
-    const uint32_t tile = item % p.tiles_x, rest = item / p.tiles_x;                                                                     \
-    const uint32_t strip = rest % strips, frame = rest / strips;                                                                         \
-    const FramePlanes f = frame_planes(p, frame);                                                                                        \
-    const uint32_t ox = tile * blockDim.x + threadIdx.x;                                                                                 \
-    const uint32_t oy0 = strip * p.scaled_rows;                                                                                          \
-    const StripTaps vt = strip_taps(oy0, p.scale_y); /* before any lane is masked off */                                                 \
-    if (TAPS == TAPS_SHARED || TAPS == TAPS_ONCE || ox < p.out_width)                                                                    \
-      scaled_strip<TAPS, HAS_ALPHA, OVER>(p, light, f, ox, oy0, min(oy0 + p.scaled_rows, p.out_height), vt, ov);                         \
-  }
+  BT709_SCALED_ITEM_LOOP(HAS_ALPHA, OVER, light, ov)
 
 template <int TAPS, bool HAS_ALPHA, bool CURVE>
 __global__ void __launch_bounds__(kBlockThreads)
@@ -115,40 +99,20 @@ decode_nv12_scaled_f16_over(const DecodeParams p) {
 }
 #undef BT709_SCALED_F16_BODY
 
-// An alpha decoder runs the sRGB mode, which has a curve: 5 tap forms x (curve, curve + alpha, no curve)
-const void *scaled_f16_kernel(int taps, bool has_alpha, bool curve, uint32_t over) {
-#define BT709_PICK_F16(T)                                                                                        \
-  case T:                                                                                                        \
-    if (has_alpha && over == kOverDestination) return reinterpret_cast<const void *>(&decode_nv12_scaled_f16_over<T, kOverDestination>); \
-    if (has_alpha && over != kOverOff) return reinterpret_cast<const void *>(&decode_nv12_scaled_f16_over<T, kOverColour>);               \
-    return has_alpha ? reinterpret_cast<const void *>(&decode_nv12_scaled_f16<T, true, true>)                    \
-                     : (curve ? reinterpret_cast<const void *>(&decode_nv12_scaled_f16<T, false, true>)          \
-                              : reinterpret_cast<const void *>(&decode_nv12_scaled_f16<T, false, false>))
-  switch (taps) {
-    BT709_PICK_F16(TAPS_ONCE);
-    BT709_PICK_F16(TAPS_SHARED);
-    BT709_PICK_F16(TAPS_WIDE);
-    BT709_PICK_F16(TAPS_PAIRS);
-    default: BT709_PICK_F16(TAPS_BYTES);
-  }
-#undef BT709_PICK_F16
-}
+// The rows of this file's kernels (bt709_rescale.h ScaledKernel: {taps, alpha, curve, over, persistent, kernel, name}), stamped out
+// per tap form; launch_decode_scaled looks them up.  Every form runs the item loop (see the head of the file).  An alpha decoder
+// runs the sRGB mode, which has a curve: its rows take any `curve`.  The name does not say whether a colour decoder's gamma has one.
+#define SCALED_F16_KERNELS(T)                                                                                                            \
+  {T, 1, kAny, kOverDestination, true, decode_nv12_scaled_f16_over<T, kOverDestination>, "decode_nv12_scaled_f16<alpha,over>"},          \
+  {T, 1, kAny, kOverColour, true, decode_nv12_scaled_f16_over<T, kOverColour>, "decode_nv12_scaled_f16<alpha,over-colour>"},             \
+  {T, 1, kAny, kOverOff, true, decode_nv12_scaled_f16<T, true, true>, "decode_nv12_scaled_f16<alpha>"},                                  \
+  {T, 0, 1, kAny, true, decode_nv12_scaled_f16<T, false, true>, "decode_nv12_scaled_f16"},                                               \
+  {T, 0, 0, kAny, true, decode_nv12_scaled_f16<T, false, false>, "decode_nv12_scaled_f16"}
+static const ScaledKernel kScaledF16Kernels[] = {
+    SCALED_F16_KERNELS(TAPS_ONCE), SCALED_F16_KERNELS(TAPS_SHARED), SCALED_F16_KERNELS(TAPS_WIDE), SCALED_F16_KERNELS(TAPS_PAIRS), SCALED_F16_KERNELS(TAPS_BYTES),
+};
+#undef SCALED_F16_KERNELS
 
-size_t scaled_f16_lds(const DecodeParams &p) {
-  return (p.half_table_bytes ? kHalfPlanLds : 0u) + static_cast<size_t>(p.table_encode_bytes);
-}
-
-hipError_t prepare_scaled_f16_kernels() {
-  const void *fns[25];
-  int n = 0;
-  for (int taps : {TAPS_BYTES, TAPS_PAIRS, TAPS_WIDE, TAPS_SHARED, TAPS_ONCE}) {
-    fns[n++] = scaled_f16_kernel(taps, true, true, kOverDestination);
-    fns[n++] = scaled_f16_kernel(taps, true, true, kOverColour);
-    fns[n++] = scaled_f16_kernel(taps, true, true);
-    fns[n++] = scaled_f16_kernel(taps, false, true);
-    fns[n++] = scaled_f16_kernel(taps, false, false);
-  }
-  return raise_lds_cap(fns, kRepLdsBytes);
-}
+ScaledKernels scaled_f16_kernels() { return kScaledF16Kernels; }
 
 }  // namespace bt709

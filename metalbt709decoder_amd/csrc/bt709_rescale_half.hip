@@ -345,6 +345,37 @@ decode_nv12_half_rep(const DecodeParams p) {
 #define BT709_REP_STEP 2  // tile rows per step of the persistent kernel (loads run one step ahead)
 #endif
 
+// One row per selectable exact-2:1 kernel, in the shape of kDecodeKernels (bt709_kernels.hip).  The selector: `rep` the persistent
+// form, `wide` the quad form of the short-lived one, alpha plane, non-temporal loads and stores -- each a value or kAny, the FIRST
+// matching row is the launch's kernel.  Both launchers look their row up here; prepare_rescale_kernels walks the rows.  The short-lived
+// alpha forms take any `nt`: the wide one is always non-temporal, the narrow ones (byte loads) never, whatever the caller asks.
+const struct HalfKernel {
+  int rep, wide, alpha, nt;
+  void (*fn)(const DecodeParams);
+  const char *name;
+} kHalfKernels[] = {
+    // rep wide  alpha nt
+    {0,    1,    1,    kAny, decode_nv12_half<true, true, true>, "decode_nv12_half<wide,alpha>"},
+    {0,    0,    1,    kAny, decode_nv12_half<false, false, true>, "decode_nv12_half<narrow,alpha>"},
+    {0,    1,    0,    1,    decode_nv12_half<true, true, false>, "decode_nv12_half<wide>"},
+    {0,    1,    0,    0,    decode_nv12_half<false, true, false>, "decode_nv12_half<wide>"},
+    {0,    0,    0,    kAny, decode_nv12_half<false, false, false>, "decode_nv12_half<narrow>"},
+    {1,    kAny, 1,    1,    decode_nv12_half_rep<true, BT709_REP_STEP, true>, "decode_nv12_half_rep<alpha>"},
+    {1,    kAny, 1,    0,    decode_nv12_half_rep<false, BT709_REP_STEP, true>, "decode_nv12_half_rep<alpha>"},
+    {1,    kAny, 0,    1,    decode_nv12_half_rep<true, BT709_REP_STEP, false>, "decode_nv12_half_rep"},
+    {1,    kAny, 0,    0,    decode_nv12_half_rep<false, BT709_REP_STEP, false>, "decode_nv12_half_rep"},
+};
+
+static const char *launch_half_kernel(const DecodeParams &p, const dim3 &grid, const dim3 &block, size_t lds, bool rep, bool wide, bool has_alpha,
+                                      bool nontemporal, hipStream_t stream) {
+  for (const HalfKernel &k : kHalfKernels) {
+    if (!selects(k.rep, rep) || !selects(k.wide, wide) || !selects(k.alpha, has_alpha) || !selects(k.nt, nontemporal)) continue;
+    hipLaunchKernelGGL(k.fn, grid, block, lds, stream, p);
+    return k.name;
+  }
+  return nullptr;  // unreachable: the rows cover every selector
+}
+
 const char *launch_decode_half(const DecodeParams &p, int frames, bool wide, bool has_alpha, bool nontemporal,
                                uint32_t grid_x, uint32_t block_threads, hipStream_t stream) {
   const uint32_t by = wide ? quads_rows_per_block(block_threads, grid_x) : 1;
@@ -352,18 +383,7 @@ const char *launch_decode_half(const DecodeParams &p, int frames, bool wide, boo
   const dim3 block(block_threads, by, 1);
   const size_t lds = static_cast<size_t>(p.table_linear_bytes) + p.table_encode_bytes;
   record_launch(grid, block, 0);
-  if (has_alpha) {
-    if (wide) hipLaunchKernelGGL((decode_nv12_half<true, true, true>), grid, block, lds, stream, p);
-    else hipLaunchKernelGGL((decode_nv12_half<false, false, true>), grid, block, lds, stream, p);
-    return wide ? "decode_nv12_half<wide,alpha>" : "decode_nv12_half<narrow,alpha>";
-  }
-  if (wide) {
-    if (nontemporal) hipLaunchKernelGGL((decode_nv12_half<true, true, false>), grid, block, lds, stream, p);
-    else hipLaunchKernelGGL((decode_nv12_half<false, true, false>), grid, block, lds, stream, p);
-    return "decode_nv12_half<wide>";
-  }
-  hipLaunchKernelGGL((decode_nv12_half<false, false, false>), grid, block, lds, stream, p);
-  return "decode_nv12_half<narrow>";
+  return launch_half_kernel(p, grid, block, lds, false, wide, has_alpha, nontemporal, stream);
 }
 
 const char *launch_decode_half_rep(const DecodeParams &p_in, int frames, bool has_alpha, bool nontemporal, uint32_t workgroups,
@@ -391,32 +411,13 @@ const char *launch_decode_half_rep(const DecodeParams &p_in, int frames, bool ha
   p.cursor_f = (workgroups / p.tiles_x) / row_pairs;
   const size_t lds = (static_cast<size_t>(p.table_linear_bytes) << r1) + (static_cast<size_t>(enc_bytes) << r2);
   record_launch(dim3(workgroups), dim3(threads), 0);
-  if (has_alpha) {
-    if (nontemporal) hipLaunchKernelGGL((decode_nv12_half_rep<true, BT709_REP_STEP, true>), dim3(workgroups), dim3(threads), lds, stream, p);
-    else hipLaunchKernelGGL((decode_nv12_half_rep<false, BT709_REP_STEP, true>), dim3(workgroups), dim3(threads), lds, stream, p);
-    return "decode_nv12_half_rep<alpha>";
-  }
-  if (nontemporal)
-    hipLaunchKernelGGL((decode_nv12_half_rep<true, BT709_REP_STEP, false>), dim3(workgroups), dim3(threads), lds, stream, p);
-  else
-    hipLaunchKernelGGL((decode_nv12_half_rep<false, BT709_REP_STEP, false>), dim3(workgroups), dim3(threads), lds, stream, p);
-  return "decode_nv12_half_rep";
+  return launch_half_kernel(p, dim3(workgroups), dim3(threads), lds, true, false, has_alpha, nontemporal, stream);
 }
 
 hipError_t prepare_rescale_kernels() {
-  const void *fns[] = {
-      reinterpret_cast<const void *>(&decode_nv12_half<true, true, false>),
-      reinterpret_cast<const void *>(&decode_nv12_half<false, true, false>),
-      reinterpret_cast<const void *>(&decode_nv12_half<false, false, false>),
-      reinterpret_cast<const void *>(&decode_nv12_half<true, true, true>),
-      reinterpret_cast<const void *>(&decode_nv12_half<false, false, true>),
-      reinterpret_cast<const void *>(&decode_nv12_half_rep<true, BT709_REP_STEP, false>),
-      reinterpret_cast<const void *>(&decode_nv12_half_rep<false, BT709_REP_STEP, false>),
-      reinterpret_cast<const void *>(&decode_nv12_half_rep<true, BT709_REP_STEP, true>),
-      reinterpret_cast<const void *>(&decode_nv12_half_rep<false, BT709_REP_STEP, true>),
-  };
-  const hipError_t e = raise_lds_cap(fns, kRepLdsBytes);
-  return e != hipSuccess ? e : prepare_scaled_kernels();
+  for (const HalfKernel &k : kHalfKernels)
+    if (const hipError_t e = raise_lds_cap(k.fn, kRepLdsBytes)) return e;
+  return prepare_scaled_kernels();
 }
 
 }  // namespace bt709

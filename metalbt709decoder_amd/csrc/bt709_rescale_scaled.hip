@@ -6,6 +6,8 @@
 //   decode_nv12_scaled_over   the same for an alpha decoder, each word blended over the destination or a colour before the store
 //   render_scaled          pass 2 alone from an 8-bit or RGBA16Float intermediate
 // Both walk a strip with walk_strip; each keeps its own fetch, its own conversion to linear light, its encode and its store.
+// Launch selection is a table: kScaledKernels here, bt709_rescale_f16.hip's rows behind scaled_f16_kernels(), kRenderKernels for
+// pass 2 -- a launch looks its row up, prepare_scaled_kernels walks all three.
 #include <atomic>
 
 #include "bt709_scaled_strip.h"
@@ -47,24 +49,13 @@ namespace bt709 {
 //  TAPS_ONCE as persistent workgroups: 1080p -> 4K x 8 24.7 against 19.8 us (profiles/r06_ab_scaled_share.txt).
 //  No one-generation cut of short launches: one 4K -> 1440p frame 19.6 against 18.8 us (profiles/r06_ab_scaled_ahead.txt).)
 
-
 // The kernel's walk behind its staged tables, as TEXT: decode_nv12_scaled_over below runs the same walk with scaled_strip in its
 // over form, and the walk has to sit in the kernel function itself -- in a function that both kernels call, hipcc takes blockIdx /
 // blockDim through the generic implicit-argument code and schedules the plain kernels' persistent forms differently, and their
 // instruction streams are pinned (profiles/LAB.md, "Round 11").
 #define BT709_SCALED_WALK(HAS_ALPHA, OVER, ov)                                                                                           \
   if (PERSISTENT) {                                                                                                                      \
-    const uint32_t strips = (p.out_height + p.scaled_rows - 1) / p.scaled_rows;                                                          \
-    for (uint32_t item = blockIdx.x; item < p.tile_rows; item += gridDim.x) {                                                            \
-      const uint32_t tile = item % p.tiles_x, rest = item / p.tiles_x;                                                                   \
-      const uint32_t strip = rest % strips, frame = rest / strips;                                                                       \
-      const FramePlanes f = frame_planes(p, frame);                                                                                      \
-      const uint32_t ox = tile * blockDim.x + threadIdx.x;                                                                               \
-      const uint32_t oy0 = strip * p.scaled_rows;                                                                                        \
-      const StripTaps vt = strip_taps(oy0, p.scale_y); /* before any lane is masked off */                                               \
-      if (TAPS == TAPS_SHARED || TAPS == TAPS_ONCE || ox < p.out_width)                                                                  \
-        scaled_strip<TAPS, HAS_ALPHA, OVER>(p, Srgb8Light{r}, f, ox, oy0, min(oy0 + p.scaled_rows, p.out_height), vt, ov);               \
-    }                                                                                                                                    \
+    BT709_SCALED_ITEM_LOOP(HAS_ALPHA, OVER, Srgb8Light{r}, ov)                                                                           \
     return;                                                                                                                              \
   }                                                                                                                                      \
   const FramePlanes f = frame_planes(p, blockIdx.z);                                                                                     \
@@ -131,12 +122,7 @@ render_scaled(const RenderParams p) {
     if (lds_address(lds_raw) != 0u) __builtin_trap();
   }
   __syncthreads();
-  RescaleLookup r = {};
-  r.enc_shift = 3;
-  r.enc_off = 1024u;  // behind lin[256]
-  r.enc_add = p.encode_log_add;
-  r.enc_log_off = r.enc_off - (p.encode_log_first << r.enc_shift);
-  r.quarter_unscale = 1.0f;  // the filter's sums are unit-range values here: the table's own domain, edges staged as they are
+  const RescaleLookup r = unit_encode_lookup(1024u, p.encode_log_add, p.encode_log_first);  // behind lin[256]
   typedef __attribute__((address_space(3))) const float *LdsFloatPtr;
   uint32_t two = 2u;  // SDWA operands cannot be inline constants
   asm("" : "+v"(two));
@@ -237,21 +223,30 @@ int scaled_taps(const DecodeParams &p, uint32_t in_align) {
   return taps;
 }
 
-// the by-wave forms run one workgroup per item (dispatched by the hardware), the per-lane forms persistent workgroups
-const void *scaled_kernel(int taps, bool has_alpha, uint32_t over = kOverOff) {
-#define BT709_PICK_SCALED(T, P)                                                                                                            \
-  case T:                                                                                                                                  \
-    if (over == kOverDestination) return reinterpret_cast<const void *>(&decode_nv12_scaled_over<T, P, kOverDestination>);                 \
-    if (over != kOverOff) return reinterpret_cast<const void *>(&decode_nv12_scaled_over<T, P, kOverColour>);                              \
-    return has_alpha ? reinterpret_cast<const void *>(&decode_nv12_scaled<T, true, P>) : reinterpret_cast<const void *>(&decode_nv12_scaled<T, false, P>)
-  switch (taps) {
-    BT709_PICK_SCALED(TAPS_ONCE, false);
-    BT709_PICK_SCALED(TAPS_SHARED, false);
-    BT709_PICK_SCALED(TAPS_WIDE, true);
-    BT709_PICK_SCALED(TAPS_PAIRS, true);
-    default: BT709_PICK_SCALED(TAPS_BYTES, true);
-  }
-#undef BT709_PICK_SCALED
+// The rows of this file's kernels (bt709_rescale.h ScaledKernel: {taps, alpha, curve, over, persistent, kernel, name}), stamped out
+// per tap form.  The by-wave forms run one workgroup per item (dispatched by the hardware), the per-lane forms persistent
+// workgroups: SCALED_KERNELS' second argument is both the template argument and the row's `persistent`.
+#define SCALED_KERNELS(T, P)                                                                                                             \
+  {T, 1, kAny, kOverDestination, P, decode_nv12_scaled_over<T, P, kOverDestination>, "decode_nv12_scaled<alpha,over>"},                  \
+  {T, 1, kAny, kOverColour, P, decode_nv12_scaled_over<T, P, kOverColour>, "decode_nv12_scaled<alpha,over-colour>"},                     \
+  {T, 1, kAny, kOverOff, P, decode_nv12_scaled<T, true, P>, "decode_nv12_scaled<alpha>"},                                                \
+  {T, 0, kAny, kAny, P, decode_nv12_scaled<T, false, P>, "decode_nv12_scaled"}
+const ScaledKernel kScaledKernels[] = {
+    SCALED_KERNELS(TAPS_ONCE, false), SCALED_KERNELS(TAPS_SHARED, false), SCALED_KERNELS(TAPS_WIDE, true), SCALED_KERNELS(TAPS_PAIRS, true), SCALED_KERNELS(TAPS_BYTES, true),
+};
+#undef SCALED_KERNELS
+
+// pass 2 alone: [the intermediate is RGBA16Float]
+const struct RenderKernel {
+  void (*fn)(const RenderParams);
+  const char *name;
+} kRenderKernels[2] = {{render_scaled<false>, "render_scaled<bgra8>"}, {render_scaled<true>, "render_scaled<rgba16f>"}};
+
+// the row of a launch: through the RGBA16Float intermediate (`f16`) bt709_rescale_f16.hip's, else this file's
+const ScaledKernel *scaled_kernel(bool f16, int taps, bool has_alpha, bool curve, uint32_t over) {
+  for (const ScaledKernel &k : f16 ? scaled_f16_kernels() : ScaledKernels(kScaledKernels))
+    if (selects(k.taps, taps) && selects(k.alpha, has_alpha) && selects(k.curve, curve) && selects(k.over, static_cast<int>(over))) return &k;
+  return nullptr;  // unreachable: the rows of a tap form end in one that takes every remaining selector
 }
 
 // As many workgroups as the chip holds at once (what the registers and the tables' LDS allow per CU).  The answer
@@ -310,9 +305,9 @@ const char *launch_render_scaled(const RenderParams &p_in, int frames, bool in_r
   const dim3 grid(cols, (p.out_height + rows - 1) / rows, static_cast<uint32_t>(frames));
   const size_t lds = static_cast<size_t>(p.table_encode_bytes) + 1024;
   record_scaled_launch(ScaledLaunchRecord{{grid.x, grid.y, grid.z}, {kBlockThreads, 1, 1}, 0, rows, 0, 0, 0, 0, static_cast<uint64_t>(grid.x) * grid.y * grid.z});
-  if (in_rgba16f) hipLaunchKernelGGL(render_scaled<true>, grid, dim3(kBlockThreads), lds, stream, p);
-  else hipLaunchKernelGGL(render_scaled<false>, grid, dim3(kBlockThreads), lds, stream, p);
-  return in_rgba16f ? "render_scaled<rgba16f>" : "render_scaled<bgra8>";
+  const RenderKernel &k = kRenderKernels[in_rgba16f];
+  hipLaunchKernelGGL(k.fn, grid, dim3(kBlockThreads), lds, stream, p);
+  return k.name;
 }
 
 const char *launch_decode_scaled(const DecodeParams &p_in, int frames, bool has_alpha, uint32_t in_align,
@@ -321,9 +316,14 @@ const char *launch_decode_scaled(const DecodeParams &p_in, int frames, bool has_
   const uint32_t cus = compute_units ? compute_units : 256u, nframes = static_cast<uint32_t>(frames);
   if (!scaled_planes_fit(p, has_alpha)) return nullptr;  // row offsets are formed in 32 bits (bt709_kernels.h)
   const int taps = scaled_taps(p, in_align);
-  // through the RGBA16Float intermediate (bt709_rescale_f16.hip): the same plan, every tap form persistent
+  // through the RGBA16Float intermediate (bt709_rescale_f16.hip): the same plan; every row of that file is persistent
   const bool f16 = p.scale_f16 != 0;
-  const bool by_wave = taps == TAPS_ONCE || taps == TAPS_SHARED, persistent = f16 || !by_wave;
+  // BT709HIP_OPT_SCALED_OVER: the *_over kernels (the one launched is the one whose occupancy sizes the grid), lin[256] behind their tables
+  const uint32_t over = has_alpha ? p.over_mode : kOverOff;
+  const ScaledKernel *k = scaled_kernel(f16, taps, has_alpha, p.half_table_bytes != 0, over);
+  if (!k) return nullptr;
+  const void *fn = reinterpret_cast<const void *>(k->fn);
+  const bool by_wave = taps == TAPS_ONCE || taps == TAPS_SHARED, persistent = k->persistent;
   // variant builds: 0 = the by-wave forms of that mode get one workgroup per item (the item loop makes one trip), as the 8-bit
   // kernel's do -- and stage their 45 KiB of tables per item (profiles/LAB.md, "Round 9")
 #ifndef BT709_SCALED_F16_WAVE_LOOP
@@ -337,10 +337,7 @@ const char *launch_decode_scaled(const DecodeParams &p_in, int frames, bool has_
   if (by_wave && rows > static_cast<uint32_t>(kScaledAheadWave + 1)) rows -= rows % static_cast<uint32_t>(kScaledAheadWave + 1);
   const size_t lds = f16 ? scaled_f16_lds(p) : static_cast<size_t>(p.table_linear_bytes) + p.table_encode_bytes;
   const dim3 block(kBlockThreads);
-  // BT709HIP_OPT_SCALED_OVER: the *_over kernels (the one launched is the one whose occupancy sizes the grid), lin[256] behind their tables
-  const uint32_t over = has_alpha ? p.over_mode : kOverOff;
   const size_t lds_launch = lds + (over != kOverOff ? kOverLinBytes : 0u);
-  const void *fn = f16 ? scaled_f16_kernel(taps, has_alpha, p.half_table_bytes != 0, over) : scaled_kernel(taps, has_alpha, over);
   const uint64_t resident = resident_workgroups(fn, lds_launch, cus);
   const uint32_t balanced_rows = one_generation_rows(cols, p.out_height, nframes, resident, max_rows, by_wave);
   if (balanced_rows) rows = balanced_rows;
@@ -358,27 +355,16 @@ const char *launch_decode_scaled(const DecodeParams &p_in, int frames, bool has_
                                           balanced_rows ? 1u : 0u, static_cast<uint32_t>(resident), 0, items});
   void *args[] = {&p};
   (void)hipLaunchKernel(fn, grid, block, args, lds_launch, stream);  // a failure is picked up by the caller's hipGetLastError
-  if (over == kOverDestination) return f16 ? "decode_nv12_scaled_f16<alpha,over>" : "decode_nv12_scaled<alpha,over>";
-  if (over != kOverOff) return f16 ? "decode_nv12_scaled_f16<alpha,over-colour>" : "decode_nv12_scaled<alpha,over-colour>";
-  if (f16) return has_alpha ? "decode_nv12_scaled_f16<alpha>" : "decode_nv12_scaled_f16";
-  return has_alpha ? "decode_nv12_scaled<alpha>" : "decode_nv12_scaled";
+  return k->name;
 }
 
 hipError_t prepare_scaled_kernels() {
-  const void *fns[] = {
-      scaled_kernel(TAPS_BYTES, false), scaled_kernel(TAPS_PAIRS, false), scaled_kernel(TAPS_WIDE, false),
-      scaled_kernel(TAPS_SHARED, false), scaled_kernel(TAPS_ONCE, false),
-      scaled_kernel(TAPS_BYTES, true), scaled_kernel(TAPS_PAIRS, true), scaled_kernel(TAPS_WIDE, true),
-      scaled_kernel(TAPS_SHARED, true), scaled_kernel(TAPS_ONCE, true),
-      scaled_kernel(TAPS_BYTES, true, kOverDestination), scaled_kernel(TAPS_PAIRS, true, kOverDestination), scaled_kernel(TAPS_WIDE, true, kOverDestination),
-      scaled_kernel(TAPS_SHARED, true, kOverDestination), scaled_kernel(TAPS_ONCE, true, kOverDestination),
-      scaled_kernel(TAPS_BYTES, true, kOverColour), scaled_kernel(TAPS_PAIRS, true, kOverColour), scaled_kernel(TAPS_WIDE, true, kOverColour),
-      scaled_kernel(TAPS_SHARED, true, kOverColour), scaled_kernel(TAPS_ONCE, true, kOverColour),
-      reinterpret_cast<const void *>(&render_scaled<true>),
-      reinterpret_cast<const void *>(&render_scaled<false>),
-  };
-  if (const hipError_t e = raise_lds_cap(fns, kRepLdsBytes)) return e;
-  return prepare_scaled_f16_kernels();
+  for (const ScaledKernels &rows : {ScaledKernels(kScaledKernels), scaled_f16_kernels()})
+    for (const ScaledKernel &k : rows)
+      if (const hipError_t e = raise_lds_cap(k.fn, kRepLdsBytes)) return e;
+  for (const RenderKernel &k : kRenderKernels)
+    if (const hipError_t e = raise_lds_cap(k.fn, kRepLdsBytes)) return e;
+  return hipSuccess;
 }
 
 }  // namespace bt709

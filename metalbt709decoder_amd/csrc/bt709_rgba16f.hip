@@ -259,7 +259,7 @@ decode_nv12_rgba16f(const DecodeParams p, const HalfParams hp) {
   }
 }
 
-// The 24 instantiations the launcher picks from: [shape: 0 large, 1 narrow, 2 small][curve][alpha plane][2-byte loads]
+// The instantiations the launcher picks from, and prepare_rgba16f_kernels walks: [shape: 0 large, 1 narrow, 2 small][curve][alpha plane][2-byte loads]
 typedef void (*F16Kernel)(DecodeParams, HalfParams);
 #define BT709_F16_AP(C, SH)                                                                                                    \
   {{&decode_nv12_rgba16f<C, false, false, SH.nb, SH.rp>, &decode_nv12_rgba16f<C, false, true, SH.nb, SH.rp>},                  \
@@ -325,9 +325,12 @@ const char *launch_decode_rgba16f(const DecodeParams &p_in, const HalfParams &hp
 }
 
 hipError_t prepare_rgba16f_kernels() {
-  const void *fns[24];
-  for (int i = 0; i < 24; ++i) fns[i] = reinterpret_cast<const void *>((&kF16Kernels[0][0][0][0])[i]);
-  return raise_lds_cap(fns, kRepLdsBytes);
+  for (const auto &shape : kF16Kernels)
+    for (const auto &curve : shape)
+      for (const auto &alpha : curve)
+        for (const F16Kernel fn : alpha)
+          if (const hipError_t e = raise_lds_cap(fn, kRepLdsBytes)) return e;
+  return hipSuccess;
 }
 
 }  // namespace bt709

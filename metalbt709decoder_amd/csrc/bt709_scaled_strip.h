@@ -1,7 +1,8 @@
 // Device-side building blocks shared by the any-ratio rescale kernels: decode_nv12_scaled and render_scaled
 // (bt709_rescale_scaled.hip) and decode_nv12_scaled_f16 (bt709_rescale_f16.hip).  The sampling geometry (strip_taps, column_taps,
 // row_taps), the row cache and the filter (RowCache), the strip walk (walk_strip) and the fused kernels' strip (scaled_strip:
-// fetch, tap forms, store) -- one copy of each, so the kernels agree bit for bit on taps, weights and summation order.
+// fetch, tap forms, store) and the persistent item loop of the fused kernels (BT709_SCALED_ITEM_LOOP) -- one copy of each, so the
+// kernels agree bit for bit on taps, weights and summation order.
 #pragma once
 #include "bt709_over.h"
 #include "bt709_rescale.h"
@@ -476,6 +477,22 @@ __device__ __forceinline__ void scaled_strip(const DecodeParams &p, const TapLig
   constexpr int D = BY_WAVE ? kScaledAheadWave : kScaledAhead;
   walk_strip<D, D == 1 && !BY_WAVE>(vt, oy0, oy1, p.height, fetch_row, landed, output_row);
 }
+
+// The PERSISTENT ITEM LOOP of a fused kernel <TAPS, ...> with parameter block `p`, as TEXT (it has to sit in the kernel function
+// itself: bt709_rescale_scaled.hip, BT709_SCALED_WALK): workgroup g takes the items g, g + G, ... of the launch, an item = 256 output
+// columns x one strip of one frame, column tiles fastest (launch_decode_scaled fills tiles_x and tile_rows).  `light`: the TapLight.
+#define BT709_SCALED_ITEM_LOOP(HAS_ALPHA, OVER, light, ov)                                                                               \
+  const uint32_t strips = (p.out_height + p.scaled_rows - 1) / p.scaled_rows;                                                            \
+  for (uint32_t item = blockIdx.x; item < p.tile_rows; item += gridDim.x) {                                                              \
+    const uint32_t tile = item % p.tiles_x, rest = item / p.tiles_x;                                                                     \
+    const uint32_t strip = rest % strips, frame = rest / strips;                                                                         \
+    const FramePlanes f = frame_planes(p, frame);                                                                                        \
+    const uint32_t ox = tile * blockDim.x + threadIdx.x;                                                                                 \
+    const uint32_t oy0 = strip * p.scaled_rows;                                                                                          \
+    const StripTaps vt = strip_taps(oy0, p.scale_y); /* before any lane is masked off */                                                 \
+    if (TAPS == TAPS_SHARED || TAPS == TAPS_ONCE || ox < p.out_width)                                                                    \
+      scaled_strip<TAPS, HAS_ALPHA, OVER>(p, light, f, ox, oy0, min(oy0 + p.scaled_rows, p.out_height), vt, ov);                         \
+  }
 
 }  // namespace
 }  // namespace bt709

@@ -4,7 +4,8 @@ by up to 8 % between allocations, so process-against-process runs cannot resolve
 (placement hunt of the first library); every library then gets its own context and decoder over the same device pointers, and
 the timed regions alternate between the libraries.
 
-    python tools/ab_libs.py [--ring 256] [--per-launch 256] [--rounds 4] [--tries 4] LIB [LIB ...]
+    python tools/ab_libs.py [--ring 256] [--per-launch 256] [--rounds 4] [--tries 4] [--call scaled --out-width 2560 --out-height 1440] LIB [LIB ...]
+--call half / scaled times the fused rescales (bt709hip_decode_half / _scaled, their _batch entries from two frames per launch).
 LIB = a path, or "shipped" for the in-tree build; LIB@K=V,K=V sets decoder options for that entry only."""
 import argparse
 import ctypes as C
@@ -49,6 +50,9 @@ def main():
     ap.add_argument("--gamma", type=int, default=0, help="MetalBT709Gamma of every decoder: 0 Apple, 1 sRGB, 2 Linear, 3 ITU-709")
     ap.add_argument("--decoder-option", action="append", default=[], metavar="K=V")
     ap.add_argument("--format", default="bgra8", choices=["bgra8", "rgba16f"], help="render target of the launches (rgba16f: 8 bytes per pixel, linear-light halves)")
+    ap.add_argument("--call", default="decode", choices=["decode", "half", "scaled"], help="the entry point of a launch: the 1:1 decode, the exact 2:1 or the any-ratio rescale")
+    ap.add_argument("--out-width", type=int, default=0, help="--call scaled: the output size")
+    ap.add_argument("--out-height", type=int, default=0)
     ap.add_argument("libs", nargs="+")
     args = ap.parse_args()
     W, H, RING = args.width, args.height, args.ring
@@ -70,7 +74,8 @@ def main():
         decs.append(d)
     lib0, h0 = libs[0], ctxs[0]
     opx = 8 if args.format == "rgba16f" else 4  # bytes per output pixel
-    yb, cb, ob = W * H, W * H // 2, W * H * opx
+    OW, OH = {"decode": (W, H), "half": (W // 2, H // 2), "scaled": (args.out_width, args.out_height)}[args.call]
+    yb, cb, ob = W * H, W * H // 2, OW * OH * opx
     in_stride = (yb + cb + 255) // 256 * 256 + args.in_pad
     out_stride = ob + args.out_pad
     d_in, d_out = C.c_void_p(), C.c_void_p()
@@ -98,16 +103,21 @@ def main():
     for i in range(RING):
         b = d_in.value + i * in_stride
         frames[i] = Frame(b, W, b + yb, W, W, H, 1, {0: 1, 1: 2, 2: 3, 3: 1}[args.gamma])
-        surfs[i] = Surface(d_out.value + i * out_stride, W * opx, W, H, 1 if opx == 8 else 0, 0)
+        surfs[i] = Surface(d_out.value + i * out_stride, OW * opx, OW, OH, 1 if opx == 8 else 0, 0)
     per = args.per_launch
 
     def run(k, n):
         lib, dec = libs[k], decs[k]
+        stem = {"decode": "bt709hip_decode", "half": "bt709hip_decode_half", "scaled": "bt709hip_decode_scaled"}[args.call]
+        one, batch = getattr(lib, stem), getattr(lib, stem + "_batch")
         for _ in range(n):
             for first in range(0, RING, per):
                 fp = C.cast(C.byref(frames, first * C.sizeof(Frame)), C.POINTER(Frame))
                 sp = C.cast(C.byref(surfs, first * C.sizeof(Surface)), C.POINTER(Surface))
-                ok(lib, lib.bt709hip_decode_batch(dec, per, fp, None, sp, None, 0))
+                if per == 1 and args.call != "decode":
+                    ok(lib, one(dec, fp, None, sp, None, 0))  # the single-frame entry: the shortest host path
+                else:
+                    ok(lib, batch(dec, per, fp, None, sp, None, 0))
 
     evs = []
     for lib, h in zip(libs, ctxs):
@@ -123,7 +133,7 @@ def main():
             run(k, 1)
             lib.bt709hip_stream_synchronize(h, None)
         host = np.empty(ob, dtype=np.uint8)
-        ok(lib, lib.bt709hip_download(h, host.ctypes.data, W * opx, d_out.value + (RING - 1) * out_stride, W * opx, W * opx, H, None))
+        ok(lib, lib.bt709hip_download(h, host.ctypes.data, OW * opx, d_out.value + (RING - 1) * out_stride, OW * opx, OW * opx, OH, None))
         lib.bt709hip_stream_synchronize(h, None)
         sums.append(int(host.view(np.uint32).astype(np.uint64).sum()))
     print("output checksums equal:", len(set(sums)) == 1)
@@ -140,7 +150,8 @@ def main():
             table[k].append(args.steps * RING * W * H / (ms.value / 1e3) / 1e9)
     for p, r in zip(args.libs, table):
         med = sorted(r)[len(r) // 2]
-        print("%-52s %s  median %.1f Gpixel/s = %.4f" % (p if p.startswith("shipped") else os.path.basename(p), " ".join("%.1f" % x for x in r), med, med * (1.5 + opx) / 8000))
+        print("%-52s %s  median %.1f Gpixel/s = %.4f; us per launch %s" % (p if p.startswith("shipped") else os.path.basename(p), " ".join("%.1f" % x for x in r), med, med * (1.5 + opx) / 8000,
+                                                                             " ".join("%.3f" % (per * W * H / x / 1e3) for x in r)))
 
 
 if __name__ == "__main__":
