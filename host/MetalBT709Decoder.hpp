@@ -69,6 +69,11 @@ class MetalRenderContext {
   // 3.9).  false (the default): they are encoded as they are.  This mirror has no encoder; a caller of the C ABI encodes on handle().
   static constexpr int kEncodePremultiplyOption = BT709HIP_CTX_OPT_ENCODE_PREMULTIPLY;
   bool setEncodePremultiply(bool on) { return (lastStatus_ = bt709hip_context_set_option(ctx_, kEncodePremultiplyOption, on ? 1 : 0)) == BT709HIP_OK; }
+  // bt709hip_encode[_batch] on this context is the reference's per-pixel +convert: (include/bt709hip_ext.h
+  // BT709HIP_CTX_OPT_ENCODE_CONVERT): BT709HIP_CONVERT_PACKED444 / _POINT420, or BT709HIP_CONVERT_OFF (the default).
+  // BGRAToBT709Converter below sets it around each of its calls and puts BT709HIP_CONVERT_OFF back.
+  static constexpr int kEncodeConvertOption = BT709HIP_CTX_OPT_ENCODE_CONVERT;
+  bool setEncodeConvert(int mode) { return (lastStatus_ = bt709hip_context_set_option(ctx_, kEncodeConvertOption, mode)) == BT709HIP_OK; }
 
  private:
   bt709hip_context *ctx_ = nullptr;
@@ -168,6 +173,47 @@ class BGRATexture {
  private:
   MetalRenderContext &ctx_;
   bt709hip_surface s_{};
+};
+
+// +convert: (BGRAToBT709Converter.h:34-46) on the GPU: per-pixel BGRA -> BT.709, floats end to end, no subsampling.  `gamma` is the
+// OUTPUT curve (BT709HIP_GAMMA_APPLE / SRGB / LINEAR / ITU709: +unconvert:'s four modes); the input is sRGB bytes, A is ignored.
+struct BGRAToBT709Converter {
+  // host words (A<<24)|(R<<16)|(G<<8)|B in, host words (Cr<<16)|(Cb<<8)|Y out, width * height of each
+  static bool convert(MetalRenderContext &mrc, const uint32_t *inBGRAPixels, uint32_t *outBT709Pixels, int width, int height,
+                      int gamma = BT709HIP_GAMMA_APPLE) {
+    if (width < 0 || height < 0 || (width & 1) || (height & 1)) return false;  // BGRAToBT709Converter.m:41-46
+    if (width == 0 || height == 0) return true;
+    BGRATexture in(mrc, width, height);
+    const size_t row = static_cast<size_t>(width) * 4, pitch = (row + 15) / 16 * 16;
+    void *words = nullptr;
+    if (in.surface()->bgra == nullptr || bt709hip_malloc(mrc.handle(), pitch * height, &words) != BT709HIP_OK) return false;
+    int rc = bt709hip_upload(mrc.handle(), in.surface()->bgra, in.surface()->stride, inBGRAPixels, row, row, height, nullptr);
+    if (rc == BT709HIP_OK) rc = bt709hip_stream_synchronize(mrc.handle(), nullptr);
+    if (rc == BT709HIP_OK) {
+      bt709hip_frame out{};
+      out.y = words;
+      out.y_stride = pitch;
+      out.width = width;
+      out.height = height;
+      rc = mrc.setEncodeConvert(BT709HIP_CONVERT_PACKED444) ? BT709HIP_OK : mrc.lastStatus();
+      if (rc == BT709HIP_OK) rc = bt709hip_encode(mrc.handle(), in.surface(), &out, BT709HIP_GAMMA_SRGB, gamma, nullptr, 1);
+      mrc.setEncodeConvert(BT709HIP_CONVERT_OFF);
+    }
+    if (rc == BT709HIP_OK) rc = bt709hip_download(mrc.handle(), outBT709Pixels, row, words, pitch, row, height, nullptr);
+    if (rc == BT709HIP_OK) rc = bt709hip_stream_synchronize(mrc.handle(), nullptr);
+    bt709hip_free(mrc.handle(), words);
+    return rc == BT709HIP_OK;
+  }
+  // +convert: then copyBT709ToCoreVideo (BGRAToBT709Converter.m:1042-1099) in one launch, no packed intermediate: Y of every
+  // pixel, a block's Cb, Cr from its odd row, even column.  The buffer leaves tagged by setBT709Attributes.
+  static bool convertIntoCoreVideoBufferPointSampled(MetalRenderContext &mrc, const BGRATexture &in, CVPixelBuffer &out,
+                                                     int gamma = BT709HIP_GAMMA_APPLE) {
+    int rc = mrc.setEncodeConvert(BT709HIP_CONVERT_POINT420) ? BT709HIP_OK : mrc.lastStatus();
+    if (rc == BT709HIP_OK) rc = bt709hip_encode(mrc.handle(), in.surface(), out.frame(), BT709HIP_GAMMA_SRGB, gamma, nullptr, 1);
+    mrc.setEncodeConvert(BT709HIP_CONVERT_OFF);
+    if (rc == BT709HIP_OK) out.setBT709Attributes();
+    return rc == BT709HIP_OK;
+  }
 };
 
 // What the reference's caller actually holds: a CVPixelBuffer whose planes live in HOST memory (the

@@ -328,6 +328,32 @@ int main(int argc, char **argv) {
         metalDecoder.lastStatus() != BT709HIP_ERR_SIZE_MISMATCH)
       ++failures;
   }
+  // the reference's own test flow on the device (MetalBT709DecoderTests.m:189-277): +convert:, copyBT709ToCoreVideo, -decodeBT709:
+  // -- the host copy against the one-launch form, which must decode to the same texels
+  {
+    const uint32_t bgra[4] = {0xFFFFFFFFu, 0xFF000000u, 0xFFFF0000u, 0xFFFFFFFFu};  // white, black / red, white
+    const uint32_t want[4] = {0x8080EBu, 0x808010u, 0xF0663Fu, 0x8080EBu};         // BT.709 video range: red is (63, 102, 240)
+    uint32_t words[4] = {0, 0, 0, 0};
+    if (!BGRAToBT709Converter::convert(metalRenderContext, bgra, words, 2, 2, BT709HIP_GAMMA_SRGB)) ++failures;
+    for (int i = 0; i < 4; ++i)
+      if (words[i] != want[i]) {
+        std::fprintf(stderr, "+convert: pixel %d: got %06x, want %06x\n", i, words[i], want[i]);
+        ++failures;
+      }
+    BGRATexture in(metalRenderContext, 2, 2), viaHost(metalRenderContext, 2, 2), viaDevice(metalRenderContext, 2, 2);
+    CVPixelBuffer hostBuf(metalRenderContext, 2, 2), deviceBuf(metalRenderContext, 2, 2);
+    hostBuf.setBT709Attributes();
+    hostBuf.copyBT709ToCoreVideo(words);
+    bool ok = bt709hip_upload(metalRenderContext.handle(), in.surface()->bgra, in.surface()->stride, bgra, 8, 8, 2, nullptr) == BT709HIP_OK &&
+              metalRenderContext.waitUntilCompleted(nullptr);
+    ok = ok && BGRAToBT709Converter::convertIntoCoreVideoBufferPointSampled(metalRenderContext, in, deviceBuf, BT709HIP_GAMMA_SRGB);
+    ok = ok && metalDecoder.decodeBT709(&hostBuf, nullptr, &viaHost, nullptr, nullptr, 2, 2, true);
+    ok = ok && metalDecoder.decodeBT709(&deviceBuf, nullptr, &viaDevice, nullptr, nullptr, 2, 2, true);
+    if (!ok || viaHost.getBGRATexturePixels() != viaDevice.getBGRATexturePixels()) {
+      std::fprintf(stderr, "+convert: then copyBT709ToCoreVideo: the one-launch form decodes differently\n");
+      ++failures;
+    }
+  }
   std::printf("%s: %d vectors, %d failures\n", failures ? "FAIL" : "ok", (argc - 1) / 6, failures);
   return failures ? 1 : 0;
 }

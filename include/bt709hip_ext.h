@@ -41,8 +41,8 @@ typedef struct {
 int bt709hip_context_info(const bt709hip_context *ctx, bt709hip_device_info *info);
 
 /* Launch-shape knobs of a context (tuning and test hooks; no reference twin).  Values are
- * clamped to their valid range; 0 restores the default.  BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT and
- * BT709HIP_CTX_OPT_ENCODE_PREMULTIPLY are no knobs and are NOT clamped: see below. */
+ * clamped to their valid range; 0 restores the default.  BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT,
+ * BT709HIP_CTX_OPT_ENCODE_PREMULTIPLY and BT709HIP_CTX_OPT_ENCODE_CONVERT are no knobs and are NOT clamped: see below. */
 typedef enum {
   BT709HIP_CTX_OPT_GRID_MULT = 1,       /* general (unaligned-layout) kernels: workgroups per launch = CUs x 8 x this; default 2 */
   BT709HIP_CTX_OPT_ENCODE_ROW_PAIRS = 2,/* encoder: consecutive row pairs per workgroup; default 0 = sized per launch */
@@ -50,8 +50,12 @@ typedef enum {
   BT709HIP_CTX_OPT_XCD_BANDS = 4,       /* encoder: 1 (default) XCD-aware work map for launches of a multiple of 8 pictures; 0 plain order */
   BT709HIP_CTX_OPT_STREAMING_TRIES = 5, /* device buffers of 256 MB or more that the library allocates itself (in-flight pool slots, the sharder's lanes) go through bt709hip_malloc_streaming with this many candidates; default 4, 1 = plain allocation */
   BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT = 6, /* BT709HIP_CHROMA_NV12 (default) or BT709HIP_CHROMA_I420: the planes bt709hip_encode[_batch] writes; any other value is refused */
-  BT709HIP_CTX_OPT_ENCODE_PREMULTIPLY = BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT + 2 /* (eight; seven is no option) 0 (default): BGRA8_SRGB input is encoded as it is; 1: it is straight alpha and is premultiplied first; any other value is refused */
+  BT709HIP_CTX_OPT_ENCODE_PREMULTIPLY = BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT + 2, /* (eight; seven is no option) 0 (default): BGRA8_SRGB input is encoded as it is; 1: it is straight alpha and is premultiplied first; any other value is refused */
+  BT709HIP_CTX_OPT_ENCODE_CONVERT = BT709HIP_CTX_OPT_ENCODE_PREMULTIPLY + 2 /* (ten; nine is no option) BT709HIP_CONVERT_OFF (default), _PACKED444 or _POINT420: bt709hip_encode[_batch] is the reference's per-pixel +convert:; any other value is refused */
 } bt709hip_context_option;
+#define BT709HIP_CONVERT_OFF 0       /* bt709hip_encode[_batch] is the subsampling encoder (+convertIntoCoreVideoBuffer:) */
+#define BT709HIP_CONVERT_PACKED444 1 /* +convert: -- one 32-bit word (Cr<<16)|(Cb<<8)|Y per pixel */
+#define BT709HIP_CONVERT_POINT420 2  /* +convert: then copyBT709ToCoreVideo in one launch: an NV12 / I420 frame, chroma point-sampled */
 int bt709hip_context_set_option(bt709hip_context *ctx, int option, int value);
 /* BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT.  The reference's encoder exists to write YUV4MPEG2 files, whose FRAME is planar: Y, then
  * U, then V (Renderer/y4m_writer.h:194-241).  With the option at BT709HIP_CHROMA_I420 (the values are BT709HIP_OPT_CHROMA_LAYOUT's,
@@ -86,6 +90,42 @@ int bt709hip_context_set_option(bt709hip_context *ctx, int option, int value);
  * "encode_bgra_nv12_blocks<premul>", "encode_bgra_i420<premul>", "encode_bgra_i420_blocks<premul>".  The call reads the option
  * once, on entry.  Any value but 0 and 1: BT709HIP_ERR_INVALID_ARG, the option keeps its value (it is not clamped).  Setting it
  * never touches the device and needs no table: it works while a stream is being captured.  At 0 nothing changes. */
+/* BT709HIP_CTX_OPT_ENCODE_CONVERT.  The reference has a SECOND BGRA -> BT.709 converter, the per-pixel pair +convert: /
+ * +unconvert: (Renderer/BGRAToBT709Converter.h:34-46); every reference XCTest builds its input frame as +convert: then
+ * copyBT709ToCoreVideo then -decodeBT709: (MetalBT709DecoderTests.m:189-277).  It is not the subsampling encoder: it keeps floats
+ * end to end (no byte-quantised intermediate) and samples per pixel (no 2x2 average), so its bytes differ.  Per pixel, with
+ * n[c] = curve(byteNorm(c)) for c = R, G, B (A is ignored):
+ *   Ey = (Kr*n[R] + Kg*n[G]) + Kb*n[B];  Eb = (n[B] - Ey) / 1.8556f;  Er = (n[R] - Ey) / 1.5748f          (BT709.h:199-268)
+ *   Y = round(Ey*219 + 16), Cb = round(Eb*224 + 128), Cr = round(Er*224 + 128)
+ * and curve, by output_gamma: SRGB the identity (BT709.h:914-944); LINEAR sRGB -> linear; APPLE sRGB -> linear -> Apple 1.961
+ * (Apple196_from_sRGB_convertRGBToYCbCr, BT709.h:743-817); ITU709 sRGB -> linear -> BT.709 (BT709_from_sRGB_convertRGBToYCbCr(., 1),
+ * the else branch of convertSoftware) -- +unconvert:'s four modes.  With the option at
+ *   BT709HIP_CONVERT_OFF (0, the default): nothing changes -- same kernels, same names, same bytes; output_gamma ITU709 stays
+ *     BT709HIP_ERR_INVALID_ARG;
+ *   BT709HIP_CONVERT_PACKED444 (1), the +convert: twin: out->y points to W x H 32-bit words (Cr<<16)|(Cb<<8)|Y, the top byte of
+ *     each word 0, rows y_stride bytes apart -- what bt709hip_unconvert reads.  out->cbcr must be NULL in every frame
+ *     (BT709HIP_ERR_INVALID_ARG otherwise); cbcr_stride and the tags are not looked at.  y_stride >= 4*W, a multiple of 4, the
+ *     pointer 4-byte aligned (BT709HIP_ERR_STRIDE otherwise).  An evenly spaced batch is one whose BGRA and word pointers are;
+ *   BT709HIP_CONVERT_POINT420 (2), +convert: followed by copyBT709ToCoreVideo (BGRAToBT709Converter.m:1042-1099) in one launch
+ *     with no packed intermediate: `out` is an ordinary NV12 frame, or three planes under BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT =
+ *     BT709HIP_CHROMA_I420.  Y of pixel (r, c) is the converted pixel's Y; Cb and Cr of block (r/2, c/2) are those of the converted
+ *     pixel in the block's ODD row and EVEN column (the odd-row rule: every row of the reference's copy overwrites chroma row
+ *     r/2, so the odd row's pair survives).
+ * Under 1 and 2: input_gamma must be BT709HIP_GAMMA_SRGB (the reference's per-pixel converters take sRGB bytes only) and
+ * in->format BGRA8_SRGB -- any other input gamma, and BGRA8_ALPHA input, is BT709HIP_ERR_UNSUPPORTED after the usual validation;
+ * output_gamma may be APPLE, SRGB, LINEAR or ITU709.  BT709HIP_CTX_OPT_ENCODE_PREMULTIPLY composes: B, G, R are premultiplied
+ * first, then converted.  Every other check, its order and its limit are the encoder's (even and equal sizes, height/2 <= 65535,
+ * pitches <= 2^32 - 1, 32 pictures in a pointer table, 65535 evenly spaced).  Launch plans (bt709hip_last_launch_info) are the
+ * plain encoder's for the same size and count; BT709HIP_CTX_OPT_ENCODE_ROW_PAIRS, _ENCODE_THREADS and _XCD_BANDS apply as they do
+ * there.  The fast kernels need W % 4 == 0 and the BGRA pointer and pitch 16-byte aligned, and for the words a 16-byte aligned
+ * pointer and pitch (for a frame: the encoder's alignments); any other call takes the general kernel.
+ * bt709hip_last_kernel_name: "convert_bgra_packed444", "convert_bgra_packed444_blocks", "convert_bgra_nv12", "convert_bgra_i420",
+ * "convert_bgra_nv12_blocks", "convert_bgra_i420_blocks", and the same names with "<premul>" behind them.  The one table is 256
+ * floats per output gamma, built per context by the first call that needs it or by bt709hip_encoder_prepare(ctx,
+ * BT709HIP_GAMMA_SRGB, output_gamma) -- which accepts ITU709 for this table alone; a call that finds it missing while its stream is
+ * being captured returns BT709HIP_ERR_NOT_SETUP.  The call reads the option once, on entry.  Any value but the three:
+ * BT709HIP_ERR_INVALID_ARG, the option keeps its value (it is not clamped).  Setting it never touches the device: it works while
+ * a stream is being captured. */
 
 /* A stream with a scheduling priority (hipStreamCreateWithPriority): 0 = normal, negative = higher, positive = lower; clamped
  * to the device's range.  (MTLCommandQueue has no twin; a renderer that decodes ahead of what it presents puts the look-ahead

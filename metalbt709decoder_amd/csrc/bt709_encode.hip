@@ -449,14 +449,19 @@ encode_alpha_y_blocks(const EncodeParams p) {
   }
 }
 
+}  // namespace bt709
+
+#include "bt709_encode_convert.h"  // BT709HIP_CTX_OPT_ENCODE_CONVERT: convert_bgra, convert_bgra_blocks over the helpers above
+
+namespace bt709 {
 namespace {
 
 // One row per selectable kernel: the selector, the kernel for either chroma layout, the two names bt709hip_last_kernel_name
-// reports, and whether the kernel stages its tables in dynamic LDS (the alpha kernels' 256 bytes are static) --
-// prepare_encode_kernels raises the cap of exactly those.  A selector field is a value or kAny; the first matching row is the
-// launch's kernel.
+// reports, and whether the kernel stages its tables in dynamic LDS (the alpha kernels' 256 bytes and the converter's 1 KiB are
+// static) -- prepare_encode_kernels raises the cap of exactly those.  A selector field is a value or kAny; the first matching row
+// is the launch's kernel.
 struct EncodeKernel {
-  int fast, alpha, premultiply;
+  int fast, alpha, premultiply, convert;  // convert: EncodeParams::convert_mode
   bool stages_table;
   void (*fn[2])(const EncodeParams);  // [chroma layout]
   const char *name[2];
@@ -464,9 +469,22 @@ struct EncodeKernel {
 // KERNEL<layout | FORM>; both names from one stem and one suffix: colour kernels spell the layout (encode_bgra_i420<premul>), the
 // alpha kernels' NV12 form names none (encode_alpha_y, encode_alpha_y<i420>)
 #define ENCODE_COLOUR(fast, premultiply, suffix, KERNEL, FORM) \
-  {fast, 0, premultiply, true, {KERNEL<kChromaNV12 | (FORM)>, KERNEL<kChromaI420 | (FORM)>}, {"encode_bgra_nv12" suffix, "encode_bgra_i420" suffix}}
-#define ENCODE_ALPHA(fast, stem, KERNEL) {fast, 1, kAny, false, {KERNEL<kChromaNV12>, KERNEL<kChromaI420>}, {stem, stem "<i420>"}}
+  {fast, 0, premultiply, kConvertOff, true, {KERNEL<kChromaNV12 | (FORM)>, KERNEL<kChromaI420 | (FORM)>}, {"encode_bgra_nv12" suffix, "encode_bgra_i420" suffix}}
+#define ENCODE_ALPHA(fast, stem, KERNEL) {fast, 1, kAny, kConvertOff, false, {KERNEL<kChromaNV12>, KERNEL<kChromaI420>}, {stem, stem "<i420>"}}
+// the converter (the shim hands it BGRA8_SRGB input alone): the packed form writes no plane, one instantiation under both layouts
+#define CONVERT_PACKED(fast, premultiply, suffix, KERNEL, FORM) \
+  {fast, 0, premultiply, kConvertPacked444, false, {KERNEL<kFormPacked | (FORM)>, KERNEL<kFormPacked | (FORM)>}, {"convert_bgra_packed444" suffix, "convert_bgra_packed444" suffix}}
+#define CONVERT_POINT(fast, premultiply, suffix, KERNEL, FORM) \
+  {fast, 0, premultiply, kConvertPoint420, false, {KERNEL<kChromaNV12 | (FORM)>, KERNEL<kChromaI420 | (FORM)>}, {"convert_bgra_nv12" suffix, "convert_bgra_i420" suffix}}
 const EncodeKernel kEncodeKernels[] = {
+    CONVERT_PACKED(1, 1, "<premul>", convert_bgra, kFormStraight),
+    CONVERT_PACKED(1, 0, "", convert_bgra, 0),
+    CONVERT_PACKED(0, 1, "_blocks<premul>", convert_bgra_blocks, kFormStraight),
+    CONVERT_PACKED(0, 0, "_blocks", convert_bgra_blocks, 0),
+    CONVERT_POINT(1, 1, "<premul>", convert_bgra, kFormStraight),
+    CONVERT_POINT(1, 0, "", convert_bgra, 0),
+    CONVERT_POINT(0, 1, "_blocks<premul>", convert_bgra_blocks, kFormStraight),
+    CONVERT_POINT(0, 0, "_blocks", convert_bgra_blocks, 0),
     ENCODE_ALPHA(1, "encode_alpha_y", encode_alpha_y),
     ENCODE_COLOUR(1, 1, "<premul>", encode_bgra, kFormStraight),
     ENCODE_COLOUR(1, 0, "", encode_bgra, 0),
@@ -476,16 +494,18 @@ const EncodeKernel kEncodeKernels[] = {
 };
 #undef ENCODE_COLOUR
 #undef ENCODE_ALPHA
+#undef CONVERT_PACKED
+#undef CONVERT_POINT
 
 // The kernel of a launch that launch_encode has planned and recorded
 const char *launch_encode_kernel(const EncodeParams &p, const dim3 &grid, const dim3 &block, size_t lds, bool fast, bool alpha, hipStream_t stream) {
   const uint32_t layout = p.chroma_layout == kChromaI420 ? kChromaI420 : kChromaNV12;
   for (const EncodeKernel &k : kEncodeKernels) {
-    if (k.fast != fast || k.alpha != alpha || !selects(k.premultiply, p.premultiply != 0)) continue;
+    if (k.fast != fast || k.alpha != alpha || !selects(k.premultiply, p.premultiply != 0) || k.convert != static_cast<int>(p.convert_mode)) continue;
     hipLaunchKernelGGL(k.fn[layout], grid, block, lds, stream, p);
     return k.name[layout];
   }
-  return nullptr;  // unreachable: the rows cover fast x alpha x premultiply
+  return nullptr;  // unreachable: the rows cover fast x alpha x premultiply, and fast x premultiply for either converter mode
 }
 
 }  // namespace
@@ -501,7 +521,7 @@ const char *launch_encode(const EncodeParams &params, int frames, bool fast, boo
   EncodeParams p = params;
   if (p.row_pairs_per_block == 0) p.row_pairs_per_block = encode_row_pairs_per_block(p.width, p.height, frames);
   const bool alpha = p.alpha_luma != nullptr;  // BT709HIP_FORMAT_BGRA8_ALPHA: same plan, the alpha kernels (static LDS)
-  const size_t lds = alpha ? 0 : 256 * sizeof(EncodeByteEntry) + p.from_linear_bytes;
+  const size_t lds = alpha || p.convert_mode != kConvertOff ? 0 : 256 * sizeof(EncodeByteEntry) + p.from_linear_bytes;  // the converter's curve is static, too
   dim3 grid((p.width / 2 + kBlockThreads - 1) / kBlockThreads, p.height / 2, frames), block(kBlockThreads);
   if (fast) {
     const uint32_t quads = p.width / 4;

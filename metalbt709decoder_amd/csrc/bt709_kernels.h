@@ -200,7 +200,18 @@ struct EncodeParams {
   // (It sits in what was padding: the kernarg block and every other field's offset are what they were.)
   uint32_t chroma_layout;  // kChromaNV12 / kChromaI420
   int64_t step_bgra, step_y, step_cbcr;
-  const EncodeByteEntry *per_byte;  // 256 entries for the (input gamma, output gamma) pair
+  // BT709HIP_CTX_OPT_ENCODE_CONVERT: convert_mode != kConvertOff selects the per-pixel converter's kernels in
+  // launch_encode (convert_bgra / convert_bgra_blocks, bt709_encode_convert.h), which read convert_curve -- 256 floats,
+  // transfer_tables.h build_convert_curve -- and none of per_byte / from_linear* / alpha_luma.
+  //   kConvertPacked444: frames[i].y is W x H 32-bit words (Cr<<16)|(Cb<<8)|Y at pitch y_stride, frames[i].cbcr nullptr;
+  //   kConvertPoint420:  frames[i] is an NV12 / I420 frame as above; a block's chroma is its bottom-left pixel's.
+  // Neither is a field of its own: a field appended to this block moves the implicit arguments behind it and with them one
+  // s_load offset and the kernarg size of EVERY encoder kernel (profiles/r15_straight_alpha_isa.txt).  The curve travels in the slot
+  // of the table the converter does not read, the mode in the upper half of the selector word no kernel reads.
+  union {
+    const EncodeByteEntry *per_byte;  // 256 entries for the (input gamma, output gamma) pair
+    const float *convert_curve;       // convert_mode != kConvertOff
+  };
   const TransferBucket *from_linear;  // two-resolution BT709_from_linear(., output gamma) table (SplitTable)
   uint32_t from_linear_bytes;
   float from_linear_scale;    // its n_fine
@@ -208,7 +219,8 @@ struct EncodeParams {
   // encode_bgra / encode_bgra_blocks in launch_encode; no kernel reads it.  (It sits where the split point of the two-resolution
   // table was carried, which nothing had read since the index became a min(): every other field's offset, and the kernarg
   // block's size, are what they were.)
-  uint32_t premultiply;
+  uint16_t premultiply;
+  uint16_t convert_mode;  // kConvert*: a selector of launch_encode as well, read by no kernel
   float from_linear_coarse;   // fine buckets below the table's split point, coarse ones above: q = (uint)(xs * coarse) + offset
   uint32_t from_linear_offset;
   uint32_t row_pairs_per_block;  // consecutive row pairs a fast-path workgroup walks; 0 = encode_row_pairs_per_block()
@@ -220,6 +232,11 @@ struct EncodeParams {
   // T[A], four per word (bt709_alpha_luma.h); per_byte / from_linear* are not read then
   const uint32_t *alpha_luma;
 };
+static_assert(sizeof(EncodeParams) == 880, "a field appended to EncodeParams moves the implicit kernel arguments behind it: every encoder kernel's code changes");
+enum : uint32_t { kConvertOff = 0, kConvertPacked444 = 1, kConvertPoint420 = 2 };  // == BT709HIP_CONVERT_*
+// Further bit of the converter kernels' FORM (beside the layout and kFormStraight): the packed 4:4:4 output
+enum : uint32_t { kFormPacked = 4 };
+constexpr bool form_packed(uint32_t form) { return (form & kFormPacked) != 0; }
 const char *launch_encode(const EncodeParams &p, int frames, bool fast, bool xcd_bands, hipStream_t stream);
 hipError_t prepare_encode_kernels();
 // Encoder fast-path geometry, measured on 4K (tools/encode_shapes.sh sweeps):

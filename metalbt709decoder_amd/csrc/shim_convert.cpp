@@ -51,6 +51,17 @@ int alpha_luma_table(bt709hip_context *ctx, hipStream_t s) {
   return upload_table(luma, sizeof luma, &ctx->d_alpha_luma);
 }
 
+// Builds (once) the device copy of the per-pixel converter's curve for one output gamma (BT709HIP_CTX_OPT_ENCODE_CONVERT;
+// transfer_tables.h build_convert_curve).  Same rules as encoder_tables: refused while `s` records a graph.
+int convert_curve_table(bt709hip_context *ctx, int output_gamma, hipStream_t s) {
+  std::lock_guard<std::mutex> lock(ctx->encoder_mutex);
+  if (ctx->d_convert_curve[output_gamma] != nullptr) return BT709HIP_OK;
+  if (capturing(s)) return BT709HIP_ERR_NOT_SETUP;
+  alignas(16) float curve[256];
+  if (!build_convert_curve(output_gamma, curve)) return BT709HIP_ERR_UNSUPPORTED;
+  return upload_table(curve, sizeof curve, &ctx->d_convert_curve[output_gamma]);
+}
+
 }  // namespace bt709shim
 
 extern "C" {
@@ -231,14 +242,18 @@ static int render_scaled_launch(bt709hip_context *ctx, int count, const bt709hip
 int bt709hip_encode_batch(bt709hip_context *ctx, int count, const bt709hip_surface *ins, const bt709hip_frame *outs,
                           int input_gamma, int output_gamma, void *stream, int wait_until_completed) {
   if (ctx == nullptr || ins == nullptr || outs == nullptr || count < 0) return BT709HIP_ERR_INVALID_ARG;
-  if (input_gamma < 0 || input_gamma > 2 || output_gamma < 0 || output_gamma > 2) return BT709HIP_ERR_INVALID_ARG;
+  // BT709HIP_CTX_OPT_ENCODE_CONVERT, read once: the call is the per-pixel converter (+convert:), whose output gamma may be ITU709;
+  // PACKED444 writes 32-bit words (Cr<<16)|(Cb<<8)|Y through out->y and takes no chroma plane; POINT420 writes an ordinary frame
+  const int convert = ctx->encode_convert;
+  const bool packed = convert == BT709HIP_CONVERT_PACKED444;
+  if (input_gamma < 0 || input_gamma > 2 || output_gamma < 0 || output_gamma > (convert != BT709HIP_CONVERT_OFF ? 3 : 2)) return BT709HIP_ERR_INVALID_ARG;
   if (count == 0) return BT709HIP_OK;
   const bt709hip_surface &in0 = ins[0];
   const bt709hip_frame &out0 = outs[0];
   // BGRA8_ALPHA: the texels read as the grey picture (A,A,A) of the reference's alpha clip; only its Y plane is ever decoded,
   // so cbcr may be NULL -- in every frame of the call or in none -- and cbcr_stride is not looked at then
   const bool alpha = in0.format == BT709HIP_FORMAT_BGRA8_ALPHA;
-  const bool no_cbcr = alpha && out0.cbcr == nullptr;
+  const bool no_cbcr = packed || (alpha && out0.cbcr == nullptr);  // the packed words: cbcr must be NULL in every frame, cbcr_stride is not looked at
   // BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT, read once: cbcr is the U plane, W/2 bytes a row, V (H/2) x cbcr_stride bytes behind it.
   // Without a chroma plane there is nothing to lay out: such a call is what it was, whatever the option holds.
   const bool planar = ctx->encode_chroma_layout == BT709HIP_CHROMA_I420 && !no_cbcr;
@@ -246,7 +261,8 @@ int bt709hip_encode_batch(bt709hip_context *ctx, int count, const bt709hip_surfa
   const bool premultiply = ctx->encode_premultiply != 0 && !alpha;
   const size_t chroma_align = planar ? 2 : 4;  // the fast kernels' chroma store: a 2-byte half per plane, or the CbCr dword
   bool uniform = count > 1;
-  bool fast = (in0.width % 4) == 0 && (in0.stride % 16) == 0 && (out0.y_stride % 4) == 0 && (no_cbcr || (out0.cbcr_stride % chroma_align) == 0);
+  const size_t y_px = packed ? 4 : 1, y_align = packed ? 16 : 4;  // bytes of a pixel in the plane out->y points to; the fast kernels' store to it
+  bool fast = (in0.width % 4) == 0 && (in0.stride % 16) == 0 && (out0.y_stride % y_align) == 0 && (no_cbcr || (out0.cbcr_stride % chroma_align) == 0);
   EncodeParams p;
   std::memset(&p, 0, sizeof p);
   for (int i = 0; i < count; ++i) {
@@ -259,17 +275,18 @@ int bt709hip_encode_batch(bt709hip_context *ctx, int count, const bt709hip_surfa
     if ((in.format != BT709HIP_FORMAT_BGRA8_SRGB && in.format != BT709HIP_FORMAT_BGRA8_ALPHA) || in.reserved != 0)
       return BT709HIP_ERR_UNSUPPORTED;
     if (in.width != in0.width || in.height != in0.height || in.stride != in0.stride || in.format != in0.format ||
-        out.y_stride != out0.y_stride || (!(alpha && (no_cbcr || out.cbcr == nullptr)) && out.cbcr_stride != out0.cbcr_stride))
+        out.y_stride != out0.y_stride || (!(packed || (alpha && (no_cbcr || out.cbcr == nullptr))) && out.cbcr_stride != out0.cbcr_stride))
       return BT709HIP_ERR_SIZE_MISMATCH;
     // the reference forces an alpha clip's gamma to linear (srgb_to_bt709.m:842-954); anything else is "alpha is not linear"
     if (alpha && (input_gamma != BT709HIP_GAMMA_LINEAR || output_gamma != BT709HIP_GAMMA_LINEAR)) return BT709HIP_ERR_ALPHA_TRANSFER;
     if (in.width == 0 || in.height == 0) continue;
     if (in.bgra == nullptr || out.y == nullptr || (out.cbcr == nullptr) != no_cbcr) return BT709HIP_ERR_INVALID_ARG;
     const size_t w = static_cast<size_t>(in.width);
-    if (in.stride < 4 * w || (in.stride & 3) || !aligned(in.bgra, 4) || out.y_stride < w || (!no_cbcr && out.cbcr_stride < (planar ? w / 2 : w)))
+    if (in.stride < 4 * w || (in.stride & 3) || !aligned(in.bgra, 4) || out.y_stride < y_px * w || (!no_cbcr && out.cbcr_stride < (planar ? w / 2 : w)))
       return BT709HIP_ERR_STRIDE;
+    if (packed && ((out.y_stride & 3) || !aligned(out.y, 4))) return BT709HIP_ERR_STRIDE;  // words
     if (in.stride > 0xffffffffu || out.y_stride > 0xffffffffu || (!no_cbcr && out.cbcr_stride > 0xffffffffu)) return BT709HIP_ERR_STRIDE;
-    fast = fast && aligned(in.bgra, 16) && aligned(out.y, 4) && aligned(out.cbcr, chroma_align);
+    fast = fast && aligned(in.bgra, 16) && aligned(out.y, y_align) && aligned(out.cbcr, chroma_align);
     if (i >= 2)
       uniform = uniform && byte_step(ins[0].bgra, in.bgra) == byte_step(ins[0].bgra, ins[1].bgra) * i &&
                 byte_step(outs[0].y, out.y) == byte_step(outs[0].y, outs[1].y) * i &&
@@ -281,12 +298,18 @@ int bt709hip_encode_batch(bt709hip_context *ctx, int count, const bt709hip_surfa
     }
   }
   if (count > (uniform ? kMaxUniformBatch : kMaxBatch)) return BT709HIP_ERR_UNSUPPORTED;
+  // the reference's per-pixel converters take sRGB bytes only, and no alpha clip goes through them
+  if (convert != BT709HIP_CONVERT_OFF && (alpha || input_gamma != BT709HIP_GAMMA_SRGB)) return BT709HIP_ERR_UNSUPPORTED;
   if (in0.width == 0 || in0.height == 0) return BT709HIP_OK;
   if (int rc = bind(ctx)) return rc;
   FLUSH_STREAM(ctx, stream);
 
   hipStream_t s = pick(ctx, stream);
-  if (alpha) {
+  if (convert != BT709HIP_CONVERT_OFF) {
+    if (int rc = convert_curve_table(ctx, output_gamma, s)) return rc;
+    p.convert_curve = static_cast<const float *>(ctx->d_convert_curve[output_gamma]);
+    p.convert_mode = static_cast<uint16_t>(convert);
+  } else if (alpha) {
     if (int rc = alpha_luma_table(ctx, s)) return rc;
     p.alpha_luma = static_cast<const uint32_t *>(ctx->d_alpha_luma);
   } else {
@@ -314,7 +337,7 @@ int bt709hip_encode_batch(bt709hip_context *ctx, int count, const bt709hip_surfa
   p.y_stride = static_cast<uint32_t>(out0.y_stride);
   p.cbcr_stride = no_cbcr ? 0u : static_cast<uint32_t>(out0.cbcr_stride);
   p.chroma_layout = planar ? kChromaI420 : kChromaNV12;
-  p.premultiply = premultiply ? 1u : 0u;
+  p.premultiply = premultiply ? 1 : 0;
   last_launch_shape() = LaunchShape{};
   set_kernel_name(launch_encode(p, count, fast, ctx->xcd_bands != 0, s));
   HIP_TRY(hipGetLastError());
@@ -324,8 +347,13 @@ int bt709hip_encode_batch(bt709hip_context *ctx, int count, const bt709hip_surfa
 
 int bt709hip_encoder_prepare(bt709hip_context *ctx, int input_gamma, int output_gamma) {
   if (ctx == nullptr) return BT709HIP_ERR_INVALID_ARG;
-  if (input_gamma < 0 || input_gamma > 2 || output_gamma < 0 || output_gamma > 2) return BT709HIP_ERR_INVALID_ARG;
+  // ITU709 is an output gamma of the per-pixel converter alone (BT709HIP_CTX_OPT_ENCODE_CONVERT), which reads sRGB bytes only
+  if (input_gamma < 0 || input_gamma > 2 || output_gamma < 0 || output_gamma > 3 || (output_gamma == 3 && input_gamma != BT709HIP_GAMMA_SRGB))
+    return BT709HIP_ERR_INVALID_ARG;
   if (int rc = bind(ctx)) return rc;
+  if (input_gamma == BT709HIP_GAMMA_SRGB)  // the converter's curve as well: 1 KiB
+    if (int rc = convert_curve_table(ctx, output_gamma, nullptr)) return rc;
+  if (output_gamma == 3) return BT709HIP_OK;  // no subsampling encoder writes ITU709
   if (input_gamma == BT709HIP_GAMMA_LINEAR && output_gamma == BT709HIP_GAMMA_LINEAR)  // the one pair BGRA8_ALPHA input encodes with
     if (int rc = alpha_luma_table(ctx, nullptr)) return rc;
   return encoder_tables(ctx, input_gamma, output_gamma, nullptr);

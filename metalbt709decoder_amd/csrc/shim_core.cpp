@@ -141,6 +141,10 @@ int bt709hip_context_set_option(bt709hip_context *ctx, int option, int value) {
       if (value != 0 && value != 1) return BT709HIP_ERR_INVALID_ARG;
       ctx->encode_premultiply = value;
       return BT709HIP_OK;
+    case BT709HIP_CTX_OPT_ENCODE_CONVERT:  // and again: its table is built by the first call that needs it, or by bt709hip_encoder_prepare
+      if (value != BT709HIP_CONVERT_OFF && value != BT709HIP_CONVERT_PACKED444 && value != BT709HIP_CONVERT_POINT420) return BT709HIP_ERR_INVALID_ARG;
+      ctx->encode_convert = value;
+      return BT709HIP_OK;
     case BT709HIP_CTX_OPT_STREAMING_TRIES:
       ctx->streaming_tries = value <= 0 ? 4 : clamp_int(value, 1, 32);
       return BT709HIP_OK;
@@ -159,6 +163,8 @@ int bt709hip_context_destroy(bt709hip_context *ctx) {
         if (t.d_per_byte) (void)hipFree(t.d_per_byte);
         if (t.d_from_linear) (void)hipFree(t.d_from_linear);
       }
+    for (void *curve : ctx->d_convert_curve)
+      if (curve) (void)hipFree(curve);
     if (ctx->d_alpha_luma) (void)hipFree(ctx->d_alpha_luma);
     if (ctx->d_render_encode) (void)hipFree(ctx->d_render_encode);
     if (ctx->d_render_lin) (void)hipFree(ctx->d_render_lin);

@@ -41,9 +41,11 @@ struct bt709hip_context {
   int xcd_bands = 1;                             // BT709HIP_CTX_OPT_XCD_BANDS: XCD-aware work map of batched encoder launches
   int encode_chroma_layout = BT709HIP_CHROMA_NV12;  // BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT: the planes bt709hip_encode[_batch] writes
   int encode_premultiply = 0;                       // BT709HIP_CTX_OPT_ENCODE_PREMULTIPLY: BGRA8_SRGB input is straight alpha, premultiplied by the encode kernels
-  int streaming_tries = 4;                     // BT709HIP_CTX_OPT_STREAMING_TRIES: placement candidates for buffers of 256 MB and more that the library allocates itself
+  int encode_convert = BT709HIP_CONVERT_OFF;        // BT709HIP_CTX_OPT_ENCODE_CONVERT: bt709hip_encode[_batch] is the per-pixel converter (+convert:)
+  int streaming_tries = 4;                    // BT709HIP_CTX_OPT_STREAMING_TRIES: placement candidates for buffers of 256 MB and more that the library allocates itself
   std::mutex encoder_mutex;
   EncoderTables encoders[3][3];  // [input gamma][output gamma], built on first use
+  void *d_convert_curve[kGammaCount] = {};  // [output gamma]: the converter's 256 floats (build_convert_curve), built on first use under encoder_mutex
   void *d_alpha_luma = nullptr;  // T[256] of BGRA8_ALPHA input (bt709_alpha_luma.h), built on first use under encoder_mutex
   // bt709hip_render_scaled (pass 2 alone): built on first use under encoder_mutex
   void *d_render_encode = nullptr, *d_render_lin = nullptr;
@@ -198,6 +200,7 @@ int decode_half_batch_layout(bt709hip_decoder *dec, int layout, int count, const
 // shim_convert.cpp
 int encoder_tables(bt709hip_context *ctx, int input_gamma, int output_gamma, hipStream_t s);
 int alpha_luma_table(bt709hip_context *ctx, hipStream_t s);
+int convert_curve_table(bt709hip_context *ctx, int output_gamma, hipStream_t s);
 
 // shim_coalesce.cpp (BT709HIP_OPT_COALESCE)
 int issue_queue(bt709hip_decoder *dec, PendingQueue &q);

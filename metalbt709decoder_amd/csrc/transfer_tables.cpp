@@ -53,6 +53,17 @@ float linear_to_apple196(float v) {
   return static_cast<float>(std::pow(static_cast<double>(v), static_cast<double>(gamma)));
 }
 
+float linear_to_itu709(float v) {
+  if (v < 0.018f) return v * 4.5f;
+  const float a = 0.099f;
+  const float gamma = 0.45f;
+  // whole expression in double, narrowed once (BT709.h:99)
+  const double r = static_cast<double>(1.0f + a) *
+                       std::pow(static_cast<double>(v), static_cast<double>(gamma)) -
+                   static_cast<double>(a);
+  return static_cast<float>(r);
+}
+
 int quantize_byte(float v) {
   const float scaled = v * 255.0f;  // float multiply first
   return static_cast<int>(std::round(static_cast<double>(scaled)));
@@ -444,6 +455,20 @@ bool build_encode_tables(int in_gamma, int out_gamma, EncodeTables *out) {
     const int e = transfer_to_byte(out->from_linear_kind, lin);  // BT709_from_linear(lin, outputGamma)
     out->per_byte[b].lin = lin;
     out->per_byte[b].enc_norm = e * (1.0f / 255.0f);  // byteNorm inside sRGB_from_sRGB_convertRGBToYCbCr
+  }
+  return true;
+}
+
+bool build_convert_curve(int out_gamma, float curve[256]) {
+  if (curve == nullptr || out_gamma < 0 || out_gamma >= kGammaCount) return false;
+  for (int b = 0; b < 256; ++b) {
+    const float n = b * (1.0f / 255.0f);  // byteNorm
+    if (out_gamma == kGammaSRGB) {        // BT709.h:914-944: the bytes are the non-linear values, no trip through linear light
+      curve[b] = n;
+      continue;
+    }
+    const float lin = srgb_to_linear(n);  // BT709.h:644-646 / 786-788
+    curve[b] = out_gamma == kGammaApple ? linear_to_apple196(lin) : (out_gamma == kGammaITU709 ? linear_to_itu709(lin) : lin);
   }
   return true;
 }

@@ -91,6 +91,7 @@ float linear_to_srgb(float v);      // Renderer/sRGB.h:62-74
 float itu709_to_linear(float v);    // Renderer/BT709.h:68-81
 float apple196_to_linear(float v);  // Renderer/BT709.h:125-137
 float linear_to_apple196(float v);  // Renderer/BT709.h:139-151
+float linear_to_itu709(float v);    // Renderer/BT709.h:90-103
 int quantize_byte(float v);         // (int)round(v * 255.0f), Renderer/BT709.h:881-883
 
 // Per-channel composite of one gamma mode.
@@ -108,6 +109,15 @@ struct EncodeTables {
   int from_linear_kind = 0;       // table kind whose buckets implement BT709_from_linear(., output gamma)
 };
 bool build_encode_tables(int in_gamma, int out_gamma, EncodeTables *out);
+
+// The per-pixel converter (+convert:, Renderer/BGRAToBT709Converter.h:34-46; BT709HIP_CTX_OPT_ENCODE_CONVERT) keeps floats end to
+// end: curve[b] is the non-linear value of the sRGB byte b that BT709_convertNonLinearRGBToYCbCr (BT709.h:199-268) is handed --
+//   kGammaSRGB    byteNorm(b) itself                                     (sRGB_from_sRGB_convertRGBToYCbCr, BT709.h:914-944)
+//   kGammaLinear  srgb_to_linear(byteNorm(b))                            (BT709.h:644-646)
+//   kGammaApple   linear_to_apple196(srgb_to_linear(byteNorm(b)))        (Apple196_from_sRGB_convertRGBToYCbCr, BT709.h:743-817)
+//   kGammaITU709  linear_to_itu709(srgb_to_linear(byteNorm(b)))          (BT709_from_sRGB_convertRGBToYCbCr(., 1), BT709.h:270-330)
+// each step with the C semantics of the reference, as the scalar functions above.  Every value is 0 or lies in [3.0e-4, 1 + 2^-22] (tests/native/convert_curve_dump.cpp prints them).
+bool build_convert_curve(int out_gamma, float curve[256]);
 
 // Two-resolution bucket table over x in [0,1] for composites whose thresholds crowd near zero
 // (the encoder's BT709_from_linear tables need N = 4096 uniformly, 33 KiB, only because of

@@ -16,6 +16,7 @@ parity tests read like EmptyiOSTests/MetalBT709DecoderTests.m:189-277:
 Everything that touches pixels runs on the GPU through libbt709hip.so; there is no
 CPU implementation of the decode in this package.
 """
+import contextlib
 import ctypes as C
 import logging
 
@@ -565,6 +566,22 @@ class MetalRenderContext:
             return False
         return True
 
+    @contextlib.contextmanager
+    def _encode_convert(self, mode, what):
+        """bt709hip_context_set_option(CTX_OPT_ENCODE_CONVERT) around ONE call of the per-pixel converter: the option is set to
+        `mode` (_capi.CONVERT_PACKED444 / CONVERT_POINT420) on entry and back to CONVERT_OFF on the way out, whatever the call
+        returned, so that every other encode call of this context stays the subsampling encoder.  The setter never touches the
+        device.  Yields True, or False when the library refused the mode."""
+        rc = self.lib.bt709hip_context_set_option(self.handle, _capi.CTX_OPT_ENCODE_CONVERT, int(mode))
+        if rc != _capi.OK:
+            log.error("%s: CTX_OPT_ENCODE_CONVERT = %d: %s", what, mode, _capi.strerror(rc))
+            yield False
+            return
+        try:
+            yield True
+        finally:
+            self.lib.bt709hip_context_set_option(self.handle, _capi.CTX_OPT_ENCODE_CONVERT, _capi.CONVERT_OFF)
+
     def _set_encode_layout(self, pixelBuffers, what):
         """The encoder's chroma layout from the buffers an encode call was handed: a planar CVPixelBuffer is written in place.  As
         MetalBT709Decoder._set_layout: the buffer's `planar` flag is authoritative, planar and NV12 buffers in one call are
@@ -800,6 +817,97 @@ class BGRAToBT709Converter:
         for b in cvPixelBuffers:
             BGRAToBT709Converter.setAlphaAttributes(b)
         return True
+
+    @staticmethod
+    def convertIntoWords(bgraTextures, wordPtrs, wordStride, gamma=MetalBT709GammaApple, commandBuffer=None, waitUntilCompleted=True):
+        """+convert: (BGRAToBT709Converter.h:34-46) on the GPU, device memory in and out, `len(bgraTextures)` same-sized pictures
+        in ONE launch (bt709hip_encode_batch under CTX_OPT_ENCODE_CONVERT = CONVERT_PACKED444): picture i's words
+        (Cr<<16)|(Cb<<8)|Y -- what unconvert reads -- go to the device address wordPtrs[i], rows wordStride bytes apart
+        (>= 4 * width, a multiple of 4; 16-byte aligned pointers and pitch take the fast kernel).  `gamma` is the OUTPUT curve,
+        MetalBT709GammaApple / SRGB / Linear / ITU709 (+unconvert:'s four modes); the input is sRGB bytes, A is ignored (or
+        multiplied in first under setEncodePremultiply).  Returns True/False like the reference (odd sizes are refused, .m:41-46)."""
+        n = len(bgraTextures)
+        if n != len(wordPtrs):
+            raise ValueError("one word buffer per input texture")
+        if n == 0:
+            return True
+        ctx = bgraTextures[0].ctx
+        surfs = (Surface * n)(*[t.surface() for t in bgraTextures])
+        frames = (Frame * n)(*[Frame(int(p), int(wordStride), None, 0, t.width, t.height, 0, 0) for p, t in zip(wordPtrs, bgraTextures)])
+        stream = commandBuffer.stream if commandBuffer is not None else None
+        with ctx._encode_convert(_capi.CONVERT_PACKED444, "convertIntoWords") as ok:
+            if not ok:
+                return False
+            rc = ctx.lib.bt709hip_encode_batch(ctx.handle, n, surfs, frames, MetalBT709GammaSRGB, int(gamma), stream, int(bool(waitUntilCompleted)))
+        if rc != _capi.OK:
+            log.error("convertIntoWords: %s", _capi.strerror(rc))
+            return False
+        return True
+
+    @staticmethod
+    def convert(mrc, inBGRAPixels, outBT709Pixels, width, height, gamma=MetalBT709GammaApple, commandBuffer=None):
+        """+convert:outBT709Pixels:width:height:type: (BGRAToBT709Converter.h:34-46, Software type) on the GPU, host arrays in
+        and out as unconvert's: `inBGRAPixels` is a BGRATexture of `mrc`, or width * height host words (A<<24)|(R<<16)|(G<<8)|B
+        (uploaded into a scratch texture); `outBT709Pixels` is a writable uint32 array of width * height words that receives
+        (Cr<<16)|(Cb<<8)|Y.  Returns True/False like the reference."""
+        return BGRAToBT709Converter.convertBatch(mrc, [inBGRAPixels], [outBT709Pixels], width, height, gamma, commandBuffer)
+
+    @staticmethod
+    def convertBatch(mrc, inBGRAPixelsList, outBT709PixelsList, width, height, gamma=MetalBT709GammaApple, commandBuffer=None):
+        """+convert: over several pictures of one size in ONE launch (no reference twin -- the reference converts a picture per
+        call): the words land in one scratch slab (evenly spaced) and are downloaded into the given host arrays."""
+        width, height, n = int(width), int(height), len(inBGRAPixelsList)
+        if n != len(outBT709PixelsList):
+            raise ValueError("one output array per input picture")
+        if not mrc.setupMetal():
+            return False
+        if (width & 1) or (height & 1):
+            log.error("convert: odd size %dx%d", width, height)  # BGRAToBT709Converter.m:41-46
+            return False
+        if n == 0 or width == 0 or height == 0:
+            return True
+        textures = [p if isinstance(p, BGRATexture) else mrc.makeBGRATexture((width, height), pixels=np.ascontiguousarray(p, dtype=np.uint32).reshape(height, width))
+                    for p in inBGRAPixelsList]
+        if any((t.width, t.height) != (width, height) for t in textures):
+            log.error("convert: a texture is not %dx%d", width, height)
+            return False
+        stride = _align_up(width * 4, 16)
+        scratch = DeviceBuffer(mrc, n * stride * height, placement_tries=1)
+        ptrs = [scratch.ptr + i * stride * height for i in range(n)]
+        try:
+            if not BGRAToBT709Converter.convertIntoWords(textures, ptrs, stride, gamma, commandBuffer, waitUntilCompleted=True):
+                return False
+            stream = commandBuffer.stream if commandBuffer is not None else None
+            for ptr, out in zip(ptrs, outBT709PixelsList):
+                host = np.empty((height, width * 4), dtype=np.uint8)
+                _capi.check(mrc.lib.bt709hip_download(mrc.handle, host.ctypes.data, host.shape[1], ptr, stride, host.shape[1], height, stream), "download")
+                mrc._sync(commandBuffer)
+                np.asarray(out).reshape(-1)[:] = host.view(np.uint32).reshape(-1)
+        finally:
+            scratch.free()
+        return True
+
+    @staticmethod
+    def convertIntoCoreVideoBufferPointSampled(bgraTexture, cvPixelBuffer, gamma=MetalBT709GammaApple, commandBuffer=None,
+                                               waitUntilCompleted=True):
+        """+convert: then copyBT709ToCoreVideo (BGRAToBT709Converter.m:1042-1099) -- how every reference XCTest builds its input
+        frame (MetalBT709DecoderTests.m:189-277) -- in ONE launch with no packed intermediate (CTX_OPT_ENCODE_CONVERT =
+        CONVERT_POINT420): Y of every pixel, and for each 2x2 block the Cb, Cr of the pixel in its odd row and even column.  A
+        planar buffer is written as Y, U, V.  The buffer leaves tagged by setBT709Attributes.  Returns True/False."""
+        ctx = bgraTexture.ctx
+        if not ctx._set_encode_layout([cvPixelBuffer], "convertIntoCoreVideoBufferPointSampled"):
+            return False
+        surf, frame = bgraTexture.surface(), cvPixelBuffer.frame()
+        stream = commandBuffer.stream if commandBuffer is not None else None
+        with ctx._encode_convert(_capi.CONVERT_POINT420, "convertIntoCoreVideoBufferPointSampled") as ok:
+            if not ok:
+                return False
+            rc = ctx.lib.bt709hip_encode(ctx.handle, C.byref(surf), C.byref(frame), MetalBT709GammaSRGB, int(gamma), stream,
+                                         int(bool(waitUntilCompleted)))
+        if rc != _capi.OK:
+            log.error("convertIntoCoreVideoBufferPointSampled: %s", _capi.strerror(rc))
+            return False
+        return BGRAToBT709Converter.setBT709Attributes(cvPixelBuffer)
 
     @staticmethod
     def unconvert(decoder, inBT709Pixels, outBGRATexture, width, height, commandBuffer=None):
