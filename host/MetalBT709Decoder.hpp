@@ -74,6 +74,11 @@ class MetalRenderContext {
   // BGRAToBT709Converter below sets it around each of its calls and puts BT709HIP_CONVERT_OFF back.
   static constexpr int kEncodeConvertOption = BT709HIP_CTX_OPT_ENCODE_CONVERT;
   bool setEncodeConvert(int mode) { return (lastStatus_ = bt709hip_context_set_option(ctx_, kEncodeConvertOption, mode)) == BT709HIP_OK; }
+  // bt709hip_encode[_batch] of BGRA8_SRGB input on this context writes TWO frames per picture from one launch, the colour frame
+  // and the alpha frame (include/bt709hip_ext.h BT709HIP_CTX_OPT_ENCODE_WITH_ALPHA).  false (the default): one.
+  // BGRAToBT709Converter::convertIntoCoreVideoBuffers below sets it around its call and puts 0 back.
+  static constexpr int kEncodeWithAlphaOption = BT709HIP_CTX_OPT_ENCODE_WITH_ALPHA;
+  bool setEncodeWithAlpha(bool on) { return (lastStatus_ = bt709hip_context_set_option(ctx_, kEncodeWithAlphaOption, on ? 1 : 0)) == BT709HIP_OK; }
 
  private:
   bt709hip_context *ctx_ = nullptr;
@@ -130,6 +135,16 @@ class CVPixelBuffer {
     if (rc == BT709HIP_OK)
       rc = bt709hip_upload(ctx_.handle(), const_cast<void *>(f_.cbcr), f_.cbcr_stride, cbcr, w, w, f_.height / 2,
                            nullptr);
+    if (rc == BT709HIP_OK) rc = bt709hip_stream_synchronize(ctx_.handle(), nullptr);
+    return rc == BT709HIP_OK;
+  }
+  // the two planes, tightly packed: W x H luma bytes, W x H/2 CbCr bytes
+  bool downloadPlanes(std::vector<uint8_t> &y, std::vector<uint8_t> &cbcr) const {
+    const size_t w = static_cast<size_t>(f_.width);
+    y.assign(w * f_.height, 0);
+    cbcr.assign(w * (f_.height / 2), 0);
+    int rc = bt709hip_download(ctx_.handle(), y.data(), w, f_.y, f_.y_stride, w, f_.height, nullptr);
+    if (rc == BT709HIP_OK) rc = bt709hip_download(ctx_.handle(), cbcr.data(), w, f_.cbcr, f_.cbcr_stride, w, f_.height / 2, nullptr);
     if (rc == BT709HIP_OK) rc = bt709hip_stream_synchronize(ctx_.handle(), nullptr);
     return rc == BT709HIP_OK;
   }
@@ -212,6 +227,19 @@ struct BGRAToBT709Converter {
     if (rc == BT709HIP_OK) rc = bt709hip_encode(mrc.handle(), in.surface(), out.frame(), BT709HIP_GAMMA_SRGB, gamma, nullptr, 1);
     mrc.setEncodeConvert(BT709HIP_CONVERT_OFF);
     if (rc == BT709HIP_OK) out.setBT709Attributes();
+    return rc == BT709HIP_OK;
+  }
+  // What `srgb_to_bt709 -alpha` makes of one picture (srgb_to_bt709.m:842-954), in ONE launch and one read of the texture: the
+  // colour frame (+convertIntoCoreVideoBuffer:, the subsampling encoder under the two gammas) into `colour`, and the A channel as
+  // the (Linear, Linear) alpha frame into `alpha` -- the pair -decodeBT709:alphaPixelBuffer: takes back.  `alpha` leaves tagged
+  // ITU_R_709_2 / Linear; the gammas govern the colour only.
+  static bool convertIntoCoreVideoBuffers(MetalRenderContext &mrc, const BGRATexture &in, CVPixelBuffer &colour, CVPixelBuffer &alpha,
+                                          int inputGamma, int outputGamma) {
+    const bt709hip_frame pair[2] = {*colour.frame(), *alpha.frame()};
+    int rc = mrc.setEncodeWithAlpha(true) ? BT709HIP_OK : mrc.lastStatus();
+    if (rc == BT709HIP_OK) rc = bt709hip_encode(mrc.handle(), in.surface(), pair, inputGamma, outputGamma, nullptr, 1);
+    mrc.setEncodeWithAlpha(false);
+    if (rc == BT709HIP_OK) alpha.setAttachments(BT709HIP_MATRIX_ITU_R_709_2, BT709HIP_TRANSFER_LINEAR);
     return rc == BT709HIP_OK;
   }
 };

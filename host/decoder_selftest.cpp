@@ -354,6 +354,26 @@ int main(int argc, char **argv) {
       ++failures;
     }
   }
+  // a picture's colour frame and alpha frame from one launch (BT709HIP_CTX_OPT_ENCODE_WITH_ALPHA) against the two launches
+  {
+    const uint32_t bgra[8] = {0xFFFFFFFFu, 0x00102030u, 0x80FF0000u, 0x4D00FF00u, 0x010000FFu, 0xFE808080u, 0x7F123456u, 0xC0FEDCBAu};
+    BGRATexture in(metalRenderContext, 4, 2);
+    CVPixelBuffer colour(metalRenderContext, 4, 2), alpha(metalRenderContext, 4, 2), colour2(metalRenderContext, 4, 2), alpha2(metalRenderContext, 4, 2);
+    bool ok = bt709hip_upload(metalRenderContext.handle(), in.surface()->bgra, in.surface()->stride, bgra, 16, 16, 2, nullptr) == BT709HIP_OK &&
+              metalRenderContext.waitUntilCompleted(nullptr);
+    ok = ok && BGRAToBT709Converter::convertIntoCoreVideoBuffers(metalRenderContext, in, colour, alpha, BT709HIP_GAMMA_SRGB, BT709HIP_GAMMA_APPLE);
+    ok = ok && alpha.frame()->transfer == BT709HIP_TRANSFER_LINEAR;
+    bt709hip_surface as_alpha = *in.surface();
+    as_alpha.format = BT709HIP_FORMAT_BGRA8_ALPHA;
+    ok = ok && bt709hip_encode(metalRenderContext.handle(), in.surface(), colour2.frame(), BT709HIP_GAMMA_SRGB, BT709HIP_GAMMA_APPLE, nullptr, 1) == BT709HIP_OK;
+    ok = ok && bt709hip_encode(metalRenderContext.handle(), &as_alpha, alpha2.frame(), BT709HIP_GAMMA_LINEAR, BT709HIP_GAMMA_LINEAR, nullptr, 1) == BT709HIP_OK;
+    std::vector<uint8_t> y[4], c[4];
+    ok = ok && colour.downloadPlanes(y[0], c[0]) && alpha.downloadPlanes(y[1], c[1]) && colour2.downloadPlanes(y[2], c[2]) && alpha2.downloadPlanes(y[3], c[3]);
+    if (!ok || y[0] != y[2] || c[0] != c[2] || y[1] != y[3] || c[1] != c[3] || y[1][0] != 235 || y[1][1] != 16) {
+      std::fprintf(stderr, "colour + alpha in one launch: not the two launches' frames\n");
+      ++failures;
+    }
+  }
   std::printf("%s: %d vectors, %d failures\n", failures ? "FAIL" : "ok", (argc - 1) / 6, failures);
   return failures ? 1 : 0;
 }

@@ -42,7 +42,8 @@ int bt709hip_context_info(const bt709hip_context *ctx, bt709hip_device_info *inf
 
 /* Launch-shape knobs of a context (tuning and test hooks; no reference twin).  Values are
  * clamped to their valid range; 0 restores the default.  BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT,
- * BT709HIP_CTX_OPT_ENCODE_PREMULTIPLY and BT709HIP_CTX_OPT_ENCODE_CONVERT are no knobs and are NOT clamped: see below. */
+ * BT709HIP_CTX_OPT_ENCODE_PREMULTIPLY, BT709HIP_CTX_OPT_ENCODE_CONVERT and BT709HIP_CTX_OPT_ENCODE_WITH_ALPHA are no knobs and are
+ * NOT clamped: see below. */
 typedef enum {
   BT709HIP_CTX_OPT_GRID_MULT = 1,       /* general (unaligned-layout) kernels: workgroups per launch = CUs x 8 x this; default 2 */
   BT709HIP_CTX_OPT_ENCODE_ROW_PAIRS = 2,/* encoder: consecutive row pairs per workgroup; default 0 = sized per launch */
@@ -51,7 +52,8 @@ typedef enum {
   BT709HIP_CTX_OPT_STREAMING_TRIES = 5, /* device buffers of 256 MB or more that the library allocates itself (in-flight pool slots, the sharder's lanes) go through bt709hip_malloc_streaming with this many candidates; default 4, 1 = plain allocation */
   BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT = 6, /* BT709HIP_CHROMA_NV12 (default) or BT709HIP_CHROMA_I420: the planes bt709hip_encode[_batch] writes; any other value is refused */
   BT709HIP_CTX_OPT_ENCODE_PREMULTIPLY = BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT + 2, /* (eight; seven is no option) 0 (default): BGRA8_SRGB input is encoded as it is; 1: it is straight alpha and is premultiplied first; any other value is refused */
-  BT709HIP_CTX_OPT_ENCODE_CONVERT = BT709HIP_CTX_OPT_ENCODE_PREMULTIPLY + 2 /* (ten; nine is no option) BT709HIP_CONVERT_OFF (default), _PACKED444 or _POINT420: bt709hip_encode[_batch] is the reference's per-pixel +convert:; any other value is refused */
+  BT709HIP_CTX_OPT_ENCODE_CONVERT = BT709HIP_CTX_OPT_ENCODE_PREMULTIPLY + 2, /* (ten; nine is no option) BT709HIP_CONVERT_OFF (default), _PACKED444 or _POINT420: bt709hip_encode[_batch] is the reference's per-pixel +convert:; any other value is refused */
+  BT709HIP_CTX_OPT_ENCODE_WITH_ALPHA = BT709HIP_CTX_OPT_ENCODE_CONVERT + 2 /* (twelve; eleven is no option) 0 (default): one frame per picture; 1: bt709hip_encode[_batch] of BGRA8_SRGB input writes the picture's alpha frame as well, `out` holds TWO frames per picture; any other value is refused */
 } bt709hip_context_option;
 #define BT709HIP_CONVERT_OFF 0       /* bt709hip_encode[_batch] is the subsampling encoder (+convertIntoCoreVideoBuffer:) */
 #define BT709HIP_CONVERT_PACKED444 1 /* +convert: -- one 32-bit word (Cr<<16)|(Cb<<8)|Y per pixel */
@@ -126,6 +128,35 @@ int bt709hip_context_set_option(bt709hip_context *ctx, int option, int value);
  * being captured returns BT709HIP_ERR_NOT_SETUP.  The call reads the option once, on entry.  Any value but the three:
  * BT709HIP_ERR_INVALID_ARG, the option keeps its value (it is not clamped).  Setting it never touches the device: it works while
  * a stream is being captured. */
+/* BT709HIP_CTX_OPT_ENCODE_WITH_ALPHA.  The reference's `srgb_to_bt709 -alpha` turns ONE BGRA picture into TWO clips: the colour as
+ * a BT.709 frame and the A channel as a second, linear frame (<name>_alpha.y4m; srgb_to_bt709.m:842-954).  bt709hip_decode takes
+ * the pair back in one launch (frame + alpha); with this option at 1 and in->format == BT709HIP_FORMAT_BGRA8_SRGB the encode side
+ * writes the pair in one launch, from one read of the surface:
+ *   bt709hip_encode(ctx, in, out, gi, go, ...): `out` points to TWO bt709hip_frames.  out[0] receives the colour frame, byte for
+ *     byte what the call writes with the option at 0 (same gammas, BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT, _ENCODE_PREMULTIPLY);
+ *     out[1] receives the alpha frame, byte for byte what a BGRA8_ALPHA call on the same surface writes: Y = T[A], and
+ *     Cb = Cr = 128 if it has a chroma plane.  gi and go govern the colour alone: the alpha frame is the (Linear, Linear) one
+ *     whatever they are.  A is read from the texel as stored, premultiplying or not;
+ *   bt709hip_encode_batch(ctx, count, ins, outs, ...): `outs` holds 2 * count frames; the colour frames are outs[0 .. count),
+ *     pair i's alpha frame is outs[count + i].
+ * The alpha frames follow BGRA8_ALPHA output's rules: the surface's width and height (BT709HIP_ERR_SIZE_MISMATCH); y non-NULL;
+ * W <= y_stride <= 2^32 - 1 (BT709HIP_ERR_STRIDE); cbcr NULL in EVERY alpha frame of the call or in none
+ * (BT709HIP_ERR_INVALID_ARG); a chroma plane follows the layout option -- under BT709HIP_CHROMA_I420 a U plane with V
+ * (H/2) * cbcr_stride behind it, every byte 128, cbcr_stride >= W/2, under NV12 >= W; equal pitches across the batch
+ * (BT709HIP_ERR_SIZE_MISMATCH).  Evenly spaced batches: all five planes (BGRA, Y, CbCr, alpha Y, alpha CbCr when present) must be
+ * evenly spaced, then any count up to 65535 goes; any two pairs always are.  Otherwise a pointer table, which holds
+ * BT709HIP_MAX_BATCH / 2 = 16 PAIRS here (the kernel argument block does not grow): more is BT709HIP_ERR_UNSUPPORTED.  The fast
+ * kernel needs, beside the colour encoder's alignments, the alpha Y pointer, pitch and step 4-byte aligned and the alpha chroma
+ * plane aligned as the colour's; any other call takes the general kernel and writes the same bytes.  Refused with
+ * BT709HIP_ERR_UNSUPPORTED after the usual validation, nothing enqueued: the option at 1 together with
+ * BT709HIP_CTX_OPT_ENCODE_CONVERT != BT709HIP_CONVERT_OFF, and the option at 1 with BGRA8_ALPHA input.  Colour and alpha planes
+ * that overlap are the caller's error.  bt709hip_encoder_prepare(ctx, gi, go) builds T as well when the option is 1 at the time
+ * of the call: a paired encode can be captured into a graph after that one prepare (BT709HIP_ERR_NOT_SETUP while capturing
+ * otherwise).  bt709hip_last_kernel_name: "encode_bgra_alpha_nv12", "encode_bgra_alpha_i420", "encode_bgra_alpha_nv12_blocks",
+ * "encode_bgra_alpha_i420_blocks", and the same names with "<premul>" behind them.  bt709hip_last_launch_info: the colour
+ * encoder's plan for the same size and count; BT709HIP_CTX_OPT_ENCODE_ROW_PAIRS, _ENCODE_THREADS and _XCD_BANDS apply as they do
+ * there.  The call reads the option once, on entry.  Any value but 0 and 1: BT709HIP_ERR_INVALID_ARG, the option keeps its value
+ * (it is not clamped).  Setting it never touches the device: it works while a stream is being captured.  At 0 nothing changes. */
 
 /* A stream with a scheduling priority (hipStreamCreateWithPriority): 0 = normal, negative = higher, positive = lower; clamped
  * to the device's range.  (MTLCommandQueue has no twin; a renderer that decodes ahead of what it presents puts the look-ahead

@@ -208,8 +208,17 @@ __device__ __forceinline__ EncodeFrame encode_frame(const EncodeParams &p, uint3
 __device__ __forceinline__ uint64_t v_plane_offset(const EncodeParams &p) {
   return static_cast<uint64_t>(p.height >> 1) * p.cbcr_stride;  // uniform: two scalar multiplies
 }
-template <uint32_t LAYOUT>
-__device__ __forceinline__ void store_quad_chroma(const EncodeParams &p, uint8_t *row, uint32_t q, uint32_t word) {
+// The alpha frame of a pair (the paired kernels, kFormPair; BT709HIP_CTX_OPT_ENCODE_WITH_ALPHA): its planes, its own
+// pitches, its V plane behind its U plane by its own chroma pitch
+struct AlphaPlanes {
+  uint8_t *y, *cbcr;  // cbcr: nullptr in every pair of the launch = the alpha frames have no chroma plane
+  uint32_t y_stride, cbcr_stride, height;
+  bool with_cbcr;     // uniform over the launch
+};
+__device__ __forceinline__ uint64_t v_plane_offset(const AlphaPlanes &a) { return static_cast<uint64_t>(a.height >> 1) * a.cbcr_stride; }
+// (Planes: EncodeParams, or -- the paired kernels' alpha frame -- AlphaPlanes: whatever v_plane_offset takes)
+template <uint32_t LAYOUT, typename Planes>
+__device__ __forceinline__ void store_quad_chroma(const Planes &p, uint8_t *row, uint32_t q, uint32_t word) {
   if (LAYOUT == kChromaI420) {
     __builtin_nontemporal_store(static_cast<uint16_t>(word), reinterpret_cast<uint16_t *>(row + 2u * q));
     __builtin_nontemporal_store(static_cast<uint16_t>(word >> 16), reinterpret_cast<uint16_t *>(row + v_plane_offset(p) + 2u * q));
@@ -227,8 +236,8 @@ __device__ __forceinline__ uint8_t second_byte(uint32_t word) {
   if (LAYOUT == kChromaI420) asm("" : "+v"(b));
   return static_cast<uint8_t>(b);
 }
-template <uint32_t LAYOUT>
-__device__ __forceinline__ void store_block_chroma(const EncodeParams &p, uint8_t *row, uint32_t bx, uint8_t cb, uint8_t cr) {
+template <uint32_t LAYOUT, typename Planes>
+__device__ __forceinline__ void store_block_chroma(const Planes &p, uint8_t *row, uint32_t bx, uint8_t cb, uint8_t cr) {
   if (LAYOUT == kChromaI420) {
     row[bx] = cb;
     (row + v_plane_offset(p))[bx] = cr;
@@ -249,6 +258,43 @@ __device__ __forceinline__ uint32_t texel(uint32_t word) {
 __device__ __forceinline__ void premultiply_row(u32x4 &row) {
   row.x = premultiply_word(row.x), row.y = premultiply_word(row.y), row.z = premultiply_word(row.z), row.w = premultiply_word(row.w);
 }
+
+// ---- T[A], the alpha frames' luma table (bt709_alpha_luma.h): 256 bytes in LDS, for the alpha kernels and the paired colour kernels
+__device__ __forceinline__ void stage_alpha_luma(uint32_t *lut, const EncodeParams &p) {
+  if (threadIdx.x < 64) lut[threadIdx.x] = p.alpha_luma[threadIdx.x];  // every workgroup has at least one wave
+}
+
+// T[byte 3] of four BGRA words, packed in memory order
+__device__ __forceinline__ uint32_t alpha_luma4(const uint32_t *lut, const u32x4 w) {
+  const uint8_t *t = reinterpret_cast<const uint8_t *>(lut);
+  return static_cast<uint32_t>(t[w.x >> 24]) | (static_cast<uint32_t>(t[w.y >> 24]) << 8) |
+         (static_cast<uint32_t>(t[w.z >> 24]) << 16) | (static_cast<uint32_t>(t[w.w >> 24]) << 24);
+}
+
+// ---- the paired kernels: the colour frame of pair i, and its alpha frame through `a`
+__device__ __forceinline__ EncodeFrame pair_frame(const EncodeParams &p, uint32_t i, AlphaPlanes &a) {
+  a.y_stride = static_cast<uint32_t>(p.pairs[0].spare);
+  a.cbcr_stride = static_cast<uint32_t>(static_cast<uint64_t>(p.pairs[0].spare) >> 32);
+  a.with_cbcr = p.pairs[0].alpha_cbcr != nullptr;
+  a.height = p.height;
+  const EncodePair &e = p.pairs[p.uniform ? 0u : i];
+  EncodeFrame f = {e.bgra, e.y, e.cbcr};
+  a.y = e.alpha_y, a.cbcr = e.alpha_cbcr;
+  if (p.uniform) {
+    f.bgra += static_cast<int64_t>(i) * p.step_bgra;
+    f.y += static_cast<int64_t>(i) * p.step_y;
+    f.cbcr += static_cast<int64_t>(i) * p.step_cbcr;
+    a.y += static_cast<int64_t>(i) * p.pairs[1].spare;
+    a.cbcr += static_cast<int64_t>(i) * p.pairs[2].spare;  // of a null plane: never dereferenced (with_cbcr)
+  }
+  return f;
+}
+// T sits in the dynamic segment behind the two tables stage_encode_tables puts at address 0 (these kernels may have no static
+// LDS): launch_encode sizes the segment for it
+__device__ __forceinline__ uint32_t *pair_alpha_lut(unsigned char *lds_raw, const EncodeParams &p) {
+  return reinterpret_cast<uint32_t *>(lds_raw + 256u * static_cast<uint32_t>(sizeof(EncodeByteEntry)) + p.from_linear_bytes);
+}
+constexpr size_t kAlphaLumaLdsBytes = 256;
 
 }  // namespace
 
@@ -334,8 +380,14 @@ encode_bgra_blocks(const EncodeParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   constexpr uint32_t LAYOUT = form_layout(FORM);
   const EncodeLds t = stage_encode_tables(lds_raw, p);
+  [[maybe_unused]] uint32_t *alpha_lut = nullptr;  // kFormPair alone
+  if constexpr (form_pair(FORM)) stage_alpha_luma(alpha_lut = pair_alpha_lut(lds_raw, p), p);
   __syncthreads();
-  const EncodeFrame f = encode_frame(p, blockIdx.z);
+  [[maybe_unused]] AlphaPlanes a;  // kFormPair alone
+  const EncodeFrame f = [&] {
+    if constexpr (form_pair(FORM)) return pair_frame(p, blockIdx.z, a);
+    else return encode_frame(p, blockIdx.z);
+  }();
   const float quarter_n = __fmul_rn(0.25f, p.from_linear_scale);
   const uint32_t bw = p.width >> 1;
   const uint32_t rp = blockIdx.y;
@@ -343,6 +395,16 @@ encode_bgra_blocks(const EncodeParams p) {
     const uint32_t *r0 = reinterpret_cast<const uint32_t *>(f.bgra + static_cast<size_t>(2 * rp) * p.bgra_stride);
     const uint32_t *r1 = reinterpret_cast<const uint32_t *>(f.bgra + static_cast<size_t>(2 * rp + 1) * p.bgra_stride);
     const uint32_t blk[4] = {texel<FORM>(r0[2 * bx]), texel<FORM>(r0[2 * bx + 1]), texel<FORM>(r1[2 * bx]), texel<FORM>(r1[2 * bx + 1])};
+    if constexpr (form_pair(FORM)) {  // the rider: T[A] of the words as loaded, byte stores as encode_alpha_y_blocks
+      const uint8_t *ta = reinterpret_cast<const uint8_t *>(alpha_lut);
+      uint8_t *a0 = a.y + static_cast<size_t>(2 * rp) * a.y_stride + 2u * bx;
+      uint8_t *a1 = a0 + a.y_stride;
+      a0[0] = ta[r0[2 * bx] >> 24];
+      a0[1] = ta[r0[2 * bx + 1] >> 24];
+      a1[0] = ta[r1[2 * bx] >> 24];
+      a1[1] = ta[r1[2 * bx + 1] >> 24];
+      if (a.with_cbcr) store_block_chroma<LAYOUT>(a, a.cbcr + static_cast<size_t>(rp) * a.cbcr_stride, bx, 128, 128);
+    }
     float v[6];
     encode_block(t, quarter_n, blk, v);
     uint32_t ytop, ybot, cbcr;
@@ -364,23 +426,7 @@ encode_bgra_blocks(const EncodeParams p) {
 // TABLE, not arithmetic: the float expression costs a conversion, four multiplies, three adds and a converting pack per pixel
 // (9 VALU, 4 of them 4-cycle); the lookup is a shift, a ds_read_u8 and a share of three v_perm/v_lshl_or per word.  The 256
 // bytes are 64 dwords = one per LDS bank: lanes that hit the same dword broadcast, different dwords never conflict.
-namespace {
-
-typedef __attribute__((address_space(3))) const uint8_t *LdsBytePtr;
-
-__device__ __forceinline__ void stage_alpha_luma(uint32_t *lut, const EncodeParams &p) {
-  if (threadIdx.x < 64) lut[threadIdx.x] = p.alpha_luma[threadIdx.x];  // every workgroup has at least one wave
-}
-
-// T[byte 3] of four BGRA words, packed in memory order
-__device__ __forceinline__ uint32_t alpha_luma4(const uint32_t *lut, const u32x4 w) {
-  const uint8_t *t = reinterpret_cast<const uint8_t *>(lut);
-  return static_cast<uint32_t>(t[w.x >> 24]) | (static_cast<uint32_t>(t[w.y >> 24]) << 8) |
-         (static_cast<uint32_t>(t[w.z >> 24]) << 16) | (static_cast<uint32_t>(t[w.w >> 24]) << 24);
-}
-
-}  // namespace
-
+// (stage_alpha_luma and alpha_luma4 stand above the colour kernels: their paired instantiations use them, too)
 // grid = (tiles, row-pair groups, frames), as encode_bgra
 template <uint32_t LAYOUT>
 __global__ void __launch_bounds__(kMaxBlockThreads)
@@ -451,6 +497,7 @@ encode_alpha_y_blocks(const EncodeParams p) {
 
 }  // namespace bt709
 
+#include "bt709_encode_pair.h"     // BT709HIP_CTX_OPT_ENCODE_WITH_ALPHA: encode_bgra_alpha over the helpers above
 #include "bt709_encode_convert.h"  // BT709HIP_CTX_OPT_ENCODE_CONVERT: convert_bgra, convert_bgra_blocks over the helpers above
 
 namespace bt709 {
@@ -461,7 +508,7 @@ namespace {
 // static) -- prepare_encode_kernels raises the cap of exactly those.  A selector field is a value or kAny; the first matching row
 // is the launch's kernel.
 struct EncodeKernel {
-  int fast, alpha, premultiply, convert;  // convert: EncodeParams::convert_mode
+  int fast, alpha, premultiply, convert;  // alpha: 0 colour, 1 alpha frame, 2 the pair; convert: EncodeParams::convert_mode
   bool stages_table;
   void (*fn[2])(const EncodeParams);  // [chroma layout]
   const char *name[2];
@@ -470,6 +517,10 @@ struct EncodeKernel {
 // alpha kernels' NV12 form names none (encode_alpha_y, encode_alpha_y<i420>)
 #define ENCODE_COLOUR(fast, premultiply, suffix, KERNEL, FORM) \
   {fast, 0, premultiply, kConvertOff, true, {KERNEL<kChromaNV12 | (FORM)>, KERNEL<kChromaI420 | (FORM)>}, {"encode_bgra_nv12" suffix, "encode_bgra_i420" suffix}}
+// the paired kernels (EncodeParams: alpha_luma and per_byte both non-null): encode_bgra_alpha (bt709_encode_pair.h) and the general
+// colour kernel's kFormPair instantiations
+#define ENCODE_PAIR(fast, premultiply, suffix, KERNEL, FORM) \
+  {fast, 2, premultiply, kConvertOff, true, {KERNEL<kChromaNV12 | kFormPair | (FORM)>, KERNEL<kChromaI420 | kFormPair | (FORM)>}, {"encode_bgra_alpha_nv12" suffix, "encode_bgra_alpha_i420" suffix}}
 #define ENCODE_ALPHA(fast, stem, KERNEL) {fast, 1, kAny, kConvertOff, false, {KERNEL<kChromaNV12>, KERNEL<kChromaI420>}, {stem, stem "<i420>"}}
 // the converter (the shim hands it BGRA8_SRGB input alone): the packed form writes no plane, one instantiation under both layouts
 #define CONVERT_PACKED(fast, premultiply, suffix, KERNEL, FORM) \
@@ -485,6 +536,10 @@ const EncodeKernel kEncodeKernels[] = {
     CONVERT_POINT(1, 0, "", convert_bgra, 0),
     CONVERT_POINT(0, 1, "_blocks<premul>", convert_bgra_blocks, kFormStraight),
     CONVERT_POINT(0, 0, "_blocks", convert_bgra_blocks, 0),
+    ENCODE_PAIR(1, 1, "<premul>", encode_bgra_alpha, kFormStraight),
+    ENCODE_PAIR(1, 0, "", encode_bgra_alpha, 0),
+    ENCODE_PAIR(0, 1, "_blocks<premul>", encode_bgra_blocks, kFormStraight),
+    ENCODE_PAIR(0, 0, "_blocks", encode_bgra_blocks, 0),
     ENCODE_ALPHA(1, "encode_alpha_y", encode_alpha_y),
     ENCODE_COLOUR(1, 1, "<premul>", encode_bgra, kFormStraight),
     ENCODE_COLOUR(1, 0, "", encode_bgra, 0),
@@ -494,18 +549,19 @@ const EncodeKernel kEncodeKernels[] = {
 };
 #undef ENCODE_COLOUR
 #undef ENCODE_ALPHA
+#undef ENCODE_PAIR
 #undef CONVERT_PACKED
 #undef CONVERT_POINT
 
 // The kernel of a launch that launch_encode has planned and recorded
-const char *launch_encode_kernel(const EncodeParams &p, const dim3 &grid, const dim3 &block, size_t lds, bool fast, bool alpha, hipStream_t stream) {
+const char *launch_encode_kernel(const EncodeParams &p, const dim3 &grid, const dim3 &block, size_t lds, bool fast, int alpha, hipStream_t stream) {
   const uint32_t layout = p.chroma_layout == kChromaI420 ? kChromaI420 : kChromaNV12;
   for (const EncodeKernel &k : kEncodeKernels) {
     if (k.fast != fast || k.alpha != alpha || !selects(k.premultiply, p.premultiply != 0) || k.convert != static_cast<int>(p.convert_mode)) continue;
     hipLaunchKernelGGL(k.fn[layout], grid, block, lds, stream, p);
     return k.name[layout];
   }
-  return nullptr;  // unreachable: the rows cover fast x alpha x premultiply, and fast x premultiply for either converter mode
+  return nullptr;  // unreachable: the rows cover fast x {colour, alpha, pair} x premultiply, and fast x premultiply for either converter mode
 }
 
 }  // namespace
@@ -520,8 +576,9 @@ const char *launch_encode(const EncodeParams &params, int frames, bool fast, boo
   }
   EncodeParams p = params;
   if (p.row_pairs_per_block == 0) p.row_pairs_per_block = encode_row_pairs_per_block(p.width, p.height, frames);
-  const bool alpha = p.alpha_luma != nullptr;  // BT709HIP_FORMAT_BGRA8_ALPHA: same plan, the alpha kernels (static LDS)
-  const size_t lds = alpha || p.convert_mode != kConvertOff ? 0 : 256 * sizeof(EncodeByteEntry) + p.from_linear_bytes;  // the converter's curve is static, too
+  // BT709HIP_FORMAT_BGRA8_ALPHA: same plan, the alpha kernels (static LDS); with the colour's tables as well: the pair, T behind them
+  const int alpha = p.convert_mode != kConvertOff ? 0 : encode_pair(p) ? 2 : p.alpha_luma != nullptr ? 1 : 0;
+  const size_t lds = alpha == 1 || p.convert_mode != kConvertOff ? 0 : 256 * sizeof(EncodeByteEntry) + p.from_linear_bytes + (alpha == 2 ? kAlphaLumaLdsBytes : 0);  // the converter's curve is static, too
   dim3 grid((p.width / 2 + kBlockThreads - 1) / kBlockThreads, p.height / 2, frames), block(kBlockThreads);
   if (fast) {
     const uint32_t quads = p.width / 4;

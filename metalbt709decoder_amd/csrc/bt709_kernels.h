@@ -190,8 +190,23 @@ struct EncodeFrame {
   uint8_t *y;
   uint8_t *cbcr;        // alpha kernels: nullptr in EVERY frame of the launch = write no CbCr plane
 };
+// BT709HIP_CTX_OPT_ENCODE_WITH_ALPHA: a picture's colour frame and its alpha frame (Y = T[A]) from one launch.  The
+// frames[] area read as kMaxPairBatch entries; entry 0 begins as frames[0] does.  The spare slots carry what has no field:
+//   pairs[0].spare = alpha_y_stride | alpha_cbcr_stride << 32, pairs[1].spare = the alpha Y step, pairs[2].spare = the alpha chroma step
+// (bytes, as step_y / step_cbcr; read under `uniform` alone).  alpha_cbcr: nullptr in EVERY pair of the launch = no alpha chroma plane.
+struct EncodePair {
+  const uint8_t *bgra;
+  uint8_t *y, *cbcr;
+  uint8_t *alpha_y, *alpha_cbcr;
+  int64_t spare;
+};
+constexpr int kMaxPairBatch = kMaxBatch / 2;  // pairs in the kernarg table
+static_assert(sizeof(EncodePair[kMaxPairBatch]) == sizeof(EncodeFrame[kMaxBatch]), "the pair table is the frame table's bytes");
 struct EncodeParams {
-  EncodeFrame frames[kMaxBatch];
+  union {
+    EncodeFrame frames[kMaxBatch];
+    EncodePair pairs[kMaxPairBatch];  // a paired launch: alpha_luma AND per_byte non-null (below)
+  };
   // uniform != 0: frame i = frames[0] + i * step_* (bytes), as in DecodeParams
   uint32_t uniform;
   // BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT: kChromaI420 = frames[i].cbcr is the U (Cb) plane, W/2 x H/2 bytes at pitch cbcr_stride,
@@ -229,14 +244,20 @@ struct EncodeParams {
   uint32_t bgra_stride, y_stride, cbcr_stride;
   uint32_t xcd_bands, frames_per_band;  // XCD-aware work map, as in DecodeParams (filled by launch_encode)
   // BT709HIP_FORMAT_BGRA8_ALPHA: non-null selects the alpha kernels (encode_alpha_y / encode_alpha_y_blocks): 256 bytes
-  // T[A], four per word (bt709_alpha_luma.h); per_byte / from_linear* are not read then
+  // T[A], four per word (bt709_alpha_luma.h); per_byte / from_linear* are not read then.
+  // Non-null TOGETHER WITH per_byte (convert_mode kConvertOff) is the selector of the paired kernels (encode_pair): they read both
+  // sets of tables and pairs[] in place of frames[].  No field or bit of its own: the alpha kernels alone leave per_byte null.
   const uint32_t *alpha_luma;
 };
+inline bool encode_pair(const EncodeParams &p) { return p.alpha_luma != nullptr && p.per_byte != nullptr; }
 static_assert(sizeof(EncodeParams) == 880, "a field appended to EncodeParams moves the implicit kernel arguments behind it: every encoder kernel's code changes");
 enum : uint32_t { kConvertOff = 0, kConvertPacked444 = 1, kConvertPoint420 = 2 };  // == BT709HIP_CONVERT_*
 // Further bit of the converter kernels' FORM (beside the layout and kFormStraight): the packed 4:4:4 output
 enum : uint32_t { kFormPacked = 4 };
 constexpr bool form_packed(uint32_t form) { return (form & kFormPacked) != 0; }
+// Further bit of the colour encoder kernels' FORM: the alpha frame rides along (EncodePair)
+enum : uint32_t { kFormPair = 8 };
+constexpr bool form_pair(uint32_t form) { return (form & kFormPair) != 0; }
 const char *launch_encode(const EncodeParams &p, int frames, bool fast, bool xcd_bands, hipStream_t stream);
 hipError_t prepare_encode_kernels();
 // Encoder fast-path geometry, measured on 4K (tools/encode_shapes.sh sweeps):

@@ -43,6 +43,10 @@ inline void advance_frames(EncodeParams &p, int head) {
   p.frames[0].bgra += static_cast<int64_t>(head) * p.step_bgra;
   p.frames[0].y += static_cast<int64_t>(head) * p.step_y;
   if (p.frames[0].cbcr) p.frames[0].cbcr += static_cast<int64_t>(head) * p.step_cbcr;  // alpha frames may have none
+  if (encode_pair(p)) {  // pairs[0] begins as frames[0]: the alpha planes behind it
+    p.pairs[0].alpha_y += static_cast<int64_t>(head) * p.pairs[1].spare;
+    if (p.pairs[0].alpha_cbcr) p.pairs[0].alpha_cbcr += static_cast<int64_t>(head) * p.pairs[2].spare;
+  }
 }
 
 // the plan of the call's FIRST launch, for bt709hip_last_launch_info

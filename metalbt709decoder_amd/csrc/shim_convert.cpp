@@ -260,9 +260,17 @@ int bt709hip_encode_batch(bt709hip_context *ctx, int count, const bt709hip_surfa
   // BT709HIP_CTX_OPT_ENCODE_PREMULTIPLY, read once: BGRA8_SRGB texels are straight alpha.  BGRA8_ALPHA input reads A alone: unaffected.
   const bool premultiply = ctx->encode_premultiply != 0 && !alpha;
   const size_t chroma_align = planar ? 2 : 4;  // the fast kernels' chroma store: a 2-byte half per plane, or the CbCr dword
+  // BT709HIP_CTX_OPT_ENCODE_WITH_ALPHA, read once: BGRA8_SRGB input writes two frames, the colour into outs[i] and the alpha frame
+  // (BGRA8_ALPHA output's rules) into outs[count + i], from one launch.  Not with the per-pixel converter and not for BGRA8_ALPHA
+  // input: refused behind the usual validation.
+  const bool with_alpha = ctx->encode_with_alpha != 0;
+  const bool pair = with_alpha && !alpha && convert == BT709HIP_CONVERT_OFF;
+  const bt709hip_frame &alpha0 = outs[pair ? count : 0];
+  const bool alpha_no_cbcr = pair && alpha0.cbcr == nullptr;
   bool uniform = count > 1;
   const size_t y_px = packed ? 4 : 1, y_align = packed ? 16 : 4;  // bytes of a pixel in the plane out->y points to; the fast kernels' store to it
   bool fast = (in0.width % 4) == 0 && (in0.stride % 16) == 0 && (out0.y_stride % y_align) == 0 && (no_cbcr || (out0.cbcr_stride % chroma_align) == 0);
+  if (pair) fast = fast && (alpha0.y_stride % 4) == 0 && (alpha_no_cbcr || (alpha0.cbcr_stride % chroma_align) == 0);
   EncodeParams p;
   std::memset(&p, 0, sizeof p);
   for (int i = 0; i < count; ++i) {
@@ -291,15 +299,35 @@ int bt709hip_encode_batch(bt709hip_context *ctx, int count, const bt709hip_surfa
       uniform = uniform && byte_step(ins[0].bgra, in.bgra) == byte_step(ins[0].bgra, ins[1].bgra) * i &&
                 byte_step(outs[0].y, out.y) == byte_step(outs[0].y, outs[1].y) * i &&
                 byte_step(outs[0].cbcr, out.cbcr) == byte_step(outs[0].cbcr, outs[1].cbcr) * i;
-    if (i < kMaxBatch) {
+    if (pair) {  // the pair's alpha frame: what a BGRA8_ALPHA call checks of its output, in that call's order
+      const bt709hip_frame &af = outs[count + i];
+      if (af.width != in.width || af.height != in.height) return BT709HIP_ERR_SIZE_MISMATCH;
+      if (af.y_stride != alpha0.y_stride || (!alpha_no_cbcr && af.cbcr != nullptr && af.cbcr_stride != alpha0.cbcr_stride)) return BT709HIP_ERR_SIZE_MISMATCH;
+      if (af.y == nullptr || (af.cbcr == nullptr) != alpha_no_cbcr) return BT709HIP_ERR_INVALID_ARG;
+      if (af.y_stride < w || (!alpha_no_cbcr && af.cbcr_stride < (planar ? w / 2 : w))) return BT709HIP_ERR_STRIDE;
+      if (af.y_stride > 0xffffffffu || (!alpha_no_cbcr && af.cbcr_stride > 0xffffffffu)) return BT709HIP_ERR_STRIDE;
+      fast = fast && aligned(af.y, 4) && aligned(af.cbcr, chroma_align);
+      if (i >= 2)
+        uniform = uniform && byte_step(alpha0.y, af.y) == byte_step(alpha0.y, outs[count + 1].y) * i &&
+                  byte_step(alpha0.cbcr, af.cbcr) == byte_step(alpha0.cbcr, outs[count + 1].cbcr) * i;
+      if (i < kMaxPairBatch) {  // the frames[] area as 16 pairs (bt709_kernels.h EncodePair): never both tables
+        EncodePair &e = p.pairs[i];
+        e.bgra = static_cast<const uint8_t *>(in.bgra);
+        e.y = static_cast<uint8_t *>(const_cast<void *>(out.y));
+        e.cbcr = static_cast<uint8_t *>(const_cast<void *>(out.cbcr));
+        e.alpha_y = static_cast<uint8_t *>(const_cast<void *>(af.y));
+        e.alpha_cbcr = static_cast<uint8_t *>(const_cast<void *>(af.cbcr));
+      }
+    } else if (i < kMaxBatch) {
       p.frames[i].bgra = static_cast<const uint8_t *>(in.bgra);
       p.frames[i].y = static_cast<uint8_t *>(const_cast<void *>(out.y));
       p.frames[i].cbcr = static_cast<uint8_t *>(const_cast<void *>(out.cbcr));
     }
   }
-  if (count > (uniform ? kMaxUniformBatch : kMaxBatch)) return BT709HIP_ERR_UNSUPPORTED;
+  if (count > (uniform ? kMaxUniformBatch : pair ? kMaxPairBatch : kMaxBatch)) return BT709HIP_ERR_UNSUPPORTED;
   // the reference's per-pixel converters take sRGB bytes only, and no alpha clip goes through them
   if (convert != BT709HIP_CONVERT_OFF && (alpha || input_gamma != BT709HIP_GAMMA_SRGB)) return BT709HIP_ERR_UNSUPPORTED;
+  if (with_alpha && !pair) return BT709HIP_ERR_UNSUPPORTED;  // the converter writes no alpha frame; an alpha clip has none beside itself
   if (in0.width == 0 || in0.height == 0) return BT709HIP_OK;
   if (int rc = bind(ctx)) return rc;
   FLUSH_STREAM(ctx, stream);
@@ -321,6 +349,10 @@ int bt709hip_encode_batch(bt709hip_context *ctx, int count, const bt709hip_surfa
     p.from_linear_scale = static_cast<float>(t.from_linear_n);
     p.from_linear_coarse = t.coarse_scale;
     p.from_linear_offset = t.coarse_offset;
+    if (pair) {  // both sets of tables: launch_encode's selector of the paired kernels
+      if (int rc = alpha_luma_table(ctx, s)) return rc;
+      p.alpha_luma = static_cast<const uint32_t *>(ctx->d_alpha_luma);
+    }
   }
 
   if (uniform) {
@@ -328,7 +360,13 @@ int bt709hip_encode_batch(bt709hip_context *ctx, int count, const bt709hip_surfa
     p.step_bgra = byte_step(ins[0].bgra, ins[1].bgra);
     p.step_y = byte_step(outs[0].y, outs[1].y);
     p.step_cbcr = byte_step(outs[0].cbcr, outs[1].cbcr);
+    if (pair) {
+      p.pairs[1].spare = byte_step(alpha0.y, outs[count + 1].y);
+      p.pairs[2].spare = byte_step(alpha0.cbcr, outs[count + 1].cbcr);
+    }
   }
+  if (pair)  // the alpha frames' pitches: the spare slot of pair 0
+    p.pairs[0].spare = static_cast<int64_t>(static_cast<uint64_t>(alpha0.y_stride) | (alpha_no_cbcr ? 0ull : static_cast<uint64_t>(alpha0.cbcr_stride) << 32));
   p.row_pairs_per_block = static_cast<uint32_t>(ctx->encode_row_pairs);  // 0: sized per launch
   p.block_threads = static_cast<uint32_t>(ctx->encode_threads);
   p.width = static_cast<uint32_t>(in0.width);
@@ -354,7 +392,8 @@ int bt709hip_encoder_prepare(bt709hip_context *ctx, int input_gamma, int output_
   if (input_gamma == BT709HIP_GAMMA_SRGB)  // the converter's curve as well: 1 KiB
     if (int rc = convert_curve_table(ctx, output_gamma, nullptr)) return rc;
   if (output_gamma == 3) return BT709HIP_OK;  // no subsampling encoder writes ITU709
-  if (input_gamma == BT709HIP_GAMMA_LINEAR && output_gamma == BT709HIP_GAMMA_LINEAR)  // the one pair BGRA8_ALPHA input encodes with
+  // T: the one gamma pair BGRA8_ALPHA input encodes with; under BT709HIP_CTX_OPT_ENCODE_WITH_ALPHA every pair's alpha frame reads it
+  if ((input_gamma == BT709HIP_GAMMA_LINEAR && output_gamma == BT709HIP_GAMMA_LINEAR) || ctx->encode_with_alpha != 0)
     if (int rc = alpha_luma_table(ctx, nullptr)) return rc;
   return encoder_tables(ctx, input_gamma, output_gamma, nullptr);
 }

@@ -145,6 +145,10 @@ int bt709hip_context_set_option(bt709hip_context *ctx, int option, int value) {
       if (value != BT709HIP_CONVERT_OFF && value != BT709HIP_CONVERT_PACKED444 && value != BT709HIP_CONVERT_POINT420) return BT709HIP_ERR_INVALID_ARG;
       ctx->encode_convert = value;
       return BT709HIP_OK;
+    case BT709HIP_CTX_OPT_ENCODE_WITH_ALPHA:  // and once more: T is built by the first paired call, or by bt709hip_encoder_prepare under the option
+      if (value != 0 && value != 1) return BT709HIP_ERR_INVALID_ARG;
+      ctx->encode_with_alpha = value;
+      return BT709HIP_OK;
     case BT709HIP_CTX_OPT_STREAMING_TRIES:
       ctx->streaming_tries = value <= 0 ? 4 : clamp_int(value, 1, 32);
       return BT709HIP_OK;

@@ -582,6 +582,21 @@ class MetalRenderContext:
         finally:
             self.lib.bt709hip_context_set_option(self.handle, _capi.CTX_OPT_ENCODE_CONVERT, _capi.CONVERT_OFF)
 
+    @contextlib.contextmanager
+    def _encode_with_alpha(self, what):
+        """bt709hip_context_set_option(CTX_OPT_ENCODE_WITH_ALPHA) around ONE paired encode: 1 on entry and back to 0 on the way
+        out, whatever the call returned or raised, so that every other encode call of this context writes one frame per picture.
+        The setter never touches the device.  Yields True, or False when the library refused the option."""
+        rc = self.lib.bt709hip_context_set_option(self.handle, _capi.CTX_OPT_ENCODE_WITH_ALPHA, 1)
+        if rc != _capi.OK:
+            log.error("%s: CTX_OPT_ENCODE_WITH_ALPHA = 1: %s", what, _capi.strerror(rc))
+            yield False
+            return
+        try:
+            yield True
+        finally:
+            self.lib.bt709hip_context_set_option(self.handle, _capi.CTX_OPT_ENCODE_WITH_ALPHA, 0)
+
     def _set_encode_layout(self, pixelBuffers, what):
         """The encoder's chroma layout from the buffers an encode call was handed: a planar CVPixelBuffer is written in place.  As
         MetalBT709Decoder._set_layout: the buffer's `planar` flag is authoritative, planar and NV12 buffers in one call are
@@ -734,12 +749,17 @@ class BGRAToBT709Converter:
 
     @staticmethod
     def convertIntoCoreVideoBuffer(bgraTexture, cvPixelBuffer, inputGamma, outputGamma, commandBuffer=None,
-                                   waitUntilCompleted=True):
+                                   waitUntilCompleted=True, alphaPixelBuffer=None):
         """+convertIntoCoreVideoBuffer:cvPixelBuffer:inputGamma:outputGamma: (BGRAToBT709Converter.h:73-76)
         -> cvpbu_ycbcr_subsample: BGRA pixels -> NV12 with linear-light 2x2 chroma averaging, on the GPU.
         The source is a BGRATexture (device memory) instead of a CGImage.  Gammas are MetalBT709Gamma*
         values Apple / SRGB / Linear.  Returns True/False like the reference.  A planar buffer
-        (createCoreVideoYCbCrBuffer(..., planar=True)) is written as Y, U, V -- the Y4M FRAME payload -- by the same launch."""
+        (createCoreVideoYCbCrBuffer(..., planar=True)) is written as Y, U, V -- the Y4M FRAME payload -- by the same launch.
+        alphaPixelBuffer: the picture's ALPHA frame as well (what convertAlphaIntoCoreVideoBuffer writes), from the same launch
+        and the same read of the texture -- the pair -decodeBT709:alphaPixelBuffer: takes back."""
+        if alphaPixelBuffer is not None:
+            return BGRAToBT709Converter.convertIntoCoreVideoBuffers([bgraTexture], [cvPixelBuffer], inputGamma, outputGamma, commandBuffer,
+                                                                    waitUntilCompleted, alphaPixelBuffers=[alphaPixelBuffer])
         ctx = bgraTexture.ctx
         if not ctx._set_encode_layout([cvPixelBuffer], "convertIntoCoreVideoBuffer"):
             return False
@@ -754,25 +774,42 @@ class BGRAToBT709Converter:
 
     @staticmethod
     def convertIntoCoreVideoBuffers(bgraTextures, cvPixelBuffers, inputGamma, outputGamma, commandBuffer=None,
-                                    waitUntilCompleted=True):
+                                    waitUntilCompleted=True, alphaPixelBuffers=None):
         """`count` same-sized pictures in one launch (no reference twin: the app converts one
-        CGImage per call, BGRAToBT709Converter.m:532-569)."""
+        CGImage per call, BGRAToBT709Converter.m:532-569).
+        alphaPixelBuffers: one more buffer per picture, which receives the picture's ALPHA frame from the same launch
+        (bt709hip_encode_batch under CTX_OPT_ENCODE_WITH_ALPHA, set around this call alone and put back whatever happens); they
+        leave tagged ITU_R_709_2 / Linear, as convertAlphaIntoCoreVideoBuffers leaves them.  The gammas govern the colour only."""
         n = len(bgraTextures)
-        if n != len(cvPixelBuffers):
+        if n != len(cvPixelBuffers) or (alphaPixelBuffers is not None and n != len(alphaPixelBuffers)):
             raise ValueError("one output buffer per input texture")
         if n == 0:
             return True
         ctx = bgraTextures[0].ctx
-        if not ctx._set_encode_layout(cvPixelBuffers, "convertIntoCoreVideoBuffers"):
+        outs = list(cvPixelBuffers) + list(alphaPixelBuffers or [])
+        # the layout option covers both frames of a pair; an alpha buffer without a chroma plane has nothing to lay out
+        laid_out = list(cvPixelBuffers) + [b for b in alphaPixelBuffers or [] if b.cbcr_ptr]
+        if not ctx._set_encode_layout(laid_out, "convertIntoCoreVideoBuffers"):
             return False
         surfs = (Surface * n)(*[t.surface() for t in bgraTextures])
-        frames = (Frame * n)(*[b.frame() for b in cvPixelBuffers])
+        frames = (Frame * len(outs))(*[b.frame() for b in outs])  # colour frames, then pair i's alpha frame at n + i
         stream = commandBuffer.stream if commandBuffer is not None else None
-        rc = ctx.lib.bt709hip_encode_batch(ctx.handle, n, surfs, frames, int(inputGamma), int(outputGamma), stream,
-                                           int(bool(waitUntilCompleted)))
+
+        def call():
+            return ctx.lib.bt709hip_encode_batch(ctx.handle, n, surfs, frames, int(inputGamma), int(outputGamma), stream,
+                                                 int(bool(waitUntilCompleted)))
+        if alphaPixelBuffers is None:
+            rc = call()
+        else:
+            with ctx._encode_with_alpha("convertIntoCoreVideoBuffers") as ok:
+                if not ok:
+                    return False
+                rc = call()
         if rc != _capi.OK:
             log.error("convertIntoCoreVideoBuffers: %s", _capi.strerror(rc))
             return False
+        for b in alphaPixelBuffers or []:
+            BGRAToBT709Converter.setAlphaAttributes(b)
         return True
 
     @staticmethod
