@@ -79,6 +79,11 @@ class MetalRenderContext {
   // BGRAToBT709Converter::convertIntoCoreVideoBuffers below sets it around its call and puts 0 back.
   static constexpr int kEncodeWithAlphaOption = BT709HIP_CTX_OPT_ENCODE_WITH_ALPHA;
   bool setEncodeWithAlpha(bool on) { return (lastStatus_ = bt709hip_context_set_option(ctx_, kEncodeWithAlphaOption, on ? 1 : 0)) == BT709HIP_OK; }
+  // bt709hip_encode[_batch] on this context accepts RGBA16Float (linear-light) textures and encodes them from their halves
+  // (include/bt709hip_ext.h BT709HIP_CTX_OPT_ENCODE_HALF_INPUT).  false (the default): such input is refused.
+  // BGRAToBT709Converter::convertIntoCoreVideoBuffer below sets it around its call and puts 0 back.
+  static constexpr int kEncodeHalfInputOption = BT709HIP_CTX_OPT_ENCODE_HALF_INPUT;
+  bool setEncodeHalfInput(bool on) { return (lastStatus_ = bt709hip_context_set_option(ctx_, kEncodeHalfInputOption, on ? 1 : 0)) == BT709HIP_OK; }
 
  private:
   bt709hip_context *ctx_ = nullptr;
@@ -227,6 +232,16 @@ struct BGRAToBT709Converter {
     if (rc == BT709HIP_OK) rc = bt709hip_encode(mrc.handle(), in.surface(), out.frame(), BT709HIP_GAMMA_SRGB, gamma, nullptr, 1);
     mrc.setEncodeConvert(BT709HIP_CONVERT_OFF);
     if (rc == BT709HIP_OK) out.setBT709Attributes();
+    return rc == BT709HIP_OK;
+  }
+  // The way back from linear light: an RGBA16Float texture (what -decodeBT709: writes into such a target, blended, filtered or
+  // graded since) into an NV12 / I420 frame, from its halves and in one launch -- BT709_average_pixel_values on the texel values
+  // themselves, saturated to [0, 1].  The input gamma is Linear by definition; `outputGamma` is APPLE, SRGB or LINEAR.
+  static bool convertIntoCoreVideoBuffer(MetalRenderContext &mrc, const BGRATexture &inRGBA16Float, CVPixelBuffer &out, int outputGamma) {
+    if (inRGBA16Float.surface()->format != BT709HIP_FORMAT_RGBA16F) return false;
+    int rc = mrc.setEncodeHalfInput(true) ? BT709HIP_OK : mrc.lastStatus();
+    if (rc == BT709HIP_OK) rc = bt709hip_encode(mrc.handle(), inRGBA16Float.surface(), out.frame(), BT709HIP_GAMMA_LINEAR, outputGamma, nullptr, 1);
+    mrc.setEncodeHalfInput(false);
     return rc == BT709HIP_OK;
   }
   // What `srgb_to_bt709 -alpha` makes of one picture (srgb_to_bt709.m:842-954), in ONE launch and one read of the texture: the

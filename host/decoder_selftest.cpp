@@ -374,6 +374,28 @@ int main(int argc, char **argv) {
       ++failures;
     }
   }
+  // an RGBA16Float (linear-light) texture back into a frame (BT709HIP_CTX_OPT_ENCODE_HALF_INPUT): a white block whose texels are
+  // 1, 2, +inf and 1, and a black one of 0, -1, NaN and -0 -- saturation makes them flat; refused while the option is off
+  {
+    const uint16_t one = 0x3C00, two = 0x4000, inf = 0x7C00, minus = 0xBC00, nan = 0x7E00, negzero = 0x8000;
+    const uint16_t top[4] = {one, two, 0, minus}, bottom[4] = {inf, one, nan, negzero};
+    uint16_t texels[2][4][4];
+    for (int x = 0; x < 4; ++x)
+      for (int c = 0; c < 4; ++c) texels[0][x][c] = top[x], texels[1][x][c] = bottom[x];
+    BGRATexture in(metalRenderContext, 4, 2, BT709HIP_FORMAT_RGBA16F);
+    CVPixelBuffer out(metalRenderContext, 4, 2);
+    bool ok = bt709hip_upload(metalRenderContext.handle(), in.surface()->bgra, in.surface()->stride, texels, 32, 32, 2, nullptr) == BT709HIP_OK &&
+              metalRenderContext.waitUntilCompleted(nullptr);
+    ok = ok && bt709hip_encode(metalRenderContext.handle(), in.surface(), out.frame(), BT709HIP_GAMMA_LINEAR, BT709HIP_GAMMA_APPLE, nullptr, 1) == BT709HIP_ERR_UNSUPPORTED;
+    ok = ok && BGRAToBT709Converter::convertIntoCoreVideoBuffer(metalRenderContext, in, out, BT709HIP_GAMMA_APPLE);
+    std::vector<uint8_t> y, c;
+    ok = ok && out.downloadPlanes(y, c);
+    const std::vector<uint8_t> wantY = {235, 235, 16, 16, 235, 235, 16, 16}, wantC = {128, 128, 128, 128};
+    if (!ok || y != wantY || c != wantC) {
+      std::fprintf(stderr, "RGBA16Float texture into a frame: not the saturated picture's planes\n");
+      ++failures;
+    }
+  }
   std::printf("%s: %d vectors, %d failures\n", failures ? "FAIL" : "ok", (argc - 1) / 6, failures);
   return failures ? 1 : 0;
 }

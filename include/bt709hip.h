@@ -225,7 +225,7 @@ int bt709hip_unconvert(bt709hip_decoder *dec, const void *ycbcr_words, size_t in
  * in->format BGRA8_ALPHA: the ALPHA frame of `in` -- Y = the reference's luma of the grey (A,A,A), every Cb, Cr = 128.  Both gammas must
  * be LINEAR (else BT709HIP_ERR_ALPHA_TRANSFER); out->cbcr may be NULL: only Y is written then.  R, G, B are not read (.m:805-841), whatever that option holds.
  * height / 2 <= 65535, i.e. up to 131070 rows (BT709HIP_ERR_UNSUPPORTED past it).  BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT
- * (bt709hip_ext.h) at BT709HIP_CHROMA_I420: `out` is written as three planes -- Y, U at out->cbcr, V behind it: a Y4M FRAME.  BT709HIP_CTX_OPT_ENCODE_CONVERT (there): the per-pixel +convert: instead, packed 4:4:4 words or a point-sampled frame.  BT709HIP_CTX_OPT_ENCODE_WITH_ALPHA (there): `out` is TWO frames per picture, the colour frame and the alpha frame, from one launch. */
+ * (bt709hip_ext.h) at BT709HIP_CHROMA_I420: `out` is written as three planes -- Y, U at out->cbcr, V behind it: a Y4M FRAME.  BT709HIP_CTX_OPT_ENCODE_CONVERT (there): the per-pixel +convert: instead, packed 4:4:4 words or a point-sampled frame.  BT709HIP_CTX_OPT_ENCODE_WITH_ALPHA (there): `out` is TWO frames per picture, the colour frame and the alpha frame, from one launch.  BT709HIP_CTX_OPT_ENCODE_HALF_INPUT (there): in->format RGBA16F is accepted -- linear-light halves, input_gamma LINEAR -- and encoded in one launch; without it such input is BT709HIP_ERR_UNSUPPORTED. */
 int bt709hip_encode(bt709hip_context *ctx, const bt709hip_surface *in, const bt709hip_frame *out, int input_gamma,
                     int output_gamma, void *stream, int wait_until_completed);
 /* The reference's on-disk 4:2:0 format is YUV4MPEG2 "C420jpeg": planar Y, U (Cb), V (Cr) per frame

@@ -42,8 +42,8 @@ int bt709hip_context_info(const bt709hip_context *ctx, bt709hip_device_info *inf
 
 /* Launch-shape knobs of a context (tuning and test hooks; no reference twin).  Values are
  * clamped to their valid range; 0 restores the default.  BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT,
- * BT709HIP_CTX_OPT_ENCODE_PREMULTIPLY, BT709HIP_CTX_OPT_ENCODE_CONVERT and BT709HIP_CTX_OPT_ENCODE_WITH_ALPHA are no knobs and are
- * NOT clamped: see below. */
+ * BT709HIP_CTX_OPT_ENCODE_PREMULTIPLY, BT709HIP_CTX_OPT_ENCODE_CONVERT, BT709HIP_CTX_OPT_ENCODE_WITH_ALPHA and
+ * BT709HIP_CTX_OPT_ENCODE_HALF_INPUT are no knobs and are NOT clamped: see below. */
 typedef enum {
   BT709HIP_CTX_OPT_GRID_MULT = 1,       /* general (unaligned-layout) kernels: workgroups per launch = CUs x 8 x this; default 2 */
   BT709HIP_CTX_OPT_ENCODE_ROW_PAIRS = 2,/* encoder: consecutive row pairs per workgroup; default 0 = sized per launch */
@@ -53,7 +53,8 @@ typedef enum {
   BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT = 6, /* BT709HIP_CHROMA_NV12 (default) or BT709HIP_CHROMA_I420: the planes bt709hip_encode[_batch] writes; any other value is refused */
   BT709HIP_CTX_OPT_ENCODE_PREMULTIPLY = BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT + 2, /* (eight; seven is no option) 0 (default): BGRA8_SRGB input is encoded as it is; 1: it is straight alpha and is premultiplied first; any other value is refused */
   BT709HIP_CTX_OPT_ENCODE_CONVERT = BT709HIP_CTX_OPT_ENCODE_PREMULTIPLY + 2, /* (ten; nine is no option) BT709HIP_CONVERT_OFF (default), _PACKED444 or _POINT420: bt709hip_encode[_batch] is the reference's per-pixel +convert:; any other value is refused */
-  BT709HIP_CTX_OPT_ENCODE_WITH_ALPHA = BT709HIP_CTX_OPT_ENCODE_CONVERT + 2 /* (twelve; eleven is no option) 0 (default): one frame per picture; 1: bt709hip_encode[_batch] of BGRA8_SRGB input writes the picture's alpha frame as well, `out` holds TWO frames per picture; any other value is refused */
+  BT709HIP_CTX_OPT_ENCODE_WITH_ALPHA = BT709HIP_CTX_OPT_ENCODE_CONVERT + 2, /* (twelve; eleven is no option) 0 (default): one frame per picture; 1: bt709hip_encode[_batch] of BGRA8_SRGB input writes the picture's alpha frame as well, `out` holds TWO frames per picture; any other value is refused */
+  BT709HIP_CTX_OPT_ENCODE_HALF_INPUT = BT709HIP_CTX_OPT_ENCODE_WITH_ALPHA + 2 /* (fourteen; thirteen is no option) 0 (default): RGBA16F input to bt709hip_encode[_batch] is BT709HIP_ERR_UNSUPPORTED; 1: it is encoded as linear light; any other value is refused */
 } bt709hip_context_option;
 #define BT709HIP_CONVERT_OFF 0       /* bt709hip_encode[_batch] is the subsampling encoder (+convertIntoCoreVideoBuffer:) */
 #define BT709HIP_CONVERT_PACKED444 1 /* +convert: -- one 32-bit word (Cr<<16)|(Cb<<8)|Y per pixel */
@@ -157,6 +158,39 @@ int bt709hip_context_set_option(bt709hip_context *ctx, int option, int value);
  * encoder's plan for the same size and count; BT709HIP_CTX_OPT_ENCODE_ROW_PAIRS, _ENCODE_THREADS and _XCD_BANDS apply as they do
  * there.  The call reads the option once, on entry.  Any value but 0 and 1: BT709HIP_ERR_INVALID_ARG, the option keeps its value
  * (it is not clamped).  Setting it never touches the device: it works while a stream is being captured.  At 0 nothing changes. */
+/* BT709HIP_CTX_OPT_ENCODE_HALF_INPUT.  The decoder writes two target formats, BGRA8_SRGB and RGBA16F (linear light); a caller who
+ * decodes into RGBA16F, blends, filters or grades there and wants a frame for an H.264 encoder needs the way back.  With the
+ * option at 1, bt709hip_encode and bt709hip_encode_batch accept in->format == BT709HIP_FORMAT_RGBA16F: texels of four binary16
+ * values R, G, B, A in memory order, A is not read.  The definition is BT709_average_pixel_values
+ * (BT709.h:1349-1509) with the result of BT709_tolinearNorm replaced by the texel's own values; per 2x2 block, pixels TL, TR, BL, BR:
+ *   v[i][c]    = sat(float(h[i][c]))      exact half -> float; sat: NaN -> 0, v < 0 (and -0) -> 0, v > 1 (and +inf) -> 1
+ *   byte[i][c] = BT709_from_linear(v[i][c], output_gamma)                                      (BT709.h:1150-1167)
+ *   Y[i]       = Y of sRGB_from_sRGB_convertRGBToYCbCr(byte[i][R,G,B])                           (BT709.h:914-944 -> 199-268)
+ *   ave[c]     = (((v[0][c] + v[1][c]) + v[2][c]) + v[3][c]) / 4.0f                             (BT709.h:1171-1190)
+ *   (Cb, Cr)   = Cb, Cr of sRGB_from_sRGB_convertRGBToYCbCr(BT709_from_linear(ave[R,G,B], output_gamma))
+ * bit for bit, in one launch that reads 8 and writes 1.5 bytes per pixel.  input_gamma must be BT709HIP_GAMMA_LINEAR (the texels
+ * hold linear light): anything else is BT709HIP_ERR_TRANSFER.  output_gamma is APPLE, SRGB or LINEAR, as for BGRA8 input.
+ * BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT is honoured: NV12 and I420 both work.  Validation follows the encoder's order and writes
+ * and enqueues nothing on refusal: in->bgra not 8-byte aligned, in->stride no multiple of 8 or below 8 * W is
+ * BT709HIP_ERR_STRIDE (the rule of an RGBA16F decode target); reserved != 0 and a batch of mixed formats are what they were
+ * (BT709HIP_ERR_UNSUPPORTED, BT709HIP_ERR_SIZE_MISMATCH).  OUT OF SCOPE, refused with BT709HIP_ERR_UNSUPPORTED behind the usual
+ * validation: BT709HIP_CTX_OPT_ENCODE_PREMULTIPLY, BT709HIP_CTX_OPT_ENCODE_CONVERT or BT709HIP_CTX_OPT_ENCODE_WITH_ALPHA away from its
+ * default while the input is RGBA16F (no straight-alpha halves, no alpha frame from a half surface's A, no +convert: from halves,
+ * no ITU709 output).  Sizes, the even-dimension rule, height / 2 <= 65535, BT709HIP_MAX_BATCH pictures in a pointer table, 65535
+ * evenly spaced, wait_until_completed and the flush of coalescing queues on the stream are the BGRA8 encoder's.  The fast kernel
+ * needs the texel pointer and pitch 16-byte aligned, the Y pointer and pitch 2-byte aligned and, under NV12, the CbCr pointer and
+ * pitch 2-byte aligned (any even W; U and V take any alignment); every other valid call takes the general kernel (byte stores)
+ * and writes the same bytes.  bt709hip_last_kernel_name: "encode_rgba16f_nv12", "encode_rgba16f_i420", "encode_rgba16f_nv12_blocks",
+ * "encode_rgba16f_i420_blocks".  bt709hip_last_launch_info: a lane of the fast kernel owns a 2x2 block where the BGRA8 kernel's
+ * owns a 4x2 quad, so the plan is the BGRA8 encoder's plan for a picture TWICE AS WIDE, same height and count;
+ * BT709HIP_CTX_OPT_ENCODE_ROW_PAIRS, _ENCODE_THREADS (lanes = blocks per tile) and _XCD_BANDS are read as they are there;
+ * BT709HIP_CTX_OPT_GRID_MULT and _STREAMING_TRIES are ignored.  Tables: the (LINEAR, output_gamma) encoder's own
+ * BT709_from_linear table, built by the first call that needs it or by bt709hip_encoder_prepare(ctx, BT709HIP_GAMMA_LINEAR,
+ * output_gamma) -- which makes everything the half path needs; a call that finds the table missing while its stream is being
+ * captured returns BT709HIP_ERR_NOT_SETUP.  BGRA8_SRGB and BGRA8_ALPHA input behave exactly as before with the option at either
+ * value: same kernels, same names, same bytes.  The call reads the option once, on entry.  Any value but 0 and 1:
+ * BT709HIP_ERR_INVALID_ARG, the option keeps its value (it is not clamped).  Setting it never touches the device: it works while a
+ * stream is being captured.  At 0 (the default) nothing changes: RGBA16F input is BT709HIP_ERR_UNSUPPORTED. */
 
 /* A stream with a scheduling priority (hipStreamCreateWithPriority): 0 = normal, negative = higher, positive = lower; clamped
  * to the device's range.  (MTLCommandQueue has no twin; a renderer that decodes ahead of what it presents puts the look-ahead

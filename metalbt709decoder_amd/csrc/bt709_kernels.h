@@ -234,7 +234,12 @@ struct EncodeParams {
   // encode_bgra / encode_bgra_blocks in launch_encode; no kernel reads it.  (It sits where the split point of the two-resolution
   // table was carried, which nothing had read since the index became a min(): every other field's offset, and the kernarg
   // block's size, are what they were.)
-  uint16_t premultiply;
+  uint8_t premultiply;
+  // BT709HIP_CTX_OPT_ENCODE_HALF_INPUT: kEncodeInputRGBA16F = frames[i].bgra holds RGBA16Float linear-light texels
+  // (8 bytes each, bgra_stride their pitch) and launch_encode runs encode_rgba16f / encode_rgba16f_blocks (bt709_encode_half.h), which
+  // read from_linear* and not per_byte.  A selector of launch_encode, read by no kernel; the upper byte of what `premultiply`
+  // (0 or 1) occupied: no offset and no size changes.
+  uint8_t input_format;  // kEncodeInput*
   uint16_t convert_mode;  // kConvert*: a selector of launch_encode as well, read by no kernel
   float from_linear_coarse;   // fine buckets below the table's split point, coarse ones above: q = (uint)(xs * coarse) + offset
   uint32_t from_linear_offset;
@@ -251,6 +256,7 @@ struct EncodeParams {
 };
 inline bool encode_pair(const EncodeParams &p) { return p.alpha_luma != nullptr && p.per_byte != nullptr; }
 static_assert(sizeof(EncodeParams) == 880, "a field appended to EncodeParams moves the implicit kernel arguments behind it: every encoder kernel's code changes");
+enum : uint8_t { kEncodeInputBGRA8 = 0, kEncodeInputRGBA16F = 1 };
 enum : uint32_t { kConvertOff = 0, kConvertPacked444 = 1, kConvertPoint420 = 2 };  // == BT709HIP_CONVERT_*
 // Further bit of the converter kernels' FORM (beside the layout and kFormStraight): the packed 4:4:4 output
 enum : uint32_t { kFormPacked = 4 };

@@ -244,7 +244,13 @@ int bt709hip_encode_batch(bt709hip_context *ctx, int count, const bt709hip_surfa
   if (ctx == nullptr || ins == nullptr || outs == nullptr || count < 0) return BT709HIP_ERR_INVALID_ARG;
   // BT709HIP_CTX_OPT_ENCODE_CONVERT, read once: the call is the per-pixel converter (+convert:), whose output gamma may be ITU709;
   // PACKED444 writes 32-bit words (Cr<<16)|(Cb<<8)|Y through out->y and takes no chroma plane; POINT420 writes an ordinary frame
-  const int convert = ctx->encode_convert;
+  // BT709HIP_CTX_OPT_ENCODE_HALF_INPUT, read once: with it at 1 RGBA16F surfaces (linear light) are input; the call
+  // takes its format from ins[0], a batch of mixed formats is a size mismatch as ever.  The half path has no converter, no pair
+  // and no premultiply: it is validated as the plain encoder's call and refused behind that if one of those options is set.
+  const bool half_input = ctx->encode_half_input != 0;
+  const bool half = count > 0 && half_input && ins[0].format == BT709HIP_FORMAT_RGBA16F;
+  const int convert_option = ctx->encode_convert;
+  const int convert = half ? BT709HIP_CONVERT_OFF : convert_option;
   const bool packed = convert == BT709HIP_CONVERT_PACKED444;
   if (input_gamma < 0 || input_gamma > 2 || output_gamma < 0 || output_gamma > (convert != BT709HIP_CONVERT_OFF ? 3 : 2)) return BT709HIP_ERR_INVALID_ARG;
   if (count == 0) return BT709HIP_OK;
@@ -258,18 +264,22 @@ int bt709hip_encode_batch(bt709hip_context *ctx, int count, const bt709hip_surfa
   // Without a chroma plane there is nothing to lay out: such a call is what it was, whatever the option holds.
   const bool planar = ctx->encode_chroma_layout == BT709HIP_CHROMA_I420 && !no_cbcr;
   // BT709HIP_CTX_OPT_ENCODE_PREMULTIPLY, read once: BGRA8_SRGB texels are straight alpha.  BGRA8_ALPHA input reads A alone: unaffected.
-  const bool premultiply = ctx->encode_premultiply != 0 && !alpha;
+  const bool premultiply = ctx->encode_premultiply != 0 && !alpha && !half;
   const size_t chroma_align = planar ? 2 : 4;  // the fast kernels' chroma store: a 2-byte half per plane, or the CbCr dword
   // BT709HIP_CTX_OPT_ENCODE_WITH_ALPHA, read once: BGRA8_SRGB input writes two frames, the colour into outs[i] and the alpha frame
   // (BGRA8_ALPHA output's rules) into outs[count + i], from one launch.  Not with the per-pixel converter and not for BGRA8_ALPHA
   // input: refused behind the usual validation.
   const bool with_alpha = ctx->encode_with_alpha != 0;
-  const bool pair = with_alpha && !alpha && convert == BT709HIP_CONVERT_OFF;
+  const bool pair = with_alpha && !alpha && !half && convert == BT709HIP_CONVERT_OFF;
   const bt709hip_frame &alpha0 = outs[pair ? count : 0];
   const bool alpha_no_cbcr = pair && alpha0.cbcr == nullptr;
   bool uniform = count > 1;
   const size_t y_px = packed ? 4 : 1, y_align = packed ? 16 : 4;  // bytes of a pixel in the plane out->y points to; the fast kernels' store to it
   bool fast = (in0.width % 4) == 0 && (in0.stride % 16) == 0 && (out0.y_stride % y_align) == 0 && (no_cbcr || (out0.cbcr_stride % chroma_align) == 0);
+  // encode_rgba16f: a 2x2 block per lane -- any even width; 2-byte stores to Y and CbCr, byte stores to U and V
+  const size_t half_chroma_align = planar ? 1 : 2;
+  if (half) fast = (in0.stride % 16) == 0 && (out0.y_stride % 2) == 0 && (out0.cbcr_stride % half_chroma_align) == 0;
+  const size_t in_px = half ? 8 : 4;  // bytes of a texel
   if (pair) fast = fast && (alpha0.y_stride % 4) == 0 && (alpha_no_cbcr || (alpha0.cbcr_stride % chroma_align) == 0);
   EncodeParams p;
   std::memset(&p, 0, sizeof p);
@@ -280,21 +290,24 @@ int bt709hip_encode_batch(bt709hip_context *ctx, int count, const bt709hip_surfa
     if (in.width != out.width || in.height != out.height) return BT709HIP_ERR_SIZE_MISMATCH;
     if ((in.width & 1) || (in.height & 1)) return BT709HIP_ERR_ODD_DIMENSIONS;  // BGRAToBT709Converter.m:540-541
     if (in.height / 2 > kMaxGridYZ) return BT709HIP_ERR_UNSUPPORTED;            // row pairs live in gridDim.y
-    if ((in.format != BT709HIP_FORMAT_BGRA8_SRGB && in.format != BT709HIP_FORMAT_BGRA8_ALPHA) || in.reserved != 0)
+    if ((in.format != BT709HIP_FORMAT_BGRA8_SRGB && in.format != BT709HIP_FORMAT_BGRA8_ALPHA &&
+         !(in.format == BT709HIP_FORMAT_RGBA16F && half_input)) || in.reserved != 0)
       return BT709HIP_ERR_UNSUPPORTED;
     if (in.width != in0.width || in.height != in0.height || in.stride != in0.stride || in.format != in0.format ||
         out.y_stride != out0.y_stride || (!(packed || (alpha && (no_cbcr || out.cbcr == nullptr))) && out.cbcr_stride != out0.cbcr_stride))
       return BT709HIP_ERR_SIZE_MISMATCH;
     // the reference forces an alpha clip's gamma to linear (srgb_to_bt709.m:842-954); anything else is "alpha is not linear"
     if (alpha && (input_gamma != BT709HIP_GAMMA_LINEAR || output_gamma != BT709HIP_GAMMA_LINEAR)) return BT709HIP_ERR_ALPHA_TRANSFER;
+    if (half && input_gamma != BT709HIP_GAMMA_LINEAR) return BT709HIP_ERR_TRANSFER;  // the texels hold linear light
     if (in.width == 0 || in.height == 0) continue;
     if (in.bgra == nullptr || out.y == nullptr || (out.cbcr == nullptr) != no_cbcr) return BT709HIP_ERR_INVALID_ARG;
     const size_t w = static_cast<size_t>(in.width);
-    if (in.stride < 4 * w || (in.stride & 3) || !aligned(in.bgra, 4) || out.y_stride < y_px * w || (!no_cbcr && out.cbcr_stride < (planar ? w / 2 : w)))
+    if (in.stride < in_px * w || (in.stride & (in_px - 1)) || !aligned(in.bgra, in_px) || out.y_stride < y_px * w || (!no_cbcr && out.cbcr_stride < (planar ? w / 2 : w)))
       return BT709HIP_ERR_STRIDE;
     if (packed && ((out.y_stride & 3) || !aligned(out.y, 4))) return BT709HIP_ERR_STRIDE;  // words
     if (in.stride > 0xffffffffu || out.y_stride > 0xffffffffu || (!no_cbcr && out.cbcr_stride > 0xffffffffu)) return BT709HIP_ERR_STRIDE;
-    fast = fast && aligned(in.bgra, 16) && aligned(out.y, y_align) && aligned(out.cbcr, chroma_align);
+    if (half) fast = fast && aligned(in.bgra, 16) && aligned(out.y, 2) && aligned(out.cbcr, half_chroma_align);
+    else fast = fast && aligned(in.bgra, 16) && aligned(out.y, y_align) && aligned(out.cbcr, chroma_align);
     if (i >= 2)
       uniform = uniform && byte_step(ins[0].bgra, in.bgra) == byte_step(ins[0].bgra, ins[1].bgra) * i &&
                 byte_step(outs[0].y, out.y) == byte_step(outs[0].y, outs[1].y) * i &&
@@ -328,6 +341,8 @@ int bt709hip_encode_batch(bt709hip_context *ctx, int count, const bt709hip_surfa
   // the reference's per-pixel converters take sRGB bytes only, and no alpha clip goes through them
   if (convert != BT709HIP_CONVERT_OFF && (alpha || input_gamma != BT709HIP_GAMMA_SRGB)) return BT709HIP_ERR_UNSUPPORTED;
   if (with_alpha && !pair) return BT709HIP_ERR_UNSUPPORTED;  // the converter writes no alpha frame; an alpha clip has none beside itself
+  // half input composes with the chroma layout alone: the converter, the pair and the premultiply are BGRA8 paths
+  if (half && (convert_option != BT709HIP_CONVERT_OFF || ctx->encode_premultiply != 0)) return BT709HIP_ERR_UNSUPPORTED;
   if (in0.width == 0 || in0.height == 0) return BT709HIP_OK;
   if (int rc = bind(ctx)) return rc;
   FLUSH_STREAM(ctx, stream);
@@ -376,6 +391,7 @@ int bt709hip_encode_batch(bt709hip_context *ctx, int count, const bt709hip_surfa
   p.cbcr_stride = no_cbcr ? 0u : static_cast<uint32_t>(out0.cbcr_stride);
   p.chroma_layout = planar ? kChromaI420 : kChromaNV12;
   p.premultiply = premultiply ? 1 : 0;
+  p.input_format = half ? kEncodeInputRGBA16F : kEncodeInputBGRA8;  // per_byte is built with the pair's tables and not read
   last_launch_shape() = LaunchShape{};
   set_kernel_name(launch_encode(p, count, fast, ctx->xcd_bands != 0, s));
   HIP_TRY(hipGetLastError());

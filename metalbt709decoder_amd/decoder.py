@@ -597,6 +597,21 @@ class MetalRenderContext:
         finally:
             self.lib.bt709hip_context_set_option(self.handle, _capi.CTX_OPT_ENCODE_WITH_ALPHA, 0)
 
+    @contextlib.contextmanager
+    def _encode_half_input(self, what):
+        """bt709hip_context_set_option(CTX_OPT_ENCODE_HALF_INPUT) around ONE encode of RGBA16Float textures: 1 on entry and back to
+        0 on the way out, whatever the call returned or raised, so that every other encode call of this context refuses such input
+        as it always did.  The setter never touches the device.  Yields True, or False when the library refused the option."""
+        rc = self.lib.bt709hip_context_set_option(self.handle, _capi.CTX_OPT_ENCODE_HALF_INPUT, 1)
+        if rc != _capi.OK:
+            log.error("%s: CTX_OPT_ENCODE_HALF_INPUT = 1: %s", what, _capi.strerror(rc))
+            yield False
+            return
+        try:
+            yield True
+        finally:
+            self.lib.bt709hip_context_set_option(self.handle, _capi.CTX_OPT_ENCODE_HALF_INPUT, 0)
+
     def _set_encode_layout(self, pixelBuffers, what):
         """The encoder's chroma layout from the buffers an encode call was handed: a planar CVPixelBuffer is written in place.  As
         MetalBT709Decoder._set_layout: the buffer's `planar` flag is authoritative, planar and NV12 buffers in one call are
@@ -756,10 +771,13 @@ class BGRAToBT709Converter:
         values Apple / SRGB / Linear.  Returns True/False like the reference.  A planar buffer
         (createCoreVideoYCbCrBuffer(..., planar=True)) is written as Y, U, V -- the Y4M FRAME payload -- by the same launch.
         alphaPixelBuffer: the picture's ALPHA frame as well (what convertAlphaIntoCoreVideoBuffer writes), from the same launch
-        and the same read of the texture -- the pair -decodeBT709:alphaPixelBuffer: takes back."""
-        if alphaPixelBuffer is not None:
+        and the same read of the texture -- the pair -decodeBT709:alphaPixelBuffer: takes back.
+        An RGBA16Float texture (linear light: what the decoder writes into such a target) is encoded from its halves, inputGamma
+        must be MetalBT709GammaLinear then; no alpha buffer goes with it."""
+        if alphaPixelBuffer is not None or bgraTexture.pixelFormat == MTLPixelFormatRGBA16Float:
             return BGRAToBT709Converter.convertIntoCoreVideoBuffers([bgraTexture], [cvPixelBuffer], inputGamma, outputGamma, commandBuffer,
-                                                                    waitUntilCompleted, alphaPixelBuffers=[alphaPixelBuffer])
+                                                                    waitUntilCompleted,
+                                                                    alphaPixelBuffers=None if alphaPixelBuffer is None else [alphaPixelBuffer])
         ctx = bgraTexture.ctx
         if not ctx._set_encode_layout([cvPixelBuffer], "convertIntoCoreVideoBuffer"):
             return False
@@ -779,7 +797,8 @@ class BGRAToBT709Converter:
         CGImage per call, BGRAToBT709Converter.m:532-569).
         alphaPixelBuffers: one more buffer per picture, which receives the picture's ALPHA frame from the same launch
         (bt709hip_encode_batch under CTX_OPT_ENCODE_WITH_ALPHA, set around this call alone and put back whatever happens); they
-        leave tagged ITU_R_709_2 / Linear, as convertAlphaIntoCoreVideoBuffers leaves them.  The gammas govern the colour only."""
+        leave tagged ITU_R_709_2 / Linear, as convertAlphaIntoCoreVideoBuffers leaves them.  The gammas govern the colour only.
+        RGBA16Float textures: CTX_OPT_ENCODE_HALF_INPUT is set around this call alone and put back whatever happens."""
         n = len(bgraTextures)
         if n != len(cvPixelBuffers) or (alphaPixelBuffers is not None and n != len(alphaPixelBuffers)):
             raise ValueError("one output buffer per input texture")
@@ -798,7 +817,15 @@ class BGRAToBT709Converter:
         def call():
             return ctx.lib.bt709hip_encode_batch(ctx.handle, n, surfs, frames, int(inputGamma), int(outputGamma), stream,
                                                  int(bool(waitUntilCompleted)))
-        if alphaPixelBuffers is None:
+        if any(t.pixelFormat == MTLPixelFormatRGBA16Float for t in bgraTextures):
+            if alphaPixelBuffers is not None:
+                log.error("convertIntoCoreVideoBuffers: no alpha frame is written from RGBA16Float textures")
+                return False
+            with ctx._encode_half_input("convertIntoCoreVideoBuffers") as ok:
+                if not ok:
+                    return False
+                rc = call()
+        elif alphaPixelBuffers is None:
             rc = call()
         else:
             with ctx._encode_with_alpha("convertIntoCoreVideoBuffers") as ok:
