@@ -84,6 +84,11 @@ class MetalRenderContext {
   // BGRAToBT709Converter::convertIntoCoreVideoBuffer below sets it around its call and puts 0 back.
   static constexpr int kEncodeHalfInputOption = BT709HIP_CTX_OPT_ENCODE_HALF_INPUT;
   bool setEncodeHalfInput(bool on) { return (lastStatus_ = bt709hip_context_set_option(ctx_, kEncodeHalfInputOption, on ? 1 : 0)) == BT709HIP_OK; }
+  // ... and such a call writes TWO frames per texture, the colour frame and the alpha frame of its A halves (include/bt709hip_ext.h
+  // BT709HIP_CTX_OPT_ENCODE_HALF_WITH_ALPHA).  false (the default): one.
+  // BGRAToBT709Converter::convertHalfIntoCoreVideoBuffersWithAlpha below sets both around its call and puts 0 back.
+  static constexpr int kEncodeHalfWithAlphaOption = BT709HIP_CTX_OPT_ENCODE_HALF_WITH_ALPHA;
+  bool setEncodeHalfWithAlpha(bool on) { return (lastStatus_ = bt709hip_context_set_option(ctx_, kEncodeHalfWithAlphaOption, on ? 1 : 0)) == BT709HIP_OK; }
 
  private:
   bt709hip_context *ctx_ = nullptr;
@@ -254,6 +259,21 @@ struct BGRAToBT709Converter {
     int rc = mrc.setEncodeWithAlpha(true) ? BT709HIP_OK : mrc.lastStatus();
     if (rc == BT709HIP_OK) rc = bt709hip_encode(mrc.handle(), in.surface(), pair, inputGamma, outputGamma, nullptr, 1);
     mrc.setEncodeWithAlpha(false);
+    if (rc == BT709HIP_OK) alpha.setAttachments(BT709HIP_MATRIX_ITU_R_709_2, BT709HIP_TRANSFER_LINEAR);
+    return rc == BT709HIP_OK;
+  }
+  // The same pair from an RGBA16Float texture (premultiplied linear colour and a linear A: what -decodeBT709:alphaPixelBuffer:
+  // writes into such a target), in ONE launch and one read: the colour frame as convertIntoCoreVideoBuffer above writes it, and the
+  // A halves as the (Linear, Linear) alpha frame, Y = T[round(255 sat(A))].  `alpha` leaves tagged ITU_R_709_2 / Linear.
+  static bool convertHalfIntoCoreVideoBuffersWithAlpha(MetalRenderContext &mrc, const BGRATexture &inRGBA16Float, CVPixelBuffer &colour,
+                                                       CVPixelBuffer &alpha, int outputGamma) {
+    if (inRGBA16Float.surface()->format != BT709HIP_FORMAT_RGBA16F) return false;
+    const bt709hip_frame pair[2] = {*colour.frame(), *alpha.frame()};
+    int rc = mrc.setEncodeHalfInput(true) ? BT709HIP_OK : mrc.lastStatus();
+    if (rc == BT709HIP_OK) rc = mrc.setEncodeHalfWithAlpha(true) ? BT709HIP_OK : mrc.lastStatus();
+    if (rc == BT709HIP_OK) rc = bt709hip_encode(mrc.handle(), inRGBA16Float.surface(), pair, BT709HIP_GAMMA_LINEAR, outputGamma, nullptr, 1);
+    mrc.setEncodeHalfWithAlpha(false);
+    mrc.setEncodeHalfInput(false);
     if (rc == BT709HIP_OK) alpha.setAttachments(BT709HIP_MATRIX_ITU_R_709_2, BT709HIP_TRANSFER_LINEAR);
     return rc == BT709HIP_OK;
   }

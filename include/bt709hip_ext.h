@@ -42,8 +42,8 @@ int bt709hip_context_info(const bt709hip_context *ctx, bt709hip_device_info *inf
 
 /* Launch-shape knobs of a context (tuning and test hooks; no reference twin).  Values are
  * clamped to their valid range; 0 restores the default.  BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT,
- * BT709HIP_CTX_OPT_ENCODE_PREMULTIPLY, BT709HIP_CTX_OPT_ENCODE_CONVERT, BT709HIP_CTX_OPT_ENCODE_WITH_ALPHA and
- * BT709HIP_CTX_OPT_ENCODE_HALF_INPUT are no knobs and are NOT clamped: see below. */
+ * BT709HIP_CTX_OPT_ENCODE_PREMULTIPLY, BT709HIP_CTX_OPT_ENCODE_CONVERT, BT709HIP_CTX_OPT_ENCODE_WITH_ALPHA,
+ * BT709HIP_CTX_OPT_ENCODE_HALF_INPUT and BT709HIP_CTX_OPT_ENCODE_HALF_WITH_ALPHA are no knobs and are NOT clamped: see below. */
 typedef enum {
   BT709HIP_CTX_OPT_GRID_MULT = 1,       /* general (unaligned-layout) kernels: workgroups per launch = CUs x 8 x this; default 2 */
   BT709HIP_CTX_OPT_ENCODE_ROW_PAIRS = 2,/* encoder: consecutive row pairs per workgroup; default 0 = sized per launch */
@@ -54,7 +54,8 @@ typedef enum {
   BT709HIP_CTX_OPT_ENCODE_PREMULTIPLY = BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT + 2, /* (eight; seven is no option) 0 (default): BGRA8_SRGB input is encoded as it is; 1: it is straight alpha and is premultiplied first; any other value is refused */
   BT709HIP_CTX_OPT_ENCODE_CONVERT = BT709HIP_CTX_OPT_ENCODE_PREMULTIPLY + 2, /* (ten; nine is no option) BT709HIP_CONVERT_OFF (default), _PACKED444 or _POINT420: bt709hip_encode[_batch] is the reference's per-pixel +convert:; any other value is refused */
   BT709HIP_CTX_OPT_ENCODE_WITH_ALPHA = BT709HIP_CTX_OPT_ENCODE_CONVERT + 2, /* (twelve; eleven is no option) 0 (default): one frame per picture; 1: bt709hip_encode[_batch] of BGRA8_SRGB input writes the picture's alpha frame as well, `out` holds TWO frames per picture; any other value is refused */
-  BT709HIP_CTX_OPT_ENCODE_HALF_INPUT = BT709HIP_CTX_OPT_ENCODE_WITH_ALPHA + 2 /* (fourteen; thirteen is no option) 0 (default): RGBA16F input to bt709hip_encode[_batch] is BT709HIP_ERR_UNSUPPORTED; 1: it is encoded as linear light; any other value is refused */
+  BT709HIP_CTX_OPT_ENCODE_HALF_INPUT = BT709HIP_CTX_OPT_ENCODE_WITH_ALPHA + 2, /* (fourteen; thirteen is no option) 0 (default): RGBA16F input to bt709hip_encode[_batch] is BT709HIP_ERR_UNSUPPORTED; 1: it is encoded as linear light; any other value is refused */
+  BT709HIP_CTX_OPT_ENCODE_HALF_WITH_ALPHA = BT709HIP_CTX_OPT_ENCODE_HALF_INPUT + 2 /* (sixteen; fifteen and seventeen are no options) 0 (default): one frame per picture; 1: bt709hip_encode[_batch] of RGBA16F input (under _ENCODE_HALF_INPUT = 1) writes the surface's alpha frame as well, `out` holds TWO frames per picture; any other value is refused */
 } bt709hip_context_option;
 #define BT709HIP_CONVERT_OFF 0       /* bt709hip_encode[_batch] is the subsampling encoder (+convertIntoCoreVideoBuffer:) */
 #define BT709HIP_CONVERT_PACKED444 1 /* +convert: -- one 32-bit word (Cr<<16)|(Cb<<8)|Y per pixel */
@@ -191,6 +192,38 @@ int bt709hip_context_set_option(bt709hip_context *ctx, int option, int value);
  * value: same kernels, same names, same bytes.  The call reads the option once, on entry.  Any value but 0 and 1:
  * BT709HIP_ERR_INVALID_ARG, the option keeps its value (it is not clamped).  Setting it never touches the device: it works while a
  * stream is being captured.  At 0 (the default) nothing changes: RGBA16F input is BT709HIP_ERR_UNSUPPORTED. */
+/* BT709HIP_CTX_OPT_ENCODE_HALF_WITH_ALPHA.  bt709hip_decode of a frame and an alpha frame into an RGBA16F surface writes premultiplied
+ * linear colour and a linear A; with this option at 1, BT709HIP_CTX_OPT_ENCODE_HALF_INPUT at 1 and in->format ==
+ * BT709HIP_FORMAT_RGBA16F the encode side writes the two frames back in one launch, from one read of the surface:
+ *   bt709hip_encode(ctx, in, out, BT709HIP_GAMMA_LINEAR, go, ...): `out` points to TWO bt709hip_frames.  out[0] receives the colour
+ *     frame, byte for byte what the call writes with the option at 0 (same output gamma, BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT);
+ *     out[1] receives the alpha frame: what the option-0 call writes under (LINEAR, LINEAR) for the surface whose R, G and B are
+ *     replaced by its A -- the reference's alpha clip is the grey picture (A,A,A) with the gamma forced to linear
+ *     (srgb_to_bt709.m:842-954), and BT709_from_linear(v, Linear) is (int)round(v * 255.0f) (BT709.h:1150-1167).  Per pixel
+ *       a = sat(float(hA))     exact half -> float; NaN -> 0, a < 0 (and -0) -> 0, a > 1 (and +inf) -> 1
+ *       Y = T[round(a * 255)]  T: the alpha frames' luma table (BGRA8_ALPHA input's)
+ *     and Cb = Cr = 128 if it has a chroma plane.  go governs the colour alone; input_gamma must be BT709HIP_GAMMA_LINEAR
+ *     (BT709HIP_ERR_TRANSFER);
+ *   bt709hip_encode_batch(ctx, count, ins, outs, ...): `outs` holds 2 * count frames; the colour frames are outs[0 .. count),
+ *     pair i's alpha frame is outs[count + i].
+ * The alpha frames are validated as BT709HIP_CTX_OPT_ENCODE_WITH_ALPHA's, in that order: the surface's width and height
+ * (BT709HIP_ERR_SIZE_MISMATCH); y non-NULL; cbcr NULL in EVERY alpha frame of the call or in none (BT709HIP_ERR_INVALID_ARG);
+ * W <= y_stride <= 2^32 - 1, cbcr_stride >= W, or >= W/2 under BT709HIP_CHROMA_I420 (BT709HIP_ERR_STRIDE); equal pitches across the
+ * batch.  The layout option covers both frames of a pair.  Evenly spaced batches: all five planes evenly spaced, then any count up
+ * to 65535 goes; otherwise a pointer table of BT709HIP_MAX_BATCH / 2 = 16 PAIRS (the kernel argument block does not grow): more is
+ * BT709HIP_ERR_UNSUPPORTED.  The fast kernel needs, beside the half encoder's alignments, the alpha Y pointer, pitch and step 2-byte
+ * aligned and, under NV12, the alpha CbCr pointer and pitch 2-byte aligned; any other valid call takes the general kernel and writes
+ * the same bytes.  Everything else stays: BT709HIP_CTX_OPT_ENCODE_WITH_ALPHA, _ENCODE_PREMULTIPLY or _ENCODE_CONVERT away from its
+ * default with half input is BT709HIP_ERR_UNSUPPORTED behind the usual validation; BGRA8_SRGB and BGRA8_ALPHA input do not read this
+ * option; RGBA16F input with _ENCODE_HALF_INPUT at 0 is refused whatever it holds.  bt709hip_encoder_prepare(ctx,
+ * BT709HIP_GAMMA_LINEAR, go) builds T as well when the option is 1 at the time of the call: a paired half encode can be captured
+ * into a graph after that one prepare (BT709HIP_ERR_NOT_SETUP while capturing otherwise, nothing enqueued).
+ * bt709hip_last_kernel_name: "encode_rgba16f_alpha_nv12", "encode_rgba16f_alpha_i420", "encode_rgba16f_alpha_nv12_blocks",
+ * "encode_rgba16f_alpha_i420_blocks".  bt709hip_last_launch_info: the plain half encoder's plan for the same size and count;
+ * BT709HIP_CTX_OPT_ENCODE_ROW_PAIRS, _ENCODE_THREADS and _XCD_BANDS apply as they do there.  OUT OF SCOPE: an alpha frame alone from
+ * a half surface, straight-alpha halves (the surface is premultiplied, as the decoder writes it), +convert: from halves.  The call
+ * reads the option once, on entry.  Any value but 0 and 1: BT709HIP_ERR_INVALID_ARG, the option keeps its value (it is not clamped).
+ * Setting it never touches the device: it works while a stream is being captured.  At 0 (the default) nothing changes. */
 
 /* A stream with a scheduling priority (hipStreamCreateWithPriority): 0 = normal, negative = higher, positive = lower; clamped
  * to the device's range.  (MTLCommandQueue has no twin; a renderer that decodes ahead of what it presents puts the look-ahead

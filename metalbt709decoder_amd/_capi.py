@@ -57,7 +57,8 @@ CTX_OPT_ENCODE_CHROMA_LAYOUT = 6  # the planes bt709hip_encode[_batch] writes: C
 CTX_OPT_ENCODE_PREMULTIPLY = 8  # 0 (default): BGRA8_SRGB input is encoded as it is; 1: it is straight alpha, premultiplied in the encode kernel; any other value is refused
 CTX_OPT_ENCODE_CONVERT = 10  # CONVERT_OFF (default): bt709hip_encode[_batch] is the subsampling encoder; CONVERT_PACKED444 / CONVERT_POINT420: the reference's per-pixel +convert:; any other value is refused
 CTX_OPT_ENCODE_WITH_ALPHA = 12  # 0 (default): one frame per picture; 1: bt709hip_encode[_batch] of BGRA8_SRGB input writes the alpha frame as well, `out` holds 2 x count frames (colour frames, then the alpha frames); any other value is refused
-CTX_OPT_ENCODE_HALF_INPUT = 14  # 0 (default): RGBA16F input to bt709hip_encode[_batch] is refused (ERR_UNSUPPORTED); 1: it is encoded as linear light (input gamma LINEAR); any other value is refused
+CTX_OPT_ENCODE_HALF_WITH_ALPHA = 16  # 0 (default): one frame per picture; 1: bt709hip_encode[_batch] of RGBA16F input (under CTX_OPT_ENCODE_HALF_INPUT = 1) writes the surface's alpha frame as well, `out` holds 2 x count frames (colour frames, then the alpha frames); any other value is refused
+CTX_OPT_ENCODE_HALF_INPUT = 14 # 0 (default): RGBA16F input to bt709hip_encode[_batch] is refused (ERR_UNSUPPORTED); 1: it is encoded as linear light (input gamma LINEAR); any other value is refused
 CONVERT_OFF = 0
 CONVERT_PACKED444 = 1  # out.y: W x H 32-bit words (Cr<<16)|(Cb<<8)|Y, out.cbcr NULL
 CONVERT_POINT420 = 2   # +convert: then copyBT709ToCoreVideo in one launch: an NV12 / I420 frame, a block's chroma from its odd row, even column

@@ -500,6 +500,7 @@ encode_alpha_y_blocks(const EncodeParams p) {
 #include "bt709_encode_pair.h"     // BT709HIP_CTX_OPT_ENCODE_WITH_ALPHA: encode_bgra_alpha over the helpers above
 #include "bt709_encode_convert.h"  // BT709HIP_CTX_OPT_ENCODE_CONVERT: convert_bgra, convert_bgra_blocks over the helpers above
 #include "bt709_encode_half.h"     // BT709HIP_CTX_OPT_ENCODE_HALF_INPUT: encode_rgba16f, encode_rgba16f_blocks over the helpers above
+#include "bt709_encode_half_alpha.h"  // BT709HIP_CTX_OPT_ENCODE_HALF_WITH_ALPHA: encode_rgba16f_alpha, encode_rgba16f_alpha_blocks over both
 
 namespace bt709 {
 namespace {
@@ -554,17 +555,20 @@ const EncodeKernel kEncodeKernels[] = {
 #undef CONVERT_PACKED
 #undef CONVERT_POINT
 
-// RGBA16Float input (EncodeParams::input_format): a table of its own, [fast]; the shim refuses every option the rows above select by
-const EncodeKernel kEncodeHalfKernels[2] = {
-    {0, 0, 0, kConvertOff, true, {encode_rgba16f_blocks<kChromaNV12>, encode_rgba16f_blocks<kChromaI420>}, {"encode_rgba16f_nv12_blocks", "encode_rgba16f_i420_blocks"}},
-    {1, 0, 0, kConvertOff, true, {encode_rgba16f<kChromaNV12>, encode_rgba16f<kChromaI420>}, {"encode_rgba16f_nv12", "encode_rgba16f_i420"}},
+// RGBA16Float input (EncodeParams::input_format): a table of its own, [fast][pair]; the shim refuses every option the rows above
+// select by.  pair: the alpha frame rides along (BT709HIP_CTX_OPT_ENCODE_HALF_WITH_ALPHA, bt709_encode_half_alpha.h)
+const EncodeKernel kEncodeHalfKernels[2][2] = {
+    {{0, 0, 0, kConvertOff, true, {encode_rgba16f_blocks<kChromaNV12>, encode_rgba16f_blocks<kChromaI420>}, {"encode_rgba16f_nv12_blocks", "encode_rgba16f_i420_blocks"}},
+     {0, 2, 0, kConvertOff, true, {encode_rgba16f_alpha_blocks<kChromaNV12>, encode_rgba16f_alpha_blocks<kChromaI420>}, {"encode_rgba16f_alpha_nv12_blocks", "encode_rgba16f_alpha_i420_blocks"}}},
+    {{1, 0, 0, kConvertOff, true, {encode_rgba16f<kChromaNV12>, encode_rgba16f<kChromaI420>}, {"encode_rgba16f_nv12", "encode_rgba16f_i420"}},
+     {1, 2, 0, kConvertOff, true, {encode_rgba16f_alpha<kChromaNV12>, encode_rgba16f_alpha<kChromaI420>}, {"encode_rgba16f_alpha_nv12", "encode_rgba16f_alpha_i420"}}},
 };
 
 // The kernel of a launch that launch_encode has planned and recorded
 const char *launch_encode_kernel(const EncodeParams &p, const dim3 &grid, const dim3 &block, size_t lds, bool fast, int alpha, hipStream_t stream) {
   const uint32_t layout = p.chroma_layout == kChromaI420 ? kChromaI420 : kChromaNV12;
   if (p.input_format == kEncodeInputRGBA16F) {
-    const EncodeKernel &k = kEncodeHalfKernels[fast ? 1 : 0];
+    const EncodeKernel &k = kEncodeHalfKernels[fast ? 1 : 0][alpha == 2 ? 1 : 0];
     hipLaunchKernelGGL(k.fn[layout], grid, block, lds, stream, p);
     return k.name[layout];
   }
@@ -593,7 +597,7 @@ const char *launch_encode(const EncodeParams &params, int frames, bool fast, boo
   if (p.row_pairs_per_block == 0) p.row_pairs_per_block = encode_row_pairs_per_block(plan_width, p.height, frames);
   // BT709HIP_FORMAT_BGRA8_ALPHA: same plan, the alpha kernels (static LDS); with the colour's tables as well: the pair, T behind them
   const int alpha = p.convert_mode != kConvertOff ? 0 : encode_pair(p) ? 2 : p.alpha_luma != nullptr ? 1 : 0;
-  const size_t lds = half ? p.from_linear_bytes : alpha == 1 || p.convert_mode != kConvertOff ? 0 : 256 * sizeof(EncodeByteEntry) + p.from_linear_bytes + (alpha == 2 ? kAlphaLumaLdsBytes : 0);  // the converter's curve is static, too
+  const size_t lds = half ? p.from_linear_bytes + (alpha == 2 ? kAlphaLumaLdsBytes : 0) : alpha == 1 || p.convert_mode != kConvertOff ? 0 : 256 * sizeof(EncodeByteEntry) + p.from_linear_bytes + (alpha == 2 ? kAlphaLumaLdsBytes : 0);  // the converter's curve is static, too
   dim3 grid((p.width / 2 + kBlockThreads - 1) / kBlockThreads, p.height / 2, frames), block(kBlockThreads);
   if (fast) {
     const uint32_t quads = plan_width / 4;
@@ -621,10 +625,11 @@ hipError_t prepare_encode_kernels() {
     const void *fns[] = {reinterpret_cast<const void *>(k.fn[0]), reinterpret_cast<const void *>(k.fn[1])};
     if (const hipError_t e = k.stages_table ? raise_lds_cap(fns, kRepLdsBytes) : hipSuccess) return e;
   }
-  for (const EncodeKernel &k : kEncodeHalfKernels) {
-    const void *fns[] = {reinterpret_cast<const void *>(k.fn[0]), reinterpret_cast<const void *>(k.fn[1])};
-    if (const hipError_t e = raise_lds_cap(fns, kRepLdsBytes)) return e;
-  }
+  for (const auto &row : kEncodeHalfKernels)
+    for (const EncodeKernel &k : row) {
+      const void *fns[] = {reinterpret_cast<const void *>(k.fn[0]), reinterpret_cast<const void *>(k.fn[1])};
+      if (const hipError_t e = raise_lds_cap(fns, kRepLdsBytes)) return e;
+    }
   return hipSuccess;
 }
 

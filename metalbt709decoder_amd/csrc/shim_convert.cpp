@@ -270,7 +270,10 @@ int bt709hip_encode_batch(bt709hip_context *ctx, int count, const bt709hip_surfa
   // (BGRA8_ALPHA output's rules) into outs[count + i], from one launch.  Not with the per-pixel converter and not for BGRA8_ALPHA
   // input: refused behind the usual validation.
   const bool with_alpha = ctx->encode_with_alpha != 0;
-  const bool pair = with_alpha && !alpha && !half && convert == BT709HIP_CONVERT_OFF;
+  // BT709HIP_CTX_OPT_ENCODE_HALF_WITH_ALPHA, read once: the same two frames per picture from RGBA16F input, the alpha
+  // frame from the texel's A half.  An option of its own: WITH_ALPHA with half input stays refused.  No other input reads it.
+  const bool half_pair = half && ctx->encode_half_with_alpha != 0;
+  const bool pair = half_pair || (with_alpha && !alpha && !half && convert == BT709HIP_CONVERT_OFF);
   const bt709hip_frame &alpha0 = outs[pair ? count : 0];
   const bool alpha_no_cbcr = pair && alpha0.cbcr == nullptr;
   bool uniform = count > 1;
@@ -280,7 +283,9 @@ int bt709hip_encode_batch(bt709hip_context *ctx, int count, const bt709hip_surfa
   const size_t half_chroma_align = planar ? 1 : 2;
   if (half) fast = (in0.stride % 16) == 0 && (out0.y_stride % 2) == 0 && (out0.cbcr_stride % half_chroma_align) == 0;
   const size_t in_px = half ? 8 : 4;  // bytes of a texel
-  if (pair) fast = fast && (alpha0.y_stride % 4) == 0 && (alpha_no_cbcr || (alpha0.cbcr_stride % chroma_align) == 0);
+  // the paired fast kernels store to the alpha frame as they do to the colour's: encode_bgra_alpha dwords, encode_rgba16f_alpha halves
+  const size_t pair_y_align = half ? 2 : 4, pair_chroma_align = half ? half_chroma_align : chroma_align;
+  if (pair) fast = fast && (alpha0.y_stride % pair_y_align) == 0 && (alpha_no_cbcr || (alpha0.cbcr_stride % pair_chroma_align) == 0);
   EncodeParams p;
   std::memset(&p, 0, sizeof p);
   for (int i = 0; i < count; ++i) {
@@ -319,7 +324,7 @@ int bt709hip_encode_batch(bt709hip_context *ctx, int count, const bt709hip_surfa
       if (af.y == nullptr || (af.cbcr == nullptr) != alpha_no_cbcr) return BT709HIP_ERR_INVALID_ARG;
       if (af.y_stride < w || (!alpha_no_cbcr && af.cbcr_stride < (planar ? w / 2 : w))) return BT709HIP_ERR_STRIDE;
       if (af.y_stride > 0xffffffffu || (!alpha_no_cbcr && af.cbcr_stride > 0xffffffffu)) return BT709HIP_ERR_STRIDE;
-      fast = fast && aligned(af.y, 4) && aligned(af.cbcr, chroma_align);
+      fast = fast && aligned(af.y, pair_y_align) && aligned(af.cbcr, pair_chroma_align);
       if (i >= 2)
         uniform = uniform && byte_step(alpha0.y, af.y) == byte_step(alpha0.y, outs[count + 1].y) * i &&
                   byte_step(alpha0.cbcr, af.cbcr) == byte_step(alpha0.cbcr, outs[count + 1].cbcr) * i;
@@ -340,7 +345,7 @@ int bt709hip_encode_batch(bt709hip_context *ctx, int count, const bt709hip_surfa
   if (count > (uniform ? kMaxUniformBatch : pair ? kMaxPairBatch : kMaxBatch)) return BT709HIP_ERR_UNSUPPORTED;
   // the reference's per-pixel converters take sRGB bytes only, and no alpha clip goes through them
   if (convert != BT709HIP_CONVERT_OFF && (alpha || input_gamma != BT709HIP_GAMMA_SRGB)) return BT709HIP_ERR_UNSUPPORTED;
-  if (with_alpha && !pair) return BT709HIP_ERR_UNSUPPORTED;  // the converter writes no alpha frame; an alpha clip has none beside itself
+  if (with_alpha && (!pair || half)) return BT709HIP_ERR_UNSUPPORTED;  // the converter writes no alpha frame; an alpha clip has none beside itself; halves have an option of their own
   // half input composes with the chroma layout alone: the converter, the pair and the premultiply are BGRA8 paths
   if (half && (convert_option != BT709HIP_CONVERT_OFF || ctx->encode_premultiply != 0)) return BT709HIP_ERR_UNSUPPORTED;
   if (in0.width == 0 || in0.height == 0) return BT709HIP_OK;
@@ -409,7 +414,8 @@ int bt709hip_encoder_prepare(bt709hip_context *ctx, int input_gamma, int output_
     if (int rc = convert_curve_table(ctx, output_gamma, nullptr)) return rc;
   if (output_gamma == 3) return BT709HIP_OK;  // no subsampling encoder writes ITU709
   // T: the one gamma pair BGRA8_ALPHA input encodes with; under BT709HIP_CTX_OPT_ENCODE_WITH_ALPHA every pair's alpha frame reads it
-  if ((input_gamma == BT709HIP_GAMMA_LINEAR && output_gamma == BT709HIP_GAMMA_LINEAR) || ctx->encode_with_alpha != 0)
+  // (and under BT709HIP_CTX_OPT_ENCODE_HALF_WITH_ALPHA every half pair's, whose input gamma is LINEAR)
+  if ((input_gamma == BT709HIP_GAMMA_LINEAR && (output_gamma == BT709HIP_GAMMA_LINEAR || ctx->encode_half_with_alpha != 0)) || ctx->encode_with_alpha != 0)
     if (int rc = alpha_luma_table(ctx, nullptr)) return rc;
   return encoder_tables(ctx, input_gamma, output_gamma, nullptr);
 }

@@ -153,6 +153,10 @@ int bt709hip_context_set_option(bt709hip_context *ctx, int option, int value) {
       if (value != 0 && value != 1) return BT709HIP_ERR_INVALID_ARG;
       ctx->encode_half_input = value;
       return BT709HIP_OK;
+    case BT709HIP_CTX_OPT_ENCODE_HALF_WITH_ALPHA:  // the half encode's alpha frame; T is built by the first such call, or by bt709hip_encoder_prepare under the option
+      if (value != 0 && value != 1) return BT709HIP_ERR_INVALID_ARG;
+      ctx->encode_half_with_alpha = value;
+      return BT709HIP_OK;
     case BT709HIP_CTX_OPT_STREAMING_TRIES:
       ctx->streaming_tries = value <= 0 ? 4 : clamp_int(value, 1, 32);
       return BT709HIP_OK;

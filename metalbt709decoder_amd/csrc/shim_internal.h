@@ -44,6 +44,7 @@ struct bt709hip_context {
   int encode_convert = BT709HIP_CONVERT_OFF;        // BT709HIP_CTX_OPT_ENCODE_CONVERT: bt709hip_encode[_batch] is the per-pixel converter (+convert:)
   int encode_with_alpha = 0;                        // BT709HIP_CTX_OPT_ENCODE_WITH_ALPHA: bt709hip_encode[_batch] of BGRA8_SRGB input writes the alpha frame as well, `out` holds 2 x count frames
   int encode_half_input = 0;                        // BT709HIP_CTX_OPT_ENCODE_HALF_INPUT: bt709hip_encode[_batch] accepts RGBA16F (linear-light) surfaces
+  int encode_half_with_alpha = 0;                   // BT709HIP_CTX_OPT_ENCODE_HALF_WITH_ALPHA: such a call writes the surface's alpha frame as well, `out` holds 2 x count frames
   int streaming_tries = 4;                   // BT709HIP_CTX_OPT_STREAMING_TRIES: placement candidates for buffers of 256 MB and more that the library allocates itself
   std::mutex encoder_mutex;
   EncoderTables encoders[3][3];  // [input gamma][output gamma], built on first use

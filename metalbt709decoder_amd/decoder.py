@@ -612,6 +612,25 @@ class MetalRenderContext:
         finally:
             self.lib.bt709hip_context_set_option(self.handle, _capi.CTX_OPT_ENCODE_HALF_INPUT, 0)
 
+    @contextlib.contextmanager
+    def _encode_half_with_alpha(self, what):
+        """CTX_OPT_ENCODE_HALF_INPUT and CTX_OPT_ENCODE_HALF_WITH_ALPHA around ONE paired encode of RGBA16Float textures: both 1 on
+        entry and both back to 0 on the way out, whatever the call returned or raised (also when the second setter is refused).
+        The setters never touch the device.  Yields True, or False when the library refused an option."""
+        with self._encode_half_input(what) as ok:
+            if not ok:
+                yield False
+                return
+            rc = self.lib.bt709hip_context_set_option(self.handle, _capi.CTX_OPT_ENCODE_HALF_WITH_ALPHA, 1)
+            if rc != _capi.OK:
+                log.error("%s: CTX_OPT_ENCODE_HALF_WITH_ALPHA = 1: %s", what, _capi.strerror(rc))
+                yield False
+                return
+            try:
+                yield True
+            finally:
+                self.lib.bt709hip_context_set_option(self.handle, _capi.CTX_OPT_ENCODE_HALF_WITH_ALPHA, 0)
+
     def _set_encode_layout(self, pixelBuffers, what):
         """The encoder's chroma layout from the buffers an encode call was handed: a planar CVPixelBuffer is written in place.  As
         MetalBT709Decoder._set_layout: the buffer's `planar` flag is authoritative, planar and NV12 buffers in one call are
@@ -836,6 +855,45 @@ class BGRAToBT709Converter:
             log.error("convertIntoCoreVideoBuffers: %s", _capi.strerror(rc))
             return False
         for b in alphaPixelBuffers or []:
+            BGRAToBT709Converter.setAlphaAttributes(b)
+        return True
+
+    @staticmethod
+    def convertHalfIntoCoreVideoBuffersWithAlpha(textures, cvPixelBuffers, alphaPixelBuffers, outputGamma, commandBuffer=None,
+                                                 waitUntilCompleted=True):
+        """`count` same-sized RGBA16Float textures (premultiplied linear colour and a linear A: what -decodeBT709:alphaPixelBuffer:
+        writes into such targets) into their colour frames AND their alpha frames, in ONE launch and one read of each texture
+        (bt709hip_encode_batch under CTX_OPT_ENCODE_HALF_INPUT and CTX_OPT_ENCODE_HALF_WITH_ALPHA, both set around this call alone
+        and both put back whatever happens).  The colour frames are what convertIntoCoreVideoBuffers writes for the
+        textures (input gamma Linear, `outputGamma` Apple / SRGB / Linear); alphaPixelBuffers[i] receives Y = T[round(255 sat(A))]
+        and Cb = Cr = 128 where it has a chroma plane, and leaves tagged ITU_R_709_2 / Linear.  Planar buffers are written in place,
+        as convertIntoCoreVideoBuffers writes them.  Returns True/False."""
+        n = len(textures)
+        if n != len(cvPixelBuffers) or n != len(alphaPixelBuffers):
+            raise ValueError("one output buffer and one alpha buffer per input texture")
+        if n == 0:
+            return True
+        what = "convertHalfIntoCoreVideoBuffersWithAlpha"
+        if any(t.pixelFormat != MTLPixelFormatRGBA16Float for t in textures):
+            log.error("%s: the sources must be RGBA16Float textures", what)
+            return False
+        ctx = textures[0].ctx
+        outs = list(cvPixelBuffers) + list(alphaPixelBuffers)
+        # the layout option covers both frames of a pair; an alpha buffer without a chroma plane has nothing to lay out
+        if not ctx._set_encode_layout(list(cvPixelBuffers) + [b for b in alphaPixelBuffers if b.cbcr_ptr], what):
+            return False
+        surfs = (Surface * n)(*[t.surface() for t in textures])
+        frames = (Frame * len(outs))(*[b.frame() for b in outs])  # colour frames, then pair i's alpha frame at n + i
+        stream = commandBuffer.stream if commandBuffer is not None else None
+        with ctx._encode_half_with_alpha(what) as ok:
+            if not ok:
+                return False
+            rc = ctx.lib.bt709hip_encode_batch(ctx.handle, n, surfs, frames, MetalBT709GammaLinear, int(outputGamma), stream,
+                                               int(bool(waitUntilCompleted)))
+        if rc != _capi.OK:
+            log.error("%s: %s", what, _capi.strerror(rc))
+            return False
+        for b in alphaPixelBuffers:
             BGRAToBT709Converter.setAlphaAttributes(b)
         return True
 
