@@ -388,6 +388,13 @@ int bt709hip_decoder_get_option(const bt709hip_decoder *dec, int option, int *va
  * QUEUED: up to n frames of one geometry and target format per stream gather and go out as ONE bt709hip_decode_batch launch
  * (evenly spaced frames as a uniform batch, any others through the pointer table).  The queue of a stream is issued
  *   - when it holds n frames, or a call with another geometry / format / decoder state arrives for that stream,
+ *   - when a call arrives that reads or writes what a queued call writes, or writes what a queued call reads (the items of a
+ *     launch run concurrently; calls made one after the other do not): the queue goes out first and the call starts a new one,
+ *     so two decodes into one surface, clips layered onto one canvas under BT709HIP_OVER_DESTINATION and a target read back
+ *     as a frame keep the order of the calls.  Targets of one pitch whose rows share a pitch grid -- windows of one canvas --
+ *     are compared as rectangles, exactly, and gather when disjoint; everything else (targets against inputs: Y, CbCr or
+ *     U + V, alpha) by byte range [base, base + (rows - 1) * pitch + row bytes), which may issue a queue early and never
+ *     late.  Overlap INSIDE one batch call stays the caller's error (THE UNIFORM RULE, below),
  *   - by any bt709hip_* call that takes that stream (stream_synchronize, event_record, stream_wait_event, download, upload,
  *     memset, graph capture, copy_probe, a decode with wait_until_completed != 0, every other decode / encode / rescale
  *     entry point -- of THIS decoder or of any other decoder of the context, coalescing or not) -- so the stream keeps its

@@ -93,6 +93,70 @@ namespace {
 bool same_shape(const bt709hip_frame &a, const bt709hip_frame &b) {
   return a.width == b.width && a.height == b.height && a.y_stride == b.y_stride && a.cbcr_stride == b.cbcr_stride;
 }
+
+// STREAM ORDER BETWEEN CALLS.  The items of one launch run concurrently, so a call may only join a queue when it neither
+// writes a byte a queued call reads or writes nor reads a byte a queued call writes; otherwise the queue goes out first, as
+// for a change of geometry.  (Overlap INSIDE one batch call stays the caller's error, as without the option.)
+bool meet(const ByteSpan &a, const ByteSpan &b) { return a.lo < b.hi && b.lo < a.hi; }
+
+void join(ByteSpan &a, const ByteSpan &b) {
+  a.lo = std::min(a.lo, b.lo);
+  a.hi = std::max(a.hi, b.hi);
+}
+
+ByteSpan plane_span(const void *base, size_t rows, size_t stride, size_t row_bytes) {
+  const uintptr_t b = reinterpret_cast<uintptr_t>(base);
+  return ByteSpan{b, b + (rows - 1) * stride + row_bytes};
+}
+
+// what a (non-empty) item reads: Y, the chroma -- CbCr rows, or the U plane and the V plane (H/2) * cbcr_stride behind it as
+// one range -- and the alpha plane where the decoder reads one
+struct ItemReads {
+  ByteSpan plane[3];
+};
+ItemReads reads_of(const bt709hip_frame &f, const bt709hip_frame *a, int layout) {
+  const size_t w = static_cast<size_t>(f.width), h = static_cast<size_t>(f.height);
+  ItemReads r;
+  r.plane[0] = plane_span(f.y, h, f.y_stride, w);
+  r.plane[1] = layout == BT709HIP_CHROMA_I420 ? plane_span(f.cbcr, h, f.cbcr_stride, w / 2) : plane_span(f.cbcr, h / 2, f.cbcr_stride, w);
+  if (a != nullptr) r.plane[2] = plane_span(a->y, h, a->y_stride, w);
+  return r;
+}
+
+size_t row_bytes_of(const bt709hip_surface &o) { return static_cast<size_t>(o.width) * (o.format == BT709HIP_FORMAT_RGBA16F ? 8 : 4); }
+
+ByteSpan write_of(const bt709hip_surface &o) { return plane_span(o.bgra, static_cast<size_t>(o.height), o.stride, row_bytes_of(o)); }
+
+// Two targets of one pitch, height and row length.  Where the later one's rows lie on the earlier one's pitch grid (windows of
+// one canvas) the rectangles are compared, exactly; where they straddle the grid's rows, the byte ranges.
+bool targets_meet(const bt709hip_surface &p, const bt709hip_surface &q) {
+  uintptr_t a = reinterpret_cast<uintptr_t>(p.bgra), b = reinterpret_cast<uintptr_t>(q.bgra);
+  if (a > b) std::swap(a, b);
+  const size_t rows = static_cast<size_t>(p.height), row = row_bytes_of(p);
+  const uintptr_t d = b - a;
+  const size_t dy = d / p.stride, dx = d % p.stride;
+  if (dx + row <= p.stride) return dy < rows && dx < row;
+  return d < (rows - 1) * p.stride + row;
+}
+
+// `alphas`: the alpha frames the decoder READS (nullptr for an opaque decoder, whatever the caller passed).  The call fits the
+// queue: one geometry, pitches, format and layout on both sides, alpha frames passed on both or on neither.
+bool conflicts(const PendingQueue &q, const ByteSpan &writes, const ByteSpan &reads, int count, const bt709hip_frame *frames,
+               const bt709hip_frame *alphas, const bt709hip_surface *outs) {
+  if (!meet(writes, q.writes) && !meet(writes, q.reads) && !meet(reads, q.writes)) return false;  // the usual case: slots of a ring
+  for (size_t j = 0; j < q.frames.size(); ++j) {
+    const ItemReads qr = reads_of(q.frames[j], alphas ? &q.alphas[j] : nullptr, q.layout);
+    const ByteSpan qw = write_of(q.outs[j]);
+    for (int i = 0; i < count; ++i) {
+      if (targets_meet(q.outs[j], outs[i])) return true;
+      const ItemReads r = reads_of(frames[i], alphas ? &alphas[i] : nullptr, q.layout);
+      const ByteSpan w = write_of(outs[i]);
+      for (int k = 0; k < 3; ++k)
+        if (meet(r.plane[k], qw) || meet(w, qr.plane[k])) return true;
+    }
+  }
+  return false;
+}
 }  // namespace
 
 // BT709HIP_OPT_COALESCE (include/bt709hip_ext.h, COALESCING SUBMIT): validate now, launch later.
@@ -126,6 +190,7 @@ int coalescing_submit(bt709hip_decoder *dec, int layout, int count, const bt709h
     BatchInfo info;
     if (int rc = gather_batch(dec, count, frames, alphas, outs, OutShape::kSame, layout, stream, &p, &info)) return rc;
     if (layout == BT709HIP_CHROMA_I420 && info.format == BT709HIP_FORMAT_RGBA16F) return BT709HIP_ERR_UNSUPPORTED;  // decode_batch_now's refusal, now
+    if (dec->composite_over != BT709HIP_OVER_OFF && info.format == BT709HIP_FORMAT_RGBA16F) return BT709HIP_ERR_UNSUPPORTED;  // BT709HIP_OPT_COMPOSITE_OVER's
     if (dec->unpremultiply != 0 && (info.format == BT709HIP_FORMAT_RGBA16F || dec->composite_over != BT709HIP_OVER_OFF)) return BT709HIP_ERR_UNSUPPORTED;  // and BT709HIP_OPT_UNPREMULTIPLY's
     if (p.width == 0) return BT709HIP_OK;  // empty frames: nothing to launch
   }
@@ -134,17 +199,31 @@ int coalescing_submit(bt709hip_decoder *dec, int layout, int count, const bt709h
     q = &dec->queues.back();
     q->stream = s;
   }
+  // the bytes this call writes and reads, as one range each: the queue keeps the union of its calls' and only a call that
+  // touches that union is compared item by item
+  const bt709hip_frame *read_alphas = dec->has_alpha ? alphas : nullptr;
+  ByteSpan writes, reads;
+  for (int i = 0; i < count; ++i) {
+    join(writes, write_of(outs[i]));
+    const ItemReads r = reads_of(frames[i], read_alphas ? &read_alphas[i] : nullptr, layout);
+    for (const ByteSpan &pl : r.plane) join(reads, pl);
+  }
   if (!q->frames.empty()) {
     const bool fits = q->frames.size() + static_cast<size_t>(count) <= static_cast<size_t>(n) &&
                       same_shape(q->frames[0], frames[0]) && q->frames[0].transfer == frames[0].transfer &&
                       q->outs[0].stride == outs[0].stride && q->outs[0].format == outs[0].format && q->layout == layout &&
                       q->with_alphas == (alphas != nullptr) && (alphas == nullptr || q->alphas[0].y_stride == alphas[0].y_stride);
-    if (!fits)
+    if (!fits || conflicts(*q, writes, reads, count, frames, read_alphas, outs))
       if (int rc = issue_queue(dec, *q)) return rc;
   }
   q->with_alphas = alphas != nullptr;
   q->layout = layout;
-  if (q->frames.empty()) q->oldest_us = now_us();
+  if (q->frames.empty()) {
+    q->oldest_us = now_us();
+    q->writes = q->reads = ByteSpan{};
+  }
+  join(q->writes, writes);
+  join(q->reads, reads);
   q->frames.insert(q->frames.end(), frames, frames + count);
   if (alphas != nullptr) q->alphas.insert(q->alphas.end(), alphas, alphas + count);
   q->outs.insert(q->outs.end(), outs, outs + count);

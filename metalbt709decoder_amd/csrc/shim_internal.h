@@ -61,6 +61,10 @@ struct bt709hip_context {
   std::vector<bt709hip_decoder *> coalescing;
 };
 
+struct ByteSpan {  // bytes [lo, hi); as constructed: empty, meets nothing
+  uintptr_t lo = UINTPTR_MAX, hi = 0;
+};
+
 // BT709HIP_OPT_COALESCE: frames validated and queued for one stream, not yet launched (include/bt709hip_ext.h, COALESCING SUBMIT)
 struct PendingQueue {
   hipStream_t stream = nullptr;
@@ -69,6 +73,7 @@ struct PendingQueue {
   int64_t oldest_us = 0;     // steady-clock time at which the oldest frame it holds was queued (BT709HIP_OPT_COALESCE_MAX_AGE_US)
   std::vector<bt709hip_frame> frames, alphas;
   std::vector<bt709hip_surface> outs;
+  ByteSpan writes, reads;    // the union of what the queued calls write / read: a call that stays clear of both joins without an item-by-item comparison
 };
 
 struct bt709hip_decoder {

@@ -6,6 +6,7 @@
 //   coalescing     two threads, each with its own stream, submit one-frame calls to ONE decoder while a third flips options
 //                  and flushes; every frame submitted must reach its stream exactly once, in submission order per stream
 //   two decoders   a coalescing decoder's queued frames go out before a later call of ANOTHER decoder on the same stream
+//   overlap        calls whose targets meet never share a launch; two threads, a third flipping options
 //   age limit      a queue older than BT709HIP_OPT_COALESCE_MAX_AGE_US is issued by a call on another stream
 //   pool           acquire / submit / wait / release churn, a failing submit, depth-3 pipeline
 //   sharder        ticket window over 4 lanes on 2 devices, cancel, refused frames
@@ -176,6 +177,103 @@ static void test_two_decoders_one_stream_and_age() {
   OK(bt709hip_decoder_destroy(b));
   OK(bt709hip_stream_destroy(ctx, s));
   OK(bt709hip_stream_destroy(ctx, other));
+  OK(bt709hip_free(ctx, d_in));
+  OK(bt709hip_free(ctx, d_out));
+  OK(bt709hip_context_destroy(ctx));
+}
+
+// Calls whose targets overlap never share a launch (COALESCING SUBMIT: a queue is issued when a call writes what a queued call
+// writes or reads).  Two threads, each with its own stream and its own 128 x 16 canvas, submit calls of 1..3 items into six
+// 64 x 8 windows of the canvas's pitch -- the 2 x 2 wall and two windows that straddle its tiles -- while a third thread flips
+// options and flushes; the queue walk runs under queue_mutex.  Per stream: every item goes out once, in submission order, and
+// no launch holds items of two calls whose windows meet.
+static void test_overlapping_targets() {
+  fake_hip_reset();
+  bt709hip_context *ctx = nullptr;
+  OK(bt709hip_context_create(0, &ctx));
+  bt709hip_decoder *dec = nullptr;
+  OK(bt709hip_decoder_create(ctx, BT709HIP_GAMMA_APPLE, 0, &dec));
+  OK(bt709hip_decoder_set_option(dec, BT709HIP_OPT_COALESCE, 8));
+  const int w = 64, h = 8, cw = 128, ch = 16, calls = 300, inputs = 8;
+  const int wx[6] = {0, 64, 0, 64, 32, 0}, wy[6] = {0, 0, 8, 8, 4, 4};  // window origins on the canvas, pixels
+  auto windows_meet = [&](int a, int b) { return std::abs(wx[a] - wx[b]) < w && std::abs(wy[a] - wy[b]) < h; };
+  void *d_in = nullptr, *d_out = nullptr;
+  OK(bt709hip_malloc(ctx, static_cast<size_t>(2 * inputs) * w * h * 3 / 2, &d_in));
+  OK(bt709hip_malloc(ctx, static_cast<size_t>(2) * cw * ch * 4, &d_out));
+  void *streams[2] = {nullptr, nullptr};
+  OK(bt709hip_stream_create(ctx, &streams[0]));
+  OK(bt709hip_stream_create(ctx, &streams[1]));
+  struct Item {
+    int call, window;
+    const void *out;
+  };
+  std::vector<Item> items[2];
+  std::atomic<bool> go{false}, done{false};
+  auto feeder = [&](int t) {
+    while (!go.load()) std::this_thread::yield();
+    uint32_t seed = 12345u + 77u * static_cast<uint32_t>(t);
+    auto next = [&seed](uint32_t n) { return ((seed = seed * 1664525u + 1013904223u) >> 16) % n; };
+    uint8_t *canvas = static_cast<uint8_t *>(d_out) + static_cast<size_t>(t) * cw * ch * 4;
+    for (int c = 0; c < calls; ++c) {
+      const int count = 1 + static_cast<int>(next(3));
+      bt709hip_frame f[3];
+      bt709hip_surface o[3];
+      int win[3];
+      bool disjoint;
+      do {  // inside ONE call the targets stay disjoint (overlap there is the caller's error)
+        for (int i = 0; i < count; ++i) win[i] = static_cast<int>(next(6));
+        disjoint = true;
+        for (int i = 0; i < count; ++i)
+          for (int j = 0; j < i; ++j) disjoint = disjoint && !windows_meet(win[i], win[j]);
+      } while (!disjoint);
+      for (int i = 0; i < count; ++i) {
+        f[i] =frame_at(static_cast<uint8_t *>(d_in) + static_cast<size_t>(t * inputs + static_cast<int>(next(inputs))) * w * h * 3 / 2, w, h);
+        o[i] = surface_at(canvas + (static_cast<size_t>(wy[win[i]]) * cw + wx[win[i]]) * 4, w, h);
+        o[i].stride = static_cast<size_t>(cw) * 4;
+      }
+      if (bt709hip_decode_batch(dec, count, f, nullptr, o, streams[t], 0) != BT709HIP_OK) {
+        ++failures;
+        continue;
+      }
+      for (int i = 0; i < count; ++i) items[t].push_back({c, win[i], o[i].bgra});
+      if (c % 41 == 0) OK(bt709hip_decoder_flush(dec, streams[t]));
+    }
+  };
+  std::thread a(feeder, 0), b(feeder, 1);
+  std::thread meddler([&] {
+    while (!go.load()) std::this_thread::yield();
+    int k = 0;
+    while (!done.load()) {
+      OK(bt709hip_decoder_set_option(dec, BT709HIP_OPT_COALESCE, (k++ % 5 == 0) ? 0 : 4 + k % 8));
+      if (k % 3 == 0) OK(bt709hip_decoder_flush_all(dec));
+      std::this_thread::yield();
+    }
+  });
+  go.store(true);
+  a.join();
+  b.join();
+  done.store(true);
+  meddler.join();
+  OK(bt709hip_decoder_flush_all(dec));
+  for (int t = 0; t < 2; ++t) {
+    OK(bt709hip_stream_synchronize(ctx, streams[t]));
+    size_t at = 0;
+    bool clean = true;
+    for (const Launch &l : launches_on(streams[t])) {
+      if (at + static_cast<size_t>(l.frames) > items[t].size() || l.out != items[t][at].out) {  // submission order, nothing twice
+        clean = false;
+        break;
+      }
+      for (size_t i = at; i < at + static_cast<size_t>(l.frames); ++i)
+        for (size_t j = at; j < i; ++j)
+          if (items[t][i].call != items[t][j].call && windows_meet(items[t][i].window, items[t][j].window)) clean = false;
+      at += static_cast<size_t>(l.frames);
+    }
+    CHECK(clean && at == items[t].size());
+  }
+  OK(bt709hip_decoder_destroy(dec));
+  OK(bt709hip_stream_destroy(ctx, streams[0]));
+  OK(bt709hip_stream_destroy(ctx, streams[1]));
   OK(bt709hip_free(ctx, d_in));
   OK(bt709hip_free(ctx, d_out));
   OK(bt709hip_context_destroy(ctx));
@@ -573,7 +671,7 @@ int main(int argc, char **argv) {
   struct {
     const char *name;
     void (*fn)();
-  } tests[] = {{"coalescing", test_coalescing_threads}, {"two_decoders", test_two_decoders_one_stream_and_age}, {"pool_sharder", test_pool_and_sharder},
+  } tests[] = {{"coalescing", test_coalescing_threads}, {"two_decoders", test_two_decoders_one_stream_and_age}, {"overlap", test_overlapping_targets}, {"pool_sharder", test_pool_and_sharder},
                {"ring", test_ring_hunts},               {"ring_set", test_ring_set},                             {"graphs", test_graphs_and_misc},
                {"host_buffers", test_host_buffer_lifetime},     {"fuzz", test_argument_fuzz}};
   for (auto &t : tests) {
