@@ -547,6 +547,21 @@ class MetalBT709Decoder {
   // behind it: a YUV4MPEG2 FRAME payload as uploaded.  BGRA8 targets of decodeBT709 only; rings and pools stay NV12.
   static constexpr int kChromaLayoutOption = BT709HIP_OPT_CHROMA_LAYOUT;
   static constexpr int kChromaNV12 = BT709HIP_CHROMA_NV12, kChromaI420 = BT709HIP_CHROMA_I420;
+  // Planar C x H x W targets of decodeBT709 (include/bt709hip_ext.h PLANAR CHW TARGETS): a bt709hip_surface whose
+  // format is one of these, bgra the base of plane 0 and stride the row pitch of every plane -- R, G, B and, from a decoder with an
+  // alpha channel, A.  The float elements are float(byte) * (1/255f) * scale + bias per channel, three binary32 operations:
+  static constexpr int kFormatCHWU8 = BT709HIP_FORMAT_CHW_U8, kFormatCHWF16 = BT709HIP_FORMAT_CHW_F16, kFormatCHWF32 = BT709HIP_FORMAT_CHW_F32;
+  // scale and bias of R, G, B (+-0 or finite with 2^-64 <= |x| <= 2^64; anything else: false, lastStatus, the values unchanged from
+  // the first refused one on).  Not to be called while another thread decodes into a CHW target with this decoder.
+  bool setCHWNormalisation(const float (&scale)[3], const float (&bias)[3]) {
+    for (int c = 0; c < 3; ++c) {
+      int s, b;
+      std::memcpy(&s, &scale[c], sizeof s);
+      std::memcpy(&b, &bias[c], sizeof b);
+      if (!setOption(BT709HIP_OPT_CHW_SCALE_R + c, s) || !setOption(BT709HIP_OPT_CHW_BIAS_R + c, b)) return false;
+    }
+    return true;
+  }
   // The encoder's twin is an option of the CONTEXT (bt709hip_context_set_option; BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT = 6): the same
   // two values select the planes bt709hip_encode[_batch] writes.  This mirror has no encoder; a caller of the C ABI sets it there.
   static constexpr int kEncodeChromaLayoutOption = BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT;

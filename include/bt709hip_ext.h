@@ -378,6 +378,46 @@ int bt709hip_decoder_get_option(const bt709hip_decoder *dec, int option, int *va
  *   - YV12 (V before U), and planar frames whose V plane is anywhere but (height/2) * cbcr_stride behind U. */
 #define BT709HIP_CHROMA_NV12 0
 #define BT709HIP_CHROMA_I420 1
+/* PLANAR CHW TARGETS.  Three further values of bt709hip_surface.format, accepted by bt709hip_decode and bt709hip_decode_batch alone,
+ * as OUTPUT alone -- every other entry point (the rescales, bt709hip_render_scaled, the encoder, bt709hip_unconvert, ring options,
+ * pools, shards, bt709hip_decoder_prepare_format) returns what it returns for any unknown format.  The decode writes the frame as
+ * the planar C x H x W tensor an inference pipeline takes, with no second pass and no scratch surface (definition: DESIGN.md 3.14).
+ * With e = 1, 2 or 4 bytes per element:
+ *   bgra     the base of plane 0, e-aligned;
+ *   stride   the row pitch of EVERY plane in bytes: >= width * e, a multiple of e, <= 2^32 - 1 (else BT709HIP_ERR_STRIDE);
+ *   plane c  starts at bgra + c * height * stride (a 64-bit product).  Planes R, G, B; a decoder created with has_alpha != 0
+ *            writes a fourth, A; an opaque decoder writes three and ignores bt709hip_decoder_set_alpha_fill.
+ * stride == width * e is a contiguous CHW tensor; an NCHW tensor is a batch of evenly spaced surfaces.  Nothing outside the
+ * width * e bytes of each plane row is written.  Per pixel, with s the word the same call writes into a BGRA8_SRGB target (same
+ * decoder, same frames, premultiplied as the frames hold it):
+ *   CHW_U8            plane c holds the byte s_c, the A plane s_A;
+ *   CHW_F16, CHW_F32  v = float(s_c) * (1.0f / 255.0f);  t = v * scale_c;  t = t + bias_c  -- binary32, every operation rounded
+ *                     on its own, no fused multiply-add; the element is t, or binary16(t) rounded to nearest even (overflow:
+ *                     +-inf).  The A plane: float(s_A) * (1.0f / 255.0f), no scale, no bias.
+ * scale_c, bias_c: BT709HIP_OPT_CHW_SCALE_R / _G / _B and BT709HIP_OPT_CHW_BIAS_R / _G / _B, whose int value is the BIT PATTERN of a
+ * binary32: defaults 1.0f and 0.0f; accepted: +-0 or a finite value with 2^-64 <= |x| <= 2^64 (no binary32 subnormal and no
+ * binary32 overflow can then arise); anything else BT709HIP_ERR_INVALID_ARG, the option keeps its value.  bt709hip_decoder_get_option
+ * returns the bits.  Decoders with and without an alpha channel take them; CHW_U8 ignores them.  A call reads each ONCE and they
+ * travel as kernel arguments (nothing is staged on the device: setting them and decoding both work inside a graph capture);
+ * setting one while a call that uses them is in flight on another thread is the caller's race -- that call may run with the old
+ * value of one and the new value of another.
+ * BT709HIP_OPT_CHROMA_LAYOUT = I420 is supported.  BT709HIP_OPT_COMPOSITE_OVER != OFF or BT709HIP_OPT_UNPREMULTIPLY = 1 with a CHW
+ * target: BT709HIP_ERR_UNSUPPORTED after the usual validation, nothing launched (the order of checks is RGBA16F's).  A batch whose
+ * surfaces differ in format: BT709HIP_ERR_INVALID_ARG.  The limits are every decode's (height / 2 <= 65535; 32 surfaces through
+ * the pointer table, any number evenly spaced).  On a coalescing decoder a call with a CHW target is never queued: the stream's
+ * queued frames are issued first, then the call launches on its own.  Fast kernels need the fast path's input alignment,
+ * width % 4 == 0 and plane 0 and the pitch 4 e-aligned; any other surface takes the general kernel.  bt709hip_last_kernel_name:
+ * "decode_nv12_quads_chw<u8,nt>", "decode_i420_quads_chw<f32,alpha>", "decode_nv12_blocks_chw<f16,quantiser>", ...;
+ * bt709hip_last_launch_info is filled as for the BGRA8 launch. */
+#define BT709HIP_FORMAT_CHW_U8 4  /* planes of bytes */
+#define BT709HIP_FORMAT_CHW_F16 5 /* planes of IEEE binary16 */
+#define BT709HIP_FORMAT_CHW_F32 6 /* planes of IEEE binary32 */
+#define BT709HIP_OPT_CHW_SCALE_R 14
+#define BT709HIP_OPT_CHW_SCALE_G 15
+#define BT709HIP_OPT_CHW_SCALE_B 16
+#define BT709HIP_OPT_CHW_BIAS_R 17
+#define BT709HIP_OPT_CHW_BIAS_G 18
+#define BT709HIP_OPT_CHW_BIAS_B 19
 
 /* COALESCING SUBMIT (extension, opt-in: bt709hip_decoder_set_option(dec, BT709HIP_OPT_COALESCE, n), n = 2..32).
  * The reference's cadence is one -decodeBT709: call per frame (MetalBT709Decoder.h:65-72, AAPLRenderer.m:914-957), each call

@@ -6,8 +6,8 @@ package is the host-side mirror of the reference's classes over it.  Nothing her
 imports, links or runs oracle/: that directory is test infrastructure.
 """
 from . import _capi
-from ._capi import FORMAT_BGRA8_ALPHA, FORMAT_BGRA8_SRGB, FORMAT_RGBA16F, Bt709Error, load as load_library
-from .decoder import (BGRATexture, BGRAToBT709Converter, CommandBuffer, CVPixelBuffer, FrameRing, FrameRingSet, FrameSharder, InFlightFramePool, MetalBT709Decoder,
+from ._capi import FORMAT_BGRA8_ALPHA, FORMAT_BGRA8_SRGB, FORMAT_CHW_F16, FORMAT_CHW_F32, FORMAT_CHW_U8, FORMAT_RGBA16F, Bt709Error, load as load_library
+from .decoder import (BGRATexture, BGRAToBT709Converter, CHWTexture, CommandBuffer, CVPixelBuffer, FrameRing, FrameRingSet, FrameSharder, InFlightFramePool, MetalBT709Decoder,
                       MetalBT709GammaApple, MetalBT709GammaITU709, MetalBT709GammaLinear, MetalBT709GammaSRGB,
                       MetalRenderContext, MetalScaleRenderContext, MTLRenderPassDescriptor, MTLPixelFormatBGRA8Unorm_sRGB, MTLPixelFormatRGBA16Float,
                       kCVImageBufferTransferFunction_ITU_R_709_2, kCVImageBufferTransferFunction_Linear,

@@ -48,6 +48,12 @@ OPT_CHROMA_LAYOUT = 11  # how the 1:1 decode reads the caller's colour frames: C
 CHROMA_NV12 = 0
 CHROMA_I420 = 1
 OPT_UNPREMULTIPLY = 12  # alpha decoders: 0 (default) the 1:1 decode writes premultiplied colour; 1: straight alpha
+# planar CHW targets of bt709hip_decode[_batch] (bt709hip_ext.h, PLANAR CHW TARGETS)
+FORMAT_CHW_U8 = 4
+FORMAT_CHW_F16 = 5
+FORMAT_CHW_F32 = 6
+OPT_CHW_SCALE_R, OPT_CHW_SCALE_G, OPT_CHW_SCALE_B = 14, 15, 16  # value: the bit pattern of a float32; default 1.0f
+OPT_CHW_BIAS_R, OPT_CHW_BIAS_G, OPT_CHW_BIAS_B = 17, 18, 19     # default 0.0f
 CTX_OPT_GRID_MULT = 1
 CTX_OPT_ENCODE_ROW_PAIRS = 2
 CTX_OPT_ENCODE_THREADS = 3

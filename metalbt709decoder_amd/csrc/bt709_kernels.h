@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
 
 #include "transfer_tables.h"
@@ -84,9 +85,21 @@ struct DecodeParams {
   // table_encode in 2^rep_enc_log2; a tile row is one tile of one row pair of one frame, tile_rows
   // of them in the launch, walked gridDim.x at a time; cursor_* = gridDim.x decomposed into
   // (tiles, row pairs, frames).  Filled by launch_decode_half_rep.
-  uint32_t rep_dec_log2, rep_enc_log2;
-  uint32_t tiles_x, tile_rows;
-  uint32_t cursor_tx, cursor_rp, cursor_f;
+  // The planar CHW targets of the 1:1 decode (bt709_chw.hip; BT709HIP_FORMAT_CHW_*) never meet that kernel, and
+  // their launch carries its element type and normalisation in the same seven words: a field of its own would move every field
+  // and implicit argument behind it, and with them the code of every kernel that takes this block.  chw_elem != kChwNone routes
+  // launch_decode to launch_decode_chw; frames[i].out is then the base of plane 0 and out_stride the row pitch of every plane.
+  union {
+    struct {
+      uint32_t rep_dec_log2, rep_enc_log2;
+      uint32_t tiles_x, tile_rows;
+      uint32_t cursor_tx, cursor_rp, cursor_f;
+    };
+    struct {
+      uint32_t chw_elem;                 // kChwNone / kChwU8 / kChwF16 / kChwF32
+      float chw_scale[3], chw_bias[3];  // R, G, B: BT709HIP_OPT_CHW_SCALE_* / _BIAS_* (bt709_chw_norm.h)
+    };
+  };
   // XCD-aware work map of the short-lived kernels (filled by the launchers): grid.x = 8 x tiles, x & 7 = the workgroup's
   // place in the round-robin over the XCDs, which owns frames [(x & 7) * frames_per_band, ...) of the launch
   uint32_t xcd_bands, frames_per_band;
@@ -115,7 +128,17 @@ struct DecodeParams {
   uint32_t straight_alpha;
   uint64_t v_offset;
 };
+// The CHW words ARE the persistent 2:1 kernel's seven, no more and no fewer, and the block is the size it was: a field that moved
+// would change every kernel that takes the block (profiles/r21_chw_isa.txt).  launch_decode reads chw_elem as its route, so a block
+// handed to it must have come from a zeroed one (gather_batch) -- launch_decode_half_rep fills rep_* in a private copy that never
+// reaches launch_decode.
+static_assert(offsetof(DecodeParams, chw_elem) == offsetof(DecodeParams, rep_dec_log2) && offsetof(DecodeParams, chw_scale) == offsetof(DecodeParams, rep_enc_log2) &&
+                  offsetof(DecodeParams, chw_bias) == offsetof(DecodeParams, cursor_tx) && offsetof(DecodeParams, chw_bias) + sizeof(float[3]) == offsetof(DecodeParams, xcd_bands),
+              "the CHW fields alias rep_dec_log2 .. cursor_f exactly");
+static_assert(sizeof(DecodeParams) == 1288 && offsetof(DecodeParams, v_offset) == 1280, "a field added to DecodeParams moves the implicit kernel arguments behind it: every decode kernel's code changes");
 enum : uint32_t { kChromaNV12 = 0, kChromaI420 = 1 };  // == BT709HIP_CHROMA_*
+enum : uint32_t { kChwNone = 0, kChwU8 = 1, kChwF16 = 2, kChwF32 = 3 };  // DecodeParams::chw_elem: BT709HIP_FORMAT_CHW_* - 3
+constexpr uint32_t chw_elem_bytes(uint32_t elem) { return elem == kChwF32 ? 4u : (elem == kChwF16 ? 2u : 1u); }
 // First template argument of the 1:1 decode kernels and the colour encoder's kernels that have a straight-alpha twin: the chroma
 // layout, plus kFormStraight for the twin (decode: R, G, B divided by A behind the arithmetic; encode: multiplied by A ahead of it)
 enum : uint32_t { kFormStraight = 2 };
@@ -145,6 +168,12 @@ constexpr uint32_t kHalfPlanLds = 40u * 1024u;
 const char *launch_decode_rgba16f(const DecodeParams &p, const HalfParams &hp, int frames, bool has_alpha,
                                   uint32_t in_align, uint32_t out_align, uint32_t compute_units, bool xcd_bands, hipStream_t stream);
 hipError_t prepare_rgba16f_kernels();  // bt709_rgba16f.hip
+
+// Pass 1 into planar CHW tensors (bt709_chw.hip): reached through launch_decode alone (chw_elem, above), which hands on what it
+// was handed.  Fast path (kVariantQuads): launch_decode's plan, tile for tile; general path: its grid-strided walk.
+const char *launch_decode_chw(const DecodeParams &p, int frames, int variant, bool has_alpha, bool quantiser, bool nontemporal,
+                              int xcd_bands, uint32_t grid_x, uint32_t block_threads, hipStream_t stream);
+hipError_t prepare_chw_kernels();  // called by prepare_kernels
 
 // Pass 2 alone (bt709_rescale_scaled.hip render_scaled): an intermediate surface -> a BGRA8 sRGB surface of any size.
 struct RenderParams {

@@ -295,6 +295,8 @@ const char *launch_decode_kernel(const DecodeParams &p, const dim3 &grid, const 
 
 const char *launch_decode(const DecodeParams &p_in, int frames, int variant, bool has_alpha, bool quantiser, bool nontemporal,
                           int xcd_bands, uint32_t grid_x, uint32_t block_threads, hipStream_t stream) {
+  // a planar CHW target (BT709HIP_FORMAT_CHW_*): the same plan over the kernels of bt709_chw.hip
+  if (p_in.chw_elem != kChwNone) return launch_decode_chw(p_in, frames, variant, has_alpha, quantiser, nontemporal, xcd_bands, grid_x, block_threads, stream);
   const bool quant = quantiser || has_alpha;  // the sRGB mode: arithmetic, no table
   const uint32_t over = has_alpha ? p_in.over_mode : kOverOff;  // BT709HIP_OPT_COMPOSITE_OVER: the *_over kernels and their two tables
   const size_t lds = over != kOverOff ? p_in.table_encode_bytes + kOverLinBytes : (quant ? 0 : p_in.table_unit_bytes);
@@ -330,7 +332,7 @@ hipError_t prepare_kernels() {
     const void *fns[] = {reinterpret_cast<const void *>(k.fn)};
     if (const hipError_t e = k.stages_table ? raise_lds_cap(fns, kRepLdsBytes) : hipSuccess) return e;
   }
-  return hipSuccess;
+  return prepare_chw_kernels();  // the CHW twins of the 1:1 kernels (bt709_chw.hip)
 }
 
 }  // namespace bt709

@@ -179,7 +179,12 @@ int coalescing_submit(bt709hip_decoder *dec, int layout, int count, const bt709h
   for (PendingQueue &c : dec->queues)
     if (c.stream == s) q = &c;
   const int n = dec->coalesce.load();  // read ONCE, behind the mutex: set_coalescing changes it under the same mutex
-  const bool eligible = n > 1 && wait_until_completed == 0 && count >= 1 && count < n && frames != nullptr && outs != nullptr;
+  // A planar CHW target is never queued (its rows are not 4-byte pixels: write_of / row_bytes_of below never see one); like any
+  // call that is not eligible it goes out behind what is queued, in stream order.  A batch with a CHW surface anywhere in it is
+  // decode_batch_now's to judge.
+  bool chw = false;
+  for (int i = 0; outs != nullptr && i < count; ++i) chw = chw || is_chw(outs[i].format);
+  const bool eligible = n > 1 && wait_until_completed == 0 && count >= 1 && count < n && frames != nullptr && outs != nullptr && !chw;
   if (!eligible) {  // in stream order: what is queued goes first
     if (q != nullptr)
       if (int rc = issue_queue(dec, *q)) return rc;

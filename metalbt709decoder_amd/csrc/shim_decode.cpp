@@ -3,6 +3,8 @@
 // batched, 2:1 and any-ratio forms of the same call.
 #include "shim_internal.h"
 
+#include "bt709_chw_norm.h"
+
 namespace bt709shim __attribute__((visibility("hidden"))) {
 
 // transfer tag the configured gamma insists on (MetalBT709Decoder.m:335-353)
@@ -17,7 +19,7 @@ int required_transfer(int gamma) {
 // Validation of one frame/alpha/surface triple in the reference's order
 // (MetalBT709Decoder.m:265-368), then the checks the texture wrappers imply.
 int validate(const bt709hip_decoder *dec, int layout, const bt709hip_frame *f, const bt709hip_frame *a,
-             const bt709hip_surface *o, int out_w, int out_h, int render_w, int render_h) {
+             const bt709hip_surface *o, int out_w, int out_h, int render_w, int render_h, bool chw_ok) {
   if (f == nullptr || o == nullptr) return BT709HIP_ERR_INVALID_ARG;
   if (f->width < 0 || f->height < 0) return BT709HIP_ERR_INVALID_ARG;
   if (o->width != out_w || o->height != out_h) return BT709HIP_ERR_SIZE_MISMATCH;          // .m:272-282
@@ -35,9 +37,9 @@ int validate(const bt709hip_decoder *dec, int layout, const bt709hip_frame *f, c
   const size_t chroma_row = static_cast<size_t>(layout == BT709HIP_CHROMA_I420 ? f->width / 2 : f->width);
   if (f->y_stride < static_cast<size_t>(f->width) || f->cbcr_stride < chroma_row) return BT709HIP_ERR_STRIDE;
   if (dec->has_alpha && a->y_stride < static_cast<size_t>(a->width)) return BT709HIP_ERR_STRIDE;
-  if ((o->format != BT709HIP_FORMAT_BGRA8_SRGB && o->format != BT709HIP_FORMAT_RGBA16F) || o->reserved != 0)
+  if ((o->format != BT709HIP_FORMAT_BGRA8_SRGB && o->format != BT709HIP_FORMAT_RGBA16F && !(chw_ok && is_chw(o->format))) || o->reserved != 0)
     return BT709HIP_ERR_INVALID_ARG;
-  const size_t px = o->format == BT709HIP_FORMAT_RGBA16F ? 8 : 4;  // bytes per output pixel
+  const size_t px = element_bytes(o->format);  // bytes per output pixel, or per element of a CHW plane's row
   if (o->stride < static_cast<size_t>(out_w) * px || (o->stride & (px - 1)) || !aligned(o->bgra, px))
     return BT709HIP_ERR_STRIDE;
   if (f->y_stride > 0xffffffffu || f->cbcr_stride > 0xffffffffu || o->stride > 0xffffffffu)
@@ -264,6 +266,11 @@ int bt709hip_decoder_set_option(bt709hip_decoder *dec, int option, int value) {
       if (!dec->has_alpha) return BT709HIP_ERR_UNSUPPORTED;  // nothing to divide by
       dec->unpremultiply = value;
       return BT709HIP_OK;
+    case BT709HIP_OPT_CHW_SCALE_R: case BT709HIP_OPT_CHW_SCALE_G: case BT709HIP_OPT_CHW_SCALE_B:
+    case BT709HIP_OPT_CHW_BIAS_R: case BT709HIP_OPT_CHW_BIAS_G: case BT709HIP_OPT_CHW_BIAS_B:  // a binary32's bits: +-0, or finite in [2^-64, 2^64]
+      if (!chw_norm_bits_valid(static_cast<uint32_t>(value))) return BT709HIP_ERR_INVALID_ARG;
+      dec->chw_norm[option - BT709HIP_OPT_CHW_SCALE_R] = static_cast<uint32_t>(value);
+      return BT709HIP_OK;
     default: return BT709HIP_ERR_INVALID_ARG;
   }
 }
@@ -283,6 +290,10 @@ int bt709hip_decoder_get_option(const bt709hip_decoder *dec, int option, int *va
     case BT709HIP_OPT_SCALED_OVER: *value = dec->scaled_over; return BT709HIP_OK;
     case BT709HIP_OPT_CHROMA_LAYOUT: *value = dec->chroma_layout; return BT709HIP_OK;
     case BT709HIP_OPT_UNPREMULTIPLY: *value = dec->unpremultiply; return BT709HIP_OK;
+    case BT709HIP_OPT_CHW_SCALE_R: case BT709HIP_OPT_CHW_SCALE_G: case BT709HIP_OPT_CHW_SCALE_B:
+    case BT709HIP_OPT_CHW_BIAS_R: case BT709HIP_OPT_CHW_BIAS_G: case BT709HIP_OPT_CHW_BIAS_B:
+      *value = static_cast<int>(dec->chw_norm[option - BT709HIP_OPT_CHW_SCALE_R].load());
+      return BT709HIP_OK;
     default: return BT709HIP_ERR_INVALID_ARG;
   }
 }
@@ -378,9 +389,10 @@ int gather_batch(bt709hip_decoder *dec, int count, const bt709hip_frame *frames,
     const int want_w = shape == OutShape::kSame ? f.width : (shape == OutShape::kHalf ? f.width / 2 : o.width);
     const int want_h = shape == OutShape::kSame ? f.height : (shape == OutShape::kHalf ? f.height / 2 : o.height);
     if (shape == OutShape::kAny && (o.width < 0 || o.height < 0)) return BT709HIP_ERR_INVALID_ARG;
-    if (int rc = validate(dec, layout, &f, a, &o, want_w, want_h, o.width, o.height)) return rc;
-    if (o.format != BT709HIP_FORMAT_BGRA8_SRGB && (shape != OutShape::kSame || o.format != BT709HIP_FORMAT_RGBA16F))
-      return BT709HIP_ERR_UNSUPPORTED;
+    if (int rc = validate(dec, layout, &f, a, &o, want_w, want_h, o.width, o.height, shape == OutShape::kSame)) return rc;
+    if (o.format != BT709HIP_FORMAT_BGRA8_SRGB && shape != OutShape::kSame) return BT709HIP_ERR_UNSUPPORTED;
+    // a planar CHW surface among surfaces of another format (CHW or not): not a batch of one kind
+    if ((is_chw(o.format) || is_chw(o0.format)) && o.format != o0.format) return BT709HIP_ERR_INVALID_ARG;
     if (f.width != f0.width || f.height != f0.height || f.y_stride != f0.y_stride || f.cbcr_stride != f0.cbcr_stride ||
         o.stride != o0.stride || o.width != o0.width || o.height != o0.height || o.format != o0.format)
       return BT709HIP_ERR_SIZE_MISMATCH;
@@ -428,6 +440,14 @@ int gather_batch(bt709hip_decoder *dec, int count, const bt709hip_frame *frames,
     p->chroma_layout = kChromaI420;
     p->v_offset = static_cast<uint64_t>(f0.height / 2) * f0.cbcr_stride;
   }
+  if (is_chw(o0.format)) {  // the element type and the normalisation, each option read once
+    p->chw_elem = static_cast<uint32_t>(o0.format - BT709HIP_FORMAT_CHW_U8) + kChwU8;
+    for (int c = 0; c < 3; ++c) {
+      const uint32_t scale = dec->chw_norm[c], bias = dec->chw_norm[3 + c];
+      std::memcpy(&p->chw_scale[c], &scale, sizeof scale);
+      std::memcpy(&p->chw_bias[c], &bias, sizeof bias);
+    }
+  }
   return BT709HIP_OK;
 }
 
@@ -445,11 +465,12 @@ int decode_batch_now(bt709hip_decoder *dec, int layout, int count, const bt709hi
   BatchInfo info;
   if (int rc = gather_batch(dec, count, frames, alphas, outs, OutShape::kSame, layout, stream, &p, &info)) return rc;
   const int over = dec->composite_over;  // BT709HIP_OPT_COMPOSITE_OVER: into BGRA8_SRGB targets only
-  if (over != BT709HIP_OVER_OFF && info.format == BT709HIP_FORMAT_RGBA16F) return BT709HIP_ERR_UNSUPPORTED;
-  if (layout == BT709HIP_CHROMA_I420 && info.format == BT709HIP_FORMAT_RGBA16F) return BT709HIP_ERR_UNSUPPORTED;  // planar chroma: BGRA8_SRGB targets only
+  const bool chw = is_chw(info.format);  // planar CHW targets: neither blended nor divided, in RGBA16F's order of checks
+  if (over != BT709HIP_OVER_OFF && (info.format == BT709HIP_FORMAT_RGBA16F || chw)) return BT709HIP_ERR_UNSUPPORTED;
+  if (layout == BT709HIP_CHROMA_I420 && info.format == BT709HIP_FORMAT_RGBA16F) return BT709HIP_ERR_UNSUPPORTED;  // planar chroma: BGRA8_SRGB and CHW targets only
   // BT709HIP_OPT_UNPREMULTIPLY: straight alpha into BGRA8_SRGB targets, and never blended (a blend needs the premultiplied source)
   const bool straight = dec->unpremultiply != 0;
-  if (straight && (info.format == BT709HIP_FORMAT_RGBA16F || over != BT709HIP_OVER_OFF)) return BT709HIP_ERR_UNSUPPORTED;
+  if (straight && (info.format == BT709HIP_FORMAT_RGBA16F || chw || over != BT709HIP_OVER_OFF)) return BT709HIP_ERR_UNSUPPORTED;
   if (p.width == 0) return BT709HIP_OK;
   p.straight_alpha = straight ? 1u : 0u;
   hipStream_t s = pick(dec->ctx, stream);
@@ -465,7 +486,10 @@ int decode_batch_now(bt709hip_decoder *dec, int layout, int count, const bt709hi
   // Fast path: one short-lived workgroup per tile of a row pair, dispatched in address order
   // (see the kernel file's header).  General path keeps the grid-strided shape.
   // Planar chroma: the luma and alpha planes as NV12's, the chroma folded on its own -- a quad's chroma is a 2-byte load per plane
-  const bool fast = (p.width % 4) == 0 && info.in_align >= 4 && info.out_align >= 16 && (layout != BT709HIP_CHROMA_I420 || info.chroma_align >= 2);
+  // A CHW target (p.chw_elem set by gather_batch; launch_decode hands the launch to the kernels of bt709_chw.hip): a quad's store is
+  // 4 elements of a plane's row, so plane 0 and the pitch -- and with them every plane -- are 4 e-aligned on the fast path
+  const uint32_t out_need = chw ? 4u * static_cast<uint32_t>(element_bytes(info.format)) : 16u;
+  const bool fast = (p.width % 4) == 0 && info.in_align >= 4 && info.out_align >= out_need && (layout != BT709HIP_CHROMA_I420 || info.chroma_align >= 2);
   const uint32_t gx = fast ? quads_tiles(p.width) : grid_x_for(dec->ctx, p.height / 2, count);
   const uint32_t threads = quads_block_threads(p.width);
   last_launch_shape() = LaunchShape{};
@@ -565,7 +589,7 @@ int bt709hip_decode(bt709hip_decoder *dec, const bt709hip_frame *frame, const bt
   // render size is a property of this call only; check it here, the rest in the batch path
   const int layout = dec->chroma_layout;  // read once: the call runs with what it read
   if (int rc = validate(dec, layout, frame, alpha, out, frame ? frame->width : 0, frame ? frame->height : 0, render_width,
-                        render_height))
+                        render_height, true))
     return rc;
   return decode_batch_layout(dec, layout, 1, frame, alpha, out, stream, wait_until_completed);
 }

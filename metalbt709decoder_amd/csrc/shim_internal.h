@@ -95,6 +95,8 @@ struct bt709hip_decoder {
   std::atomic<int> scaled_over{BT709HIP_OVER_OFF};     // BT709HIP_OPT_SCALED_OVER: the same three forms, read by the rescale paths alone
   std::atomic<int> chroma_layout{BT709HIP_CHROMA_NV12};  // BT709HIP_OPT_CHROMA_LAYOUT: how bt709hip_decode[_batch] read the CALLER's colour frames
   std::atomic<int> unpremultiply{0};                     // BT709HIP_OPT_UNPREMULTIPLY: the 1:1 decode of an alpha decoder writes straight alpha
+  // BT709HIP_OPT_CHW_SCALE_R, _G, _B, BT709HIP_OPT_CHW_BIAS_R, _G, _B: binary32 bit patterns (1.0f, 0.0f), read by decodes into CHW targets
+  std::atomic<uint32_t> chw_norm[6] = {{0x3f800000u}, {0x3f800000u}, {0x3f800000u}, {0u}, {0u}, {0u}};
   std::mutex queue_mutex;   // guards queues
   std::vector<PendingQueue> queues;  // one per stream that has (had) queued frames
   std::mutex setup_mutex;
@@ -175,8 +177,19 @@ int finish_launch(hipStream_t s, int wait_until_completed);
 int required_transfer(int gamma);
 // `layout` (here and below): BT709HIP_CHROMA_* of the colour frames.  The public entry points pass the decoder's option; the
 // objects that allocate their own (NV12) frames -- ring, ring set, pool, shard -- pass BT709HIP_CHROMA_NV12 whatever it holds.
+// `chw_ok`: the call is a 1:1 decode, the one place a planar CHW surface (BT709HIP_FORMAT_CHW_*) is a format at all
 int validate(const bt709hip_decoder *dec, int layout, const bt709hip_frame *f, const bt709hip_frame *a, const bt709hip_surface *o, int out_w,
-             int out_h, int render_w, int render_h);
+             int out_h, int render_w, int render_h, bool chw_ok = false);
+inline bool is_chw(int format) { return format >= BT709HIP_FORMAT_CHW_U8 && format <= BT709HIP_FORMAT_CHW_F32; }
+// bytes per element of a surface's rows: a pixel of the interleaved formats, a plane's element of the CHW ones
+inline size_t element_bytes(int format) {
+  switch (format) {
+    case BT709HIP_FORMAT_RGBA16F: return 8;
+    case BT709HIP_FORMAT_CHW_U8: return 1;
+    case BT709HIP_FORMAT_CHW_F16: return 2;
+    default: return 4;  // BGRA8_SRGB, CHW_F32
+  }
+}
 int ensure_setup(bt709hip_decoder *dec, void *stream);
 int ensure_half_table(bt709hip_decoder *dec, void *stream);
 int ensure_over_table(bt709hip_decoder *dec, void *stream);

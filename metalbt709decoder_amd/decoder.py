@@ -421,6 +421,61 @@ class BGRATexture:
         return Surface(self.ptr, self.stride, self.width, self.height, _FORMAT_OF[self.pixelFormat], 0)
 
 
+_CHW_FORMAT_OF = {"uint8": _capi.FORMAT_CHW_U8, "float16": _capi.FORMAT_CHW_F16, "float32": _capi.FORMAT_CHW_F32}
+
+
+class CHWTexture:
+    """Planar C x H x W decode target in device memory (bt709hip_ext.h, PLANAR CHW TARGETS): `planes` planes --
+    R, G, B, and A from a decoder with an alpha channel (4) -- of `dtype` elements ("uint8", "float16" or "float32"), every
+    plane's rows `stride` bytes apart and plane c starting c * height * stride bytes behind plane 0.  decodeBT709 and
+    decodeBT709Batch take one wherever they take a BGRATexture; nothing else does.  The default stride is width * itemsize: a
+    contiguous tensor."""
+
+    def __init__(self, ctx, width, height, dtype, planes=3, stride=None, ptr=None):
+        name = np.dtype(dtype).name if not isinstance(dtype, str) else dtype
+        if name not in _CHW_FORMAT_OF:
+            raise ValueError("CHWTexture: dtype uint8, float16 or float32, not %r" % (dtype,))
+        if planes not in (3, 4):
+            raise ValueError("CHWTexture: 3 planes (R, G, B) or 4 (R, G, B, A)")
+        self.ctx, self.width, self.height, self.planes = ctx, int(width), int(height), int(planes)
+        self.dtype = np.dtype(name)
+        self.itemsize = self.dtype.itemsize
+        self.stride = int(stride) if stride else self.width * self.itemsize
+        if self.stride < self.width * self.itemsize or self.stride % self.itemsize:
+            raise ValueError("CHWTexture: stride %d is below a row's %d bytes or no multiple of the element's %d"
+                             % (self.stride, self.width * self.itemsize, self.itemsize))
+        self.planeBytes = self.stride * self.height
+        self._buf = None
+        if ptr is None:
+            self._buf = DeviceBuffer(ctx, max(self.planeBytes * self.planes, 16))
+            ptr = self._buf.ptr
+        self.ptr = ptr
+
+    def surface(self):
+        return Surface(self.ptr, self.stride, self.width, self.height, _CHW_FORMAT_OF[self.dtype.name], 0)
+
+    @staticmethod
+    def fromTensor(ctx, tensor):
+        """Wraps a torch tensor on the context's device WITHOUT a copy: a (C, H, W) tensor, or ONE image of an NCHW tensor (index
+        it: CHWTexture.fromTensor(ctx, batch[i]); the images of a contiguous batch are evenly spaced surfaces, one launch of
+        decodeBT709Batch).  C is 3 or 4; dtype uint8, float16 or float32; the element stride along W must be 1 and the plane
+        stride H times the row stride (what the surface can describe).  The tensor owns the memory and must outlive the
+        decodes; torch is imported here and nowhere else in the package."""
+        import torch
+        names = {torch.uint8: "uint8", torch.float16: "float16", torch.float32: "float32"}
+        if tensor.dtype not in names:
+            raise ValueError("CHWTexture.fromTensor: dtype uint8, float16 or float32, not %s" % tensor.dtype)
+        if tensor.dim() != 3 or tensor.shape[0] not in (3, 4):
+            raise ValueError("CHWTexture.fromTensor: a (C, H, W) tensor with C = 3 or 4, not %s" % (tuple(tensor.shape),))
+        if not tensor.is_cuda or (ctx is not None and tensor.device.index != int(ctx.device)):
+            raise ValueError("CHWTexture.fromTensor: the tensor is on %s, not on the context's device" % (tensor.device,))
+        planes, h, w = (int(v) for v in tensor.shape)
+        sc, sh, sw = (int(v) for v in tensor.stride())
+        if (w > 1 and sw != 1) or (planes > 1 and h > 0 and sc != h * sh) or sh < w:
+            raise ValueError("CHWTexture.fromTensor: strides %s: W must be dense and a plane H rows of one pitch" % ((sc, sh, sw),))
+        return CHWTexture(ctx, w, h, names[tensor.dtype], planes=planes, stride=sh * tensor.element_size(), ptr=tensor.data_ptr())
+
+
 class MTLRenderPassDescriptor:
     """As far as the decoder reads it: colorAttachments[0].texture, the view's drawable (a BGRATexture).  The
     reference renders straight into it when bgraSRGBTexture is nil (MetalBT709Decoder.m:272-281, 462-466;
@@ -701,6 +756,25 @@ class MetalRenderContext:
                                                    out.shape[1], tex.height, stream), "download")
             self._sync(commandBuffer)
         return out.view(np.uint32).reshape(tex.height, tex.width)
+
+    def makeCHWTexture(self, size, dtype, planes=3, stride=None):
+        """A zeroed planar decode target (CHWTexture): `planes` planes of size = (W, H), `dtype` "uint8", "float16" or "float32"."""
+        w, h = size
+        tex = CHWTexture(self, w, h, dtype, planes=planes, stride=stride)
+        _capi.check(self.lib.bt709hip_memset(self.handle, tex.ptr, 0, max(tex.planeBytes * tex.planes, 1), None))
+        self._sync(None)
+        return tex
+
+    def getCHWTexturePixels(self, tex, commandBuffer=None):
+        """Read-back of a CHWTexture as a (planes, H, W) array of its dtype (the row padding of a pitched texture is left out)."""
+        row = tex.width * tex.itemsize
+        out = np.empty((tex.planes * tex.height, row), dtype=np.uint8)
+        if out.size:
+            stream = commandBuffer.stream if commandBuffer else None
+            _capi.check(self.lib.bt709hip_download(self.handle, out.ctypes.data, row, tex.ptr, tex.stride, row, tex.planes * tex.height,
+                                                   stream), "download")
+            self._sync(commandBuffer)
+        return out.view(tex.dtype).reshape(tex.planes, tex.height, tex.width)
 
     # -- internals
     def _upload(self, dptr, dpitch, arr, commandBuffer, wait=True):
@@ -1188,6 +1262,37 @@ class MetalBT709Decoder:
         self._options[_capi.OPT_UNPREMULTIPLY] = value
         self.lastStatus = _capi.OK
         return True
+
+    def setCHWNormalisation(self, scale=(1.0, 1.0, 1.0), bias=(0.0, 0.0, 0.0)):
+        """Per-channel (R, G, B) scale and bias of the float CHW targets (_capi.OPT_CHW_SCALE_* / OPT_CHW_BIAS_*): an element is
+        float32(byte) * float32(1/255) * scale + bias, three float32 operations each rounded on its own.  The
+        values are taken as float32 and must be +-0 or finite with 2^-64 <= |x| <= 2^64 (ValueError otherwise, nothing changed).
+        CHW_U8 targets and the alpha plane ignore them.  Returns True, or False with lastStatus set."""
+        values = np.array(list(scale) + list(bias), dtype=np.float32)
+        if values.shape != (6,):
+            raise ValueError("setCHWNormalisation: three scales and three biases")
+        mag = values.view(np.uint32) & 0x7FFFFFFF
+        if not np.all((mag == 0) | ((mag >= 0x1F800000) & (mag <= 0x5F800000))):
+            raise ValueError("setCHWNormalisation: every value +-0 or finite with 2^-64 <= |x| <= 2^64, got %s" % (values,))
+        bits = values.view(np.int32)
+        for i in range(6):
+            opt = _capi.OPT_CHW_SCALE_R + i
+            if self._handle:
+                rc = self.metalRenderContext.lib.bt709hip_decoder_set_option(self._handle, opt, int(bits[i]))
+                if rc != _capi.OK:
+                    return self._fail(rc, "setCHWNormalisation")
+            self._options[opt] = int(bits[i])
+        self.lastStatus = _capi.OK
+        return True
+
+    def setCHWMeanStd(self, mean, std):
+        """The usual (x - mean) / std as setCHWNormalisation's scale and bias, computed in float32 exactly like this:
+        scale = float32(1) / float32(std) and bias = float32(-mean) / float32(std), one float32 division each.  An element is then
+        float32(byte) * float32(1/255) * scale + bias -- close to, but not bit for bit, a framework's (x / 255 - mean) / std."""
+        mean, std = np.asarray(mean, dtype=np.float32), np.asarray(std, dtype=np.float32)
+        with np.errstate(divide="ignore", invalid="ignore"):  # a zero std gives inf or NaN: setCHWNormalisation's ValueError
+            scale, bias = np.float32(1.0) / std, -mean / std
+        return self.setCHWNormalisation(scale, bias)
 
     def _over_get(self, option):
         v = self._options.get(option, _capi.OVER_OFF)

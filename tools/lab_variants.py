@@ -863,13 +863,13 @@ GATES += [
 #endif
 """),
     ("shim_decode.cpp",
-     """  const bool fast = (p.width % 4) == 0 && info.in_align >= 4 && info.out_align >= 16 && (layout != BT709HIP_CHROMA_I420 || info.chroma_align >= 2);
+     """  const bool fast = (p.width % 4) == 0 && info.in_align >= 4 && info.out_align >= out_need && (layout != BT709HIP_CHROMA_I420 || info.chroma_align >= 2);
 """,
      """#if defined(BT709_LAB_I420_PAIRED)  // the paired fetch is in bounds for these frames only; the others take the general kernel
-  const bool fast = (p.width % 4) == 0 && info.in_align >= 4 && info.out_align >= 16 &&
+  const bool fast = (p.width % 4) == 0 && info.in_align >= 4 && info.out_align >= out_need &&
                     (layout != BT709HIP_CHROMA_I420 || ((p.width % 8) == 0 && info.chroma_align >= 4 && p.v_offset + p.width / 2 <= 0xffffffffull));
 #else
-  const bool fast = (p.width % 4) == 0 && info.in_align >= 4 && info.out_align >= 16 && (layout != BT709HIP_CHROMA_I420 || info.chroma_align >= 2);
+  const bool fast = (p.width % 4) == 0 && info.in_align >= 4 && info.out_align >= out_need && (layout != BT709HIP_CHROMA_I420 || info.chroma_align >= 2);
 #endif
 """),
 ]
