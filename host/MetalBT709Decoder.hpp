@@ -89,6 +89,24 @@ class MetalRenderContext {
   // BGRAToBT709Converter::convertHalfIntoCoreVideoBuffersWithAlpha below sets both around its call and puts 0 back.
   static constexpr int kEncodeHalfWithAlphaOption = BT709HIP_CTX_OPT_ENCODE_HALF_WITH_ALPHA;
   bool setEncodeHalfWithAlpha(bool on) { return (lastStatus_ = bt709hip_context_set_option(ctx_, kEncodeHalfWithAlphaOption, on ? 1 : 0)) == BT709HIP_OK; }
+  // bt709hip_encode[_batch] on this context accepts planar CHW surfaces (BT709HIP_FORMAT_CHW_U8 / _F16 / _F32: a model's output
+  // tensor) and encodes them in one launch (include/bt709hip_ext.h PLANAR CHW INPUT).  false (the default): such
+  // input is an unknown format.  BGRAToBT709Converter::convertCHWIntoCoreVideoBuffers below sets it around its call and puts 0 back.
+  static constexpr int kEncodeCHWInputOption = BT709HIP_CTX_OPT_ENCODE_CHW_INPUT;
+  bool setEncodeCHWInput(bool on) { return (lastStatus_ = bt709hip_context_set_option(ctx_, kEncodeCHWInputOption, on ? 1 : 0)) == BT709HIP_OK; }
+  // Per-channel (R, G, B) scale and bias of float CHW input: an element t becomes the byte round(255 * sat(t * scale + bias)), the
+  // product and the sum binary32 operations each rounded on its own.  Values outside +-0 / 2^-64 <= |x| <= 2^64 are refused.
+  bool setEncodeCHWNormalisation(const float scale[3], const float bias[3]) {
+    for (int i = 0; i < 6; ++i) {
+      const float v = i < 3 ? scale[i] : bias[i - 3];
+      int32_t bits;
+      std::memcpy(&bits, &v, sizeof bits);
+      if ((lastStatus_ = bt709hip_context_set_option(ctx_, BT709HIP_CTX_OPT_ENCODE_CHW_SCALE_R + i, bits)) != BT709HIP_OK) return false;
+    }
+    return true;
+  }
+  // The inverse of MetalBT709Decoder::setCHWMeanStd: a tensor holding (x - mean) / std is encoded as x; scale = std, bias = mean
+  bool setEncodeCHWMeanStd(const float mean[3], const float std[3]) { return setEncodeCHWNormalisation(std, mean); }
 
  private:
   bt709hip_context *ctx_ = nullptr;
@@ -275,6 +293,22 @@ struct BGRAToBT709Converter {
     mrc.setEncodeHalfWithAlpha(false);
     mrc.setEncodeHalfInput(false);
     if (rc == BT709HIP_OK) alpha.setAttachments(BT709HIP_MATRIX_ITU_R_709_2, BT709HIP_TRANSFER_LINEAR);
+    return rc == BT709HIP_OK;
+  }
+  // `count` same-sized planar tensors (surfaces of format BT709HIP_FORMAT_CHW_U8 / _F16 / _F32: bgra the base of plane R, stride the
+  // pitch of every plane, G and B height * stride bytes on each; the images of a contiguous NCHW tensor are evenly spaced surfaces)
+  // into their frames, in ONE launch with no de-normalise / round / permute pass.  Float elements go through the
+  // context's setEncodeCHWNormalisation values; the frame is the one the BGRA8 picture of the resulting bytes encodes to.
+  static bool convertCHWIntoCoreVideoBuffers(MetalRenderContext &mrc, const bt709hip_surface *tensors, CVPixelBuffer *const *outs, int count,
+                                             int inputGamma, int outputGamma) {
+    std::vector<bt709hip_frame> frames;
+    for (int i = 0; i < count; ++i) {
+      if (tensors[i].format < BT709HIP_FORMAT_CHW_U8 || tensors[i].format > BT709HIP_FORMAT_CHW_F32) return false;
+      frames.push_back(*outs[i]->frame());
+    }
+    int rc = mrc.setEncodeCHWInput(true) ? BT709HIP_OK : mrc.lastStatus();
+    if (rc == BT709HIP_OK) rc = bt709hip_encode_batch(mrc.handle(), count, tensors, frames.data(), inputGamma, outputGamma, nullptr, 1);
+    mrc.setEncodeCHWInput(false);
     return rc == BT709HIP_OK;
   }
 };

@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -395,6 +396,38 @@ int main(int argc, char **argv) {
       std::fprintf(stderr, "RGBA16Float texture into a frame: not the saturated picture's planes\n");
       ++failures;
     }
+  }
+  // a planar float tensor back into a frame (BT709HIP_CTX_OPT_ENCODE_CHW_INPUT): a white block of 1, 2, +inf and 1 and a black one of
+  // 0, -1, NaN and -0 in each of R, G, B under scale 1, bias 0, then the same picture as (t - 0.5) / 0.25 under (std, mean) =
+  // (0.25, 0.5); refused while the option is off
+  {
+    const float inf = std::numeric_limits<float>::infinity(), nan = std::numeric_limits<float>::quiet_NaN();
+    const float rows[2][4] = {{1.0f, 2.0f, 0.0f, -1.0f}, {inf, 1.0f, nan, -0.0f}};
+    float planes[3][2][4], normalised[3][2][4];
+    for (int c = 0; c < 3; ++c)
+      for (int r = 0; r < 2; ++r)
+        for (int x = 0; x < 4; ++x) planes[c][r][x] = rows[r][x], normalised[c][r][x] = x < 2 ? 2.0f : -2.0f;
+    void *tensor = nullptr;
+    CVPixelBuffer out(metalRenderContext, 4, 2), out2(metalRenderContext, 4, 2);
+    CVPixelBuffer *outs[1] = {&out}, *outs2[1] = {&out2};
+    bool ok = bt709hip_malloc(metalRenderContext.handle(), sizeof planes, &tensor) == BT709HIP_OK;
+    const bt709hip_surface surface = {tensor, 16, 4, 2, BT709HIP_FORMAT_CHW_F32, 0};
+    ok = ok && bt709hip_upload(metalRenderContext.handle(), tensor, 16, planes, 16, 16, 6, nullptr) == BT709HIP_OK && metalRenderContext.waitUntilCompleted(nullptr);
+    ok = ok && bt709hip_encode(metalRenderContext.handle(), &surface, out.frame(), BT709HIP_GAMMA_SRGB, BT709HIP_GAMMA_APPLE, nullptr, 1) == BT709HIP_ERR_UNSUPPORTED;
+    ok = ok && BGRAToBT709Converter::convertCHWIntoCoreVideoBuffers(metalRenderContext, &surface, outs, 1, BT709HIP_GAMMA_SRGB, BT709HIP_GAMMA_APPLE);
+    const float mean[3] = {0.5f, 0.5f, 0.5f}, std[3] = {0.25f, 0.25f, 0.25f}, one[3] = {1.0f, 1.0f, 1.0f}, zero[3] = {0.0f, 0.0f, 0.0f};
+    ok = ok && bt709hip_upload(metalRenderContext.handle(), tensor, 16, normalised, 16, 16, 6, nullptr) == BT709HIP_OK && metalRenderContext.waitUntilCompleted(nullptr);
+    ok = ok && metalRenderContext.setEncodeCHWMeanStd(mean, std);
+    ok = ok && BGRAToBT709Converter::convertCHWIntoCoreVideoBuffers(metalRenderContext, &surface, outs2, 1, BT709HIP_GAMMA_SRGB, BT709HIP_GAMMA_APPLE);
+    ok = metalRenderContext.setEncodeCHWNormalisation(one, zero) && ok;
+    std::vector<uint8_t> y, c, y2, c2;
+    ok = ok && out.downloadPlanes(y, c) && out2.downloadPlanes(y2, c2);
+    const std::vector<uint8_t> wantY = {235, 235, 16, 16, 235, 235, 16, 16}, wantC = {128, 128, 128, 128};
+    if (!ok || y != wantY || c != wantC || y2 != wantY || c2 != wantC) {
+      std::fprintf(stderr, "planar float tensor into a frame: not the saturated picture's planes\n");
+      ++failures;
+    }
+    bt709hip_free(metalRenderContext.handle(), tensor);
   }
   std::printf("%s: %d vectors, %d failures\n", failures ? "FAIL" : "ok", (argc - 1) / 6, failures);
   return failures ? 1 : 0;

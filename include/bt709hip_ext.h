@@ -43,7 +43,8 @@ int bt709hip_context_info(const bt709hip_context *ctx, bt709hip_device_info *inf
 /* Launch-shape knobs of a context (tuning and test hooks; no reference twin).  Values are
  * clamped to their valid range; 0 restores the default.  BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT,
  * BT709HIP_CTX_OPT_ENCODE_PREMULTIPLY, BT709HIP_CTX_OPT_ENCODE_CONVERT, BT709HIP_CTX_OPT_ENCODE_WITH_ALPHA,
- * BT709HIP_CTX_OPT_ENCODE_HALF_INPUT and BT709HIP_CTX_OPT_ENCODE_HALF_WITH_ALPHA are no knobs and are NOT clamped: see below. */
+ * BT709HIP_CTX_OPT_ENCODE_HALF_INPUT, BT709HIP_CTX_OPT_ENCODE_HALF_WITH_ALPHA, BT709HIP_CTX_OPT_ENCODE_CHW_INPUT and the six
+ * BT709HIP_CTX_OPT_ENCODE_CHW_SCALE_* / _BIAS_* are no knobs and are NOT clamped: see below. */
 typedef enum {
   BT709HIP_CTX_OPT_GRID_MULT = 1,       /* general (unaligned-layout) kernels: workgroups per launch = CUs x 8 x this; default 2 */
   BT709HIP_CTX_OPT_ENCODE_ROW_PAIRS = 2,/* encoder: consecutive row pairs per workgroup; default 0 = sized per launch */
@@ -55,7 +56,14 @@ typedef enum {
   BT709HIP_CTX_OPT_ENCODE_CONVERT = BT709HIP_CTX_OPT_ENCODE_PREMULTIPLY + 2, /* (ten; nine is no option) BT709HIP_CONVERT_OFF (default), _PACKED444 or _POINT420: bt709hip_encode[_batch] is the reference's per-pixel +convert:; any other value is refused */
   BT709HIP_CTX_OPT_ENCODE_WITH_ALPHA = BT709HIP_CTX_OPT_ENCODE_CONVERT + 2, /* (twelve; eleven is no option) 0 (default): one frame per picture; 1: bt709hip_encode[_batch] of BGRA8_SRGB input writes the picture's alpha frame as well, `out` holds TWO frames per picture; any other value is refused */
   BT709HIP_CTX_OPT_ENCODE_HALF_INPUT = BT709HIP_CTX_OPT_ENCODE_WITH_ALPHA + 2, /* (fourteen; thirteen is no option) 0 (default): RGBA16F input to bt709hip_encode[_batch] is BT709HIP_ERR_UNSUPPORTED; 1: it is encoded as linear light; any other value is refused */
-  BT709HIP_CTX_OPT_ENCODE_HALF_WITH_ALPHA = BT709HIP_CTX_OPT_ENCODE_HALF_INPUT + 2 /* (sixteen; fifteen and seventeen are no options) 0 (default): one frame per picture; 1: bt709hip_encode[_batch] of RGBA16F input (under _ENCODE_HALF_INPUT = 1) writes the surface's alpha frame as well, `out` holds TWO frames per picture; any other value is refused */
+  BT709HIP_CTX_OPT_ENCODE_HALF_WITH_ALPHA = BT709HIP_CTX_OPT_ENCODE_HALF_INPUT + 2, /* (sixteen; fifteen and seventeen are no options) 0 (default): one frame per picture; 1: bt709hip_encode[_batch] of RGBA16F input (under _ENCODE_HALF_INPUT = 1) writes the surface's alpha frame as well, `out` holds TWO frames per picture; any other value is refused */
+  BT709HIP_CTX_OPT_ENCODE_CHW_INPUT = BT709HIP_CTX_OPT_ENCODE_HALF_WITH_ALPHA + 2, /* (eighteen; seventeen and nineteen are no options) 0 (default): planar CHW input to bt709hip_encode[_batch] is what any unknown format is; 1: CHW_U8 / _F16 / _F32 surfaces are encoded; any other value is refused */
+  BT709HIP_CTX_OPT_ENCODE_CHW_SCALE_R = BT709HIP_CTX_OPT_ENCODE_CHW_INPUT + 2, /* (twenty) twenty to twenty-five: the BIT PATTERN of a binary32 each -- scale (default 1.0f) and bias (default 0.0f) of the R, G and B plane of float CHW input; +-0 or finite with 2^-64 <= |x| <= 2^64, anything else is refused */
+  BT709HIP_CTX_OPT_ENCODE_CHW_SCALE_G = BT709HIP_CTX_OPT_ENCODE_CHW_SCALE_R + 1,
+  BT709HIP_CTX_OPT_ENCODE_CHW_SCALE_B = BT709HIP_CTX_OPT_ENCODE_CHW_SCALE_G + 1,
+  BT709HIP_CTX_OPT_ENCODE_CHW_BIAS_R = BT709HIP_CTX_OPT_ENCODE_CHW_SCALE_B + 1,
+  BT709HIP_CTX_OPT_ENCODE_CHW_BIAS_G = BT709HIP_CTX_OPT_ENCODE_CHW_BIAS_R + 1,
+  BT709HIP_CTX_OPT_ENCODE_CHW_BIAS_B = BT709HIP_CTX_OPT_ENCODE_CHW_BIAS_G + 1 /* (twenty-five) */
 } bt709hip_context_option;
 #define BT709HIP_CONVERT_OFF 0       /* bt709hip_encode[_batch] is the subsampling encoder (+convertIntoCoreVideoBuffer:) */
 #define BT709HIP_CONVERT_PACKED444 1 /* +convert: -- one 32-bit word (Cr<<16)|(Cb<<8)|Y per pixel */
@@ -378,9 +386,10 @@ int bt709hip_decoder_get_option(const bt709hip_decoder *dec, int option, int *va
  *   - YV12 (V before U), and planar frames whose V plane is anywhere but (height/2) * cbcr_stride behind U. */
 #define BT709HIP_CHROMA_NV12 0
 #define BT709HIP_CHROMA_I420 1
-/* PLANAR CHW TARGETS.  Three further values of bt709hip_surface.format, accepted by bt709hip_decode and bt709hip_decode_batch alone,
- * as OUTPUT alone -- every other entry point (the rescales, bt709hip_render_scaled, the encoder, bt709hip_unconvert, ring options,
- * pools, shards, bt709hip_decoder_prepare_format) returns what it returns for any unknown format.  The decode writes the frame as
+/* PLANAR CHW TARGETS.  Three further values of bt709hip_surface.format, accepted as OUTPUT by bt709hip_decode and
+ * bt709hip_decode_batch, and as INPUT by bt709hip_encode and bt709hip_encode_batch once BT709HIP_CTX_OPT_ENCODE_CHW_INPUT is 1 (PLANAR
+ * CHW INPUT, below) -- every other entry point (the rescales, bt709hip_render_scaled, the encoder with that option at 0,
+ * bt709hip_unconvert, ring options, pools, shards, bt709hip_decoder_prepare_format) returns what it returns for any unknown format.  The decode writes the frame as
  * the planar C x H x W tensor an inference pipeline takes, with no second pass and no scratch surface (definition: DESIGN.md 3.14).
  * With e = 1, 2 or 4 bytes per element:
  *   bgra     the base of plane 0, e-aligned;
@@ -418,6 +427,41 @@ int bt709hip_decoder_get_option(const bt709hip_decoder *dec, int option, int *va
 #define BT709HIP_OPT_CHW_BIAS_R 17
 #define BT709HIP_OPT_CHW_BIAS_G 18
 #define BT709HIP_OPT_CHW_BIAS_B 19
+/* PLANAR CHW INPUT (BT709HIP_CTX_OPT_ENCODE_CHW_INPUT; definition: DESIGN.md 3.15).  The way back of the targets above: a model's output
+ * -- super-resolution, denoising, interpolation -- is a CHW or NCHW tensor, and with the option at 1 bt709hip_encode and
+ * bt709hip_encode_batch take it as it lies, in ONE launch that reads 3 e and writes 1.5 bytes per pixel (e = 1, 2 or 4): no
+ * de-normalising, rounding, permuting or interleaving pass by the caller.  The call takes its format from ins[0]; a batch of mixed
+ * formats is BT709HIP_ERR_SIZE_MISMATCH, as ever.  The layout is the targets': bgra is the base of plane 0 and is e-aligned; stride is
+ * the pitch of EVERY plane in bytes, a multiple of e with width * e <= stride <= 2^32 - 1 (else BT709HIP_ERR_STRIDE); plane c starts at
+ * bgra + c * height * stride (a 64-bit product).  Planes R, G, B are read; a fourth plane may lie behind them and is NEVER read (the
+ * BGRA8_SRGB encode ignores A, too).  Per element, t being its value (a binary16 converts to binary32 exactly):
+ *   CHW_U8            s_c = t, the byte itself;
+ *   CHW_F16, CHW_F32  u = t * scale_c;  u = u + bias_c  -- binary32, every operation rounded on its own, no fused multiply-add;
+ *                     x = sat(u): NaN -> 0, u < 0 (and -0) -> 0, u > 1 (and +inf) -> 1;
+ *                     s_c = (int)round(x * 255.0f), halves away from zero (exact for every float in [0, 1]).
+ * The frame written is, byte for byte, the frame the same call writes for the BGRA8_SRGB surface whose texels are
+ * (B, G, R, A) = (s_B, s_G, s_R, 255): same input gamma (all three work: the path starts from a byte), same output gamma, same
+ * BT709HIP_CTX_OPT_ENCODE_CHROMA_LAYOUT (NV12 and I420).  scale_c, bias_c: BT709HIP_CTX_OPT_ENCODE_CHW_SCALE_R / _G / _B = 20, 21, 22
+ * and BT709HIP_CTX_OPT_ENCODE_CHW_BIAS_R / _G / _B = 23, 24, 25, whose int value is the BIT PATTERN of a binary32: defaults 1.0f and
+ * 0.0f; accepted: +-0 or a finite value with 2^-64 <= |x| <= 2^64; anything else BT709HIP_ERR_INVALID_ARG, the option keeps its value.
+ * They are the INVERSE of the decode's pair: where a decoder holds (1 / std, -mean / std), the encoder holds (std, mean).  A call
+ * reads each ONCE and they travel as kernel arguments (nothing is staged on the device: setting them and encoding both work inside a
+ * graph capture once the encoder's tables exist); CHW_U8 ignores them; there is no getter.  Setting one while a call that uses them
+ * is in flight on another thread is the caller's race.
+ * Validation keeps the encoder's order and codes -- sizes, odd dimensions, height / 2 <= 65535, strides, NULLs -- with the element
+ * size in place of the texel size, and enqueues nothing on refusal.  BT709HIP_CTX_OPT_ENCODE_ROW_PAIRS, _ENCODE_THREADS and _XCD_BANDS
+ * apply as they do to BGRA8_SRGB input, and bt709hip_last_launch_info is the BGRA8 encoder's plan for the same size and count.
+ * BT709HIP_CTX_OPT_ENCODE_PREMULTIPLY, _ENCODE_CONVERT, _ENCODE_WITH_ALPHA or _ENCODE_HALF_WITH_ALPHA away from its default with CHW
+ * input: BT709HIP_ERR_UNSUPPORTED behind the usual validation, nothing launched.  BT709HIP_CTX_OPT_ENCODE_HALF_INPUT is independent.
+ * Batches: any count of evenly spaced surfaces up to 65535 (a contiguous NCHW tensor is one); otherwise a pointer table of
+ * BT709HIP_MAX_BATCH - 1 = 31 surfaces (the kernel argument block does not grow: the six values ride in the table's last entry):
+ * more is BT709HIP_ERR_UNSUPPORTED.  The fast kernel needs width % 4 == 0, plane 0 and the pitch 4 e-aligned and the frame aligned as
+ * the BGRA8 fast kernel needs it; every other valid call takes the general kernel (element loads, byte stores) and writes the same
+ * bytes.  bt709hip_last_kernel_name: "encode_chw_nv12<u8>", "encode_chw_i420<f32>", "encode_chw_nv12_blocks<f16>", ... .  Tables: the
+ * (input_gamma, output_gamma) encoder's own, built by the first call or by bt709hip_encoder_prepare.  BGRA8 and RGBA16F input behave
+ * exactly as before with the option at either value.  Any value but 0 and 1: BT709HIP_ERR_INVALID_ARG, the option keeps its value (it
+ * is not clamped); setting it never touches the device.  OUT OF SCOPE: float tensors as linear light without the 8-bit step (the
+ * RGBA16F route exists for that); an alpha frame from a fourth plane; straight-alpha tensors; HWC tensors. */
 
 /* COALESCING SUBMIT (extension, opt-in: bt709hip_decoder_set_option(dec, BT709HIP_OPT_COALESCE, n), n = 2..32).
  * The reference's cadence is one -decodeBT709: call per frame (MetalBT709Decoder.h:65-72, AAPLRenderer.m:914-957), each call

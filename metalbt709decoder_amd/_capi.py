@@ -64,6 +64,9 @@ CTX_OPT_ENCODE_PREMULTIPLY = 8  # 0 (default): BGRA8_SRGB input is encoded as it
 CTX_OPT_ENCODE_CONVERT = 10  # CONVERT_OFF (default): bt709hip_encode[_batch] is the subsampling encoder; CONVERT_PACKED444 / CONVERT_POINT420: the reference's per-pixel +convert:; any other value is refused
 CTX_OPT_ENCODE_WITH_ALPHA = 12  # 0 (default): one frame per picture; 1: bt709hip_encode[_batch] of BGRA8_SRGB input writes the alpha frame as well, `out` holds 2 x count frames (colour frames, then the alpha frames); any other value is refused
 CTX_OPT_ENCODE_HALF_WITH_ALPHA = 16  # 0 (default): one frame per picture; 1: bt709hip_encode[_batch] of RGBA16F input (under CTX_OPT_ENCODE_HALF_INPUT = 1) writes the surface's alpha frame as well, `out` holds 2 x count frames (colour frames, then the alpha frames); any other value is refused
+CTX_OPT_ENCODE_CHW_INPUT = 18  # 0 (default): planar CHW input to bt709hip_encode[_batch] is refused as any unknown format is; 1: FORMAT_CHW_U8 / _F16 / _F32 surfaces are encoded; any other value is refused
+CTX_OPT_ENCODE_CHW_SCALE_R, CTX_OPT_ENCODE_CHW_SCALE_G, CTX_OPT_ENCODE_CHW_SCALE_B = 20, 21, 22  # float32 bit patterns (default 1.0): an element t of float CHW input becomes the byte round(255 * sat(t * scale + bias))
+CTX_OPT_ENCODE_CHW_BIAS_R, CTX_OPT_ENCODE_CHW_BIAS_G, CTX_OPT_ENCODE_CHW_BIAS_B = 23, 24, 25     # float32 bit patterns (default 0.0); +-0 or finite with 2^-64 <= |x| <= 2^64, anything else is refused
 CTX_OPT_ENCODE_HALF_INPUT = 14 # 0 (default): RGBA16F input to bt709hip_encode[_batch] is refused (ERR_UNSUPPORTED); 1: it is encoded as linear light (input gamma LINEAR); any other value is refused
 CONVERT_OFF = 0
 CONVERT_PACKED444 = 1  # out.y: W x H 32-bit words (Cr<<16)|(Cb<<8)|Y, out.cbcr NULL

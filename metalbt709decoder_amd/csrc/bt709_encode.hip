@@ -501,6 +501,7 @@ encode_alpha_y_blocks(const EncodeParams p) {
 #include "bt709_encode_convert.h"  // BT709HIP_CTX_OPT_ENCODE_CONVERT: convert_bgra, convert_bgra_blocks over the helpers above
 #include "bt709_encode_half.h"     // BT709HIP_CTX_OPT_ENCODE_HALF_INPUT: encode_rgba16f, encode_rgba16f_blocks over the helpers above
 #include "bt709_encode_half_alpha.h"  // BT709HIP_CTX_OPT_ENCODE_HALF_WITH_ALPHA: encode_rgba16f_alpha, encode_rgba16f_alpha_blocks over both
+#include "bt709_encode_chw.h"      // BT709HIP_CTX_OPT_ENCODE_CHW_INPUT: encode_chw, encode_chw_blocks over the helpers above
 
 namespace bt709 {
 namespace {
@@ -564,11 +565,26 @@ const EncodeKernel kEncodeHalfKernels[2][2] = {
      {1, 2, 0, kConvertOff, true, {encode_rgba16f_alpha<kChromaNV12>, encode_rgba16f_alpha<kChromaI420>}, {"encode_rgba16f_alpha_nv12", "encode_rgba16f_alpha_i420"}}},
 };
 
+// Planar-tensor input (EncodeParams::input_format kEncodeInputCHW*): [fast][element]; the shim refuses every option the first table
+// selects by, and the pair
+#define ENCODE_CHW(fast, suffix, KERNEL, ELEM, elem) \
+  {fast, 0, 0, kConvertOff, true, {KERNEL<kChromaNV12, ELEM>, KERNEL<kChromaI420, ELEM>}, {"encode_chw_nv12" suffix "<" elem ">", "encode_chw_i420" suffix "<" elem ">"}}
+const EncodeKernel kEncodeChwKernels[2][3] = {
+    {ENCODE_CHW(0, "_blocks", encode_chw_blocks, kChwU8, "u8"), ENCODE_CHW(0, "_blocks", encode_chw_blocks, kChwF16, "f16"), ENCODE_CHW(0, "_blocks", encode_chw_blocks, kChwF32, "f32")},
+    {ENCODE_CHW(1, "", encode_chw, kChwU8, "u8"), ENCODE_CHW(1, "", encode_chw, kChwF16, "f16"), ENCODE_CHW(1, "", encode_chw, kChwF32, "f32")},
+};
+#undef ENCODE_CHW
+
 // The kernel of a launch that launch_encode has planned and recorded
 const char *launch_encode_kernel(const EncodeParams &p, const dim3 &grid, const dim3 &block, size_t lds, bool fast, int alpha, hipStream_t stream) {
   const uint32_t layout = p.chroma_layout == kChromaI420 ? kChromaI420 : kChromaNV12;
   if (p.input_format == kEncodeInputRGBA16F) {
     const EncodeKernel &k = kEncodeHalfKernels[fast ? 1 : 0][alpha == 2 ? 1 : 0];
+    hipLaunchKernelGGL(k.fn[layout], grid, block, lds, stream, p);
+    return k.name[layout];
+  }
+  if (encode_input_chw(p.input_format)) {
+    const EncodeKernel &k = kEncodeChwKernels[fast ? 1 : 0][encode_chw_elem(p.input_format) - kChwU8];
     hipLaunchKernelGGL(k.fn[layout], grid, block, lds, stream, p);
     return k.name[layout];
   }
@@ -626,6 +642,11 @@ hipError_t prepare_encode_kernels() {
     if (const hipError_t e = k.stages_table ? raise_lds_cap(fns, kRepLdsBytes) : hipSuccess) return e;
   }
   for (const auto &row : kEncodeHalfKernels)
+    for (const EncodeKernel &k : row) {
+      const void *fns[] = {reinterpret_cast<const void *>(k.fn[0]), reinterpret_cast<const void *>(k.fn[1])};
+      if (const hipError_t e = raise_lds_cap(fns, kRepLdsBytes)) return e;
+    }
+  for (const auto &row : kEncodeChwKernels)
     for (const EncodeKernel &k : row) {
       const void *fns[] = {reinterpret_cast<const void *>(k.fn[0]), reinterpret_cast<const void *>(k.fn[1])};
       if (const hipError_t e = raise_lds_cap(fns, kRepLdsBytes)) return e;

@@ -231,10 +231,20 @@ struct EncodePair {
 };
 constexpr int kMaxPairBatch = kMaxBatch / 2;  // pairs in the kernarg table
 static_assert(sizeof(EncodePair[kMaxPairBatch]) == sizeof(EncodeFrame[kMaxBatch]), "the pair table is the frame table's bytes");
+// BT709HIP_CTX_OPT_ENCODE_CHW_INPUT: a planar-tensor launch (input_format kEncodeInputCHW*).  The frames[] area again, as
+// EncodePair shortened it: one entry fewer, and in its 24 bytes the six binary32 the float kernels read -- s = sat(t * scale[c] + bias[c]),
+// c = R, G, B (bt709_chw_denorm.h).  Entry i IS frames[i]: encode_frame and advance_frames read it through that member.
+constexpr int kMaxChwBatch = kMaxBatch - 1;  // surfaces in the kernarg table of a CHW launch
+struct EncodeChwTable {
+  EncodeFrame frames[kMaxChwBatch];  // bgra: the base of plane 0 (R); plane c is c * height * bgra_stride bytes behind it
+  float scale[3], bias[3];
+};
+static_assert(sizeof(EncodeChwTable) == sizeof(EncodeFrame[kMaxBatch]), "the CHW table is the frame table's bytes");
 struct EncodeParams {
   union {
     EncodeFrame frames[kMaxBatch];
     EncodePair pairs[kMaxPairBatch];  // a paired launch: alpha_luma AND per_byte non-null (below)
+    EncodeChwTable chw;               // a planar-tensor launch: input_format kEncodeInputCHW*
   };
   // uniform != 0: frame i = frames[0] + i * step_* (bytes), as in DecodeParams
   uint32_t uniform;
@@ -268,6 +278,8 @@ struct EncodeParams {
   // (8 bytes each, bgra_stride their pitch) and launch_encode runs encode_rgba16f / encode_rgba16f_blocks (bt709_encode_half.h), which
   // read from_linear* and not per_byte.  A selector of launch_encode, read by no kernel; the upper byte of what `premultiply`
   // (0 or 1) occupied: no offset and no size changes.
+  // kEncodeInputCHWU8 / F16 / F32: frames[i].bgra is plane 0 of a planar tensor of that element type, bgra_stride
+  // the pitch of every plane's rows, and launch_encode runs encode_chw / encode_chw_blocks (bt709_encode_chw.h).
   uint8_t input_format;  // kEncodeInput*
   uint16_t convert_mode;  // kConvert*: a selector of launch_encode as well, read by no kernel
   float from_linear_coarse;   // fine buckets below the table's split point, coarse ones above: q = (uint)(xs * coarse) + offset
@@ -285,7 +297,9 @@ struct EncodeParams {
 };
 inline bool encode_pair(const EncodeParams &p) { return p.alpha_luma != nullptr && p.per_byte != nullptr; }
 static_assert(sizeof(EncodeParams) == 880, "a field appended to EncodeParams moves the implicit kernel arguments behind it: every encoder kernel's code changes");
-enum : uint8_t { kEncodeInputBGRA8 = 0, kEncodeInputRGBA16F = 1 };
+enum : uint8_t { kEncodeInputBGRA8 = 0, kEncodeInputRGBA16F = 1, kEncodeInputCHWU8 = 2, kEncodeInputCHWF16 = 3, kEncodeInputCHWF32 = 4 };
+constexpr bool encode_input_chw(uint8_t format) { return format >= kEncodeInputCHWU8 && format <= kEncodeInputCHWF32; }
+constexpr uint32_t encode_chw_elem(uint8_t format) { return static_cast<uint32_t>(format - kEncodeInputCHWU8) + 1u; }  // kChwU8 / kChwF16 / kChwF32
 enum : uint32_t { kConvertOff = 0, kConvertPacked444 = 1, kConvertPoint420 = 2 };  // == BT709HIP_CONVERT_*
 // Further bit of the converter kernels' FORM (beside the layout and kFormStraight): the packed 4:4:4 output
 enum : uint32_t { kFormPacked = 4 };

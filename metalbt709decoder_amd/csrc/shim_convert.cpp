@@ -249,8 +249,13 @@ int bt709hip_encode_batch(bt709hip_context *ctx, int count, const bt709hip_surfa
   // and no premultiply: it is validated as the plain encoder's call and refused behind that if one of those options is set.
   const bool half_input = ctx->encode_half_input != 0;
   const bool half = count > 0 && half_input && ins[0].format == BT709HIP_FORMAT_RGBA16F;
+  // BT709HIP_CTX_OPT_ENCODE_CHW_INPUT, read once: with it at 1 planar CHW_U8 / _F16 / _F32 surfaces are input, again by
+  // ins[0]'s format.  Such a call is the plain BGRA8 encoder's call with the element size in place of the texel's; the converter, the
+  // pair and the premultiply are refused behind the usual validation.  At 0 the three formats are what they were: unknown.
+  const bool chw_input = ctx->encode_chw_input != 0;
+  const bool chw = count > 0 && chw_input && is_chw(ins[0].format);
   const int convert_option = ctx->encode_convert;
-  const int convert = half ? BT709HIP_CONVERT_OFF : convert_option;
+  const int convert = half || chw ? BT709HIP_CONVERT_OFF : convert_option;
   const bool packed = convert == BT709HIP_CONVERT_PACKED444;
   if (input_gamma < 0 || input_gamma > 2 || output_gamma < 0 || output_gamma > (convert != BT709HIP_CONVERT_OFF ? 3 : 2)) return BT709HIP_ERR_INVALID_ARG;
   if (count == 0) return BT709HIP_OK;
@@ -264,7 +269,7 @@ int bt709hip_encode_batch(bt709hip_context *ctx, int count, const bt709hip_surfa
   // Without a chroma plane there is nothing to lay out: such a call is what it was, whatever the option holds.
   const bool planar = ctx->encode_chroma_layout == BT709HIP_CHROMA_I420 && !no_cbcr;
   // BT709HIP_CTX_OPT_ENCODE_PREMULTIPLY, read once: BGRA8_SRGB texels are straight alpha.  BGRA8_ALPHA input reads A alone: unaffected.
-  const bool premultiply = ctx->encode_premultiply != 0 && !alpha && !half;
+  const bool premultiply = ctx->encode_premultiply != 0 && !alpha && !half && !chw;
   const size_t chroma_align = planar ? 2 : 4;  // the fast kernels' chroma store: a 2-byte half per plane, or the CbCr dword
   // BT709HIP_CTX_OPT_ENCODE_WITH_ALPHA, read once: BGRA8_SRGB input writes two frames, the colour into outs[i] and the alpha frame
   // (BGRA8_ALPHA output's rules) into outs[count + i], from one launch.  Not with the per-pixel converter and not for BGRA8_ALPHA
@@ -273,7 +278,7 @@ int bt709hip_encode_batch(bt709hip_context *ctx, int count, const bt709hip_surfa
   // BT709HIP_CTX_OPT_ENCODE_HALF_WITH_ALPHA, read once: the same two frames per picture from RGBA16F input, the alpha
   // frame from the texel's A half.  An option of its own: WITH_ALPHA with half input stays refused.  No other input reads it.
   const bool half_pair = half && ctx->encode_half_with_alpha != 0;
-  const bool pair = half_pair || (with_alpha && !alpha && !half && convert == BT709HIP_CONVERT_OFF);
+  const bool pair = half_pair || (with_alpha && !alpha && !half && !chw && convert == BT709HIP_CONVERT_OFF);
   const bt709hip_frame &alpha0 = outs[pair ? count : 0];
   const bool alpha_no_cbcr = pair && alpha0.cbcr == nullptr;
   bool uniform = count > 1;
@@ -282,7 +287,10 @@ int bt709hip_encode_batch(bt709hip_context *ctx, int count, const bt709hip_surfa
   // encode_rgba16f: a 2x2 block per lane -- any even width; 2-byte stores to Y and CbCr, byte stores to U and V
   const size_t half_chroma_align = planar ? 1 : 2;
   if (half) fast = (in0.stride % 16) == 0 && (out0.y_stride % 2) == 0 && (out0.cbcr_stride % half_chroma_align) == 0;
-  const size_t in_px = half ? 8 : 4;  // bytes of a texel
+  const size_t in_px = chw ? element_bytes(in0.format) : half ? 8 : 4;  // bytes of a texel, or of a CHW plane's element
+  // encode_chw: a quad per lane and plane -- 4 elements a load; its stores are encode_bgra's
+  const size_t chw_align = 4 * in_px;
+  if (chw) fast = (in0.width % 4) == 0 && (in0.stride % chw_align) == 0 && (out0.y_stride % y_align) == 0 && (out0.cbcr_stride % chroma_align) == 0;
   // the paired fast kernels store to the alpha frame as they do to the colour's: encode_bgra_alpha dwords, encode_rgba16f_alpha halves
   const size_t pair_y_align = half ? 2 : 4, pair_chroma_align = half ? half_chroma_align : chroma_align;
   if (pair) fast = fast && (alpha0.y_stride % pair_y_align) == 0 && (alpha_no_cbcr || (alpha0.cbcr_stride % pair_chroma_align) == 0);
@@ -296,7 +304,7 @@ int bt709hip_encode_batch(bt709hip_context *ctx, int count, const bt709hip_surfa
     if ((in.width & 1) || (in.height & 1)) return BT709HIP_ERR_ODD_DIMENSIONS;  // BGRAToBT709Converter.m:540-541
     if (in.height / 2 > kMaxGridYZ) return BT709HIP_ERR_UNSUPPORTED;            // row pairs live in gridDim.y
     if ((in.format != BT709HIP_FORMAT_BGRA8_SRGB && in.format != BT709HIP_FORMAT_BGRA8_ALPHA &&
-         !(in.format == BT709HIP_FORMAT_RGBA16F && half_input)) || in.reserved != 0)
+         !(in.format == BT709HIP_FORMAT_RGBA16F && half_input) && !(is_chw(in.format) && chw_input)) || in.reserved != 0)
       return BT709HIP_ERR_UNSUPPORTED;
     if (in.width != in0.width || in.height != in0.height || in.stride != in0.stride || in.format != in0.format ||
         out.y_stride != out0.y_stride || (!(packed || (alpha && (no_cbcr || out.cbcr == nullptr))) && out.cbcr_stride != out0.cbcr_stride))
@@ -312,6 +320,7 @@ int bt709hip_encode_batch(bt709hip_context *ctx, int count, const bt709hip_surfa
     if (packed && ((out.y_stride & 3) || !aligned(out.y, 4))) return BT709HIP_ERR_STRIDE;  // words
     if (in.stride > 0xffffffffu || out.y_stride > 0xffffffffu || (!no_cbcr && out.cbcr_stride > 0xffffffffu)) return BT709HIP_ERR_STRIDE;
     if (half) fast = fast && aligned(in.bgra, 16) && aligned(out.y, 2) && aligned(out.cbcr, half_chroma_align);
+    else if (chw) fast = fast && aligned(in.bgra, chw_align) && aligned(out.y, y_align) && aligned(out.cbcr, chroma_align);
     else fast = fast && aligned(in.bgra, 16) && aligned(out.y, y_align) && aligned(out.cbcr, chroma_align);
     if (i >= 2)
       uniform = uniform && byte_step(ins[0].bgra, in.bgra) == byte_step(ins[0].bgra, ins[1].bgra) * i &&
@@ -336,18 +345,20 @@ int bt709hip_encode_batch(bt709hip_context *ctx, int count, const bt709hip_surfa
         e.alpha_y = static_cast<uint8_t *>(const_cast<void *>(af.y));
         e.alpha_cbcr = static_cast<uint8_t *>(const_cast<void *>(af.cbcr));
       }
-    } else if (i < kMaxBatch) {
+    } else if (i < (chw ? kMaxChwBatch : kMaxBatch)) {  // a CHW launch: one entry fewer, scale and bias in its place
       p.frames[i].bgra = static_cast<const uint8_t *>(in.bgra);
       p.frames[i].y = static_cast<uint8_t *>(const_cast<void *>(out.y));
       p.frames[i].cbcr = static_cast<uint8_t *>(const_cast<void *>(out.cbcr));
     }
   }
-  if (count > (uniform ? kMaxUniformBatch : pair ? kMaxPairBatch : kMaxBatch)) return BT709HIP_ERR_UNSUPPORTED;
+  if (count > (uniform ? kMaxUniformBatch : pair ? kMaxPairBatch : chw ? kMaxChwBatch : kMaxBatch)) return BT709HIP_ERR_UNSUPPORTED;
   // the reference's per-pixel converters take sRGB bytes only, and no alpha clip goes through them
   if (convert != BT709HIP_CONVERT_OFF && (alpha || input_gamma != BT709HIP_GAMMA_SRGB)) return BT709HIP_ERR_UNSUPPORTED;
   if (with_alpha && (!pair || half)) return BT709HIP_ERR_UNSUPPORTED;  // the converter writes no alpha frame; an alpha clip has none beside itself; halves have an option of their own
   // half input composes with the chroma layout alone: the converter, the pair and the premultiply are BGRA8 paths
   if (half && (convert_option != BT709HIP_CONVERT_OFF || ctx->encode_premultiply != 0)) return BT709HIP_ERR_UNSUPPORTED;
+  // so does CHW input; the half pair's option is an option of another input, but away from its default it is refused all the same
+  if (chw && (convert_option != BT709HIP_CONVERT_OFF || ctx->encode_premultiply != 0 || ctx->encode_half_with_alpha != 0)) return BT709HIP_ERR_UNSUPPORTED;
   if (in0.width == 0 || in0.height == 0) return BT709HIP_OK;
   if (int rc = bind(ctx)) return rc;
   FLUSH_STREAM(ctx, stream);
@@ -397,6 +408,14 @@ int bt709hip_encode_batch(bt709hip_context *ctx, int count, const bt709hip_surfa
   p.chroma_layout = planar ? kChromaI420 : kChromaNV12;
   p.premultiply = premultiply ? 1 : 0;
   p.input_format = half ? kEncodeInputRGBA16F : kEncodeInputBGRA8;  // per_byte is built with the pair's tables and not read
+  if (chw) {  // the element type, and the six values, each read once: kernel arguments, nothing staged (CHW_U8 ignores them)
+    p.input_format = static_cast<uint8_t>(kEncodeInputCHWU8 + (in0.format - BT709HIP_FORMAT_CHW_U8));
+    for (int c = 0; c < 3; ++c) {
+      const uint32_t scale = ctx->encode_chw_norm[c], bias = ctx->encode_chw_norm[3 + c];
+      std::memcpy(&p.chw.scale[c], &scale, sizeof scale);
+      std::memcpy(&p.chw.bias[c], &bias, sizeof bias);
+    }
+  }
   last_launch_shape() = LaunchShape{};
   set_kernel_name(launch_encode(p, count, fast, ctx->xcd_bands != 0, s));
   HIP_TRY(hipGetLastError());

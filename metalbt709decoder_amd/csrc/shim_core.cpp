@@ -6,6 +6,8 @@
 // BT709HIP_ERR_NO_DEVICE / BT709HIP_ERR_HIP.
 #include "shim_internal.h"
 
+#include "bt709_chw_norm.h"
+
 namespace bt709shim __attribute__((visibility("hidden"))) {
 
 // This thread's last failing HIP call and last launched kernel.  Touched through the functions below ONLY: an `extern
@@ -156,6 +158,15 @@ int bt709hip_context_set_option(bt709hip_context *ctx, int option, int value) {
     case BT709HIP_CTX_OPT_ENCODE_HALF_WITH_ALPHA:  // the half encode's alpha frame; T is built by the first such call, or by bt709hip_encoder_prepare under the option
       if (value != 0 && value != 1) return BT709HIP_ERR_INVALID_ARG;
       ctx->encode_half_with_alpha = value;
+      return BT709HIP_OK;
+    case BT709HIP_CTX_OPT_ENCODE_CHW_INPUT:  // the gate of planar CHW input; closed, formats 4, 5 and 6 stay what the encoder answers for an unknown format
+      if (value != 0 && value != 1) return BT709HIP_ERR_INVALID_ARG;
+      ctx->encode_chw_input = value;
+      return BT709HIP_OK;
+    case BT709HIP_CTX_OPT_ENCODE_CHW_SCALE_R: case BT709HIP_CTX_OPT_ENCODE_CHW_SCALE_G: case BT709HIP_CTX_OPT_ENCODE_CHW_SCALE_B:
+    case BT709HIP_CTX_OPT_ENCODE_CHW_BIAS_R: case BT709HIP_CTX_OPT_ENCODE_CHW_BIAS_G: case BT709HIP_CTX_OPT_ENCODE_CHW_BIAS_B:  // a binary32's bits: +-0, or finite in [2^-64, 2^64]
+      if (!bt709::chw_norm_bits_valid(static_cast<uint32_t>(value))) return BT709HIP_ERR_INVALID_ARG;
+      ctx->encode_chw_norm[option - BT709HIP_CTX_OPT_ENCODE_CHW_SCALE_R] = static_cast<uint32_t>(value);
       return BT709HIP_OK;
     case BT709HIP_CTX_OPT_STREAMING_TRIES:
       ctx->streaming_tries = value <= 0 ? 4 : clamp_int(value, 1, 32);

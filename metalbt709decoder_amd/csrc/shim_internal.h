@@ -45,6 +45,9 @@ struct bt709hip_context {
   int encode_with_alpha = 0;                        // BT709HIP_CTX_OPT_ENCODE_WITH_ALPHA: bt709hip_encode[_batch] of BGRA8_SRGB input writes the alpha frame as well, `out` holds 2 x count frames
   int encode_half_input = 0;                        // BT709HIP_CTX_OPT_ENCODE_HALF_INPUT: bt709hip_encode[_batch] accepts RGBA16F (linear-light) surfaces
   int encode_half_with_alpha = 0;                   // BT709HIP_CTX_OPT_ENCODE_HALF_WITH_ALPHA: such a call writes the surface's alpha frame as well, `out` holds 2 x count frames
+  int encode_chw_input = 0;                         // BT709HIP_CTX_OPT_ENCODE_CHW_INPUT: bt709hip_encode[_batch] accepts planar CHW_U8 / _F16 / _F32 surfaces
+  // BT709HIP_CTX_OPT_ENCODE_CHW_SCALE_R, _G, _B, _BIAS_R, _G, _B: binary32 bit patterns (1.0f, 0.0f), read once by an encode of float CHW surfaces
+  std::atomic<uint32_t> encode_chw_norm[6] = {{0x3f800000u}, {0x3f800000u}, {0x3f800000u}, {0u}, {0u}, {0u}};
   int streaming_tries = 4;                   // BT709HIP_CTX_OPT_STREAMING_TRIES: placement candidates for buffers of 256 MB and more that the library allocates itself
   std::mutex encoder_mutex;
   EncoderTables encoders[3][3];  // [input gamma][output gamma], built on first use

@@ -686,6 +686,53 @@ class MetalRenderContext:
             finally:
                 self.lib.bt709hip_context_set_option(self.handle, _capi.CTX_OPT_ENCODE_HALF_WITH_ALPHA, 0)
 
+    @contextlib.contextmanager
+    def _encode_chw_input(self, what):
+        """bt709hip_context_set_option(CTX_OPT_ENCODE_CHW_INPUT) around ONE encode of CHWTextures: 1 on entry and back to 0 on the
+        way out, whatever the call returned or raised, so that every other encode call of this context refuses such input as it
+        always did.  The setter never touches the device.  Yields True, or False when the library refused the option."""
+        rc = self.lib.bt709hip_context_set_option(self.handle, _capi.CTX_OPT_ENCODE_CHW_INPUT, 1)
+        if rc != _capi.OK:
+            log.error("%s: CTX_OPT_ENCODE_CHW_INPUT = 1: %s", what, _capi.strerror(rc))
+            yield False
+            return
+        try:
+            yield True
+        finally:
+            self.lib.bt709hip_context_set_option(self.handle, _capi.CTX_OPT_ENCODE_CHW_INPUT, 0)
+
+    def setEncodeCHWNormalisation(self, scale=(1.0, 1.0, 1.0), bias=(0.0, 0.0, 0.0)):
+        """Per-channel (R, G, B) scale and bias of float CHW encoder INPUT (_capi.CTX_OPT_ENCODE_CHW_SCALE_* / _BIAS_*): an element
+        t becomes the byte round(255 * sat(t * scale + bias)), the product and the sum float32 operations each rounded on its own
+        (DESIGN.md 3.15).  The values are taken as float32 and must be +-0 or finite with 2^-64 <= |x| <= 2^64 (ValueError
+        otherwise, nothing changed).  uint8 CHWTextures ignore them.  Returns True/False."""
+        values = np.array(list(scale) + list(bias), dtype=np.float32)
+        if values.shape != (6,):
+            raise ValueError("setEncodeCHWNormalisation: three scales and three biases")
+        mag = values.view(np.uint32) & 0x7FFFFFFF
+        if not np.all((mag == 0) | ((mag >= 0x1F800000) & (mag <= 0x5F800000))):
+            raise ValueError("setEncodeCHWNormalisation: every value +-0 or finite with 2^-64 <= |x| <= 2^64, got %s" % (values,))
+        bits = values.view(np.int32)
+        for i in range(6):
+            rc = self.lib.bt709hip_context_set_option(self.handle, _capi.CTX_OPT_ENCODE_CHW_SCALE_R + i, int(bits[i]))
+            if rc != _capi.OK:
+                log.error("setEncodeCHWNormalisation: option %d: %s", _capi.CTX_OPT_ENCODE_CHW_SCALE_R + i, _capi.strerror(rc))
+                return False
+        return True
+
+    def setEncodeCHWMeanStd(self, mean, std):
+        """The inverse of MetalBT709Decoder.setCHWMeanStd: a tensor holding (x - mean) / std is encoded as x.  scale = float32(std)
+        and bias = float32(mean), handed to setEncodeCHWNormalisation as they are -- no division on this side."""
+        return self.setEncodeCHWNormalisation(np.asarray(std, dtype=np.float32), np.asarray(mean, dtype=np.float32))
+
+    def fillCHWTexture(self, tex, array, commandBuffer=None):
+        """Uploads a (planes, H, W) array of the texture's dtype into a CHWTexture (row padding of a pitched texture is left as it
+        is).  Fewer planes than the texture has fill the first ones."""
+        a = np.ascontiguousarray(array, dtype=tex.dtype)
+        if a.ndim != 3 or a.shape[0] > tex.planes or a.shape[1:] != (tex.height, tex.width):
+            raise ValueError("fillCHWTexture: a (%d, %d, %d) array at most, not %s" % (tex.planes, tex.height, tex.width, a.shape))
+        self._upload(tex.ptr, tex.stride, a.view(np.uint8).reshape(a.shape[0] * tex.height, tex.width * tex.itemsize), commandBuffer)
+
     def _set_encode_layout(self, pixelBuffers, what):
         """The encoder's chroma layout from the buffers an encode call was handed: a planar CVPixelBuffer is written in place.  As
         MetalBT709Decoder._set_layout: the buffer's `planar` flag is authoritative, planar and NV12 buffers in one call are
@@ -930,6 +977,39 @@ class BGRAToBT709Converter:
             return False
         for b in alphaPixelBuffers or []:
             BGRAToBT709Converter.setAlphaAttributes(b)
+        return True
+
+    @staticmethod
+    def convertCHWIntoCoreVideoBuffers(chwTextures, cvPixelBuffers, inputGamma, outputGamma, commandBuffer=None, waitUntilCompleted=True):
+        """`count` same-sized planar tensors (CHWTexture; CHWTexture.fromTensor of a model's output, or of each image of an NCHW
+        batch) into their frames in ONE launch, with no de-normalise / round / permute pass (bt709hip_encode_batch under
+        CTX_OPT_ENCODE_CHW_INPUT, set around this call alone and put back whatever happens).  Planes R, G, B are
+        read, a fourth is ignored.  A uint8 element is the byte; a float element t is round(255 * sat(t * scale + bias)) with the
+        context's setEncodeCHWNormalisation / setEncodeCHWMeanStd values, and the frame is the one convertIntoCoreVideoBuffers
+        writes for the BGRA8 picture of those bytes under the same gammas.  Planar buffers are written in place.  True/False."""
+        n = len(chwTextures)
+        if n != len(cvPixelBuffers):
+            raise ValueError("one output buffer per input texture")
+        if n == 0:
+            return True
+        what = "convertCHWIntoCoreVideoBuffers"
+        if any(not isinstance(t, CHWTexture) for t in chwTextures):
+            log.error("%s: the sources must be CHWTextures", what)
+            return False
+        ctx = chwTextures[0].ctx
+        if not ctx._set_encode_layout(list(cvPixelBuffers), what):
+            return False
+        surfs = (Surface * n)(*[t.surface() for t in chwTextures])
+        frames = (Frame * n)(*[b.frame() for b in cvPixelBuffers])
+        stream = commandBuffer.stream if commandBuffer is not None else None
+        with ctx._encode_chw_input(what) as ok:
+            if not ok:
+                return False
+            rc = ctx.lib.bt709hip_encode_batch(ctx.handle, n, surfs, frames, int(inputGamma), int(outputGamma), stream,
+                                               int(bool(waitUntilCompleted)))
+        if rc != _capi.OK:
+            log.error("%s: %s", what, _capi.strerror(rc))
+            return False
         return True
 
     @staticmethod
