@@ -524,6 +524,27 @@ class MetalBT709Decoder {
                               : bt709hip_decode_scaled(dec_, f, a, s, commandBuffer, waitUntilCompleted ? 1 : 0);
     return rc == BT709HIP_OK ? ok() : fail(rc);
   }
+  // The same into a PLANAR view (include/bt709hip_ext.h PLANAR CHW VIEWS, BT709HIP_OPT_SCALED_CHW): `out` describes a
+  // kFormatCHW* surface of the view's size, as under kFormatCHWU8 below -- the rescaled, normalised C x OH x OW tensor in the one fused
+  // launch.  With setScaledCHW off such a surface is an unknown format to the rescales: false, lastStatus BT709HIP_ERR_INVALID_ARG.
+  bool decodeBT709Scaled(const CVPixelBuffer *in, const bt709hip_surface &out, void *commandBuffer, bool waitUntilCompleted,
+                         const CVPixelBuffer *alphaPixelBuffer = nullptr) {
+    if (!setupMetal()) return false;
+    if (in == nullptr) return fail(BT709HIP_ERR_INVALID_ARG);
+    const bt709hip_frame *f = in->frame();
+    const bt709hip_frame *a = alphaPixelBuffer ? alphaPixelBuffer->frame() : nullptr;
+    const bool exact_half = 2 * out.width == f->width && 2 * out.height == f->height && f->width % 4 == 0 && f->height % 4 == 0;
+    const int rc = exact_half ? bt709hip_decode_half(dec_, f, a, &out, commandBuffer, waitUntilCompleted ? 1 : 0)
+                              : bt709hip_decode_scaled(dec_, f, a, &out, commandBuffer, waitUntilCompleted ? 1 : 0);
+    return rc == BT709HIP_OK ? ok() : fail(rc);
+  }
+  static constexpr int kScaledCHWOption = BT709HIP_OPT_SCALED_CHW;
+  bool setScaledCHW(bool on) { return setOption(BT709HIP_OPT_SCALED_CHW, on ? 1 : 0); }
+  bool scaledCHW() const {
+    int on = 0;
+    if (dec_ != nullptr) (void)bt709hip_decoder_get_option(dec_, BT709HIP_OPT_SCALED_CHW, &on);
+    return on != 0;
+  }
 
   // kernel-selection knob (bt709hip_decoder_option): tuning and test hook
   bool setOption(int option, int value) {

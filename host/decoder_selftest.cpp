@@ -162,6 +162,21 @@ static int run_two_pass(MetalRenderContext &ctx, MetalBT709Decoder &dec) {
   if (scale.renderScaled(ctx, view, ow + 2, oh, nullptr, nullptr, inter16, true) ||
       scale.lastStatus() != BT709HIP_ERR_SIZE_MISMATCH)
     ++failures;
+  // the same view as a planar byte tensor (BT709HIP_OPT_SCALED_CHW): three planes of ow x oh bytes in a texture's memory; refused while
+  // the option is off, then plane c = byte c of the fused call's words
+  BGRATexture planes(ctx, ow, oh);
+  const bt709hip_surface chw = {planes.surface()->bgra, static_cast<size_t>(ow), ow, oh, MetalBT709Decoder::kFormatCHWU8, 0};
+  if (dec.scaledCHW() || dec.decodeBT709Scaled(&buf, chw, nullptr, true) || dec.lastStatus() != BT709HIP_ERR_INVALID_ARG) ++failures;
+  if (!dec.setScaledCHW(true) || !dec.scaledCHW() || !dec.decodeBT709Scaled(&buf, chw, nullptr, true)) ++failures;
+  {
+    const std::vector<uint32_t> words = fused.getBGRATexturePixels(), packed_planes = planes.getBGRATexturePixels();
+    const uint8_t *bytes = reinterpret_cast<const uint8_t *>(packed_planes.data());
+    const size_t n = static_cast<size_t>(ow) * oh;
+    for (size_t i = 0; i < n; ++i)
+      for (int c = 0; c < 3; ++c)  // planes R, G, B of (A<<24)|(R<<16)|(G<<8)|B
+        if (bytes[static_cast<size_t>(c) * n + i] != ((words[i] >> (16 - 8 * c)) & 0xffu)) ++failures;
+  }
+  if (!dec.setScaledCHW(false)) ++failures;
   std::printf("%s: two-pass pipeline, %d failures\n", failures ? "FAIL" : "ok", failures);
   return failures ? 1 : 0;
 }

@@ -387,8 +387,9 @@ int bt709hip_decoder_get_option(const bt709hip_decoder *dec, int option, int *va
 #define BT709HIP_CHROMA_NV12 0
 #define BT709HIP_CHROMA_I420 1
 /* PLANAR CHW TARGETS.  Three further values of bt709hip_surface.format, accepted as OUTPUT by bt709hip_decode and
- * bt709hip_decode_batch, and as INPUT by bt709hip_encode and bt709hip_encode_batch once BT709HIP_CTX_OPT_ENCODE_CHW_INPUT is 1 (PLANAR
- * CHW INPUT, below) -- every other entry point (the rescales, bt709hip_render_scaled, the encoder with that option at 0,
+ * bt709hip_decode_batch, by bt709hip_decode_scaled[_batch] and bt709hip_decode_half[_batch] once BT709HIP_OPT_SCALED_CHW is 1 (PLANAR
+ * CHW VIEWS, below), and as INPUT by bt709hip_encode and bt709hip_encode_batch once BT709HIP_CTX_OPT_ENCODE_CHW_INPUT is 1 (PLANAR
+ * CHW INPUT, below) -- every other entry point (the rescales with that option at 0, bt709hip_render_scaled, the encoder with that option at 0,
  * bt709hip_unconvert, ring options, pools, shards, bt709hip_decoder_prepare_format) returns what it returns for any unknown format.  The decode writes the frame as
  * the planar C x H x W tensor an inference pipeline takes, with no second pass and no scratch surface (definition: DESIGN.md 3.14).
  * With e = 1, 2 or 4 bytes per element:
@@ -427,6 +428,36 @@ int bt709hip_decoder_get_option(const bt709hip_decoder *dec, int option, int *va
 #define BT709HIP_OPT_CHW_BIAS_R 17
 #define BT709HIP_OPT_CHW_BIAS_G 18
 #define BT709HIP_OPT_CHW_BIAS_B 19
+/* PLANAR CHW VIEWS (BT709HIP_OPT_SCALED_CHW; definition: DESIGN.md 3.16).  A model rarely takes a frame at its own size: with this
+ * decoder option at 1, bt709hip_decode_scaled, bt709hip_decode_scaled_batch, bt709hip_decode_half and bt709hip_decode_half_batch
+ * accept BT709HIP_FORMAT_CHW_U8 / _F16 / _F32 surfaces of the view's size OW x OH (the half calls: W/2 x H/2) as OUTPUT and write the
+ * rescaled, normalised planar tensor in the one fused launch -- no BGRA8 scratch surface and no second pass.  Values 0 (default) and 1;
+ * anything else BT709HIP_ERR_INVALID_ARG, the option keeps its value; bt709hip_decoder_get_option returns it.  Setting it never
+ * touches the device and works during a graph capture; decoders with and without an alpha channel take it.  At 0 nothing changes:
+ * the same kernels, names, bytes and return codes (a CHW surface is then an unknown format to the rescales).
+ * The surface is laid out as under PLANAR CHW TARGETS with the view's size for the frame's: bgra the e-aligned base of plane 0,
+ * stride the pitch of every plane (a multiple of e, OW * e <= stride <= 2^32 - 1, else BT709HIP_ERR_STRIDE), plane c starting
+ * c * OH * stride bytes (a 64-bit product) behind plane 0; planes R, G, B, and A from an alpha decoder; an opaque decoder ignores
+ * bt709hip_decoder_set_alpha_fill.  Nothing outside the OW * e bytes of each plane row is written.
+ * Per output pixel, with s the word the same call, on the same decoder and frames, writes into a BGRA8_SRGB target of the same size
+ * with BT709HIP_OPT_SCALE_INTERMEDIATE at its default (DESIGN.md 3.3's filter in linear light on sRGB bytes): the element of plane c
+ * is PLANAR CHW TARGETS' function of the byte s_c -- CHW_U8 the byte; CHW_F16 / _F32 float(s_c) * (1/255f), * scale_c, + bias_c in
+ * three separately rounded binary32 operations (BT709HIP_OPT_CHW_SCALE_* / _BIAS_*, each read once per call, travelling as kernel
+ * arguments), then binary16 for CHW_F16; the A plane float(s_A) * (1/255f) of the FILTERED alpha, colour staying premultiplied.
+ * bt709hip_decode_half[_batch] with a CHW target runs the any-ratio kernel at ratio 2.0 (as under BT709HIP_OPT_SCALED_OVER: no
+ * persistent 2:1 variant, the half-kernel options ignored; W, H % 4 == 0 stays) and equals bt709hip_decode_scaled at exactly half.
+ * Validation order, codes and limits are the rescale's own (OH <= 65535; 32 surfaces through the pointer table, 65535 evenly
+ * spaced); a batch whose surfaces differ in format where one is CHW: BT709HIP_ERR_INVALID_ARG.  Refused with
+ * BT709HIP_ERR_UNSUPPORTED behind the usual validation and the I420 / COMPOSITE_OVER / UNPREMULTIPLY refusals, nothing written or
+ * launched: a CHW target while BT709HIP_OPT_SCALE_INTERMEDIATE is BT709HIP_FORMAT_RGBA16F; a CHW target while
+ * BT709HIP_OPT_SCALED_OVER is not BT709HIP_OVER_OFF; a CHW surface whose planes together (planes * OH * stride) reach 2 GiB (the
+ * kernels form offsets into the surface in 32 bits).  bt709hip_last_kernel_name: "decode_nv12_scaled_chw<u8>",
+ * "decode_nv12_scaled_chw<f16,alpha>", "decode_nv12_scaled_chw<f32>", ...; bt709hip_last_scaled_launch_info is filled as for the
+ * BGRA8 launch, with the tap form the BGRA8 call of the same frames and view takes (the count of resident workgroups is the launched
+ * kernel's own).  NOT covered: CHW through the RGBA16Float intermediate; blended or straight-alpha CHW views; I420 input to the
+ * rescales; bt709hip_render_scaled into CHW; rings (half_scale), pools and shards with CHW targets; bt709hip_decoder_prepare_format
+ * of a CHW format; an antialiased (area) filter -- the filter is bt709hip_decode_scaled's two-tap bilinear. */
+#define BT709HIP_OPT_SCALED_CHW 22 /* 0 (default) / 1; ids 13, 20 and 21 are no option */
 /* PLANAR CHW INPUT (BT709HIP_CTX_OPT_ENCODE_CHW_INPUT; definition: DESIGN.md 3.15).  The way back of the targets above: a model's output
  * -- super-resolution, denoising, interpolation -- is a CHW or NCHW tensor, and with the option at 1 bt709hip_encode and
  * bt709hip_encode_batch take it as it lies, in ONE launch that reads 3 e and writes 1.5 bytes per pixel (e = 1, 2 or 4): no

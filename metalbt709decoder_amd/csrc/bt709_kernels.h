@@ -135,6 +135,17 @@ struct DecodeParams {
 static_assert(offsetof(DecodeParams, chw_elem) == offsetof(DecodeParams, rep_dec_log2) && offsetof(DecodeParams, chw_scale) == offsetof(DecodeParams, rep_enc_log2) &&
                   offsetof(DecodeParams, chw_bias) == offsetof(DecodeParams, cursor_tx) && offsetof(DecodeParams, chw_bias) + sizeof(float[3]) == offsetof(DecodeParams, xcd_bands),
               "the CHW fields alias rep_dec_log2 .. cursor_f exactly");
+// The any-ratio rescale into CHW targets (bt709_rescale_chw.hip) meets the same union from its other side: gather_batch
+// fills chw_elem, chw_scale and chw_bias, and launch_decode_scaled fills tiles_x and tile_rows for its persistent forms -- the words of
+// chw_scale[1] and chw_scale[2].  So that launcher moves the three scales, in its private copy and before it plans the grid, into
+// over_lin[3], which a CHW launch never needs (it is never blended) and which is the only place the CHW rescale kernels read them from;
+// chw_elem and chw_bias lie on rep_dec_log2 and cursor_*, which no any-ratio kernel reads or launcher writes, and stay where they are.
+static_assert(offsetof(DecodeParams, tiles_x) == offsetof(DecodeParams, chw_scale) + sizeof(float) &&
+                  offsetof(DecodeParams, tile_rows) == offsetof(DecodeParams, chw_scale) + 2 * sizeof(float) &&
+                  offsetof(DecodeParams, chw_bias) == offsetof(DecodeParams, cursor_tx),
+              "launch_decode_scaled's tiles_x / tile_rows overwrite chw_scale[1..2] and nothing else of the CHW fields");
+static_assert(offsetof(DecodeParams, over_lin) >= offsetof(DecodeParams, xcd_bands) && sizeof(DecodeParams::over_lin) == sizeof(DecodeParams::chw_scale),
+              "the CHW rescale's scales travel in over_lin, outside the words the launcher fills");
 static_assert(sizeof(DecodeParams) == 1288 && offsetof(DecodeParams, v_offset) == 1280, "a field added to DecodeParams moves the implicit kernel arguments behind it: every decode kernel's code changes");
 enum : uint32_t { kChromaNV12 = 0, kChromaI420 = 1 };  // == BT709HIP_CHROMA_*
 enum : uint32_t { kChwNone = 0, kChwU8 = 1, kChwF16 = 2, kChwF32 = 3 };  // DecodeParams::chw_elem: BT709HIP_FORMAT_CHW_* - 3
@@ -205,9 +216,12 @@ void record_scaled_launch(const ScaledLaunchRecord &record);
 // The any-ratio kernels and pass 2 alone form row offsets in 32 bits (the scalar offset of a raw buffer resource of 2^31 - 1
 // records): a plane of `rows` rows must end below 2 GiB.  What the two launchers refuse with nullptr (and their test doubles with them).
 inline bool plane_fits(uint64_t rows, uint64_t stride) { return rows * stride < (1ull << 31); }
+// A planar CHW target (chw_elem set): its 3 or 4 planes are ONE surface to the kernels, which reach plane c through a 32-bit offset
+// c x OH x pitch -- all of them together must end below 2 GiB.
 inline bool scaled_planes_fit(const DecodeParams &p, bool has_alpha) {
+  const uint64_t out_planes = p.chw_elem != kChwNone ? (has_alpha ? 4u : 3u) : 1u;
   return plane_fits(p.height, p.y_stride) && plane_fits(p.height / 2, p.cbcr_stride) && (!has_alpha || plane_fits(p.height, p.alpha_stride)) &&
-         plane_fits(p.out_height, p.out_stride);
+         plane_fits(out_planes * p.out_height, p.out_stride);
 }
 inline bool render_planes_fit(const RenderParams &p) { return plane_fits(p.height, p.in_stride) && plane_fits(p.out_height, p.out_stride); }
 // grid = (column tiles, strips of `rows` output rows, frames)

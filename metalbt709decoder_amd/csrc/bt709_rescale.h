@@ -223,5 +223,8 @@ ScaledKernels scaled_f16_kernels();
 inline size_t scaled_f16_lds(const DecodeParams &p) {
   return (p.half_table_bytes ? kHalfPlanLds : 0u) + static_cast<size_t>(p.table_encode_bytes);
 }
+// bt709_rescale_chw.hip: the rows into planar CHW targets of element type `elem` (DecodeParams::chw_elem: kChwU8 / kChwF16 / kChwF32);
+// `curve` and `over` take anything (such a launch goes through the 8-bit intermediate and is never blended), the LDS is the 8-bit kernels'
+ScaledKernels scaled_chw_kernels(uint32_t elem);
 
 }  // namespace bt709

@@ -6,8 +6,8 @@
 //   decode_nv12_scaled_over   the same for an alpha decoder, each word blended over the destination or a colour before the store
 //   render_scaled          pass 2 alone from an 8-bit or RGBA16Float intermediate
 // Both walk a strip with walk_strip; each keeps its own fetch, its own conversion to linear light, its encode and its store.
-// Launch selection is a table: kScaledKernels here, bt709_rescale_f16.hip's rows behind scaled_f16_kernels(), kRenderKernels for
-// pass 2 -- a launch looks its row up, prepare_scaled_kernels walks all three.
+// Launch selection is a table: kScaledKernels here, bt709_rescale_f16.hip's rows behind scaled_f16_kernels(), bt709_rescale_chw.hip's
+// (planar CHW views) behind scaled_chw_kernels(), kRenderKernels for pass 2 -- a launch looks its row up, prepare_scaled_kernels walks them all.
 #include <atomic>
 
 #include "bt709_scaled_strip.h"
@@ -242,9 +242,10 @@ const struct RenderKernel {
   const char *name;
 } kRenderKernels[2] = {{render_scaled<false>, "render_scaled<bgra8>"}, {render_scaled<true>, "render_scaled<rgba16f>"}};
 
-// the row of a launch: through the RGBA16Float intermediate (`f16`) bt709_rescale_f16.hip's, else this file's
-const ScaledKernel *scaled_kernel(bool f16, int taps, bool has_alpha, bool curve, uint32_t over) {
-  for (const ScaledKernel &k : f16 ? scaled_f16_kernels() : ScaledKernels(kScaledKernels))
+// the row of a launch: into a planar CHW target (`elem`) bt709_rescale_chw.hip's, through the RGBA16Float intermediate (`f16`)
+// bt709_rescale_f16.hip's, else this file's
+const ScaledKernel *scaled_kernel(uint32_t elem, bool f16, int taps, bool has_alpha, bool curve, uint32_t over) {
+  for (const ScaledKernel &k : elem != kChwNone ? scaled_chw_kernels(elem) : (f16 ? scaled_f16_kernels() : ScaledKernels(kScaledKernels)))
     if (selects(k.taps, taps) && selects(k.alpha, has_alpha) && selects(k.curve, curve) && selects(k.over, static_cast<int>(over))) return &k;
   return nullptr;  // unreachable: the rows of a tap form end in one that takes every remaining selector
 }
@@ -320,7 +321,15 @@ const char *launch_decode_scaled(const DecodeParams &p_in, int frames, bool has_
   const bool f16 = p.scale_f16 != 0;
   // BT709HIP_OPT_SCALED_OVER: the *_over kernels (the one launched is the one whose occupancy sizes the grid), lin[256] behind their tables
   const uint32_t over = has_alpha ? p.over_mode : kOverOff;
-  const ScaledKernel *k = scaled_kernel(f16, taps, has_alpha, p.half_table_bytes != 0, over);
+  // a planar CHW target (BT709HIP_OPT_SCALED_CHW; gather_batch set chw_elem): the kernels of bt709_rescale_chw.hip, the same plan.
+  // Their scales move to over_lin HERE, in the private copy: tiles_x and tile_rows below are the words of chw_scale[1..2]
+  // (bt709_kernels.h).  Neither through the RGBA16Float intermediate nor blended: the shim refuses both before it gets here.
+  const uint32_t elem = p.chw_elem;
+  if (elem != kChwNone) {
+    if (elem > kChwF32 || f16 || over != kOverOff) return nullptr;
+    for (int c = 0; c < 3; ++c) p.over_lin[c] = p.chw_scale[c];
+  }
+  const ScaledKernel *k = scaled_kernel(elem, f16, taps, has_alpha, p.half_table_bytes != 0, over);
   if (!k) return nullptr;
   const void *fn = reinterpret_cast<const void *>(k->fn);
   const bool by_wave = taps == TAPS_ONCE || taps == TAPS_SHARED, persistent = k->persistent;
@@ -359,7 +368,7 @@ const char *launch_decode_scaled(const DecodeParams &p_in, int frames, bool has_
 }
 
 hipError_t prepare_scaled_kernels() {
-  for (const ScaledKernels &rows : {ScaledKernels(kScaledKernels), scaled_f16_kernels()})
+  for (const ScaledKernels &rows : {ScaledKernels(kScaledKernels), scaled_f16_kernels(), scaled_chw_kernels(kChwU8), scaled_chw_kernels(kChwF16), scaled_chw_kernels(kChwF32)})
     for (const ScaledKernel &k : rows)
       if (const hipError_t e = raise_lds_cap(k.fn, kRepLdsBytes)) return e;
   for (const RenderKernel &k : kRenderKernels)

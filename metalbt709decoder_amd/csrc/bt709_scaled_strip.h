@@ -6,6 +6,8 @@
 #pragma once
 #include "bt709_over.h"
 #include "bt709_rescale.h"
+// behind the HIP runtime's header (bt709_rescale.h): its functions are __host__ __device__ __forceinline__ under hipcc
+#include "bt709_chw_norm.h"
 
 namespace bt709 {
 namespace {
@@ -293,10 +295,19 @@ struct Srgb8Light {
 //     mode: the lane loads the word it is about to overwrite at the top of output_row (the row's conversion and filter hide the
 //     latency; the wait also covers the rows fetched ahead, issued before it -- vmcnt is in order).  A by-wave lane past the row's
 //     end loads the last column's word again (in bounds) and drops it with its store.
-template <int TAPS, bool HAS_ALPHA, int OVER = kOverOff, typename TapLight>
+//   ELEM (kChwU8 / kChwF16 / kChwF32; bt709_rescale_chw.hip; never together with OVER): the output is a planar CHW
+//     surface -- f.out the base of plane 0, p.out_stride the pitch of every plane, plane c starting c * OH * pitch behind it.  R, G, B
+//     and the alpha byte are worked out exactly as for the word; in place of the word's store the lane stores, per plane, ONE element
+//     (bt709_chw_norm.h of that byte) at vector offset ox * e, the plane and the row riding in the scalar offset.  Consecutive lanes
+//     own consecutive columns: a wave's store instruction fills 64 e contiguous bytes of a plane's row.  The scales travel in
+//     p.over_lin (launch_decode_scaled moves them there: bt709_kernels.h).  BOUNDS of a store: c < PLANES, oy < oy1 <= OH, ox < OW
+//     (the caller's early return, or `live`): inside the OW e bytes of a row of a plane the surface has; the launcher holds
+//     PLANES * OH * pitch under 2 GiB (scaled_planes_fit), so the 32-bit offsets do not wrap.
+template <int TAPS, bool HAS_ALPHA, int OVER = kOverOff, uint32_t ELEM = kChwNone, typename TapLight>
 __device__ __forceinline__ void scaled_strip(const DecodeParams &p, const TapLight &light, const FramePlanes &f, uint32_t ox_raw, uint32_t oy0,
                                              uint32_t oy1, const StripTaps &vt, const OverLookup &ov = OverLookup{}) {
   static_assert(OVER == kOverOff || HAS_ALPHA, "there is nothing to composite without an alpha channel");
+  static_assert(ELEM == kChwNone || OVER == kOverOff, "a planar CHW view is never blended");
   // TAPS_SHARED / TAPS_ONCE: every lane of the wave stays alive; one past the row's end works on the last column again and does not store
   constexpr bool BY_WAVE = TAPS == TAPS_SHARED || TAPS == TAPS_ONCE;
   constexpr int N = HAS_ALPHA ? 4 : 3;  // R, G, B and the byteNorm of the alpha tap (alpha decoders)
@@ -467,6 +478,27 @@ __device__ __forceinline__ void scaled_strip(const DecodeParams &p, const TapLig
                                               ox * 4u, oy * p.out_stride, kScaledStoreAux);
       return;
     }
+    if constexpr (ELEM != kChwNone) {
+      constexpr int PLANES = HAS_ALPHA ? 4 : 3;
+      const uint32_t code[4] = {R, G, B, aw >> 24};
+      const uint32_t plane = p.out_height * p.out_stride, row = oy * p.out_stride;  // uniform: scalar arithmetic
+#pragma unroll
+      for (int c = 0; c < PLANES; ++c) {
+        const uint32_t so = static_cast<uint32_t>(c) * plane + row;
+        if constexpr (ELEM == kChwU8) {
+          if (!BY_WAVE || live) __builtin_amdgcn_raw_buffer_store_b8(static_cast<uint8_t>(code[c]), ro, ox, so, kScaledStoreAux);
+        } else {
+          float t = c < 3 ? chw_norm(static_cast<float>(code[c]), p.over_lin[c], p.chw_bias[c % 3]) : chw_unit(static_cast<float>(code[c]));
+          asm("" : "+v"(t));  // binary32 first, then binary16 (bt709_chw.hip chw_row): the pin keeps the conversion a conversion
+          if constexpr (ELEM == kChwF16) {
+            if (!BY_WAVE || live) __builtin_amdgcn_raw_buffer_store_b16(chw_half_bits(t), ro, ox * 2u, so, kScaledStoreAux);
+          } else {
+            if (!BY_WAVE || live) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(t), ro, ox * 4u, so, kScaledStoreAux);
+          }
+        }
+      }
+      return;
+    }
     if (!BY_WAVE || live)
       __builtin_amdgcn_raw_buffer_store_b32(pack_bgra(R, G, B, aw), ro, ox * 4u, oy * p.out_stride, kScaledStoreAux);
   };
@@ -481,6 +513,7 @@ __device__ __forceinline__ void scaled_strip(const DecodeParams &p, const TapLig
 // The PERSISTENT ITEM LOOP of a fused kernel <TAPS, ...> with parameter block `p`, as TEXT (it has to sit in the kernel function
 // itself: bt709_rescale_scaled.hip, BT709_SCALED_WALK): workgroup g takes the items g, g + G, ... of the launch, an item = 256 output
 // columns x one strip of one frame, column tiles fastest (launch_decode_scaled fills tiles_x and tile_rows).  `light`: the TapLight.
+// OVER is handed on as scaled_strip's template arguments behind HAS_ALPHA: bt709_rescale_chw.hip passes "kOverOff, ELEM" through it.
 #define BT709_SCALED_ITEM_LOOP(HAS_ALPHA, OVER, light, ov)                                                                               \
   const uint32_t strips = (p.out_height + p.scaled_rows - 1) / p.scaled_rows;                                                            \
   for (uint32_t item = blockIdx.x; item < p.tile_rows; item += gridDim.x) {                                                              \

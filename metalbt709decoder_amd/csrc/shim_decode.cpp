@@ -266,6 +266,10 @@ int bt709hip_decoder_set_option(bt709hip_decoder *dec, int option, int value) {
       if (!dec->has_alpha) return BT709HIP_ERR_UNSUPPORTED;  // nothing to divide by
       dec->unpremultiply = value;
       return BT709HIP_OK;
+    case BT709HIP_OPT_SCALED_CHW:  // host state alone: nothing is built for it, so it may change while a graph is recorded
+      if (value != 0 && value != 1) return BT709HIP_ERR_INVALID_ARG;
+      dec->scaled_chw = value;
+      return BT709HIP_OK;
     case BT709HIP_OPT_CHW_SCALE_R: case BT709HIP_OPT_CHW_SCALE_G: case BT709HIP_OPT_CHW_SCALE_B:
     case BT709HIP_OPT_CHW_BIAS_R: case BT709HIP_OPT_CHW_BIAS_G: case BT709HIP_OPT_CHW_BIAS_B:  // a binary32's bits: +-0, or finite in [2^-64, 2^64]
       if (!chw_norm_bits_valid(static_cast<uint32_t>(value))) return BT709HIP_ERR_INVALID_ARG;
@@ -290,6 +294,7 @@ int bt709hip_decoder_get_option(const bt709hip_decoder *dec, int option, int *va
     case BT709HIP_OPT_SCALED_OVER: *value = dec->scaled_over; return BT709HIP_OK;
     case BT709HIP_OPT_CHROMA_LAYOUT: *value = dec->chroma_layout; return BT709HIP_OK;
     case BT709HIP_OPT_UNPREMULTIPLY: *value = dec->unpremultiply; return BT709HIP_OK;
+    case BT709HIP_OPT_SCALED_CHW: *value = dec->scaled_chw; return BT709HIP_OK;
     case BT709HIP_OPT_CHW_SCALE_R: case BT709HIP_OPT_CHW_SCALE_G: case BT709HIP_OPT_CHW_SCALE_B:
     case BT709HIP_OPT_CHW_BIAS_R: case BT709HIP_OPT_CHW_BIAS_G: case BT709HIP_OPT_CHW_BIAS_B:
       *value = static_cast<int>(dec->chw_norm[option - BT709HIP_OPT_CHW_SCALE_R].load());
@@ -371,6 +376,8 @@ int gather_batch(bt709hip_decoder *dec, int count, const bt709hip_frame *frames,
   if (dec == nullptr || frames == nullptr || outs == nullptr || count < 0) return BT709HIP_ERR_INVALID_ARG;
   // an alpha buffer handed to an opaque decoder is validated (.m:294-306, 357-368) but not read
   const bt709hip_frame *planes_a = dec->has_alpha ? alphas : nullptr;
+  // planar CHW surfaces: the 1:1 decode's, and with BT709HIP_OPT_SCALED_CHW (read once) the fused rescales' 
+  const bool chw_ok = shape == OutShape::kSame || dec->scaled_chw != 0;
   info->uniform = evenly_spaced(count, frames, planes_a, outs);
   if (count > (info->uniform ? kMaxUniformBatch : kMaxBatch)) return BT709HIP_ERR_UNSUPPORTED;
   if (int rc = ensure_setup(dec, stream)) return rc;
@@ -389,8 +396,8 @@ int gather_batch(bt709hip_decoder *dec, int count, const bt709hip_frame *frames,
     const int want_w = shape == OutShape::kSame ? f.width : (shape == OutShape::kHalf ? f.width / 2 : o.width);
     const int want_h = shape == OutShape::kSame ? f.height : (shape == OutShape::kHalf ? f.height / 2 : o.height);
     if (shape == OutShape::kAny && (o.width < 0 || o.height < 0)) return BT709HIP_ERR_INVALID_ARG;
-    if (int rc = validate(dec, layout, &f, a, &o, want_w, want_h, o.width, o.height, shape == OutShape::kSame)) return rc;
-    if (o.format != BT709HIP_FORMAT_BGRA8_SRGB && shape != OutShape::kSame) return BT709HIP_ERR_UNSUPPORTED;
+    if (int rc = validate(dec, layout, &f, a, &o, want_w, want_h, o.width, o.height, chw_ok)) return rc;
+    if (o.format != BT709HIP_FORMAT_BGRA8_SRGB && !is_chw(o.format) && shape != OutShape::kSame) return BT709HIP_ERR_UNSUPPORTED;  // RGBA16F: the 1:1 decode's alone
     // a planar CHW surface among surfaces of another format (CHW or not): not a batch of one kind
     if ((is_chw(o.format) || is_chw(o0.format)) && o.format != o0.format) return BT709HIP_ERR_INVALID_ARG;
     if (f.width != f0.width || f.height != f0.height || f.y_stride != f0.y_stride || f.cbcr_stride != f0.cbcr_stride ||
@@ -498,9 +505,17 @@ int decode_batch_now(bt709hip_decoder *dec, int layout, int count, const bt709hi
   return finish_launch(s, wait_until_completed);
 }
 
+// BT709HIP_OPT_SCALED_CHW: a planar CHW view comes from the 8-bit sRGB intermediate and is never blended.  Checked
+// by both fused rescales behind their I420 / COMPOSITE_OVER / UNPREMULTIPLY refusals (`over`: the BT709HIP_OPT_SCALED_OVER they read).
+static int scaled_chw_refusal(const bt709hip_decoder *dec, const BatchInfo &info, int over) {
+  if (!is_chw(info.format)) return BT709HIP_OK;
+  if (dec->scale_intermediate == BT709HIP_FORMAT_RGBA16F) return BT709HIP_ERR_UNSUPPORTED;
+  return over != BT709HIP_OVER_OFF ? BT709HIP_ERR_UNSUPPORTED : BT709HIP_OK;
+}
+
 // The any-ratio launch of a gathered batch (p.out_width x p.out_height set): bt709hip_decode_scaled_batch, and
-// bt709hip_decode_half_batch when the rescale goes through the RGBA16Float intermediate (BT709HIP_OPT_SCALE_INTERMEDIATE) or blends
-// (`over`: the value of BT709HIP_OPT_SCALED_OVER the call read)
+// bt709hip_decode_half_batch when the rescale goes through the RGBA16Float intermediate (BT709HIP_OPT_SCALE_INTERMEDIATE), blends
+// (`over`: the value of BT709HIP_OPT_SCALED_OVER the call read) or writes planar CHW surfaces (BT709HIP_OPT_SCALED_CHW)
 static int launch_scaled(bt709hip_decoder *dec, DecodeParams &p, const BatchInfo &info, int count, int over, void *stream, int wait_until_completed) {
   if (p.out_height > static_cast<uint32_t>(kMaxGridYZ)) return BT709HIP_ERR_UNSUPPORTED;
   if (over != BT709HIP_OVER_OFF)
@@ -519,7 +534,7 @@ static int launch_scaled(bt709hip_decoder *dec, DecodeParams &p, const BatchInfo
   hipStream_t s = pick(dec->ctx, stream);
   const char *name = launch_decode_scaled(p, count, dec->has_alpha != 0, info.in_align,
                                           static_cast<uint32_t>(dec->ctx->props.multiProcessorCount), s);
-  if (name == nullptr) return BT709HIP_ERR_UNSUPPORTED;  // a plane of 2 GiB or more
+  if (name == nullptr) return BT709HIP_ERR_UNSUPPORTED;  // a plane of 2 GiB or more (a CHW surface: its planes together)
   set_kernel_name(name);
   return finish_launch(s, wait_until_completed);
 }
@@ -548,9 +563,12 @@ int decode_half_batch_layout(bt709hip_decoder *dec, int layout, int count, const
   const int over = dec->scaled_over;
   if (over == BT709HIP_OVER_OFF && dec->composite_over != BT709HIP_OVER_OFF) return BT709HIP_ERR_UNSUPPORTED;
   if (dec->unpremultiply != 0) return BT709HIP_ERR_UNSUPPORTED;  // BT709HIP_OPT_UNPREMULTIPLY: the filters want premultiplied colour
+  if (int rc = scaled_chw_refusal(dec, info, over)) return rc;
   if (p.width == 0) return BT709HIP_OK;
-  // through the RGBA16Float intermediate, or blended: the any-ratio kernel at ratio 2.0 (no persistent 2:1 variant; the half-kernel options are not read)
-  if (dec->scale_intermediate == BT709HIP_FORMAT_RGBA16F || over != BT709HIP_OVER_OFF) return launch_scaled(dec, p, info, count, over, stream, wait_until_completed);
+  // through the RGBA16Float intermediate, blended, or into planar CHW surfaces: the any-ratio kernel at ratio 2.0 (no persistent 2:1
+  // variant; the half-kernel options are not read)
+  if (dec->scale_intermediate == BT709HIP_FORMAT_RGBA16F || over != BT709HIP_OVER_OFF || is_chw(info.format))
+    return launch_scaled(dec, p, info, count, over, stream, wait_until_completed);
   hipStream_t s = pick(dec->ctx, stream);
   // wide: same tiling as the 1:1 kernel over the source width; narrow: 256 output pixels per workgroup
   const bool wide = info.in_align >= 4 && info.out_align >= 8;
@@ -619,6 +637,7 @@ int bt709hip_decode_scaled_batch(bt709hip_decoder *dec, int count, const bt709hi
   const int over = dec->scaled_over;  // BT709HIP_OPT_SCALED_OVER blends here; without it BT709HIP_OPT_COMPOSITE_OVER (the 1:1 path only) refuses
   if (over == BT709HIP_OVER_OFF && dec->composite_over != BT709HIP_OVER_OFF) return BT709HIP_ERR_UNSUPPORTED;
   if (dec->unpremultiply != 0) return BT709HIP_ERR_UNSUPPORTED;  // BT709HIP_OPT_UNPREMULTIPLY: the filters want premultiplied colour
+  if (int rc = scaled_chw_refusal(dec, info, over)) return rc;
   if (p.width == 0) return BT709HIP_OK;
   return launch_scaled(dec, p, info, count, over, stream, wait_until_completed);
 }

@@ -98,6 +98,7 @@ struct bt709hip_decoder {
   std::atomic<int> scaled_over{BT709HIP_OVER_OFF};     // BT709HIP_OPT_SCALED_OVER: the same three forms, read by the rescale paths alone
   std::atomic<int> chroma_layout{BT709HIP_CHROMA_NV12};  // BT709HIP_OPT_CHROMA_LAYOUT: how bt709hip_decode[_batch] read the CALLER's colour frames
   std::atomic<int> unpremultiply{0};                     // BT709HIP_OPT_UNPREMULTIPLY: the 1:1 decode of an alpha decoder writes straight alpha
+  std::atomic<int> scaled_chw{0};                        // BT709HIP_OPT_SCALED_CHW: the fused rescales take planar CHW targets
   // BT709HIP_OPT_CHW_SCALE_R, _G, _B, BT709HIP_OPT_CHW_BIAS_R, _G, _B: binary32 bit patterns (1.0f, 0.0f), read by decodes into CHW targets
   std::atomic<uint32_t> chw_norm[6] = {{0x3f800000u}, {0x3f800000u}, {0x3f800000u}, {0u}, {0u}, {0u}};
   std::mutex queue_mutex;   // guards queues
@@ -180,7 +181,8 @@ int finish_launch(hipStream_t s, int wait_until_completed);
 int required_transfer(int gamma);
 // `layout` (here and below): BT709HIP_CHROMA_* of the colour frames.  The public entry points pass the decoder's option; the
 // objects that allocate their own (NV12) frames -- ring, ring set, pool, shard -- pass BT709HIP_CHROMA_NV12 whatever it holds.
-// `chw_ok`: the call is a 1:1 decode, the one place a planar CHW surface (BT709HIP_FORMAT_CHW_*) is a format at all
+// `chw_ok`: a planar CHW surface (BT709HIP_FORMAT_CHW_*) is a format at all: the call is a 1:1 decode, or a fused rescale of a decoder
+// with BT709HIP_OPT_SCALED_CHW on
 int validate(const bt709hip_decoder *dec, int layout, const bt709hip_frame *f, const bt709hip_frame *a, const bt709hip_surface *o, int out_w,
              int out_h, int render_w, int render_h, bool chw_ok = false);
 inline bool is_chw(int format) { return format >= BT709HIP_FORMAT_CHW_U8 && format <= BT709HIP_FORMAT_CHW_F32; }

@@ -1343,6 +1343,30 @@ class MetalBT709Decoder:
         self.lastStatus = _capi.OK
         return True
 
+    @property
+    def scaledCHW(self):
+        """True: decodeBT709Scaled / decodeBT709ScaledBatch take CHWTextures of the view's size and write the rescaled, normalised
+        planar tensor in the one fused launch (_capi.OPT_SCALED_CHW): per element setCHWNormalisation's function of
+        the byte the BGRA8 rescale of the same frames writes.  False (the default): a CHWTexture is no target of the rescales.
+        While it is on, a CHW view under resizeTexturePixelFormat = RGBA16Float or scaledCompositeOver fails with ERR_UNSUPPORTED."""
+        return bool(self._options.get(_capi.OPT_SCALED_CHW, 0))
+
+    @scaledCHW.setter
+    def scaledCHW(self, flag):
+        self.setScaledCHW(flag)
+
+    def setScaledCHW(self, flag):
+        """The scaledCHW property with a status: True, or False with lastStatus set.  Never touches the device: it works while a
+        graph is recorded (before setupMetal the value is kept and applied there, like every option)."""
+        value = int(bool(flag))
+        if self._handle:
+            rc = self.metalRenderContext.lib.bt709hip_decoder_set_option(self._handle, _capi.OPT_SCALED_CHW, value)
+            if rc != _capi.OK:
+                return self._fail(rc, "scaledCHW")
+        self._options[_capi.OPT_SCALED_CHW] = value
+        self.lastStatus = _capi.OK
+        return True
+
     def setCHWNormalisation(self, scale=(1.0, 1.0, 1.0), bias=(0.0, 0.0, 0.0)):
         """Per-channel (R, G, B) scale and bias of the float CHW targets (_capi.OPT_CHW_SCALE_* / OPT_CHW_BIAS_*): an element is
         float32(byte) * float32(1/255) * scale + bias, three float32 operations each rounded on its own.  The
@@ -1512,7 +1536,10 @@ class MetalBT709Decoder:
                           alphaPixelBuffer=None):
         """-decodeBT709 into an intermediate + MetalScaleRenderContext -renderScaled:
         (AAPLRenderer.m:940-977), fused: the tuned kernel for the exact 2:1 ratio, the general
-        bilinear kernel for any other view size (bit-identical where both apply)."""
+        bilinear kernel for any other view size (bit-identical where both apply).
+        bgraSRGBTexture may be a CHWTexture of the view's size once scaledCHW is on (an exact half view takes the
+        half call, which then runs the any-ratio kernel at ratio 2.0).  With scaledCHW off a CHWTexture is an unknown format to the
+        rescales: False, lastStatus = ERR_INVALID_ARG."""
         if not self.setupMetal() or not self._set_layout([yCbCrInputTexture], "decodeBT709Scaled"):
             return False
         frame, surf = yCbCrInputTexture.frame(), bgraSRGBTexture.surface()
@@ -1533,7 +1560,9 @@ class MetalBT709Decoder:
                                alphaPixelBuffers=None):
         """Fused decode + rescale of `count` same-geometry frames into same-sized outputs in one launch
         (no reference twin): the 2:1 kernels when every output is exactly half the frame (large launches
-        run the persistent conflict-free kernel), the general bilinear kernel otherwise."""
+        run the persistent conflict-free kernel), the general bilinear kernel otherwise.
+        The textures may be CHWTextures of one element type once scaledCHW is on: an NCHW tensor's slices are an
+        evenly spaced batch, any number of them in one launch.  With scaledCHW off: False, lastStatus = ERR_INVALID_ARG."""
         if not self.setupMetal() or not self._set_layout(pixelBuffers, "decodeBT709ScaledBatch"):
             return False
         n = len(pixelBuffers)
