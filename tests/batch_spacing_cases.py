@@ -1,7 +1,8 @@
 """Where the frames of a batched call lie (tests/test_batch_spacing_cpu.py, tests/test_batch_spacing_gpu.py; numpy and ctypes only).
 
-Every batched entry point finds frame i of a launch either in a pointer table (32 entries) or, when the caller's pointers are
-evenly spaced, as frame 0 + i * step with one signed 64-bit step per plane -- and ANY two frames are evenly spaced.  The rest
+Every batched entry point finds frame i of a launch either in a pointer table (32 entries; 31 for an encode of planar CHW
+tensors) or, when the caller's pointers are evenly spaced, as frame 0 + i * step with one signed 64-bit step per plane -- and
+ANY two frames are evenly spaced.  The rest
 of the suite carves its frames in ascending order at one positive pitch from one slab.  build(route, cls) lays the planes of a
 ROUTE (an entry point and a kernel form: its planes, sizes, decoder options and the kernel it must report) out in one input and
 one output slab under a SPACING CLASS:
@@ -23,12 +24,21 @@ whole span), the far classes one per frame and plane -- the samples with a guard
 plane where a step cut to its low 32 bits would land: frame 0 + d (far: zero- or sign-extended alike), frame 0 - d
 (far-descending, sign-extended; zero-extended it leaves the slab, which is why that class is never run against a variant that
 cuts the step).  Layout.check() asserts, on the CPU, that all of them lie inside their slab, apart from one another by at least
-a guard band."""
+a guard band.
+
+A plane is rows at one pitch.  Two kinds of plane STACK several: the "cbcr" plane of an I420 frame (U's rows, then V's) and a
+planar CHW surface (planes R, G, B and, from an alpha decoder, A; plane c starts c x H x pitch behind
+plane 0) -- one Plane of planes x H rows of W x e bytes, unit e.  An opaque decoder's CHW target is given the ROOM of a fourth
+plane behind its three, inside the frame's window: that nothing is written there is part of every comparison.  The CHW routes
+close the table: the 1:1 decode into CHW targets (fast and general kernel, u8 / f16 / f32, NV12 and I420 frames), the fused
+rescale into CHW views (a per-lane and a by-wave tap form) and the encoder reading CHW tensors (into NV12 and into I420)."""
 import ctypes as C
 import zlib
 
 import numpy as np
 
+import chw_cases as cc
+import encode_chw_cases as ecc
 from metalbt709decoder_amd import _capi
 from metalbt709decoder_amd._capi import Frame, Surface
 
@@ -61,11 +71,13 @@ def _up(v, a):
 
 class Plane:
     """rows x row_bytes samples at pitch `stride`; unit: what the entry point requires a base pointer to be a multiple of (1: any
-    address is accepted, so the skewed classes apply)."""
+    address is accepted, so the skewed classes apply); room: bytes behind the last row that hold no sample and lie inside a
+    window all the same (an opaque decoder's planar CHW target: where a fourth plane would be); stacked: how many planes of a
+    planar CHW surface the rows are (1: no such surface)."""
 
-    def __init__(self, name, row_bytes, rows, stride, unit=1):
-        assert stride >= row_bytes
-        self.name, self.row_bytes, self.rows, self.stride, self.unit = name, row_bytes, rows, stride, unit
+    def __init__(self, name, row_bytes, rows, stride, unit=1, room=0, stacked=1):
+        assert stride >= row_bytes and rows % stacked == 0
+        self.name, self.row_bytes, self.rows, self.stride, self.unit, self.room, self.stacked = name, row_bytes, rows, stride, unit, room, stacked
         self.extent = stride * (rows - 1) + row_bytes
 
     def index(self, off):
@@ -76,14 +88,34 @@ class Plane:
 class Route:
     """entry: "decode" | "half" | "scaled" | "render" | "unconvert" | "encode".  size / out_size: (w, h) of a frame and of its
     target.  kernel: what bt709hip_last_kernel_name must report; taps: (tap form, persistent) of bt709hip_last_scaled_launch_info;
-    skew: skew residue -> (kernel, taps) of the demoted launch; bands: the launch splits under bands-tail-descending."""
+    skew: skew residue -> (kernel, taps) of the demoted launch; bands: the launch splits under bands-tail-descending.
+    chw: the element type ("uint8" / "float16" / "float32") of the route's planar CHW side -- the target of a decode, the input
+    of an encode -- which is ONE plane of chw_planes x H rows of W x e bytes; norm: its (scale, bias) setting, which the decoder
+    options / context options carry; ctx_options: context options set for every call and put back to CTX_DEFAULTS after it;
+    table: the most frames the entry point's pointer table holds."""
 
     def __init__(self, name, entry, size, out_size, ins, outs, kernel, gamma=GAMMA_APPLE, alpha=False, options=(), over=None, fmt=SRGB8,
-                 in_fmt=SRGB8, taps=None, skew=None, bands=False, reads_destination=False, pair=None, no_skew=None):
+                 in_fmt=SRGB8, taps=None, skew=None, bands=False, reads_destination=False, pair=None, no_skew=None, chw=None, norm=None,
+                 ctx_options=(), table=32):
         self.name, self.entry, self.size, self.out_size, self.ins, self.outs, self.kernel = name, entry, size, out_size, ins, outs, kernel
         self.gamma, self.alpha, self.options, self.over, self.fmt, self.in_fmt = gamma, alpha, tuple(options), over, fmt, in_fmt
         self.taps, self.skew, self.bands, self.reads_destination, self.pair, self.no_skew = taps, skew, bands, reads_destination, pair, no_skew
+        self.chw, self.norm, self.ctx_options, self.table = chw, norm, tuple(ctx_options), table
         self.key = name  # what frame_data / want remember a route's frames under: a resized copy (tests/extent_cases.py) takes its own
+
+    @property
+    def planar_chroma(self):
+        """The "cbcr" plane is U's rows, then V's, at one pitch (I420): the frames a decoder reads, or the ones the encoder writes."""
+        return (dict(self.options).get(_capi.OPT_CHROMA_LAYOUT) == _capi.CHROMA_I420
+                or dict(self.ctx_options).get(_capi.CTX_OPT_ENCODE_CHROMA_LAYOUT) == _capi.CHROMA_I420)
+
+    @property
+    def elem(self):
+        return np.dtype(self.chw).itemsize
+
+    @property
+    def chw_planes(self):
+        return 4 if self.alpha and self.entry != "encode" else 3
 
     def plane(self, name):
         return next(p for p in self.ins + self.outs if p.name == name)
@@ -111,8 +143,32 @@ def _out(ow, oh, pad, px=4):
     return [Plane("out", px * ow, oh, px * ow + pad, unit=px)]
 
 
+def _chw_out(ow, oh, dtype, planes, pad):
+    """A planar CHW target: planes R, G, B (and A) stacked at one pitch, as the "cbcr" plane of an I420 frame stacks U and V.  An
+    opaque decoder's three planes are given the room of a fourth behind them."""
+    e = np.dtype(dtype).itemsize
+    return [Plane("out", e * ow, planes * oh, e * ow + pad, unit=e, room=(4 - planes) * oh * (e * ow + pad), stacked=planes)]
+
+
+def _chw_in(w, h, dtype, pad):
+    """A planar CHW tensor the encoder reads: planes R, G, B (a fourth is never touched)."""
+    e = np.dtype(dtype).itemsize
+    return [Plane("chw", e * w, 3 * h, e * w + pad, unit=e, stacked=3)]
+
+
+def _settings(first, setting):
+    return tuple((first + i, cc.bits(v)) for i, v in enumerate(tuple(setting[0]) + tuple(setting[1])))
+
+
+CHW_NORM = _settings(_capi.OPT_CHW_SCALE_R, cc.IMAGENET)  # BT709HIP_OPT_CHW_SCALE_R .. _BIAS_B of a decoder
+NV12, I420 = _capi.CHROMA_NV12, _capi.CHROMA_I420
+# what a context holds before and after a call of a route with ctx_options
+CTX_DEFAULTS = dict(((_capi.CTX_OPT_ENCODE_CHW_INPUT, 0), (_capi.CTX_OPT_ENCODE_CHROMA_LAYOUT, NV12)) + _settings(_capi.CTX_OPT_ENCODE_CHW_SCALE_R, ecc.IDENTITY))
+_encode_chw = lambda layout: ((_capi.CTX_OPT_ENCODE_CHW_INPUT, 1), (_capi.CTX_OPT_ENCODE_CHROMA_LAYOUT, layout)) + _settings(_capi.CTX_OPT_ENCODE_CHW_SCALE_R, ecc.IMAGENET)
+_chw_kernel = lambda dtype, layout, fast: ecc.kernel_name(dtype, layout, fast).encode()
+
 W, H = 64, 16
-HALF_REP = ((_capi.OPT_HALF_KERNEL, 1), (_capi.OPT_HALF_WORKGROUPS, 3))  # three persistent workgroups: the cursor wraps from frame to frame
+HALF_REP =((_capi.OPT_HALF_KERNEL, 1), (_capi.OPT_HALF_WORKGROUPS, 3))  # three persistent workgroups: the cursor wraps from frame to frame
 ONCE, WIDE, PAIRS, BYTES = _capi.SCALED_TAPS_ONCE, _capi.SCALED_TAPS_WIDE, _capi.SCALED_TAPS_PAIRS, _capi.SCALED_TAPS_BYTES
 DOWN = dict(size=(W, H), out_size=(40, 10))  # 1.6 : 1 both ways, the per-lane (persistent) forms
 _scaled_skew = lambda kernel: {2: (kernel, (PAIRS, 1)), 1: (kernel, (BYTES, 1))}
@@ -168,6 +224,38 @@ ROUTES = [
     # an alpha clip's luma with cbcr == NULL in every frame: the split launch's tail passes advance_frames' `if (cbcr)`
     Route("encode-alpha-y", "encode", (W, H), (W, H), [Plane("bgra", 4 * W, H, 4 * W + 16, unit=4)], [Plane("y", W, H, 80)], b"encode_alpha_y",
           pair=(GAMMA_LINEAR, GAMMA_LINEAR), in_fmt=ALPHA8, bands=True, skew={2: (b"encode_alpha_y_blocks", None), 1: (b"encode_alpha_y_blocks", None)}),
+    # ---- planar CHW: plane c of a surface starts c x H x pitch behind plane 0, the one address product no
+    # route above forms.  Appended: _route_seed is the index.
+    # bt709hip_decode_batch into CHW targets.  A u8 plane is byte-addressed: a skewed step skews the target as well
+    Route("chw-quads-u8", "decode", (W, H), (W, H), _nv12(W, H, 80, 80), _chw_out(W, H, "uint8", 3, 16), b"decode_nv12_quads_chw<u8,nt>",
+          fmt=cc.FORMATS["uint8"], chw="uint8", bands=True, skew={2: (b"decode_nv12_blocks_chw<u8>", None), 1: (b"decode_nv12_blocks_chw<u8>", None)}),
+    Route("chw-quads-f16-alpha", "decode", (W, H), (W, H), _nv12(W, H, 80, 80, 96), _chw_out(W, H, "float16", 4, 16), b"decode_nv12_quads_chw<f16,alpha>",
+          gamma=GAMMA_SRGB, alpha=True, options=CHW_NORM, fmt=cc.FORMATS["float16"], chw="float16", norm=cc.IMAGENET, bands=True,
+          skew={2: (b"decode_nv12_blocks_chw<f16,alpha>", None), 1: (b"decode_nv12_blocks_chw<f16,alpha>", None)}),
+    Route("chw-quads-f32-i420", "decode", (W, H), (W, H), [Plane("y", W, H, 80), Plane("cbcr", W // 2, H, 48)], _chw_out(W, H, "float32", 3, 16),
+          b"decode_i420_quads_chw<f32,nt>", options=((_capi.OPT_CHROMA_LAYOUT, I420),) + CHW_NORM, fmt=cc.FORMATS["float32"], chw="float32",
+          norm=cc.IMAGENET, bands=True, skew={2: (b"decode_i420_blocks_chw<f32>", None), 1: (b"decode_i420_blocks_chw<f32>", None)}),
+    Route("chw-blocks-f16", "decode", (W, H), (W, H), _nv12(W, H, 65, 67), _chw_out(W, H, "float16", 3, 2), b"decode_nv12_blocks_chw<f16>",
+          options=CHW_NORM, fmt=cc.FORMATS["float16"], chw="float16", norm=cc.IMAGENET,
+          no_skew="already the kernel a skewed step demotes to (the chw-quads routes run the class)"),
+    # bt709hip_decode_scaled_batch under BT709HIP_OPT_SCALED_CHW: the plane offset rides in 32 bits (scaled_planes_fit)
+    Route("scaled-chw-u8", "scaled", ins=_nv12(W, H, 80, 80), outs=_chw_out(40, 10, "uint8", 3, 16), kernel=b"decode_nv12_scaled_chw<u8>", taps=(WIDE, 1),
+          options=((_capi.OPT_SCALED_CHW, 1),), fmt=cc.FORMATS["uint8"], chw="uint8", skew=_scaled_skew(b"decode_nv12_scaled_chw<u8>"), **DOWN),
+    Route("scaled-chw-f32-alpha", "scaled", (32, 8), (64, 16), _nv12(32, 8, 48, 48, 64), _chw_out(64, 16, "float32", 4, 16), b"decode_nv12_scaled_chw<f32,alpha>",
+          gamma=GAMMA_SRGB, alpha=True, taps=(ONCE, 0), options=((_capi.OPT_SCALED_CHW, 1),) + CHW_NORM, fmt=cc.FORMATS["float32"], chw="float32",
+          norm=cc.IMAGENET, skew={2: (b"decode_nv12_scaled_chw<f32,alpha>", (ONCE, 0)), 1: (b"decode_nv12_scaled_chw<f32,alpha>", (BYTES, 1))}),
+    # bt709hip_encode_batch under BT709HIP_CTX_OPT_ENCODE_CHW_INPUT: the pointer table of such a launch holds 31 surfaces
+    Route("encode-chw-f16", "encode", (W, H), (W, H), _chw_in(W, H, "float16", 16), _nv12(W, H, 80, 80), _chw_kernel("float16", NV12, True),
+          pair=(GAMMA_SRGB, GAMMA_APPLE), in_fmt=cc.FORMATS["float16"], chw="float16", norm=ecc.IMAGENET, ctx_options=_encode_chw(NV12), table=ecc.MAX_TABLE,
+          bands=True, skew={2: (_chw_kernel("float16", NV12, False), None), 1: (_chw_kernel("float16", NV12, False), None)}),
+    Route("encode-chw-f32-blocks", "encode", (W, H), (W, H), _chw_in(W, H, "float32", 4), _nv12(W, H, 65, 67), _chw_kernel("float32", NV12, False),
+          pair=(GAMMA_SRGB, GAMMA_APPLE), in_fmt=cc.FORMATS["float32"], chw="float32", norm=ecc.IMAGENET, ctx_options=_encode_chw(NV12), table=ecc.MAX_TABLE,
+          no_skew="already the kernel a skewed step demotes to (the encode-chw-f16 route runs the class)"),
+    # into planar I420: the "cbcr" plane as the i420 decode route has it
+    Route("encode-chw-u8-i420", "encode", (W, H), (W, H), _chw_in(W, H, "uint8", 16), [Plane("y", W, H, 80), Plane("cbcr", W // 2, H, 48)],
+          _chw_kernel("uint8", I420, True), pair=(GAMMA_SRGB, GAMMA_APPLE), in_fmt=cc.FORMATS["uint8"], chw="uint8", norm=ecc.IMAGENET,
+          ctx_options=_encode_chw(I420), table=ecc.MAX_TABLE, bands=True,
+          skew={2: (_chw_kernel("uint8", I420, False), None), 1: (_chw_kernel("uint8", I420, False), None)}),
 ]
 ROUTE = {r.name: r for r in ROUTES}
 PAIRS_RUN = [(r.name, c) for r in ROUTES for c in r.classes()]
@@ -215,6 +303,10 @@ class Layout:
                 assert sum(1 for wl, wh in windows if wl <= lo - g and hi + g <= wh) == 1, (r.name, self.cls, which, lo, hi)
             for p in planes:
                 o, step = off[p.name], self.steps[p.name]
+                if p.room:  # the place of a fourth plane: in the frame's own window, and no other frame or alias window in it
+                    for v in o:
+                        assert sum(1 for wl, wh in windows if wl <= v and v + p.extent + p.room + GUARD <= wh) == 1, (r.name, self.cls, p.name)
+                        assert all(hi <= v or lo >= v + p.extent + p.room + GUARD for lo, hi in ext if lo != v), (r.name, self.cls, p.name)
                 assert len(o) == n and all(v % p.unit == 0 for v in o) and o[0] % 16 == 0
                 if self.uniform:
                     assert all(o[i] == o[0] + i * step for i in range(n)), (r.name, self.cls, p.name)
@@ -275,20 +367,21 @@ def build(route, cls):
         if kind in ("far", "far-descending"):
             cursor = 0
             for p in planes:
-                d = _up(p.extent + 2 * GUARD + 16, 16)
+                span = p.extent + p.room
+                d = _up(span + 2 * GUARD + 16, 16)
                 low = cursor + GUARD
                 high = low + FAR + d
                 off[p.name] = [low, high] if kind == "far" else [high, low]
                 L.steps[p.name] = off[p.name][1] - off[p.name][0]
                 a = low + d if kind == "far" else low + FAR  # frame 0 + the step's low 32 bits
                 alias.append((a, a + p.extent))
-                windows += [(low - GUARD, low + p.extent + GUARD), (high - GUARD, high + p.extent + GUARD), (a, a + p.extent)]
-                cursor += _up(2 * GUARD + d + p.extent, 256)
+                windows += [(low - GUARD, low + span + GUARD), (high - GUARD, high + span + GUARD), (a, a + p.extent)]
+                cursor += _up(2 * GUARD + d + span, 256)
             assert cursor <= (1 << 20) - GUARD
         else:
             cursor = NEAR_ORIGIN
             for j, p in enumerate(planes):
-                pitch = _up(p.extent + 2 * GUARD, 256) + (SKEW.get(cls, 0) if p.unit == 1 else 0)
+                pitch = _up(p.extent + p.room + 2 * GUARD, 256) + (SKEW.get(cls, 0) if p.unit == 1 else 0)
                 slots = _slots(kind, n, which, j)
                 off[p.name] = [cursor + GUARD + k * pitch for k in slots]
                 L.steps[p.name] = off[p.name][1] - off[p.name][0] if L.uniform else None
@@ -326,11 +419,33 @@ class Call:
             self.surfs = (Surface * n)(*[Surface(o_ptr("out", i), r.plane("out").stride, w, h, SRGB8, 0) for i in range(n)])
         else:
             cbcr = len(r.outs) > 1
-            self.ins = (Surface * n)(*[Surface(i_ptr("bgra", i), r.plane("bgra").stride, w, h, r.in_fmt, 0) for i in range(n)])
+            src = r.ins[0]  # "bgra", or the "chw" tensor: plane 0 and the pitch of every plane's rows
+            self.ins = (Surface * n)(*[Surface(i_ptr(src.name, i), src.stride, w, h, r.in_fmt, 0) for i in range(n)])
             self.frames = (Frame * n)(*[Frame(o_ptr("y", i), r.plane("y").stride, o_ptr("cbcr", i) if cbcr else None, r.plane("cbcr").stride if cbcr else 0,
                                               w, h, 0, 0) for i in range(n)])
 
+    def _under_ctx_options(self, lib, ctx, call):
+        """The route's context options for this call alone: the context is shared, so they are put back whatever happens."""
+        try:
+            for opt, val in self.route.ctx_options:
+                rc = lib.bt709hip_context_set_option(ctx, opt, val)
+                assert rc == 0, (self.route.name, opt, val, rc)
+            return call()
+        finally:
+            for opt, _ in self.route.ctx_options:
+                assert lib.bt709hip_context_set_option(ctx, opt, CTX_DEFAULTS[opt]) == 0, (self.route.name, opt)
+
     def batch(self, lib, ctx, dec, stream=None, wait=1, count=None):
+        if self.route.ctx_options:
+            return self._under_ctx_options(lib, ctx, lambda: self._batch(lib, ctx, dec, stream, wait, count))
+        return self._batch(lib, ctx, dec, stream, wait, count)
+
+    def single(self, lib, ctx, dec, i, stream=None, wait=1):
+        if self.route.ctx_options:
+            return self._under_ctx_options(lib, ctx, lambda: self._single(lib, ctx, dec, i, stream, wait))
+        return self._single(lib, ctx, dec, i, stream, wait)
+
+    def _batch(self, lib, ctx, dec, stream=None, wait=1, count=None):
         r, n = self.route, self.n if count is None else count
         if r.entry == "decode":
             return lib.bt709hip_decode_batch(dec, n, self.frames, self.alphas, self.surfs, stream, wait)
@@ -344,7 +459,7 @@ class Call:
             return lib.bt709hip_unconvert_batch(dec, n, self.ptrs, r.plane("in").stride, r.size[0], r.size[1], self.surfs, stream, wait)
         return lib.bt709hip_encode_batch(ctx, n, self.ins, self.frames, r.pair[0], r.pair[1], stream, wait)
 
-    def single(self, lib, ctx, dec, i, stream=None, wait=1):
+    def _single(self, lib, ctx, dec, i, stream=None, wait=1):
         r = self.route
         if r.entry in ("decode", "half", "scaled"):
             f, a, s = C.byref(self.frames[i]), C.byref(self.alphas[i]) if self.alphas is not None else None, C.byref(self.surfs[i])
@@ -364,7 +479,7 @@ class Call:
             return [s["y"], s["cbcr"], s["alpha"] if r.alpha else 0, s["out"]]
         if r.entry in ("render", "unconvert"):
             return [s["in"], s["out"], 0, 0]
-        return [s["bgra"], s["y"], s["cbcr"] if len(r.outs) > 1 else 0, 0]
+        return [s[r.ins[0].name], s["y"], s["cbcr"] if len(r.outs) > 1 else 0, 0]
 
 
 # ------------------------------------------------------------------ samples, backgrounds and what they must become
@@ -391,6 +506,8 @@ def frame_data(route, k):
                 d[p.name] = (rng.random((h, w, 4)) * 1.25).astype(np.float16).view(np.uint8).reshape(h, 8 * w)
             elif route.entry == "unconvert":  # Y | Cb << 8 | Cr << 16
                 d[p.name] = rng.integers(0, 1 << 24, (h, w), dtype=np.uint32).view(np.uint8).reshape(h, 4 * w)
+            elif p.name == "chw" and route.chw != "uint8":  # finite elements; de-normalised (ImageNet's std and mean) they span -0.2 .. 1.2
+                d[p.name] = (rng.random((3 * h, w)) * 6.0 - 3.0).astype(route.chw).view(np.uint8).reshape(3 * h, route.elem * w)
             else:
                 d[p.name] = rng.integers(0, 256, (p.rows, p.row_bytes), dtype=np.uint8)
         _data[key] = d
@@ -423,7 +540,7 @@ def want(route, oracle, tabs, T, k, bg_index):
     g = route.gamma
     if route.entry in ("decode", "half", "scaled"):
         y, a = d["y"], d.get("alpha")
-        c = interleave(d["cbcr"]) if route.name == "i420" else d["cbcr"]
+        c = interleave(d["cbcr"]) if route.planar_chroma else d["cbcr"]
         if route.entry == "decode":
             out = oracle.decode_nv12_rgba16f(g, y, c, a).view(np.uint8).reshape(h, 8 * w) if route.fmt == F16 else oracle.decode_nv12(g, y, c, alpha=a)
         elif route.entry == "half":
@@ -436,6 +553,8 @@ def want(route, oracle, tabs, T, k, bg_index):
         if route.reads_destination:
             import over_cases as oc
             out = oc.composite_over(out.reshape(oh, ow, 4), background(route, bg_index).reshape(oh, ow, 4), *tabs).reshape(oh, 4 * ow)
+        if route.chw:  # the definition (chw_cases.chw_of) over the 8-bit words: planes R, G, B (A), stacked
+            out = cc.chw_of(cc.words_of(out), route.chw, *(route.norm or ((1.0, 1.0, 1.0), (0.0, 0.0, 0.0))), planes=route.chw_planes).view(np.uint8)
         res = {"out": out}
     elif route.entry == "render":
         src = d["in"].view(np.float16).reshape(h, w, 4) if route.in_fmt == F16 else d["in"]
@@ -450,6 +569,10 @@ def want(route, oracle, tabs, T, k, bg_index):
         res = {"u": d["cbcr"][:, 0::2], "v": d["cbcr"][:, 1::2]}
     elif route.in_fmt == ALPHA8:
         res = {"y": T[d["bgra"].reshape(h, w, 4)[:, :, 3]]}
+    elif route.chw:  # the BGRA8 picture the tensor stands for (encode_chw_cases.words_of_planes), encoded by the oracle
+        tensor = np.ascontiguousarray(d["chw"]).view(route.chw).reshape(3, h, w)
+        y, c = oracle.encode_nv12(ecc.words_of_planes(tensor, route.norm) & np.uint32(0xFFFFFF), w, h, route.pair[0], route.pair[1])
+        res = {"y": y, "cbcr": ecc.planar(c).reshape(h, w // 2) if route.planar_chroma else c}
     else:
         y, c = oracle.encode_nv12(d["bgra"].view(np.uint32).reshape(h, w), w, h, route.pair[0], route.pair[1])
         res = {"y": y, "cbcr": c}

@@ -7,7 +7,8 @@ RESIZED copy of the route (resized(): other sizes, every pitch congruent to the 
 256, so the kernel on record stays the route's, and batch_spacing_cases.want() keeps calling the oracle the route's own tests
 use) and lays its planes out, frame after frame, in one input and one output slab under an EXTENT CLASS:
 
-    tallest            one frame at the largest height the entry point accepts: 131070 rows (decode, encode), 131068 (half: H % 4
+    tallest            one frame at the largest height the entry point accepts: 131070 rows (decode, encode; a planar CHW surface:
+                       131070 rows in each of its 3 or 4 stacked planes), 131068 (half: H % 4
                        == 0), 65534 (unconvert), chroma height 65535 (the plane shuffles), out height 65535 from a source of FOUR
                        rows (scaled, render: every output row between the same few source rows, both edge clamps).  The width is
                        the smallest that still selects the kernel (8, 4 or 6; scaled, render: 8 -> 16 or 16 -> 10 columns, the
@@ -33,8 +34,9 @@ the expected bytes of 65535 items take 251 oracle calls.  251 is prime: an item 
 (tests/test_extents_cpu.py has the argument, and the one mistake it does NOT cover at every k: an index cut to 8 bits is 64256 =
 256 x 251 short for the items 64256..64511, and wrong content everywhere else).
 
-The slabs are SLAB_BYTES (the largest case, tens of MB -- nothing here needs the addressing modules' 4 GiB); a layout is ONE
-window a side, [0, total): a guard band of canary either end, ITEM_GAP bytes between two items, every pitch's padding.  The
+The slabs are SLAB_BYTES (the largest case, tens of MB: the four float32 planes of a wide CHW view -- nothing here needs the
+addressing modules' 4 GiB); a layout is ONE window a side, [0, total): a guard band of canary either end, ITEM_GAP bytes
+between two items (behind an opaque decoder's planar CHW target first the room of a fourth plane), every pitch's padding.  The
 helpers below are batch_spacing_cases.upload_inputs / reset_outputs / collect over such a layout without their per-row Python
 loop (a layout has up to 262140 rows); tests/test_extents_cpu.py holds them to those on a small layout."""
 import copy
@@ -68,7 +70,7 @@ def shuffles(route):
 
 def general(route):
     """The routes whose own pitches demote them to a kernel that takes any width: they run at width 6."""
-    return route.name in ("blocks", "unconvert-pixel", "encode-blocks", "interleave-bytes", "deinterleave-bytes")
+    return route.name in ("blocks", "unconvert-pixel", "encode-blocks", "interleave-bytes", "deinterleave-bytes", "chw-blocks-f16", "encode-chw-f32-blocks")
 
 
 def refusal(route, cls):
@@ -147,7 +149,9 @@ def _shape(route, p, which, w, h, ow, oh):
     if p.name in ("y", "alpha"):
         return w, h
     if p.name == "cbcr":
-        return (w // 2, h) if route.name == "i420" else (w, h // 2)
+        return (w // 2, h) if route.planar_chroma else (w, h // 2)
+    if route.chw and p.name in ("out", "chw"):  # a planar CHW surface: its planes stacked at one pitch
+        return (route.elem * w, 3 * h) if which == "in" else (route.elem * ow, route.chw_planes * oh)
     if which == "in":
         return (8 if route.in_fmt == F16 else 4) * w, h
     return (8 if route.fmt == F16 else 4) * ow, oh
@@ -180,7 +184,8 @@ def resized(route, cls):
         out = []
         for p in planes:
             row_bytes, rows = _shape(route, p, which, w, h, ow, oh)
-            out.append(Plane(p.name, row_bytes, rows, rp._at_least(row_bytes, p.stride % 16), p.unit))
+            stride = rp._at_least(row_bytes, p.stride % 16)
+            out.append(Plane(p.name, row_bytes, rows, stride, p.unit, room=rows // 3 * stride if p.room else 0, stacked=p.stacked))  # room: a fourth plane's
         return out
     r.ins, r.outs = swap(route.ins, "in"), swap(route.outs, "out")
     if cls == "longest-unbanded" and route.entry != "encode":  # the encoder's map is the context's (the GPU test sets and restores it)
@@ -242,7 +247,7 @@ class Layout:
             for p in planes:
                 o, step = off[p.name], self.steps[p.name]
                 assert len(o) == n and o[0] % 256 == 0 and step % 16 == 0 and (n == 1 or step >= p.extent + ITEM_GAP), (name, cls, p.name)
-                ext.append((o[0], o[n - 1] + p.extent))  # the items of a plane, a gap apart, lie in one run
+                ext.append((o[0], o[n - 1] + p.extent + p.room))  # the items of a plane (each with its room), a gap apart, lie in one run
             ext.sort()
             assert ext[0][0] >= GUARD and ext[-1][1] + GUARD <= self.total[which], (name, cls, which, "outside the window")
             assert all(b[0] - a[1] >= GUARD for a, b in zip(ext, ext[1:])), (name, cls, which, "overlapping or adjacent")
@@ -255,10 +260,10 @@ def _lay(L):
         cursor = GUARD
         for p in planes:
             first = bs._up(cursor, 256)
-            step = bs._up(p.extent + ITEM_GAP, 16) if L.n > 1 else 0
+            step = bs._up(p.extent + p.room + ITEM_GAP, 16) if L.n > 1 else 0
             off[p.name] = _Evenly(first, step, L.n)
             L.steps[p.name] = step
-            cursor = first + (L.n - 1) * step + p.extent + GUARD
+            cursor = first + (L.n - 1) * step + p.extent + p.room + GUARD
         L.total[which] = bs._up(cursor, 256)
         windows.append((0, L.total[which]))
     return L

@@ -10,7 +10,7 @@ it mod 16 -- the alignment folds pick the same kernel, the kernel name and tap f
                  32-bit number it lands 2^32 lower, inside the slab, where the plane's alias window is
     past-2^32    base at k * 8 KiB, the pitch the route's residue rounded up from (2^32 + d) / (rows - 1): the last row lies
                  above 2^32, the rows before it sweep [2^31, 2^32); a product cut to 32 bits lands on base + d, the alias window.
-                 The planar route's "cbcr" plane is U's rows, then V's: U's stay below 2^32, V's last passes it (v_offset + row
+                 The planar routes' "cbcr" plane is U's rows, then V's: U's stay below 2^32, V's last passes it (v_offset + row
                  offset is the sum under test)
     under-2-GiB  the any-ratio and pass-2 routes only (they form row offsets in 32 bits and refuse planes with rows x pitch >=
                  2^31): every plane at the LARGEST pitch of its residue the contract accepts
@@ -20,6 +20,15 @@ it mod 16 -- the alignment folds pick the same kernel, the kernel name and tap f
 A kernel that walks row PAIRS forms the product for the even row and adds one pitch: for such a plane (Y, alpha, a 1:1 target)
 the product itself stops one row short of the class's boundary, and it is the chroma plane, the general kernels' odd-row
 product and every single-row kernel that cross it.
+
+A planar CHW surface (batch_spacing_cases: planes R, G, B (A) stacked at one pitch) is ONE plane of planes x H rows here, too, and
+its address is a SUM: c x H x pitch + row x pitch.  Under the past- classes every plane but the last lies below the boundary,
+the last one begins below it and the sum crosses it for that plane's last row alone.  (A slab ends 1 MiB past 2^32, so ONE row
+of a plane can lie past a boundary: the sum for the last EVEN row, which the 1:1 kernels and the encoder form before they add
+one pitch, stops a row short of it as a Y plane's product does.)  Behind the fused rescale the same sum rides in 32 bits and
+the contract is planes x OH x pitch < 2^31 (scaled_planes_fit): under-2-GiB and at-2-GiB take rows = planes x OH.  The room of
+a fourth plane batch_spacing_cases gives an opaque decoder's target is NOT given here: at these pitches it lies outside the
+slab (the spacing and extent suites and the CHW families' own tests watch that place).
 
 A layout holds two frames, frame 1's planes 4 KiB behind frame 0's, and names the WINDOWS the host touches: one per row (the
 samples and a guard band either side) and the alias windows.  Layout.check() asserts, on the CPU, that all of them lie inside
@@ -97,7 +106,7 @@ def pitch_for(p, cls, victim=False):
 def repitched(route, cls, victim=None):
     """The route with every plane at the class's pitch (at-2-GiB: plane `victim` alone)."""
     r = copy.copy(route)
-    swap = lambda planes: [Plane(p.name, p.row_bytes, p.rows, pitch_for(p, cls, p.name == victim), p.unit) for p in planes]
+    swap = lambda planes: [Plane(p.name, p.row_bytes, p.rows, pitch_for(p, cls, p.name == victim), p.unit, stacked=p.stacked) for p in planes]
     r.ins, r.outs = swap(route.ins), swap(route.outs)
     return r
 
@@ -160,7 +169,7 @@ class Layout:
                     assert TWO31 <= (p.rows - 2) * p.stride < TWO32 <= last and max(o) < (1 << 20), (name, p.name)
                     assert last - TWO32 >= p.row_bytes + 2 * GUARD  # not row 0
                     landed = [v + (last & 0xFFFFFFFF) for v in o]
-                    if name == "i420" and p.name == "cbcr":  # U's rows below 2^32, V's last above: v_offset + row offset crosses it
+                    if self.base.planar_chroma and p.name == "cbcr":  # U's rows below 2^32, V's last above: v_offset + row offset crosses it
                         assert (p.rows // 2 - 1) * p.stride + p.row_bytes < TWO32 <= (p.rows // 2) * p.stride + (p.rows // 2 - 1) * p.stride
                 elif cls == "under-2-GiB":  # the largest accepted pitch of the residue
                     assert area < TWO31 <= p.rows * (p.stride + 16), (name, p.name)
@@ -171,6 +180,15 @@ class Layout:
                     else:
                         assert p.stride == self.base.plane(p.name).stride
                     landed = []
+                assert (p.stacked > 1) == (bool(self.base.chw) and p.name in ("out", "chw")), (name, p.name)
+                if cls in PAST and p.stacked > 1:
+                    # the planes of a CHW surface: every plane but the last lies below the boundary, the last one BEGINS below it,
+                    # and c x H x pitch + row x pitch crosses it for that plane's last row alone
+                    boundary, h = (TWO31 if cls == "past-2^31" else TWO32), p.rows // p.stacked
+                    plane = h * p.stride
+                    assert p.stacked in (3, 4) and h == self.base.out_size[1] and h >= 2
+                    assert (p.stacked - 1) * plane + p.row_bytes <= boundary, (name, p.name)  # planes 0 .. count - 2 whole, and row 0 of the last
+                    assert (p.stacked - 1) * plane + (h - 2) * p.stride + p.row_bytes <= boundary <= (p.stacked - 1) * plane + (h - 1) * p.stride, (name, p.name)
                 for v in landed:
                     assert (v, v + p.row_bytes) in alias, (name, cls, p.name)
         if cls == "at-2-GiB":
@@ -236,7 +254,7 @@ def unchecked(base, strides):
     """A layout of `base` with the pitches of `strides` (plane name -> pitch) in place of the route's, the planes at their low
     slots, NO windows and no self-check: for calls on the fake runtime, which dereferences nothing."""
     L = Layout(base, "at-2-GiB", None)
-    swap = lambda planes: [Plane(p.name, p.row_bytes, p.rows, max(strides.get(p.name, p.stride), p.row_bytes), p.unit) for p in planes]
+    swap = lambda planes: [Plane(p.name, p.row_bytes, p.rows, max(strides.get(p.name, p.stride), p.row_bytes), p.unit, stacked=p.stacked) for p in planes]
     L.route.ins, L.route.outs = swap(base.ins), swap(base.outs)
     for p in L.route.ins + L.route.outs:  # Plane() asserts pitch >= row; a smaller one under test is put in afterwards
         p.stride = strides.get(p.name, p.stride)

@@ -22,7 +22,7 @@ def test_every_layout_passes_its_self_checks():
     """Layout.check() for every (route, class) of the GPU file: every true and every alias window inside its slab, pairwise
     disjoint, a guard band apart; the steps are what the class says; and beyond check(): the far classes really leave the low
     4 GiB, their windows are all the host touches, and the small classes stay a GiB away from either end of the slab."""
-    assert len(set(bs.PAIRS_RUN)) == len(bs.PAIRS_RUN) >= 200
+    assert len(set(bs.PAIRS_RUN)) == len(bs.PAIRS_RUN) == 324  # 215 before the nine planar CHW routes
     for name, cls in bs.PAIRS_RUN:
         route = bs.ROUTE[name]
         L = bs.build(route, cls)
@@ -54,7 +54,13 @@ def test_every_route_runs_every_class_or_says_why_not():
     entries = {}
     for r in bs.ROUTES:
         entries.setdefault(r.entry, []).append(r.kernel)
-    assert {k: len(v) for k, v in entries.items()} == {"decode": 5, "half": 3, "scaled": 4, "render": 2, "unconvert": 2, "encode": 3}
+    # the planar CHW routes: the fast kernels split under the band map (two launches, the first banded: the GPU file asserts it)
+    chw = [r for r in bs.ROUTES if r.chw]
+    assert [r.name for r in chw] == [r.name for r in bs.ROUTES[-9:]] and all(p.stacked == r.chw_planes for r in chw for p in r.ins + r.outs if p.name in ("out", "chw"))
+    assert sorted(r.name for r in chw if r.bands) == ["chw-quads-f16-alpha", "chw-quads-f32-i420", "chw-quads-u8", "encode-chw-f16", "encode-chw-u8-i420"]
+    assert all((r.name, "bands-tail-descending") in run for r in chw if r.bands)
+    assert all((r.name, c) in run for r in chw for c in ("far", "far-descending", "fan-out", "plane-skew", "descending-33", "table-twin"))
+    assert {k: len(v) for k, v in entries.items()} == {"decode": 9, "half": 3, "scaled": 6, "render": 2, "unconvert": 2, "encode": 6}
 
 
 # ------------------------------------------------------------------ the shim on the fake HIP runtime
@@ -160,10 +166,13 @@ def test_entry_point_takes_the_uniform_path_with_the_builders_steps(fake, fake_r
         _bump(call, route, 17, 16)
         mark = lib.fake_hip_log_size()
         assert call.batch(lib, rig.ctx, dec) == _capi.ERR_UNSUPPORTED, route.name
-        assert call.batch(lib, rig.ctx, dec, count=32) == (_capi.ERR_UNSUPPORTED if entry == "render" else 0), route.name
+        assert route.table in (31, 32)  # 31: a planar CHW encode, whose table gives one entry to the scale and bias
+        if route.table < 32:
+            assert call.batch(lib, rig.ctx, dec, count=32) == _capi.ERR_UNSUPPORTED and rig.kernels(mark) == [], route.name
+        assert call.batch(lib, rig.ctx, dec, count=route.table) == (_capi.ERR_UNSUPPORTED if entry == "render" else 0), route.name
         assert len(rig.kernels(mark)) == (0 if entry == "render" else 1)
         if entry != "render":
-            assert rig.addressing()[:2] == (0, 32)
+            assert rig.addressing()[:2] == (0, route.table)
 
 
 @pytest.mark.parametrize("count", [2, 3])

@@ -19,12 +19,19 @@ def test_every_layout_passes_its_self_checks():
     a run of their own, a guard band from the next and from either end; and beyond check(): the extent is the one the class
     names, the slabs are tens of MB, two items of a plane are ITEM_GAP or more apart."""
     assert len(set(ec.PAIRS_ALL)) == len(ec.PAIRS_ALL) == len(ec.PAIRS_RUN) + len(ec.PAIRS_REFUSED)
-    assert (1 << 20) <= ec.SLAB_BYTES <= (64 << 20)
+    # the largest case: scaled-chw-f32-alpha's wide target, 4 planes x 4 rows of 2^20 + 12 floats = 64 MiB + 768 bytes
+    assert (1 << 20) <= ec.SLAB_BYTES == (67 << 20)
     for name, cls in ec.PAIRS_ALL:
         L = ec.build(name, cls)
         base, r = L.base, L.route
         (w, h), (ow, oh) = r.size, r.out_size
         assert L.n == {"longest": 65535, "longest-unbanded": 65535, "too-many": 65536}.get(cls, 1)
+        for p in r.ins + r.outs:  # a planar CHW surface: 3 or 4 planes of the frame's (the view's) size each, a target's fourth given room
+            assert (p.stacked > 1) == (bool(base.chw) and p.name in ("out", "chw"))
+            if p.stacked > 1:
+                pw, ph = (w, h) if p in r.ins else (ow, oh)
+                assert p.stacked == base.chw_planes and (p.row_bytes, p.rows) == (base.elem * pw, p.stacked * ph)
+                assert p.room == ((4 - p.stacked) * ph * p.stride if p in r.outs else 0)
         for which in ("in", "out"):
             planes, off, windows, _ = L.side(which)
             for p in planes:
@@ -68,14 +75,14 @@ def test_every_route_runs_every_class_or_says_why_not():
         r = ec.ROUTE[name]
         assert reason and ((cls in ("longest", "longest-unbanded", "too-many") and ec.shuffles(r)) or (cls == "longest-unbanded" and not r.bands)
                            or (cls in ("tallest-from-tall", "wide-down") and not ec.rescales(r))), (name, cls)
-    assert len(ec.PAIRS_RUN) == 23 + 6 + 19 + 6 + 23 + 6 and len(ec.PAIRS_REFUSED) == 23 + 19
+    assert len(ec.PAIRS_RUN) == 32 + 8 + 28 + 11 + 32 + 8 and len(ec.PAIRS_REFUSED) == 32 + 28
 
 
 def test_every_kernel_name_meets_every_extent():
     """Every kernel name a route can leave on record appears in a tallest, a wide and -- where a batched form exists -- a longest
     case, and the resized route still asks for it."""
     names = {r.kernel for r in ec.ROUTES}
-    assert len(names) == 20  # of 23 routes: decode_nv12_scaled in two tap forms, the plane-shuffle kernels in a wide and a byte branch
+    assert len(names) == 29  # of 32 routes: decode_nv12_scaled in two tap forms, the plane-shuffle kernels in a wide and a byte branch
     for cls in ("tallest", "longest", "wide"):
         met = {ec.resized(ec.ROUTE[name], c).kernel for name, c in ec.PAIRS_RUN if c == cls}
         batched = {r.kernel for r in ec.ROUTES if not ec.shuffles(r)}
@@ -146,7 +153,7 @@ def test_resized_routes_keep_what_selects_their_kernel():
         if base.taps is not None:
             sy = r.size[1] / r.out_size[1]
             assert r.taps[1] == (1 if sy >= 1 or name == "scaled-f16" else 0), (name, cls, r.taps)
-            assert r.taps[0] == {"scaled-once": ec.ONCE}.get(name, ec.SHARED) if sy < 1 else r.taps[0] == ec.WIDE_TAPS, (name, cls, r.taps)
+            assert r.taps[0] == {"scaled-once": ec.ONCE, "scaled-chw-f32-alpha": ec.ONCE}.get(name, ec.SHARED) if sy < 1 else r.taps[0] == ec.WIDE_TAPS, (name, cls, r.taps)
 
 
 class _Memory:

@@ -27,10 +27,13 @@ from test_batch_spacing_gpu import GAMMA, Slabs, alpha_luma, gh, rig, tabs  # no
 
 pytestmark = pytest.mark.gpu
 
-STACKED = ("quads", "quads-over", "i420", "half-wide")          # narrow frames: row pairs stacked in blockDim.y (quads_rows_per_block)
-FULL_GRID_Y = ("half-narrow", "encode-blocks", "interleave-wide", "interleave-bytes", "deinterleave-wide", "deinterleave-bytes")
-WALKS_ROW_PAIRS = ("encode-fast", "encode-alpha-y")             # 3 to 9 row pairs a workgroup
-TILED = ("quads", "quads-over", "i420", "rgba16f-alpha", "half-wide", "half-rep-alpha", "encode-fast", "encode-alpha-y")
+CHW_QUADS = ("chw-quads-u8", "chw-quads-f16-alpha", "chw-quads-f32-i420")  # launch_decode's plan over the planar CHW kernels
+CHW_ENCODE = ("encode-chw-f16", "encode-chw-u8-i420")                      # launch_encode's own plan
+STACKED = ("quads", "quads-over", "i420", "half-wide") + CHW_QUADS  # narrow frames: row pairs stacked in blockDim.y (quads_rows_per_block)
+FULL_GRID_Y = ("half-narrow", "encode-blocks", "encode-chw-f32-blocks", "interleave-wide", "interleave-bytes", "deinterleave-wide", "deinterleave-bytes")
+WALKS_ROW_PAIRS = ("encode-fast", "encode-alpha-y") + CHW_ENCODE  # 3 to 9 row pairs a workgroup
+TILED = ("quads", "quads-over", "i420", "rgba16f-alpha", "half-wide", "half-rep-alpha", "encode-fast", "encode-alpha-y") + CHW_QUADS + CHW_ENCODE
+GENERAL_DECODE = ("blocks", "chw-blocks-f16")                   # grid-strided over the row pairs; the frames live in gridDim.y
 RECORDS_LAUNCH = ("decode", "half", "encode", "interleave", "deinterleave")  # bt709hip_last_launch_info
 
 
@@ -115,12 +118,12 @@ def _check_record(rig, L, label):  # noqa: F811
             assert grid[1] == rows and rows >= ec.MOST_ROWS - 1, (label, grid, rows)
         elif name in WALKS_ROW_PAIRS:
             assert grid[1] in [_ceil(rows, k) for k in range(3, 10)], (label, grid, rows)
-        elif name == "blocks":  # grid-strided over the row pairs; the frames live in gridDim.y
+        elif name in GENERAL_DECODE:
             assert grid[1:] == (1, 1), (label, grid)
     elif cls in ("longest", "longest-unbanded"):
         if base.bands and cls == "longest":
             assert launches == 2 and grid[2] == 8191 and bands == 1, (label, grid, block, launches, bands)
-        elif name == "blocks":  # the general path's frames live in gridDim.y
+        elif name in GENERAL_DECODE:  # the general path's frames live in gridDim.y
             assert launches == 1 and grid[1] == n and bands == 0, (label, grid, launches)
         elif name == "half-rep-alpha":
             assert launches == 1 and grid == (3, 1, 1), (label, grid)

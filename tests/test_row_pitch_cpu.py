@@ -19,7 +19,7 @@ from test_batch_spacing_cpu import IN_BASE, OUT_BASE, FakeRig, fake  # noqa: F40
 def test_every_layout_passes_its_self_checks():
     """Layout.check() for every (route, class) and every at-2-GiB plane of the GPU file, and beyond check(): the pitches are the
     extreme ones of their residue, what the host touches stays small, and the two past- classes really differ by 2^32."""
-    assert len(set(rp.PAIRS_RUN)) == len(rp.PAIRS_RUN) == 2 * 17 + 6 and len(set(rp.AT_LIMIT)) == len(rp.AT_LIMIT) == 17
+    assert len(set(rp.PAIRS_RUN)) == len(rp.PAIRS_RUN) == 2 * 24 + 8 and len(set(rp.AT_LIMIT)) == len(rp.AT_LIMIT) == 24
     for name, cls in rp.PAIRS_RUN:
         L = rp.build(rp.ROUTE[name], cls)
         assert L.n == 2
@@ -31,6 +31,7 @@ def test_every_layout_passes_its_self_checks():
                 if cls in rp.PAST:
                     boundary = rp.TWO31 if cls == "past-2^31" else rp.TWO32
                     assert 0 <= last - boundary - rp.alias_gap(p) < 17 * (p.rows - 1)  # rounded up to a whole pitch of the residue, no further
+                    assert (p.stacked > 1) == (p.name in ("out", "chw") and bool(rp.ROUTE[name].chw))  # a planar CHW surface: its planes in one
                     assert max(off[p.name]) + last + p.row_bytes > rp.TWO32     # the last row's ADDRESS is past 2^32 in both
                 else:
                     assert p.rows * p.stride < rp.TWO31 <= p.rows * (p.stride + 16)
@@ -40,7 +41,7 @@ def test_every_layout_passes_its_self_checks():
         assert v.rows * v.stride >= rp.TWO31 > v.rows * (v.stride - 16)
     # the order the GPU file runs them in: every past-2^31 pair first
     firsts = [i for i, (_, c) in enumerate(rp.PAIRS_RUN) if c == "past-2^32"]
-    assert all(c == "past-2^31" for _, c in rp.PAIRS_RUN[:firsts[0]]) and firsts[0] == 17
+    assert all(c == "past-2^31" for _, c in rp.PAIRS_RUN[:firsts[0]]) and firsts[0] == 24
 
 
 def test_every_route_runs_every_class_or_says_why_not():
@@ -52,7 +53,7 @@ def test_every_route_runs_every_class_or_says_why_not():
     # the list holds the two contract-based groups and nothing else
     for (name, cls), reason in rp.CLASSES_NOT_RUN.items():
         assert reason and (cls in rp.PAST) == rp.limited(rp.ROUTE[name]) and (cls in rp.LIMIT) != rp.limited(rp.ROUTE[name])
-    assert sorted(r.name for r in rp.ROUTES if rp.limited(r)) == ["render-bgra8", "render-rgba16f", "scaled-f16", "scaled-once", "scaled-over", "scaled-wide"]
+    assert sorted(r.name for r in rp.ROUTES if rp.limited(r)) == ["render-bgra8", "render-rgba16f", "scaled-chw-f32-alpha", "scaled-chw-u8", "scaled-f16", "scaled-once", "scaled-over", "scaled-wide"]
     assert {(n, p) for n, p in rp.AT_LIMIT if n == "scaled-over"} == {("scaled-over", p) for p in ("y", "cbcr", "alpha", "out")}
 
 
