@@ -31,7 +31,15 @@ planar CHW surface (planes R, G, B and, from an alpha dec
 plane 0) -- one Plane of planes x H rows of W x e bytes, unit e.  An opaque decoder's CHW target is given the ROOM of a fourth
 plane behind its three, inside the frame's window: that nothing is written there is part of every comparison.  The CHW routes
 close the table: the 1:1 decode into CHW targets (fast and general kernel, u8 / f16 / f32, NV12 and I420 frames), the fused
-rescale into CHW views (a per-lane and a by-wave tap form) and the encoder reading CHW tensors (into NV12 and into I420)."""
+rescale into CHW views (a per-lane and a by-wave tap form) and the encoder reading CHW tensors (into NV12 and into I420).
+
+The encoder's other families follow them, each with address products of its own (bt709_encode.hip, bt709_encode_pair.h,
+bt709_encode_convert.h, bt709_encode_half.h, bt709_encode_half_alpha.h): BGRA into planar I420 (V's rows (H/2) x pitch behind
+U's), the per-pixel converter (packed 4-byte words through the "y" pointer and pitch: a plane of unit 4 and no "cbcr"; and its
+subsampled frame), the colour + alpha PAIR (two frames a picture: the planes "alpha_y" and "alpha_cbcr" have pitches and steps
+of their own, which ride in spare slots of the pointer table -- which therefore holds 16 pairs), RGBA16Float input (8-byte
+texels; its fast kernel stores halves, so a step = 2 (mod 4) keeps it) and the RGBA16Float pair.  FORMS_NOT_ROUTED names the
+kernel forms that have no route, each with the routed form whose body it instantiates."""
 import ctypes as C
 import zlib
 
@@ -39,6 +47,9 @@ import numpy as np
 
 import chw_cases as cc
 import encode_chw_cases as ecc
+import encode_half_alpha_cases as ehac
+import encode_half_cases as ehc
+import straight_alpha_cases as sac
 from metalbt709decoder_amd import _capi
 from metalbt709decoder_amd._capi import Frame, Surface
 
@@ -92,7 +103,7 @@ class Route:
     chw: the element type ("uint8" / "float16" / "float32") of the route's planar CHW side -- the target of a decode, the input
     of an encode -- which is ONE plane of chw_planes x H rows of W x e bytes; norm: its (scale, bias) setting, which the decoder
     options / context options carry; ctx_options: context options set for every call and put back to CTX_DEFAULTS after it;
-    table: the most frames the entry point's pointer table holds."""
+    table: the most frames the entry point's pointer table holds (a paired encode: pairs)."""
 
     def __init__(self, name, entry, size, out_size, ins, outs, kernel, gamma=GAMMA_APPLE, alpha=False, options=(), over=None, fmt=SRGB8,
                  in_fmt=SRGB8, taps=None, skew=None, bands=False, reads_destination=False, pair=None, no_skew=None, chw=None, norm=None,
@@ -108,6 +119,16 @@ class Route:
         """The "cbcr" plane is U's rows, then V's, at one pitch (I420): the frames a decoder reads, or the ones the encoder writes."""
         return (dict(self.options).get(_capi.OPT_CHROMA_LAYOUT) == _capi.CHROMA_I420
                 or dict(self.ctx_options).get(_capi.CTX_OPT_ENCODE_CHROMA_LAYOUT) == _capi.CHROMA_I420)
+
+    @property
+    def paired(self):
+        """Two frames a picture (BT709HIP_CTX_OPT_ENCODE_WITH_ALPHA / _HALF_WITH_ALPHA): the colour frames, then the alpha frames."""
+        o = dict(self.ctx_options)
+        return bool(o.get(_capi.CTX_OPT_ENCODE_WITH_ALPHA) or o.get(_capi.CTX_OPT_ENCODE_HALF_WITH_ALPHA))
+
+    @property
+    def convert(self):
+        return dict(self.ctx_options).get(_capi.CTX_OPT_ENCODE_CONVERT, _capi.CONVERT_OFF)
 
     @property
     def elem(self):
@@ -163,9 +184,45 @@ def _settings(first, setting):
 CHW_NORM = _settings(_capi.OPT_CHW_SCALE_R, cc.IMAGENET)  # BT709HIP_OPT_CHW_SCALE_R .. _BIAS_B of a decoder
 NV12, I420 = _capi.CHROMA_NV12, _capi.CHROMA_I420
 # what a context holds before and after a call of a route with ctx_options
-CTX_DEFAULTS = dict(((_capi.CTX_OPT_ENCODE_CHW_INPUT, 0), (_capi.CTX_OPT_ENCODE_CHROMA_LAYOUT, NV12)) + _settings(_capi.CTX_OPT_ENCODE_CHW_SCALE_R, ecc.IDENTITY))
+CTX_DEFAULTS = dict(((_capi.CTX_OPT_ENCODE_CHW_INPUT, 0), (_capi.CTX_OPT_ENCODE_CHROMA_LAYOUT, NV12), (_capi.CTX_OPT_ENCODE_PREMULTIPLY, 0),
+                     (_capi.CTX_OPT_ENCODE_CONVERT, _capi.CONVERT_OFF), (_capi.CTX_OPT_ENCODE_WITH_ALPHA, 0), (_capi.CTX_OPT_ENCODE_HALF_INPUT, 0),
+                     (_capi.CTX_OPT_ENCODE_HALF_WITH_ALPHA, 0)) + _settings(_capi.CTX_OPT_ENCODE_CHW_SCALE_R, ecc.IDENTITY))
 _encode_chw = lambda layout: ((_capi.CTX_OPT_ENCODE_CHW_INPUT, 1), (_capi.CTX_OPT_ENCODE_CHROMA_LAYOUT, layout)) + _settings(_capi.CTX_OPT_ENCODE_CHW_SCALE_R, ecc.IMAGENET)
 _chw_kernel = lambda dtype, layout, fast: ecc.kernel_name(dtype, layout, fast).encode()
+
+_LAYOUT_I420 = (_capi.CTX_OPT_ENCODE_CHROMA_LAYOUT, I420)
+_PREMUL, _WITH_ALPHA = (_capi.CTX_OPT_ENCODE_PREMULTIPLY, 1), (_capi.CTX_OPT_ENCODE_WITH_ALPHA, 1)
+_HALF_INPUT, _HALF_WITH_ALPHA = (_capi.CTX_OPT_ENCODE_HALF_INPUT, 1), (_capi.CTX_OPT_ENCODE_HALF_WITH_ALPHA, 1)
+_convert = lambda mode: (_capi.CTX_OPT_ENCODE_CONVERT, mode)
+PAIR_TABLE = 16  # BT709HIP_MAX_BATCH / 2: the pointer table of a paired launch
+
+
+def _bgra_in(w, h, pad):
+    return [Plane("bgra", 4 * w, h, 4 * w + pad, unit=4)]
+
+
+def _half_in(w, h, pad):
+    return [Plane("rgba16f", 8 * w, h, 8 * w + pad, unit=8)]
+
+
+def _i420(w, h, sy, sc):
+    """The planes an I420 encode writes: Y, and U's H/2 rows then V's at one pitch."""
+    return [Plane("y", w, h, sy), Plane("cbcr", w // 2, h, sc)]
+
+
+def _alpha_nv12(w, h, sy, sc=None):
+    """The alpha frame of a pair, behind the colour frame's planes: its Y and (sc) its interleaved chroma plane."""
+    return [Plane("alpha_y", w, h, sy)] + ([Plane("alpha_cbcr", w, h // 2, sc)] if sc else [])
+
+
+def _words(w, h, pad):
+    """The packed converter's target: W x H 4-byte words through the frame's `y` pointer and pitch, no chroma plane."""
+    return [Plane("y", 4 * w, h, 4 * w + pad, unit=4)]
+
+
+_both = lambda kernel: {2: (kernel, None), 1: (kernel, None)}
+NO_BYTE_PLANE = "no byte-addressed plane: texels in, 4-byte words out (BT709HIP_ERR_STRIDE off a multiple of 4)"
+_demoted = lambda name: "already the kernel a skewed step demotes to (the %s route runs the class)" % name
 
 W, H = 64, 16
 HALF_REP =((_capi.OPT_HALF_KERNEL, 1), (_capi.OPT_HALF_WORKGROUPS, 3))  # three persistent workgroups: the cursor wraps from frame to frame
@@ -256,6 +313,37 @@ ROUTES = [
           _chw_kernel("uint8", I420, True), pair=(GAMMA_SRGB, GAMMA_APPLE), in_fmt=cc.FORMATS["uint8"], chw="uint8", norm=ecc.IMAGENET,
           ctx_options=_encode_chw(I420), table=ecc.MAX_TABLE, bands=True,
           skew={2: (_chw_kernel("uint8", I420, False), None), 1: (_chw_kernel("uint8", I420, False), None)}),
+    # ---- the encoder's other families (appended: _route_seed is the index).  Pad 16 selects a fast kernel, pad 4 (8 for half
+    # texels) the general one; a skewed route's demotion is read off the alignment rules of include/bt709hip_ext.h: the BGRA8 forms
+    # and the BGRA8 pair store dwords to Y and alpha Y (pointer, pitch and step 4-byte aligned), the RGBA16Float forms halves
+    # BGRA -> planar I420: V's rows lie (H/2) x pitch behind U's (v_plane_offset)
+    Route("encode-i420", "encode", (W, H), (W, H), _bgra_in(W, H, 16), _i420(W, H, 80, 48), b"encode_bgra_i420", pair=(GAMMA_SRGB, GAMMA_APPLE),
+          ctx_options=(_LAYOUT_I420,), bands=True, skew=_both(b"encode_bgra_i420_blocks")),
+    Route("encode-i420-blocks-premul", "encode", (W, H), (W, H), _bgra_in(W, H, 4), _i420(W, H, 65, 35), b"encode_bgra_i420_blocks<premul>",
+          pair=(GAMMA_SRGB, GAMMA_APPLE), ctx_options=(_LAYOUT_I420, _PREMUL), no_skew=_demoted("encode-i420")),
+    # +convert: packed words through the `y` pointer and pitch, and the point-sampled frame
+    Route("convert-packed", "encode", (W, H), (W, H), _bgra_in(W, H, 16), _words(W, H, 32), b"convert_bgra_packed444", pair=(GAMMA_SRGB, GAMMA_APPLE),
+          ctx_options=(_convert(_capi.CONVERT_PACKED444),), bands=True, no_skew=NO_BYTE_PLANE),
+    Route("convert-packed-blocks", "encode", (W, H), (W, H), _bgra_in(W, H, 4), _words(W, H, 4), b"convert_bgra_packed444_blocks",
+          pair=(GAMMA_SRGB, GAMMA_APPLE), ctx_options=(_convert(_capi.CONVERT_PACKED444),), no_skew=NO_BYTE_PLANE),
+    Route("convert-point-i420", "encode", (W, H), (W, H), _bgra_in(W, H, 16), _i420(W, H, 80, 48), b"convert_bgra_i420", pair=(GAMMA_SRGB, GAMMA_APPLE),
+          ctx_options=(_convert(_capi.CONVERT_POINT420), _LAYOUT_I420), bands=True, skew=_both(b"convert_bgra_i420_blocks")),
+    # the colour + alpha pair: five planes, the alpha frame's pitches and steps in the table's spare slots, 16 pairs in the table
+    Route("encode-pair", "encode", (W, H), (W, H), _bgra_in(W, H, 16), _nv12(W, H, 80, 80) + _alpha_nv12(W, H, 96, 112), b"encode_bgra_alpha_nv12",
+          pair=(GAMMA_SRGB, GAMMA_APPLE), ctx_options=(_WITH_ALPHA,), table=PAIR_TABLE, bands=True, skew=_both(b"encode_bgra_alpha_nv12_blocks")),
+    # ... into I420, premultiplying, the alpha frames without a chroma plane (NULL in every pair)
+    Route("encode-pair-i420-blocks", "encode", (W, H), (W, H), _bgra_in(W, H, 4), _i420(W, H, 65, 35) + _alpha_nv12(W, H, 67),
+          b"encode_bgra_alpha_i420_blocks<premul>", pair=(GAMMA_SRGB, GAMMA_APPLE), ctx_options=(_WITH_ALPHA, _LAYOUT_I420, _PREMUL), table=PAIR_TABLE,
+          no_skew=_demoted("encode-pair")),
+    # RGBA16Float input (linear light): the fast kernel needs 2-byte Y and CbCr only -- a step = 2 (mod 4) keeps it, an odd one demotes
+    Route("encode-half", "encode", (W, H), (W, H), _half_in(W, H, 16), _nv12(W, H, 80, 80), b"encode_rgba16f_nv12", pair=(GAMMA_LINEAR, GAMMA_APPLE),
+          in_fmt=F16, ctx_options=(_HALF_INPUT,), bands=True, skew={2: (b"encode_rgba16f_nv12", None), 1: (b"encode_rgba16f_nv12_blocks", None)}),
+    Route("encode-half-i420-blocks", "encode", (W, H), (W, H), _half_in(W, H, 8), _i420(W, H, 65, 35), b"encode_rgba16f_i420_blocks",
+          pair=(GAMMA_LINEAR, GAMMA_APPLE), in_fmt=F16, ctx_options=(_HALF_INPUT, _LAYOUT_I420), no_skew=_demoted("encode-half")),
+    # the RGBA16Float pair, under a second output curve
+    Route("encode-half-pair", "encode", (W, H), (W, H), _half_in(W, H, 16), _nv12(W, H, 80, 80) + _alpha_nv12(W, H, 96, 112), b"encode_rgba16f_alpha_nv12",
+          pair=(GAMMA_LINEAR, GAMMA_SRGB), in_fmt=F16, ctx_options=(_HALF_INPUT, _HALF_WITH_ALPHA), table=PAIR_TABLE, bands=True,
+          skew={2: (b"encode_rgba16f_alpha_nv12", None), 1: (b"encode_rgba16f_alpha_nv12_blocks", None)}),
 ]
 ROUTE = {r.name: r for r in ROUTES}
 PAIRS_RUN = [(r.name, c) for r in ROUTES for c in r.classes()]
@@ -263,6 +351,52 @@ PAIRS_RUN = [(r.name, c) for r in ROUTES for c in r.classes()]
 CLASSES_NOT_RUN = {(r.name, c): r.no_skew for r in ROUTES if r.no_skew for c in SKEW}
 CLASSES_NOT_RUN.update({(r.name, "plane-skew"): "one input plane and one output plane" for r in ROUTES if len(r.ins) == 1 and len(r.outs) == 1})
 CLASSES_NOT_RUN.update({(r.name, "bands-tail-descending"): "the launch is never split (no XCD-band map for this kernel)" for r in ROUTES if not r.bands})
+# every kernel name a route leaves on record: its own, and the one a skewed step demotes it to
+REPORTED = {r.kernel.decode() for r in ROUTES} | {k.decode() for r in ROUTES if r.skew for k, _ in r.skew.values()}
+
+
+def _forms_not_routed():
+    """kernel name -> why it has no route: the name on record (above) whose body it instantiates.  The names
+    bt709hip_last_kernel_name can report for the 1:1 alpha decodes, the RGBA16Float target, the fused rescales and the encoder
+    that no route or skew class reaches -- every layout and <premul> combination of the encoder; of the decode side the forms
+    that differ from a routed one in what they do with A alone (no census of its quantiser and log-table instantiations, which
+    the decoder's state selects, not its addressing)."""
+    same = lambda what, routed: "%s of the body %s addresses through" % (what, routed)
+    forms = {}
+    for layout in ("nv12", "i420"):
+        for shape, over in (("quads", "decode_nv12_quads<alpha,over>"), ("blocks", "decode_nv12_blocks<alpha,over>")):
+            plain = "decode_nv12_quads<nt>" if shape == "quads" else "decode_nv12_blocks"
+            forms["decode_%s_%s<alpha,straight>" % (layout, shape)] = same("the alpha instantiation that divides A out in registers,", plain)
+            forms["decode_%s_%s<alpha,over-colour>" % (layout, shape)] = same("the composite over a constant colour,", over)
+    forms["decode_nv12_rgba16f"] = same("the opaque instantiation", "decode_nv12_rgba16f<alpha>")
+    forms["decode_nv12_scaled<alpha,over-colour>"] = same("the composite over a constant colour,", "decode_nv12_scaled<alpha,over>")
+    for suffix in ("<alpha>", "<alpha,over>", "<alpha,over-colour>"):
+        forms["decode_nv12_scaled_f16" + suffix] = same("the alpha / composite instantiation through the RGBA16Float intermediate,", "decode_nv12_scaled_f16")
+    # the encoder: every family is one fast and one general body over the chroma layout (and, BGRA8 input, the premultiply bit)
+    families = [("encode_bgra_%s", "encode_bgra_nv12", "encode_bgra_nv12_blocks", True),
+                ("convert_bgra_%s", "convert_bgra_i420", "convert_bgra_i420_blocks", True),
+                ("encode_bgra_alpha_%s", "encode_bgra_alpha_nv12", "encode_bgra_alpha_nv12_blocks", True),
+                ("encode_rgba16f_%s", "encode_rgba16f_nv12", "encode_rgba16f_nv12_blocks", False),
+                ("encode_rgba16f_alpha_%s", "encode_rgba16f_alpha_nv12", "encode_rgba16f_alpha_nv12_blocks", False)]
+    for stem, fast, blocks, premul in families:
+        for layout in ("nv12", "i420"):
+            for general in (False, True):
+                for straight in ((False, True) if premul else (False,)):
+                    name = stem % layout + ("_blocks" if general else "") + ("<premul>" if straight else "")
+                    forms[name] = same("the %s%s instantiation" % (layout.upper(), ", premultiplying" if straight else ""), blocks if general else fast)
+    for general in (False, True):  # the packed words: one instantiation under both layouts
+        name = "convert_bgra_packed444" + ("_blocks" if general else "")
+        forms[name + "<premul>"] = same("the premultiplying instantiation", name)
+    for elem in ("u8", "f16", "f32"):
+        for layout in ("nv12", "i420"):
+            forms["encode_chw_%s<%s>" % (layout, elem)] = same("the %s, %s instantiation" % (layout.upper(), elem), "encode_chw_nv12<f16>")
+            forms["encode_chw_%s_blocks<%s>" % (layout, elem)] = same("the %s, %s instantiation" % (layout.upper(), elem), "encode_chw_nv12_blocks<f32>")
+    forms["encode_alpha_y<i420>"] = same("the alpha frame with U and V planes of 128,", "encode_alpha_y")
+    forms["encode_alpha_y_blocks<i420>"] = same("the alpha frame with U and V planes of 128,", "encode_alpha_y_blocks")
+    return {name: why for name, why in forms.items() if name not in REPORTED}
+
+
+FORMS_NOT_ROUTED = _forms_not_routed()
 
 
 class Layout:
@@ -418,11 +552,16 @@ class Call:
             self.ptrs = (C.c_void_p * n)(*[i_ptr("in", i) for i in range(n)])
             self.surfs = (Surface * n)(*[Surface(o_ptr("out", i), r.plane("out").stride, w, h, SRGB8, 0) for i in range(n)])
         else:
-            cbcr = len(r.outs) > 1
-            src = r.ins[0]  # "bgra", or the "chw" tensor: plane 0 and the pitch of every plane's rows
+            src = r.ins[0]  # "bgra", "rgba16f", or the "chw" tensor: plane 0 and the pitch of every plane's rows
             self.ins = (Surface * n)(*[Surface(i_ptr(src.name, i), src.stride, w, h, r.in_fmt, 0) for i in range(n)])
-            self.frames = (Frame * n)(*[Frame(o_ptr("y", i), r.plane("y").stride, o_ptr("cbcr", i) if cbcr else None, r.plane("cbcr").stride if cbcr else 0,
-                                              w, h, 0, 0) for i in range(n)])
+
+            def frame(y, c, i):  # a plane the route does not have: NULL, pitch 0 (the packed words: no "cbcr"; an alpha frame without chroma)
+                has = any(p.name == c for p in r.outs)
+                return Frame(o_ptr(y, i), r.plane(y).stride, o_ptr(c, i) if has else None, r.plane(c).stride if has else 0, w, h, 0, 0)
+            frames = [frame("y", "cbcr", i) for i in range(n)]
+            if r.paired:  # 2n frames: the colour frames, then the alpha frames
+                frames += [frame("alpha_y", "alpha_cbcr", i) for i in range(n)]
+            self.frames = (Frame * len(frames))(*frames)
 
     def _under_ctx_options(self, lib, ctx, call):
         """The route's context options for this call alone: the context is shared, so they are put back whatever happens."""
@@ -457,7 +596,12 @@ class Call:
             return lib.bt709hip_render_scaled_batch(ctx, n, self.ins, self.surfs, stream, wait)
         if r.entry == "unconvert":
             return lib.bt709hip_unconvert_batch(dec, n, self.ptrs, r.plane("in").stride, r.size[0], r.size[1], self.surfs, stream, wait)
-        return lib.bt709hip_encode_batch(ctx, n, self.ins, self.frames, r.pair[0], r.pair[1], stream, wait)
+        return lib.bt709hip_encode_batch(ctx, n, self.ins, self._pairs(range(n)) if r.paired and n != self.n else self.frames, r.pair[0], r.pair[1], stream, wait)
+
+    def _pairs(self, items):
+        """The frames of a paired call over `items` of the layout: their colour frames, then their alpha frames."""
+        items = list(items)
+        return (Frame * (2 * len(items)))(*[self.frames[i] for i in items] + [self.frames[self.n + i] for i in items])
 
     def _single(self, lib, ctx, dec, i, stream=None, wait=1):
         r = self.route
@@ -470,16 +614,18 @@ class Call:
             return lib.bt709hip_render_scaled(ctx, C.byref(self.ins[i]), C.byref(self.surfs[i]), stream, wait)
         if r.entry == "unconvert":
             return lib.bt709hip_unconvert(dec, self.ptrs[i], r.plane("in").stride, r.size[0], r.size[1], C.byref(self.surfs[i]), stream, wait)
-        return lib.bt709hip_encode(ctx, C.byref(self.ins[i]), C.byref(self.frames[i]), r.pair[0], r.pair[1], stream, wait)
+        out = self._pairs([i]) if r.paired else C.byref(self.frames[i])  # a paired call: `out` points to the pair's two frames
+        return lib.bt709hip_encode(ctx, C.byref(self.ins[i]), out, r.pair[0], r.pair[1], stream, wait)
 
     def expected_steps(self, layout):
-        """What the launch's step fields must hold, in the order the fake runtime reports them (fake_hip.h fake_hip_addressing)."""
+        """What the launch's step fields must hold, in the order the fake runtime reports them (fake_hip.h fake_hip_addressing):
+        six values; the last but one pair are the alpha frames' of a paired encode, where the kernels read them."""
         r, s = self.route, layout.steps
         if r.entry in ("decode", "half", "scaled"):
-            return [s["y"], s["cbcr"], s["alpha"] if r.alpha else 0, s["out"]]
+            return [s["y"], s["cbcr"], s["alpha"] if r.alpha else 0, s["out"], 0, 0]
         if r.entry in ("render", "unconvert"):
-            return [s["in"], s["out"], 0, 0]
-        return [s[r.ins[0].name], s["y"], s["cbcr"] if len(r.outs) > 1 else 0, 0]
+            return [s["in"], s["out"], 0, 0, 0, 0]
+        return [s[r.ins[0].name], s["y"], s.get("cbcr", 0), s["alpha_y"] if r.paired else 0, s.get("alpha_cbcr", 0), 0]
 
 
 # ------------------------------------------------------------------ samples, backgrounds and what they must become
@@ -508,7 +654,9 @@ def frame_data(route, k):
                 d[p.name] = rng.integers(0, 1 << 24, (h, w), dtype=np.uint32).view(np.uint8).reshape(h, 4 * w)
             elif p.name == "chw" and route.chw != "uint8":  # finite elements; de-normalised (ImageNet's std and mean) they span -0.2 .. 1.2
                 d[p.name] = (rng.random((3 * h, w)) * 6.0 - 3.0).astype(route.chw).view(np.uint8).reshape(3 * h, route.elem * w)
-            else:
+            elif p.name == "rgba16f":  # the half encoder's own texels: -0.25 .. 1.25, zeros, subnormals, infinities and NaNs among them
+                d[p.name] = ehc.random_texels(rng, h, w).view(np.uint8).reshape(h, 8 * w)
+            else:  # BGRA8 words: A is random, too (the premultiplying and the paired kernels read it)
                 d[p.name] = rng.integers(0, 256, (p.rows, p.row_bytes), dtype=np.uint8)
         _data[key] = d
     return _data[key]
@@ -525,6 +673,29 @@ def interleave(uv_planes):
     c = np.empty((half, 2 * uv_planes.shape[1]), np.uint8)
     c[:, 0::2], c[:, 1::2] = uv_planes[:half], uv_planes[half:]
     return c
+
+
+_expects = {}
+
+
+def _half_expect(oracle):
+    """encode_half_cases.Expect(oracle), one for all routes: it remembers the oracle's answers."""
+    if id(oracle) not in _expects:
+        _expects[id(oracle)] = (oracle, ehc.Expect(oracle))
+    return _expects[id(oracle)][1]
+
+
+def _frames_of(route, colour, alpha):
+    """(y, cbcr) NV12 of an encoder route's colour frame (and of its alpha frame) -> the route's planes: an I420 route's chroma
+    planes are encode_chw_cases.planar of the NV12 rows, a plane the route does not have is left out."""
+    w, h = route.size
+    chroma = lambda c: ecc.planar(c).reshape(h, w // 2) if route.planar_chroma else c
+    res = {"y": colour[0], "cbcr": chroma(colour[1])}
+    if alpha is not None:
+        res["alpha_y"] = alpha[0]
+        if any(p.name == "alpha_cbcr" for p in route.outs):
+            res["alpha_cbcr"] = chroma(alpha[1])
+    return res
 
 
 def want(route, oracle, tabs, T, k, bg_index):
@@ -573,9 +744,23 @@ def want(route, oracle, tabs, T, k, bg_index):
         tensor = np.ascontiguousarray(d["chw"]).view(route.chw).reshape(3, h, w)
         y, c = oracle.encode_nv12(ecc.words_of_planes(tensor, route.norm) & np.uint32(0xFFFFFF), w, h, route.pair[0], route.pair[1])
         res = {"y": y, "cbcr": ecc.planar(c).reshape(h, w // 2) if route.planar_chroma else c}
+    elif route.in_fmt == F16:  # RGBA16Float input: the composition of encode_half_cases; the pair's alpha frame is encode_half_alpha_cases'
+        texels = np.ascontiguousarray(d["rgba16f"]).view(np.uint16).reshape(h, w, 4)
+        expect = _half_expect(oracle)
+        res = _frames_of(route, expect.planes(texels, route.pair[1]), ehac.alpha_planes(expect, texels) if route.paired else None)
     else:
-        y, c = oracle.encode_nv12(d["bgra"].view(np.uint32).reshape(h, w), w, h, route.pair[0], route.pair[1])
-        res = {"y": y, "cbcr": c}
+        words = np.ascontiguousarray(d["bgra"]).view(np.uint32).reshape(h, w)
+        colour = sac.premultiply(words) if dict(route.ctx_options).get(_capi.CTX_OPT_ENCODE_PREMULTIPLY) else words
+        if route.convert != _capi.CONVERT_OFF:  # +convert: of the picture; POINT420: copyBT709ToCoreVideo of those words
+            packed = oracle.convert_packed(route.pair[1], colour, w, h)
+            assert packed is not None
+            if route.convert == _capi.CONVERT_PACKED444:
+                res = {"y": packed.astype(np.uint32).view(np.uint8).reshape(h, 4 * w)}
+            else:
+                res = _frames_of(route, oracle.packed_to_nv12(packed, w, h), None)
+        else:  # the pair's alpha frame reads A as stored, premultiplying or not: Y = T[A], every chroma byte 128
+            alpha = (T[(words >> 24).astype(np.uint8)], np.full((h // 2, w), 128, np.uint8)) if route.paired else None
+            res = _frames_of(route, oracle.encode_nv12(colour, w, h, route.pair[0], route.pair[1]), alpha)
     for name, arr in res.items():
         p = route.plane(name)
         res[name] = np.ascontiguousarray(arr).reshape(p.rows, p.row_bytes)

@@ -1,7 +1,9 @@
 """How MUCH one launch carries (tests/test_extents_cpu.py, tests/test_extents_gpu.py; numpy and ctypes only).
 
 tests/batch_spacing_cases.py pins how every kernel finds a frame, tests/row_pitch_cases.py how it finds a row.  This module takes
-the same routes -- row_pitch_cases.ROUTES: every kernel form the project can report -- to the other end of the same index space:
+the same routes -- row_pitch_cases.ROUTES: a route for every kernel body the project launches; the names it can report beside
+them are instantiations of those bodies, listed with the routed form in batch_spacing_cases.FORMS_NOT_ROUTED -- to the other
+end of the same index space:
 the most rows, frames and columns an entry point accepts ("Extents"), and one past it.  build(name, cls) derives a
 RESIZED copy of the route (resized(): other sizes, every pitch congruent to the route's own mod 16 and every base a multiple of
 256, so the kernel on record stays the route's, and batch_spacing_cases.want() keeps calling the oracle the route's own tests
@@ -17,7 +19,8 @@ use) and lays its planes out, frame after frame, in one input and one output sla
     too-tall           the first refused height: +2 rows, +4 for half, out height 65536, chroma height 65536
     longest            65535 evenly spaced items through the batched entry point, each the smallest geometry that selects the
                        kernel (at most 16 x 4).  Routes whose launch splits under the XCD-band map (Route.bands) run with the map
-                       at its default: 65528 frames under it, grid.z 8191, and 7 behind advance_frames
+                       at its default: 65528 frames under it, grid.z 8191, and 7 behind advance_frames.  An item of a paired
+                       encode is a PAIR: the call passes 2 x 65535 frames, all five planes evenly spaced
     longest-unbanded   the same with BT709HIP_OPT_XCD_BANDS (the encoder: BT709HIP_CTX_OPT_XCD_BANDS) at 0: one launch, grid.z 65535
     too-many           65536 evenly spaced items: refused
     wide               one frame of width 2^20 + 12 (+ the route's own width mod 4; chroma width 2^20 + 8 / + 6 for the plane
@@ -70,7 +73,8 @@ def shuffles(route):
 
 def general(route):
     """The routes whose own pitches demote them to a kernel that takes any width: they run at width 6."""
-    return route.name in ("blocks", "unconvert-pixel", "encode-blocks", "interleave-bytes", "deinterleave-bytes", "chw-blocks-f16", "encode-chw-f32-blocks")
+    return route.name in ("blocks", "unconvert-pixel", "encode-blocks", "interleave-bytes", "deinterleave-bytes", "chw-blocks-f16", "encode-chw-f32-blocks",
+                          "encode-i420-blocks-premul", "convert-packed-blocks", "encode-pair-i420-blocks", "encode-half-i420-blocks")
 
 
 def refusal(route, cls):
@@ -146,13 +150,15 @@ def _shape(route, p, which, w, h, ow, oh):
     e = route.entry
     if shuffles(route):
         return (2 * w if p.name == "cbcr" else w), h
-    if p.name in ("y", "alpha"):
+    if p.name == "y" and p.unit == 4:  # the packed converter's words, through the frame's `y`
+        return 4 * w, h
+    if p.name in ("y", "alpha", "alpha_y"):
         return w, h
-    if p.name == "cbcr":
+    if p.name in ("cbcr", "alpha_cbcr"):
         return (w // 2, h) if route.planar_chroma else (w, h // 2)
     if route.chw and p.name in ("out", "chw"):  # a planar CHW surface: its planes stacked at one pitch
         return (route.elem * w, 3 * h) if which == "in" else (route.elem * ow, route.chw_planes * oh)
-    if which == "in":
+    if which == "in":  # texels: 8 bytes each of an RGBA16Float surface (pass 2's source, the half encoder's input), else 4
         return (8 if route.in_fmt == F16 else 4) * w, h
     return (8 if route.fmt == F16 else 4) * ow, oh
 

@@ -519,9 +519,9 @@ hipError_t hipGraphLaunch(hipGraphExec_t g, hipStream_t s) {
 namespace bt709 {
 
 // what fake_hip_last_addressing reports: filled by every launcher below
-static thread_local fake_hip_addressing tl_addressing = {-1, 0, {0, 0, 0, 0}};
-static void note_addressing(bool uniform, int frames, int64_t s0, int64_t s1, int64_t s2 = 0, int64_t s3 = 0) {
-  tl_addressing = fake_hip_addressing{uniform ? 1 : 0, frames, {s0, s1, s2, s3}};
+static thread_local fake_hip_addressing tl_addressing = {-1, 0, {0, 0, 0, 0, 0, 0}};
+static void note_addressing(bool uniform, int frames, int64_t s0, int64_t s1, int64_t s2 = 0, int64_t s3 = 0, int64_t s4 = 0) {
+  tl_addressing = fake_hip_addressing{uniform ? 1 : 0, frames, {s0, s1, s2, s3, s4, 0}};
 }
 static void note_addressing(const DecodeParams &p, int frames) { note_addressing(p.uniform != 0, frames, p.step_y, p.step_cbcr, p.step_alpha, p.step_out); }
 int last_addressing(fake_hip_addressing *out) {
@@ -599,7 +599,9 @@ const char *launch_render_scaled(const RenderParams &p, int frames, bool, uint32
   return launch(stream, "render_scaled", frames, p.in, p.out, frames * 4.0 * (static_cast<double>(p.width) * p.height + static_cast<double>(p.out_width) * p.out_height));
 }
 const char *launch_encode(const EncodeParams &p, int frames, bool fast, bool xcd_bands, hipStream_t stream) {
-  note_addressing(p.uniform != 0, frames, p.step_bgra, p.step_y, p.step_cbcr);
+  // a paired launch: the alpha frames' steps from the spare slots pair_frame and advance_frames read them from
+  const bool pair_steps = encode_pair(p) && p.uniform;
+  note_addressing(p.uniform != 0, frames, p.step_bgra, p.step_y, p.step_cbcr, pair_steps ? p.pairs[1].spare : 0, pair_steps ? p.pairs[2].spare : 0);
   // the plan the real launcher would record for a plain (single-launch) call: tiles x row-pair groups x pictures
   LaunchShape &shape = last_launch_shape();
   if (shape.launches++ == 0) {

@@ -31,10 +31,11 @@ void fake_hip_fail_launch_after_free(int64_t nth); /* the same, counted from the
 void fake_hip_set_output_rate(const void *ptr, uint64_t bytes, double GBps);
 void fake_hip_set_rate_by_allocation_order(const double *GBps, int n); /* the k-th LARGE (>= 64 MiB) hipMalloc from now gets GBps[k % n] */
 /* How the last kernel launch THIS THREAD made finds frame i: uniform != 0 = frame 0 + i * step (no pointer table), else the table.
-   steps, in bytes -- decode launches: Y, CbCr, alpha, output; encoder: BGRA, Y, CbCr; unconvert / render_scaled: input, output. */
+   steps, in bytes -- decode launches: Y, CbCr, alpha, output; encoder: BGRA (or texels, or plane 0), Y, CbCr, and of an evenly
+   spaced PAIRED launch alpha Y, alpha CbCr (0 otherwise); unconvert / render_scaled: input, output.  Unused entries are 0. */
 typedef struct {
   int32_t uniform, frames;
-  int64_t steps[4];
+  int64_t steps[6];
 } fake_hip_addressing;
 int fake_hip_last_addressing(fake_hip_addressing *out); /* 0, or -1 before the thread's first launch */
 #ifdef __cplusplus

@@ -30,6 +30,11 @@ the contract is planes x OH x pitch < 2^31 (scaled_planes_fit): under-2-GiB and 
 a fourth plane batch_spacing_cases gives an opaque decoder's target is NOT given here: at these pitches it lies outside the
 slab (the spacing and extent suites and the CHW families' own tests watch that place).
 
+The encoder's families (batch_spacing_cases: I420, the converter, the pairs, RGBA16Float input) each spell these products out in
+a header of their own.  The packed converter's "y" plane is 4-byte words and a single-row product (every row is formed on its
+own, as a BGRA target's); a pair's "alpha_y" is walked in row pairs as Y is, with the alpha frame's own pitch, and its
+"alpha_cbcr" -- under I420 v_plane_offset(AlphaPlanes) + the row offset -- crosses the boundary in its last row as "cbcr" does.
+
 A layout holds two frames, frame 1's planes 4 KiB behind frame 0's, and names the WINDOWS the host touches: one per row (the
 samples and a guard band either side) and the alias windows.  Layout.check() asserts, on the CPU, that all of them lie inside
 their slab, apart from one another, that the class's inequality holds for every plane and that every alias window is where the
@@ -169,7 +174,7 @@ class Layout:
                     assert TWO31 <= (p.rows - 2) * p.stride < TWO32 <= last and max(o) < (1 << 20), (name, p.name)
                     assert last - TWO32 >= p.row_bytes + 2 * GUARD  # not row 0
                     landed = [v + (last & 0xFFFFFFFF) for v in o]
-                    if self.base.planar_chroma and p.name == "cbcr":  # U's rows below 2^32, V's last above: v_offset + row offset crosses it
+                    if self.base.planar_chroma and p.name in ("cbcr", "alpha_cbcr"):  # U's rows below 2^32, V's last above: v_offset + row offset crosses it
                         assert (p.rows // 2 - 1) * p.stride + p.row_bytes < TWO32 <= (p.rows // 2) * p.stride + (p.rows // 2 - 1) * p.stride
                 elif cls == "under-2-GiB":  # the largest accepted pitch of the residue
                     assert area < TWO31 <= p.rows * (p.stride + 16), (name, p.name)

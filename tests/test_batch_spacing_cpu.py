@@ -13,7 +13,7 @@ IN_BASE, OUT_BASE = 1 << 44, 1 << 45  # "device" addresses: a fake launch touche
 
 
 class Addressing(C.Structure):  # fake_hip_addressing
-    _fields_ = [("uniform", C.c_int32), ("frames", C.c_int32), ("steps", C.c_int64 * 4)]
+    _fields_ = [("uniform", C.c_int32), ("frames", C.c_int32), ("steps", C.c_int64 * 6)]
 
 
 # ------------------------------------------------------------------ the builder
@@ -22,7 +22,7 @@ def test_every_layout_passes_its_self_checks():
     """Layout.check() for every (route, class) of the GPU file: every true and every alias window inside its slab, pairwise
     disjoint, a guard band apart; the steps are what the class says; and beyond check(): the far classes really leave the low
     4 GiB, their windows are all the host touches, and the small classes stay a GiB away from either end of the slab."""
-    assert len(set(bs.PAIRS_RUN)) == len(bs.PAIRS_RUN) == 324  # 215 before the nine planar CHW routes
+    assert len(set(bs.PAIRS_RUN)) == len(bs.PAIRS_RUN) == 438  # 215 before the nine planar CHW routes, 324 before the ten of the encoder's other families
     for name, cls in bs.PAIRS_RUN:
         route = bs.ROUTE[name]
         L = bs.build(route, cls)
@@ -56,11 +56,46 @@ def test_every_route_runs_every_class_or_says_why_not():
         entries.setdefault(r.entry, []).append(r.kernel)
     # the planar CHW routes: the fast kernels split under the band map (two launches, the first banded: the GPU file asserts it)
     chw = [r for r in bs.ROUTES if r.chw]
-    assert [r.name for r in chw] == [r.name for r in bs.ROUTES[-9:]] and all(p.stacked == r.chw_planes for r in chw for p in r.ins + r.outs if p.name in ("out", "chw"))
+    assert [r.name for r in chw] == [r.name for r in bs.ROUTES[19:28]] and all(p.stacked == r.chw_planes for r in chw for p in r.ins + r.outs if p.name in ("out", "chw"))
     assert sorted(r.name for r in chw if r.bands) == ["chw-quads-f16-alpha", "chw-quads-f32-i420", "chw-quads-u8", "encode-chw-f16", "encode-chw-u8-i420"]
     assert all((r.name, "bands-tail-descending") in run for r in chw if r.bands)
     assert all((r.name, c) in run for r in chw for c in ("far", "far-descending", "fan-out", "plane-skew", "descending-33", "table-twin"))
-    assert {k: len(v) for k, v in entries.items()} == {"decode": 9, "half": 3, "scaled": 6, "render": 2, "unconvert": 2, "encode": 6}
+    assert {k: len(v) for k, v in entries.items()} == {"decode": 9, "half": 3, "scaled": 6, "render": 2, "unconvert": 2, "encode": 16}
+    # the encoder's other families, appended behind them: five families, a fast and a general kernel of each but the last
+    new = bs.ROUTES[28:]
+    assert [r.name for r in new] == ["encode-i420", "encode-i420-blocks-premul", "convert-packed", "convert-packed-blocks", "convert-point-i420",
+                                     "encode-pair", "encode-pair-i420-blocks", "encode-half", "encode-half-i420-blocks", "encode-half-pair"]
+    assert all(r.entry == "encode" and r.size == r.out_size == (64, 16) and r.ctx_options and set(dict(r.ctx_options)) <= set(bs.CTX_DEFAULTS) for r in new)
+    assert sorted(r.name for r in new if r.bands) == ["convert-packed", "convert-point-i420", "encode-half", "encode-half-pair", "encode-i420", "encode-pair"]
+    assert all((r.name, c) in run for r in new for c in ("far", "far-descending", "fan-out", "crossed-up-down", "descending-33", "table-twin"))
+    assert all(((r.name, "plane-skew") in run) == (not r.name.startswith("convert-packed")) for r in new)
+    assert all((r.name, "bands-tail-descending") in run for r in new if r.bands)
+    assert [r.name for r in new if r.paired] == ["encode-pair", "encode-pair-i420-blocks", "encode-half-pair"] and all((r.table == 16) == r.paired for r in new)
+    # the skewed classes run on the five fast routes that have a byte-addressed plane; what they must report follows from the
+    # header's alignment rules: dword stores to Y (and alpha Y) demote the BGRA8 forms under either skew, the RGBA16Float forms
+    # store halves -- a step = 2 (mod 4) keeps the fast kernel, an odd one demotes
+    skewed = {r.name: {k: v[0] for k, v in r.skew.items()} for r in new if r.skew}
+    assert skewed == {"encode-i420": {2: b"encode_bgra_i420_blocks", 1: b"encode_bgra_i420_blocks"},
+                      "convert-point-i420": {2: b"convert_bgra_i420_blocks", 1: b"convert_bgra_i420_blocks"},
+                      "encode-pair": {2: b"encode_bgra_alpha_nv12_blocks", 1: b"encode_bgra_alpha_nv12_blocks"},
+                      "encode-half": {2: b"encode_rgba16f_nv12", 1: b"encode_rgba16f_nv12_blocks"},
+                      "encode-half-pair": {2: b"encode_rgba16f_alpha_nv12", 1: b"encode_rgba16f_alpha_nv12_blocks"}}
+    assert all((name, c) in run for name in skewed for c in bs.SKEW)
+    assert all("no byte-addressed plane" in bs.CLASSES_NOT_RUN[(name, c)] for name in ("convert-packed", "convert-packed-blocks") for c in bs.SKEW)
+    assert len(run) - 324 == 114
+
+
+def test_forms_without_a_route_say_whose_body_they_share():
+    """FORMS_NOT_ROUTED: no listed name is one a route (or a route's skew class) leaves on record, and every reason names one
+    that is."""
+    assert bs.FORMS_NOT_ROUTED and {r.kernel.decode() for r in bs.ROUTES} <= bs.REPORTED
+    for name, reason in bs.FORMS_NOT_ROUTED.items():
+        assert name not in bs.REPORTED and reason, name
+        assert any(reason.endswith("body %s addresses through" % routed) for routed in bs.REPORTED), (name, reason)
+    for name in ("decode_nv12_quads<alpha,straight>", "decode_nv12_blocks<alpha,over-colour>", "decode_nv12_rgba16f", "decode_nv12_scaled_f16<alpha>",
+                 "decode_nv12_scaled_f16<alpha,over>", "encode_alpha_y<i420>", "encode_bgra_nv12<premul>", "encode_bgra_alpha_i420", "convert_bgra_nv12",
+                 "convert_bgra_packed444<premul>", "encode_rgba16f_i420", "encode_rgba16f_alpha_i420_blocks"):
+        assert name in bs.FORMS_NOT_ROUTED, name
 
 
 # ------------------------------------------------------------------ the shim on the fake HIP runtime
@@ -136,7 +171,9 @@ def test_entry_point_takes_the_uniform_path_with_the_builders_steps(fake, fake_r
     """bt709hip_{decode, decode_half, decode_scaled, render_scaled, unconvert, encode}_batch over every route and class of the
     GPU file: one launch of all the frames; counts 2 and 3 (and 33, and 70) evenly spaced launch WITHOUT the table, with the steps
     the builder computed -- negative, zero, 2^32 + d, another for every plane; table-twin launches with the table (the one entry
-    point without a table refuses it); 33 frames of which one is moved are BT709HIP_ERR_UNSUPPORTED, nothing launched."""
+    point without a table refuses it); 33 frames of which one is moved are BT709HIP_ERR_UNSUPPORTED, nothing launched.  A PAIRED
+    encode (colour + alpha frames, from BGRA8 or RGBA16Float) has five steps: the alpha frames' two must arrive in the spare slots
+    pair_frame and advance_frames read them from -- the fake launcher reports those slots -- and its table holds 16 pairs."""
     lib, rig = fake, fake_rig
     routes = [r for r in bs.ROUTES if r.entry == entry]
     assert routes
@@ -159,16 +196,20 @@ def test_entry_point_takes_the_uniform_path_with_the_builders_steps(fake, fake_r
             if L.uniform:
                 assert uniform == 1 and steps == call.expected_steps(L), (route.name, cls, steps, call.expected_steps(L))
             else:
-                assert uniform == 0 and steps == [0, 0, 0, 0], (route.name, cls, uniform, steps)
+                assert uniform == 0 and steps == [0] * 6, (route.name, cls, uniform, steps)
+            if L.uniform and route.paired:  # all five steps of a paired batch, each its own plane's (plane-skew: five different ones)
+                s = L.steps
+                assert steps[:5] == [s[route.ins[0].name], s["y"], s["cbcr"], s["alpha_y"], s.get("alpha_cbcr", 0)], (route.name, cls, steps)
         # past the table: evenly spaced is accepted (above), anything else refused before a launch
         L = bs.build(route, "descending-33")
         call = bs.Call(route, L, IN_BASE, OUT_BASE)
-        _bump(call, route, 17, 16)
+        assert route.table in (16, 31, 32)  # 31: a planar CHW encode, whose table gives one entry to the scale and bias; 16: PAIRS
+        _bump(call, route, min(17, route.table - 1), 16)  # a frame the table's own count still holds
         mark = lib.fake_hip_log_size()
         assert call.batch(lib, rig.ctx, dec) == _capi.ERR_UNSUPPORTED, route.name
-        assert route.table in (31, 32)  # 31: a planar CHW encode, whose table gives one entry to the scale and bias
         if route.table < 32:
             assert call.batch(lib, rig.ctx, dec, count=32) == _capi.ERR_UNSUPPORTED and rig.kernels(mark) == [], route.name
+            assert call.batch(lib, rig.ctx, dec, count=route.table + 1) == _capi.ERR_UNSUPPORTED and rig.kernels(mark) == [], route.name
         assert call.batch(lib, rig.ctx, dec, count=route.table) == (_capi.ERR_UNSUPPORTED if entry == "render" else 0), route.name
         assert len(rig.kernels(mark)) == (0 if entry == "render" else 1)
         if entry != "render":

@@ -9,6 +9,9 @@ the batched entry point runs once, and
   * every output byte outside the pixels is what it was (the canary), the far classes' alias windows -- where a step cut to
     32 bits would have landed -- included.
 
+A paired encode route (colour + alpha frames of one picture) passes 2n frames -- the colour frames, then the alpha frames -- and
+its single call the two frames of one pair; all five planes take part in every comparison above.
+
 The slabs are allocated once (module fixture), never filled or read whole: the host touches the layouts' windows only.
 Not run, with the reason: batch_spacing_cases.CLASSES_NOT_RUN (the skewed classes on routes whose pointers must be texel
 aligned or whose kernel is already the general one -- variant_cases.LAUNCH_CASES' step_pad pins that one -- plane-skew on

@@ -119,7 +119,7 @@ def test_option_domain_and_round_trip(lib, has_alpha):
 # ------------------------------------------------------------------ the shim on the fake HIP runtime
 
 class Addressing(C.Structure):  # fake_hip_addressing
-    _fields_ = [("uniform", C.c_int32), ("frames", C.c_int32), ("steps", C.c_int64 * 4)]
+    _fields_ = [("uniform", C.c_int32), ("frames", C.c_int32), ("steps", C.c_int64 * 6)]
 
 
 @pytest.fixture(scope="module")

@@ -37,6 +37,10 @@ def test_every_layout_passes_its_self_checks():
             for p in planes:
                 o = off[p.name]
                 assert L.n == 1 or (o[1] - o[0] == L.steps[p.name] >= p.extent + ec.ITEM_GAP and o[L.n - 1] == o[0] + (L.n - 1) * L.steps[p.name])
+        if base.entry == "encode":  # texels of 4 bytes, 8 of an RGBA16Float surface; elements of a CHW tensor
+            texel = base.elem if base.chw else 8 if base.in_fmt == bs.F16 else 4
+            assert r.ins[0].row_bytes == texel * w and r.ins[0].unit == texel, (name, cls)
+            assert [p.name for p in r.outs] == [p.name for p in base.outs] and ("alpha_y" in [p.name for p in r.outs]) == base.paired
         if cls in ("longest", "longest-unbanded", "too-many"):
             assert w <= 16 and h <= 4 and ow <= 16 and oh <= 4
         elif cls in ("tallest", "tallest-from-tall", "too-tall"):
@@ -75,14 +79,15 @@ def test_every_route_runs_every_class_or_says_why_not():
         r = ec.ROUTE[name]
         assert reason and ((cls in ("longest", "longest-unbanded", "too-many") and ec.shuffles(r)) or (cls == "longest-unbanded" and not r.bands)
                            or (cls in ("tallest-from-tall", "wide-down") and not ec.rescales(r))), (name, cls)
-    assert len(ec.PAIRS_RUN) == 32 + 8 + 28 + 11 + 32 + 8 and len(ec.PAIRS_REFUSED) == 32 + 28
+    assert len(ec.PAIRS_RUN) == 42 + 8 + 38 + 17 + 42 + 8 and len(ec.PAIRS_REFUSED) == 42 + 38  # ten routes, six of them banded, more than 32 / 28 / 11
 
 
 def test_every_kernel_name_meets_every_extent():
     """Every kernel name a route can leave on record appears in a tallest, a wide and -- where a batched form exists -- a longest
     case, and the resized route still asks for it."""
     names = {r.kernel for r in ec.ROUTES}
-    assert len(names) == 29  # of 32 routes: decode_nv12_scaled in two tap forms, the plane-shuffle kernels in a wide and a byte branch
+    assert len(names) == 39  # of 42 routes: decode_nv12_scaled in two tap forms, the plane-shuffle kernels in a wide and a byte branch
+    assert not names & {n.encode() for n in bs.FORMS_NOT_ROUTED}  # the names without a route: instantiations of these bodies
     for cls in ("tallest", "longest", "wide"):
         met = {ec.resized(ec.ROUTE[name], c).kernel for name, c in ec.PAIRS_RUN if c == cls}
         batched = {r.kernel for r in ec.ROUTES if not ec.shuffles(r)}
@@ -111,7 +116,8 @@ def test_an_item_index_gone_wrong_lands_on_other_content():
     assert ec.SINGLES == [0, 8191 - 1, 8191, 8 * 8191 - 1, 8 * 8191, ec.MOST_ITEMS - 1] and 8 * 8191 == ec.MOST_ITEMS - ec.MOST_ITEMS % 8
 
 
-@pytest.mark.parametrize("name", ["quads", "half-narrow", "scaled-wide", "scaled-over", "unconvert-pixel", "encode-fast"])
+@pytest.mark.parametrize("name", ["quads", "half-narrow", "scaled-wide", "scaled-over", "unconvert-pixel", "encode-fast", "convert-packed", "encode-pair-i420-blocks",
+                                  "encode-half-pair"])
 def test_two_residues_give_distinct_expected_bytes(oracle, name):
     import json
     import os
@@ -147,7 +153,8 @@ def test_resized_routes_keep_what_selects_their_kernel():
         w = r.size[0]
         assert w % 2 == 0 and (ec.general(base) or ec.rescales(base) or w % 4 == 0) and (base.entry != "half" or w % 4 == 0)
         if ec.general(base):
-            assert any(p.stride % 4 for p in r.ins + r.outs) or w % 4 or name.endswith("-bytes")
+            # a byte plane off a 4-byte pitch, a plane of texels or words (its pitch is a multiple of 4 by contract) off a 16-byte one
+            assert any(p.stride % (4 if p.unit == 1 else 16) for p in r.ins + r.outs) or w % 4 or name.endswith("-bytes")
         if name.endswith("-wide") and ec.shuffles(base):
             assert w % 8 == 0
         if base.taps is not None:

@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 
 import batch_spacing_cases as bs
+import encoder_cases as enc
 import extent_cases as ec
 import row_pitch_cases as rp
 from metalbt709decoder_amd import _capi
@@ -29,10 +30,13 @@ pytestmark = pytest.mark.gpu
 
 CHW_QUADS = ("chw-quads-u8", "chw-quads-f16-alpha", "chw-quads-f32-i420")  # launch_decode's plan over the planar CHW kernels
 CHW_ENCODE = ("encode-chw-f16", "encode-chw-u8-i420")                      # launch_encode's own plan
+ENCODE_HALF = ("encode-half", "encode-half-pair")  # launch_encode's plan of a BGRA8 picture twice as wide (a 2x2 block a lane)
+ENCODE_FAMILIES = ("encode-i420", "convert-packed", "convert-point-i420", "encode-pair") + ENCODE_HALF  # launch_encode's plan, fast kernels
+ENCODE_GENERAL = ("encode-i420-blocks-premul", "convert-packed-blocks", "encode-pair-i420-blocks", "encode-half-i420-blocks")
 STACKED = ("quads", "quads-over", "i420", "half-wide") + CHW_QUADS  # narrow frames: row pairs stacked in blockDim.y (quads_rows_per_block)
-FULL_GRID_Y = ("half-narrow", "encode-blocks", "encode-chw-f32-blocks", "interleave-wide", "interleave-bytes", "deinterleave-wide", "deinterleave-bytes")
-WALKS_ROW_PAIRS = ("encode-fast", "encode-alpha-y") + CHW_ENCODE  # 3 to 9 row pairs a workgroup
-TILED = ("quads", "quads-over", "i420", "rgba16f-alpha", "half-wide", "half-rep-alpha", "encode-fast", "encode-alpha-y") + CHW_QUADS + CHW_ENCODE
+FULL_GRID_Y = ("half-narrow", "encode-blocks", "encode-chw-f32-blocks", "interleave-wide", "interleave-bytes", "deinterleave-wide", "deinterleave-bytes") + ENCODE_GENERAL
+WALKS_ROW_PAIRS = ("encode-fast", "encode-alpha-y") + CHW_ENCODE + ENCODE_FAMILIES  # 3 to 9 row pairs a workgroup
+TILED = ("quads", "quads-over", "i420", "rgba16f-alpha", "half-wide", "half-rep-alpha", "encode-fast", "encode-alpha-y") + CHW_QUADS + CHW_ENCODE + ENCODE_FAMILIES
 GENERAL_DECODE = ("blocks", "chw-blocks-f16")                   # grid-strided over the row pairs; the frames live in gridDim.y
 RECORDS_LAUNCH = ("decode", "half", "encode", "interleave", "deinterleave")  # bt709hip_last_launch_info
 
@@ -109,6 +113,12 @@ def _check_record(rig, L, label):  # noqa: F811
         return
     grid, block, launches, bands = rig.launch()
     rows = _rows_walked(route)
+    if name in ENCODE_HALF + ("encode-half-i420-blocks",):
+        # RGBA16Float input: the BGRA8 encoder's plan of a picture TWICE AS WIDE, same height and count (the general kernel's: of
+        # the picture itself, a 2x2 block a lane either way) -- from the restated plan, not from the record
+        fast = name in ENCODE_HALF
+        plan = enc.expected_plan(2 * route.size[0] if fast else route.size[0], route.size[1], n, fast=fast, bands=cls != "longest-unbanded")
+        assert (tuple(grid), block[0], launches, bands) == (tuple(plan["grid"]), plan["block"], plan["launches"], plan["xcd_bands"]), (label, grid, block, launches, bands, plan)
     if cls == "tallest":
         assert launches == 1, (label, launches)
         if name in STACKED:  # the ragged last workgroup: its loads are clamped to the last row pair

@@ -19,7 +19,7 @@ from test_batch_spacing_cpu import IN_BASE, OUT_BASE, FakeRig, fake  # noqa: F40
 def test_every_layout_passes_its_self_checks():
     """Layout.check() for every (route, class) and every at-2-GiB plane of the GPU file, and beyond check(): the pitches are the
     extreme ones of their residue, what the host touches stays small, and the two past- classes really differ by 2^32."""
-    assert len(set(rp.PAIRS_RUN)) == len(rp.PAIRS_RUN) == 2 * 24 + 8 and len(set(rp.AT_LIMIT)) == len(rp.AT_LIMIT) == 24
+    assert len(set(rp.PAIRS_RUN)) == len(rp.PAIRS_RUN) == 2 * 34 + 8 and len(set(rp.AT_LIMIT)) == len(rp.AT_LIMIT) == 24
     for name, cls in rp.PAIRS_RUN:
         L = rp.build(rp.ROUTE[name], cls)
         assert L.n == 2
@@ -41,7 +41,7 @@ def test_every_layout_passes_its_self_checks():
         assert v.rows * v.stride >= rp.TWO31 > v.rows * (v.stride - 16)
     # the order the GPU file runs them in: every past-2^31 pair first
     firsts = [i for i, (_, c) in enumerate(rp.PAIRS_RUN) if c == "past-2^32"]
-    assert all(c == "past-2^31" for _, c in rp.PAIRS_RUN[:firsts[0]]) and firsts[0] == 24
+    assert all(c == "past-2^31" for _, c in rp.PAIRS_RUN[:firsts[0]]) and firsts[0] == 34
 
 
 def test_every_route_runs_every_class_or_says_why_not():
@@ -54,6 +54,11 @@ def test_every_route_runs_every_class_or_says_why_not():
     for (name, cls), reason in rp.CLASSES_NOT_RUN.items():
         assert reason and (cls in rp.PAST) == rp.limited(rp.ROUTE[name]) and (cls in rp.LIMIT) != rp.limited(rp.ROUTE[name])
     assert sorted(r.name for r in rp.ROUTES if rp.limited(r)) == ["render-bgra8", "render-rgba16f", "scaled-chw-f32-alpha", "scaled-chw-u8", "scaled-f16", "scaled-once", "scaled-over", "scaled-wide"]
+    # the encoder's families form 64-bit row products: none is limited, each runs both past- classes, the alpha frame's planes included
+    for name, planes in (("encode-pair", ["bgra", "y", "cbcr", "alpha_y", "alpha_cbcr"]), ("encode-pair-i420-blocks", ["bgra", "y", "cbcr", "alpha_y"]),
+                         ("encode-half-pair", ["rgba16f", "y", "cbcr", "alpha_y", "alpha_cbcr"]), ("convert-packed", ["bgra", "y"])):
+        r = rp.ROUTE[name]
+        assert not rp.limited(r) and [p.name for p in r.ins + r.outs] == planes and all((name, c) in run for c in rp.PAST)
     assert {(n, p) for n, p in rp.AT_LIMIT if n == "scaled-over"} == {("scaled-over", p) for p in ("y", "cbcr", "alpha", "out")}
 
 
