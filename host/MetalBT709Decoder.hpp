@@ -129,6 +129,22 @@ class CVPixelBuffer {
       f_.cbcr = static_cast<uint8_t *>(p) + ysz;
     }
   }
+  // planar = true: an I420 buffer (the YUV4MPEG2 layout; BT709HIP_OPT_CHROMA_LAYOUT = BT709HIP_CHROMA_I420) -- frame()->cbcr is the U
+  // plane, W/2 x H/2 bytes at pitch cbcr_stride, V the same shape (height/2) * cbcr_stride behind it.  The decoder reads it as such
+  // once the caller has set kChromaLayoutOption to kChromaI420 (and setScaledPlanar for the rescales); filled by uploadYUV.
+  CVPixelBuffer(MetalRenderContext &ctx, int width, int height, bool planar) : ctx_(ctx), planar_(planar) {
+    f_.width = width;
+    f_.height = height;
+    f_.y_stride = (static_cast<size_t>(width) + 15) / 16 * 16;
+    f_.cbcr_stride = (static_cast<size_t>(planar ? width / 2 : width) + 15) / 16 * 16;
+    const size_t ysz = (f_.y_stride * height + 255) / 256 * 256;
+    void *p = nullptr;
+    if (bt709hip_malloc(ctx.handle(), ysz + f_.cbcr_stride * (height / 2) * (planar ? 2 : 1) + 16, &p) == BT709HIP_OK) {
+      base_ = p;
+      f_.y = p;
+      f_.cbcr = static_cast<uint8_t *>(p) + ysz;
+    }
+  }
   ~CVPixelBuffer() { bt709hip_free(ctx_.handle(), base_); }
   CVPixelBuffer(const CVPixelBuffer &) = delete;
   CVPixelBuffer &operator=(const CVPixelBuffer &) = delete;
@@ -176,12 +192,25 @@ class CVPixelBuffer {
     if (rc == BT709HIP_OK) rc = bt709hip_stream_synchronize(ctx_.handle(), nullptr);
     return rc == BT709HIP_OK;
   }
+  // a planar buffer's three planes, tightly packed: W x H luma bytes, W/2 x H/2 bytes of U and of V
+  bool uploadYUV(const uint8_t *y, const uint8_t *u, const uint8_t *v) {
+    if (!planar_) return false;
+    const size_t w = static_cast<size_t>(f_.width), cw = w / 2, ch = static_cast<size_t>(f_.height) / 2;
+    uint8_t *up = static_cast<uint8_t *>(const_cast<void *>(f_.cbcr));
+    int rc = bt709hip_upload(ctx_.handle(), const_cast<void *>(f_.y), f_.y_stride, y, w, w, f_.height, nullptr);
+    if (rc == BT709HIP_OK) rc = bt709hip_upload(ctx_.handle(), up, f_.cbcr_stride, u, cw, cw, static_cast<int>(ch), nullptr);
+    if (rc == BT709HIP_OK) rc = bt709hip_upload(ctx_.handle(), up + ch * f_.cbcr_stride, f_.cbcr_stride, v, cw, cw, static_cast<int>(ch), nullptr);
+    if (rc == BT709HIP_OK) rc = bt709hip_stream_synchronize(ctx_.handle(), nullptr);
+    return rc == BT709HIP_OK;
+  }
+  bool planar() const { return planar_; }
   const bt709hip_frame *frame() const { return &f_; }
 
  private:
   MetalRenderContext &ctx_;
   bt709hip_frame f_{};
   void *base_ = nullptr;
+  bool planar_ = false;
 };
 
 // Render target (-makeBGRATexture / -getBGRATexturePixels, MetalRenderContext.h:62-105): BGRA8Unorm_sRGB by
@@ -543,6 +572,18 @@ class MetalBT709Decoder {
   bool scaledCHW() const {
     int on = 0;
     if (dec_ != nullptr) (void)bt709hip_decoder_get_option(dec_, BT709HIP_OPT_SCALED_CHW, &on);
+    return on != 0;
+  }
+
+  // Planar I420 buffers into decodeBT709Scaled (include/bt709hip_ext.h PLANAR FRAMES INTO THE RESCALES, BT709HIP_OPT_SCALED_PLANAR;
+  // DESIGN.md 3.17): with this on and kChromaLayoutOption at kChromaI420, a CVPixelBuffer(ctx, w, h, true) is rescaled in place, byte
+  // for byte as its NV12 twin -- into BGRATextures and, with setScaledCHW, kFormatCHW* surfaces.  Off (the default): such a call is
+  // false, lastStatus BT709HIP_ERR_UNSUPPORTED.  Still refused while on: the RGBA16Float intermediate, setScaledCompositeOver.
+  static constexpr int kScaledPlanarOption = BT709HIP_OPT_SCALED_PLANAR;
+  bool setScaledPlanar(bool on) { return setOption(BT709HIP_OPT_SCALED_PLANAR, on ? 1 : 0); }
+  bool scaledPlanar() const {
+    int on = 0;
+    if (dec_ != nullptr) (void)bt709hip_decoder_get_option(dec_, BT709HIP_OPT_SCALED_PLANAR, &on);
     return on != 0;
   }
 

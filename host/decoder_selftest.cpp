@@ -177,6 +177,21 @@ static int run_two_pass(MetalRenderContext &ctx, MetalBT709Decoder &dec) {
         if (bytes[static_cast<size_t>(c) * n + i] != ((words[i] >> (16 - 8 * c)) & 0xffu)) ++failures;
   }
   if (!dec.setScaledCHW(false)) ++failures;
+  // the same frame as a planar I420 buffer (BT709HIP_OPT_SCALED_PLANAR): its chroma de-interleaved on the host; refused while the
+  // option is off, then word for word the fused call's view of the NV12 buffer
+  {
+    std::vector<uint8_t> y, cbcr, u(static_cast<size_t>(w / 2) * (h / 2)), v(u.size());
+    if (!buf.downloadPlanes(y, cbcr)) ++failures;
+    for (size_t i = 0; i < u.size() && 2 * i + 1 < cbcr.size(); ++i) u[i] = cbcr[2 * i], v[i] = cbcr[2 * i + 1];
+    CVPixelBuffer planar(ctx, w, h, true);
+    planar.setBT709Attributes();
+    BGRATexture in_place(ctx, ow, oh);
+    if (!planar.uploadYUV(y.data(), u.data(), v.data()) || !dec.setOption(MetalBT709Decoder::kChromaLayoutOption, MetalBT709Decoder::kChromaI420)) ++failures;
+    if (dec.scaledPlanar() || dec.decodeBT709Scaled(&planar, &in_place, nullptr, true) || dec.lastStatus() != BT709HIP_ERR_UNSUPPORTED) ++failures;
+    if (!dec.setScaledPlanar(true) || !dec.scaledPlanar() || !dec.decodeBT709Scaled(&planar, &in_place, nullptr, true)) ++failures;
+    if (in_place.getBGRATexturePixels() != fused.getBGRATexturePixels()) ++failures;
+    if (!dec.setScaledPlanar(false) || !dec.setOption(MetalBT709Decoder::kChromaLayoutOption, MetalBT709Decoder::kChromaNV12)) ++failures;
+  }
   std::printf("%s: two-pass pipeline, %d failures\n", failures ? "FAIL" : "ok", failures);
   return failures ? 1 : 0;
 }

@@ -379,6 +379,8 @@ int bt709hip_decoder_get_option(const bt709hip_decoder *dec, int option, int *va
  * launch.  NOT covered:
  *   - RGBA16F targets, bt709hip_decode_half[_batch] and bt709hip_decode_scaled[_batch] return BT709HIP_ERR_UNSUPPORTED after
  *     their usual validation and write nothing while the option is BT709HIP_CHROMA_I420 (their strip loaders read NV12);
+ *     with BT709HIP_OPT_SCALED_PLANAR at 1 the four rescale calls DO read planar frames (PLANAR FRAMES INTO THE RESCALES, below),
+ *     RGBA16F targets stay refused;
  *   - objects that allocate their own frames -- ring, ring set, pool, shard -- stay NV12 whatever the option holds (their
  *     launches pass the layout instead of reading the option; bt709hip_ring_frame keeps describing NV12 planes);
  *   - bt709hip_unconvert and bt709hip_render_scaled have no chroma plane to lay out and are unchanged; the encoder WRITES one,
@@ -455,9 +457,38 @@ int bt709hip_decoder_get_option(const bt709hip_decoder *dec, int option, int *va
  * "decode_nv12_scaled_chw<f16,alpha>", "decode_nv12_scaled_chw<f32>", ...; bt709hip_last_scaled_launch_info is filled as for the
  * BGRA8 launch, with the tap form the BGRA8 call of the same frames and view takes (the count of resident workgroups is the launched
  * kernel's own).  NOT covered: CHW through the RGBA16Float intermediate; blended or straight-alpha CHW views; I420 input to the
- * rescales; bt709hip_render_scaled into CHW; rings (half_scale), pools and shards with CHW targets; bt709hip_decoder_prepare_format
+ * rescales (unless BT709HIP_OPT_SCALED_PLANAR is 1: PLANAR FRAMES INTO THE RESCALES, below); bt709hip_render_scaled into CHW; rings (half_scale), pools and shards with CHW targets; bt709hip_decoder_prepare_format
  * of a CHW format; an antialiased (area) filter -- the filter is bt709hip_decode_scaled's two-tap bilinear. */
-#define BT709HIP_OPT_SCALED_CHW 22 /* 0 (default) / 1; ids 13, 20 and 21 are no option */
+#define BT709HIP_OPT_SCALED_CHW 22 /* 0 (default) / 1; ids 13, 20, 21 and 23 are no option */
+/* PLANAR FRAMES INTO THE RESCALES (BT709HIP_OPT_SCALED_PLANAR; definition: DESIGN.md 3.17).  A Y4M or yuv420p clip is planar, and
+ * a caller who wants its frames at another size would have to interleave each into an NV12 staging plane first
+ * (bt709hip_interleave_cbcr).  With this decoder option at 1 AND BT709HIP_OPT_CHROMA_LAYOUT = BT709HIP_CHROMA_I420,
+ * bt709hip_decode_scaled, bt709hip_decode_scaled_batch, bt709hip_decode_half and bt709hip_decode_half_batch read the colour frame
+ * as BT709HIP_OPT_CHROMA_LAYOUT (above) defines it -- cbcr the U plane at pitch cbcr_stride >= W/2, V of the same pitch
+ * (height/2) * cbcr_stride behind it, pixel (x, y) taking U[y/2][x/2] and V[y/2][x/2] -- in the one fused launch.  Values 0
+ * (default) and 1; anything else BT709HIP_ERR_INVALID_ARG, the option keeps its value; bt709hip_decoder_get_option returns it.
+ * Setting it never touches the device and works during a graph capture; decoders with and without an alpha channel take it.  At 0
+ * nothing changes, and at 1 nothing changes for NV12 frames: the same kernels, names, launch plans, bytes and return codes.
+ * The output is byte for byte what the same call, on the same decoder, writes for the NV12 interleaved twin of the planes:
+ * BGRA8_SRGB views, CHW_U8 / _F16 / _F32 views (BT709HIP_OPT_SCALED_CHW at 1), every gamma, decoders with and without an alpha
+ * channel (alpha frames are Y-only and do not change).  bt709hip_decode_half[_batch] of planar frames runs the any-ratio kernel at
+ * ratio 2.0 (as for CHW and blended views: no persistent 2:1 planar kernel, the half-kernel options ignored; W, H % 4 == 0 stays)
+ * and equals bt709hip_decode_scaled at exactly half, hence the NV12 bt709hip_decode_half of the twin.
+ * Validation is the I420 decode's: cbcr_stride < W/2 is BT709HIP_ERR_STRIDE, extents are the U plane's and the V plane's, an evenly
+ * spaced batch is one whose U planes are.  The rescale's own limits hold with each of the Y, U, V and alpha planes taken on its own:
+ * OH <= 65535, every plane under 2 GiB (U and V TOGETHER may pass it), 32 surfaces through the pointer table, 65535 evenly spaced.
+ * Tap forms (bt709hip_last_scaled_launch_info reports the one launched): BT709HIP_SCALED_TAPS_ONCE under the ratio conditions of
+ * the NV12 call, whatever the alignment (three byte loads per lane); _WIDE when W % 8 == 0, W >= 16 and the luma, alpha and U
+ * pointers, every pitch and an evenly spaced batch's steps are 4-byte aligned; _BYTES for every other frame (where NV12 would take
+ * _PAIRS, too).  BT709HIP_SCALED_TAPS_SHARED is not built for planar frames: where an NV12 call takes it (scale_y < 1 with
+ * scale_x > 0.95) the planar call takes the per-lane form.  bt709hip_last_kernel_name: "decode_i420_scaled",
+ * "decode_i420_scaled<alpha>", "decode_i420_scaled_chw<u8>", "decode_i420_scaled_chw<f16,alpha>", ...
+ * Still refused with BT709HIP_ERR_UNSUPPORTED while the frames are I420, behind the usual validation and where the I420 refusal has
+ * always stood (in front of the COMPOSITE_OVER, UNPREMULTIPLY and CHW refusals), nothing launched, built or copied:
+ * BT709HIP_OPT_SCALE_INTERMEDIATE = BT709HIP_FORMAT_RGBA16F; BT709HIP_OPT_SCALED_OVER other than BT709HIP_OVER_OFF; an RGBA16F
+ * target of the 1:1 decode.  NOT covered: rings (half_scale), ring sets, pools and shards with planar frames (they stay NV12);
+ * a planar TAPS_SHARED; a persistent 2:1 planar kernel; YV12.  bt709hip_render_scaled and bt709hip_unconvert are unchanged. */
+#define BT709HIP_OPT_SCALED_PLANAR 24 /* 0 (default) / 1; id 23 is no option */
 /* PLANAR CHW INPUT (BT709HIP_CTX_OPT_ENCODE_CHW_INPUT; definition: DESIGN.md 3.15).  The way back of the targets above: a model's output
  * -- super-resolution, denoising, interpolation -- is a CHW or NCHW tensor, and with the option at 1 bt709hip_encode and
  * bt709hip_encode_batch take it as it lies, in ONE launch that reads 3 e and writes 1.5 bytes per pixel (e = 1, 2 or 4): no

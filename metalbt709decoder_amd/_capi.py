@@ -54,6 +54,7 @@ FORMAT_CHW_F16 = 5
 FORMAT_CHW_F32 = 6
 OPT_CHW_SCALE_R, OPT_CHW_SCALE_G, OPT_CHW_SCALE_B = 14, 15, 16  # value: the bit pattern of a float32; default 1.0f
 OPT_CHW_BIAS_R, OPT_CHW_BIAS_G, OPT_CHW_BIAS_B = 17, 18, 19     # default 0.0f
+OPT_SCALED_PLANAR = 24  # 0 (default) / 1: under OPT_CHROMA_LAYOUT = CHROMA_I420, decode_scaled / decode_half and their batches read planar frames in place; 23 is no option
 OPT_SCALED_CHW = 22  # 0 (default) / 1: decode_scaled / decode_half and their batches take planar CHW targets of the view's size
 CTX_OPT_GRID_MULT = 1
 CTX_OPT_ENCODE_ROW_PAIRS = 2

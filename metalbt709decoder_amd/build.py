@@ -17,10 +17,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libbt709hip.so")
 ASM = os.path.join(HERE, "build", "bt709_kernels.s")  # decode + rescale + encode kernels, concatenated
-SOURCES = ["bt709_kernels.hip", "bt709_rescale_half.hip", "bt709_rescale_scaled.hip", "bt709_rescale_f16.hip", "bt709_rescale_chw.hip", "bt709_rgba16f.hip", "bt709_chw.hip", "bt709_encode.hip", "bt709_planes.hip",
+SOURCES = ["bt709_kernels.hip", "bt709_rescale_half.hip", "bt709_rescale_scaled.hip", "bt709_rescale_f16.hip", "bt709_rescale_chw.hip", "bt709_rescale_planar.hip", "bt709_rgba16f.hip", "bt709_chw.hip", "bt709_encode.hip", "bt709_planes.hip",
            "shim_core.cpp", "shim_decode.cpp", "shim_convert.cpp", "shim_coalesce.cpp", "shim_pool_shard.cpp", "shim_introspect.cpp",
            "bt709_ring.cpp", "transfer_tables.cpp"]
-KERNEL_SOURCES = ["bt709_kernels.hip", "bt709_rescale_half.hip", "bt709_rescale_scaled.hip", "bt709_rescale_f16.hip", "bt709_rgba16f.hip", "bt709_encode.hip", "bt709_chw.hip", "bt709_rescale_chw.hip"]
+KERNEL_SOURCES = ["bt709_kernels.hip", "bt709_rescale_half.hip", "bt709_rescale_scaled.hip", "bt709_rescale_f16.hip", "bt709_rgba16f.hip", "bt709_encode.hip", "bt709_chw.hip", "bt709_rescale_chw.hip", "bt709_rescale_planar.hip"]
 HEADERS = ["bt709_kernels.h", "bt709_device.h", "bt709_constants.h", "bt709_quantise.h", "bt709_split_lookup.h", "bt709_alpha_luma.h", "bt709_stage.h", "bt709_tile.h", "bt709_launch.h", "transfer_tables.h", "shim_internal.h", "bt709_rescale.h", "bt709_scaled_strip.h", "bt709_half_lookup.h", "bt709_over.h", "bt709_decode_body.h", "bt709_premultiply.h", "bt709_unpremultiply.h", "bt709_encode_convert.h", "bt709_encode_pair.h", "bt709_encode_half.h", "bt709_encode_half_alpha.h", "bt709_half_alpha_step.h", "bt709_chw_norm.h", "bt709_encode_chw.h", "bt709_chw_denorm.h"]
 ARCH = "gfx950"
 # -fno-slp-vectorize: hipcc otherwise pairs scalar f32 multiplies/adds into v_pk_* ops, which run

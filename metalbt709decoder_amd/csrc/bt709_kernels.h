@@ -120,7 +120,8 @@ struct DecodeParams {
   const void *over_table_lin;
   // BT709HIP_OPT_CHROMA_LAYOUT (the 1:1 kernels of the caller's frames): kChromaI420 = frames[i].cbcr is the U (Cb) plane, W/2 x
   // H/2 bytes at pitch cbcr_stride, and the V (Cr) plane the same shape v_offset = (H/2) * cbcr_stride bytes behind it;
-  // launch_decode then runs the kChromaI420 instantiations of its kernels.  Every other launcher reads NV12 whatever this holds.
+  // launch_decode then runs the kChromaI420 instantiations of its kernels, and launch_decode_scaled (BT709HIP_OPT_SCALED_PLANAR: the
+  // shim hands it such a block only with that option on) the kernels of bt709_rescale_planar.hip.  Every other launcher reads NV12 whatever this holds.
   uint32_t chroma_layout;  // kChromaNV12 / kChromaI420
   // BT709HIP_OPT_UNPREMULTIPLY (alpha decoders, the 1:1 kernels into BGRA8_SRGB): != 0 selects the straight-alpha
   // instantiations in launch_decode; the shim never sets it together with over_mode.  (It sits in what was a reserved word: every

@@ -226,5 +226,9 @@ inline size_t scaled_f16_lds(const DecodeParams &p) {
 // bt709_rescale_chw.hip: the rows into planar CHW targets of element type `elem` (DecodeParams::chw_elem: kChwU8 / kChwF16 / kChwF32);
 // `curve` and `over` take anything (such a launch goes through the 8-bit intermediate and is never blended), the LDS is the 8-bit kernels'
 ScaledKernels scaled_chw_kernels(uint32_t elem);
+// bt709_rescale_planar.hip: the rows that read planar I420 frames (DecodeParams::chroma_layout == kChromaI420) into BGRA8 words
+// (`elem` kChwNone) or planar CHW targets; TAPS_ONCE, TAPS_WIDE and TAPS_BYTES alone (scaled_taps picks no other form for them),
+// through the 8-bit intermediate and never blended, the LDS the 8-bit kernels'
+ScaledKernels scaled_planar_kernels(uint32_t elem);
 
 }  // namespace bt709

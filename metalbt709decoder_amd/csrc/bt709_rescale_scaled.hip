@@ -7,7 +7,7 @@
 //   render_scaled          pass 2 alone from an 8-bit or RGBA16Float intermediate
 // Both walk a strip with walk_strip; each keeps its own fetch, its own conversion to linear light, its encode and its store.
 // Launch selection is a table: kScaledKernels here, bt709_rescale_f16.hip's rows behind scaled_f16_kernels(), bt709_rescale_chw.hip's
-// (planar CHW views) behind scaled_chw_kernels(), kRenderKernels for pass 2 -- a launch looks its row up, prepare_scaled_kernels walks them all.
+// (planar CHW views) behind scaled_chw_kernels(), bt709_rescale_planar.hip's (planar I420 frames) behind scaled_planar_kernels(), kRenderKernels for pass 2 -- a launch looks its row up, prepare_scaled_kernels walks them all.
 #include <atomic>
 
 #include "bt709_scaled_strip.h"
@@ -208,9 +208,20 @@ uint32_t rows_per_strip(uint32_t cols, uint32_t out_height, uint32_t frames, uin
 }
 
 // widest tap fetch the layout allows (see the kernel); the frame spacing of a uniform batch counts too
-int scaled_taps(const DecodeParams &p, uint32_t in_align) {
+// Planar frames (`layout` kChromaI420): in_align covers the luma and alpha planes, `chroma_align` the U pointers and the chroma pitch
+// (hence v_offset, a whole number of rows, and the V plane).  TAPS_WIDE or TAPS_BYTES per lane, TAPS_ONCE by the wave.
+int scaled_taps(const DecodeParams &p, uint32_t in_align, uint32_t layout, uint32_t chroma_align) {
   uint32_t align = in_align > 4 ? 4 : in_align;
   auto fold = [&align](uint64_t v) { while (align > 1 && v % align) align /= 2; };
+  if (layout == kChromaI420) {
+    fold(chroma_align > 4 ? 4 : chroma_align);
+    if (p.uniform) fold(static_cast<uint64_t>(p.step_y)), fold(static_cast<uint64_t>(p.step_cbcr)), fold(static_cast<uint64_t>(p.step_alpha));
+    // the wide form's chroma window is clamped to W/2 - 8, which is 4-aligned only when W % 8 == 0; where NV12 would load pairs
+    // a plane's sample is a byte; where NV12 would fetch by the wave (TAPS_SHARED: not built for these frames) the per-lane form
+    const int taps = (align == 4 && p.width % 8 == 0 && p.width >= 16) ? TAPS_WIDE : TAPS_BYTES;
+    // the lane's own pixel is three byte loads: no alignment is asked of the chroma planes
+    return p.scale_x <= BT709_SCALED_ONCE_BELOW && p.scale_y < BT709_SCALED_SHARED_BELOW ? TAPS_ONCE : taps;
+  }
   if (p.uniform) fold(static_cast<uint64_t>(p.step_y)), fold(static_cast<uint64_t>(p.step_cbcr)), fold(static_cast<uint64_t>(p.step_alpha));
   int taps = (align == 4 && p.width % 4 == 0 && p.width >= 8) ? TAPS_WIDE : (align >= 2 ? TAPS_PAIRS : TAPS_BYTES);
   // Fetching by the wave pays when most fetched rows are not decoded (enlarging: the two loads per output
@@ -221,6 +232,19 @@ int scaled_taps(const DecodeParams &p, uint32_t in_align) {
   // source columns of lane 0's left tap: x0(lane 63) - x0(lane 0) <= floor(63 scale_x) + 1, plus one for the right tap.
   if (align >= 2 && p.scale_x <= BT709_SCALED_ONCE_BELOW && p.scale_y < BT709_SCALED_SHARED_BELOW) taps = TAPS_ONCE;
   return taps;
+}
+
+// Planar frames: the largest power of two <= 16 that divides every U pointer the launch reads and the chroma pitch -- what the shim's
+// BatchInfo::chroma_align holds, worked out HERE from the block the kernel itself reads (the launcher's signature is the one its test
+// doubles link against, and in_align covers the luma and alpha planes alone).  An evenly spaced batch reads frames[0] + i * step_cbcr
+// (scaled_taps folds the step), any other its pointer table.
+uint32_t planar_chroma_align(const DecodeParams &p, uint32_t frames) {
+  uint32_t align = 16;
+  auto fold = [&align](uint64_t v) { while (align > 1 && v % align) align /= 2; };
+  fold(p.cbcr_stride), fold(p.v_offset);
+  const uint32_t listed = p.uniform ? 1u : (frames < static_cast<uint32_t>(kMaxBatch) ? frames : static_cast<uint32_t>(kMaxBatch));
+  for (uint32_t i = 0; i < listed; ++i) fold(reinterpret_cast<uintptr_t>(p.frames[i].cbcr));
+  return align;
 }
 
 // The rows of this file's kernels (bt709_rescale.h ScaledKernel: {taps, alpha, curve, over, persistent, kernel, name}), stamped out
@@ -242,12 +266,13 @@ const struct RenderKernel {
   const char *name;
 } kRenderKernels[2] = {{render_scaled<false>, "render_scaled<bgra8>"}, {render_scaled<true>, "render_scaled<rgba16f>"}};
 
-// the row of a launch: into a planar CHW target (`elem`) bt709_rescale_chw.hip's, through the RGBA16Float intermediate (`f16`)
-// bt709_rescale_f16.hip's, else this file's
-const ScaledKernel *scaled_kernel(uint32_t elem, bool f16, int taps, bool has_alpha, bool curve, uint32_t over) {
-  for (const ScaledKernel &k : elem != kChwNone ? scaled_chw_kernels(elem) : (f16 ? scaled_f16_kernels() : ScaledKernels(kScaledKernels)))
+// the row of a launch: from planar frames (`layout` kChromaI420) bt709_rescale_planar.hip's, whatever the target; else into a planar
+// CHW target (`elem`) bt709_rescale_chw.hip's, through the RGBA16Float intermediate (`f16`) bt709_rescale_f16.hip's, else this file's
+const ScaledKernel *scaled_kernel(uint32_t layout, uint32_t elem, bool f16, int taps, bool has_alpha, bool curve, uint32_t over) {
+  const ScaledKernels nv12 = elem != kChwNone ? scaled_chw_kernels(elem) : (f16 ? scaled_f16_kernels() : ScaledKernels(kScaledKernels));
+  for (const ScaledKernel &k : layout == kChromaI420 ? scaled_planar_kernels(elem) : nv12)
     if (selects(k.taps, taps) && selects(k.alpha, has_alpha) && selects(k.curve, curve) && selects(k.over, static_cast<int>(over))) return &k;
-  return nullptr;  // unreachable: the rows of a tap form end in one that takes every remaining selector
+  return nullptr;  // unreachable: the rows of a tap form end in one that takes every remaining selector (planar: of the three forms scaled_taps picks)
 }
 
 // As many workgroups as the chip holds at once (what the registers and the tables' LDS allow per CU).  The answer
@@ -316,7 +341,11 @@ const char *launch_decode_scaled(const DecodeParams &p_in, int frames, bool has_
   DecodeParams p = p_in;
   const uint32_t cus = compute_units ? compute_units : 256u, nframes = static_cast<uint32_t>(frames);
   if (!scaled_planes_fit(p, has_alpha)) return nullptr;  // row offsets are formed in 32 bits (bt709_kernels.h)
-  const int taps = scaled_taps(p, in_align);
+  // planar I420 frames (BT709HIP_OPT_SCALED_PLANAR; gather_batch set chroma_layout and v_offset): the kernels of
+  // bt709_rescale_planar.hip, the same plan.  Neither through the RGBA16Float intermediate nor blended: the shim refuses both first.
+  const uint32_t layout = p.chroma_layout;
+  if (layout == kChromaI420 && (p.scale_f16 != 0 || (has_alpha && p.over_mode != kOverOff))) return nullptr;
+  const int taps = scaled_taps(p, in_align, layout, layout == kChromaI420 ? planar_chroma_align(p, nframes) : 0u);
   // through the RGBA16Float intermediate (bt709_rescale_f16.hip): the same plan; every row of that file is persistent
   const bool f16 = p.scale_f16 != 0;
   // BT709HIP_OPT_SCALED_OVER: the *_over kernels (the one launched is the one whose occupancy sizes the grid), lin[256] behind their tables
@@ -329,7 +358,7 @@ const char *launch_decode_scaled(const DecodeParams &p_in, int frames, bool has_
     if (elem > kChwF32 || f16 || over != kOverOff) return nullptr;
     for (int c = 0; c < 3; ++c) p.over_lin[c] = p.chw_scale[c];
   }
-  const ScaledKernel *k = scaled_kernel(elem, f16, taps, has_alpha, p.half_table_bytes != 0, over);
+  const ScaledKernel *k = scaled_kernel(layout, elem, f16, taps, has_alpha, p.half_table_bytes != 0, over);
   if (!k) return nullptr;
   const void *fn = reinterpret_cast<const void *>(k->fn);
   const bool by_wave = taps == TAPS_ONCE || taps == TAPS_SHARED, persistent = k->persistent;
@@ -368,7 +397,8 @@ const char *launch_decode_scaled(const DecodeParams &p_in, int frames, bool has_
 }
 
 hipError_t prepare_scaled_kernels() {
-  for (const ScaledKernels &rows : {ScaledKernels(kScaledKernels), scaled_f16_kernels(), scaled_chw_kernels(kChwU8), scaled_chw_kernels(kChwF16), scaled_chw_kernels(kChwF32)})
+  for (const ScaledKernels &rows : {ScaledKernels(kScaledKernels), scaled_f16_kernels(), scaled_chw_kernels(kChwU8), scaled_chw_kernels(kChwF16), scaled_chw_kernels(kChwF32),
+                                    scaled_planar_kernels(kChwNone), scaled_planar_kernels(kChwU8), scaled_planar_kernels(kChwF16), scaled_planar_kernels(kChwF32)})
     for (const ScaledKernel &k : rows)
       if (const hipError_t e = raise_lds_cap(k.fn, kRepLdsBytes)) return e;
   for (const RenderKernel &k : kRenderKernels)

@@ -303,11 +303,25 @@ struct Srgb8Light {
 //     p.over_lin (launch_decode_scaled moves them there: bt709_kernels.h).  BOUNDS of a store: c < PLANES, oy < oy1 <= OH, ox < OW
 //     (the caller's early return, or `live`): inside the OW e bytes of a row of a plane the surface has; the launcher holds
 //     PLANES * OH * pitch under 2 GiB (scaled_planes_fit), so the 32-bit offsets do not wrap.
-template <int TAPS, bool HAS_ALPHA, int OVER = kOverOff, uint32_t ELEM = kChwNone, typename TapLight>
+//   LAYOUT (kChromaI420: bt709_rescale_planar.hip; BT709HIP_OPT_SCALED_PLANAR): f.cbcr is the U plane, W/2 bytes a row at
+//     pitch p.cbcr_stride, and V the same shape p.v_offset bytes behind it -- its base formed in 64 bits, a buffer resource of its own
+//     (U and V together may pass 2 GiB; each alone is below it: scaled_planes_fit).  Pixel x takes U[x >> 1], V[x >> 1] of chroma row
+//     srow >> 1.  Only the FRONT END differs -- the loads, what `landed` names and how the tap word {Cb0, Cr0, Cb1, Cr1} is put
+//     together; from that word on this is the NV12 text.  Three tap forms (never TAPS_PAIRS or TAPS_SHARED):
+//       TAPS_ONCE   the lane's own pixel: Y[own_x], U[own_x >> 1], V[own_x >> 1], three byte loads (no alignment asked of anything)
+//       TAPS_BYTES  U[k0], V[k0], U[k1], V[k1] with k = xs >> 1: four byte loads, as many as NV12's TAPS_BYTES
+//       TAPS_WIDE   (W % 8 == 0, W >= 16, every plane and pitch 4-byte aligned) the taps' columns are neighbours, so k1 is k0 or k0 + 1:
+//                   ONE aligned 8-byte window per chroma plane, starting at min(k0 & ~3, W/2 - 8), holds both samples -- an 8-byte load
+//                   at 4-byte granularity, the access the NV12 form makes; two v_perm_b32 pick the samples, a third interleaves them
+//     BOUNDS of a chroma load: chroma row (srow >> 1) <= H/2 - 1, byte k <= (W - 1) >> 1 = W/2 - 1 (a window: [base, base + 8) with
+//     base + 8 <= W/2): inside the W/2 bytes of a row of a plane the frame has, whatever the pitch.
+template <int TAPS, bool HAS_ALPHA, int OVER = kOverOff, uint32_t ELEM = kChwNone, uint32_t LAYOUT = kChromaNV12, typename TapLight>
 __device__ __forceinline__ void scaled_strip(const DecodeParams &p, const TapLight &light, const FramePlanes &f, uint32_t ox_raw, uint32_t oy0,
                                              uint32_t oy1, const StripTaps &vt, const OverLookup &ov = OverLookup{}) {
   static_assert(OVER == kOverOff || HAS_ALPHA, "there is nothing to composite without an alpha channel");
   static_assert(ELEM == kChwNone || OVER == kOverOff, "a planar CHW view is never blended");
+  constexpr bool PLANAR = LAYOUT == kChromaI420;
+  static_assert(!PLANAR || ((TAPS == TAPS_ONCE || TAPS == TAPS_WIDE || TAPS == TAPS_BYTES) && OVER == kOverOff), "planar frames: three tap forms, never blended");
   // TAPS_SHARED / TAPS_ONCE: every lane of the wave stays alive; one past the row's end works on the last column again and does not store
   constexpr bool BY_WAVE = TAPS == TAPS_SHARED || TAPS == TAPS_ONCE;
   constexpr int N = HAS_ALPHA ? 4 : 3;  // R, G, B and the byteNorm of the alpha tap (alpha decoders)
@@ -333,6 +347,11 @@ __device__ __forceinline__ void scaled_strip(const DecodeParams &p, const TapLig
   const uint32_t wx0 = __builtin_amdgcn_readfirstlane(xs[0]);
   const uint32_t own_x = min(wx0 + lane, p.width - 1u), own_c = 2u * (own_x >> 1);
   const uint32_t tap_lane[2] = {4u * (xs[0] - wx0), 4u * (xs[1] - wx0)};
+  // PLANAR: the taps' chroma columns k = xs >> 1 (<= W/2 - 1), k[1] = k[0] or k[0] + 1.  TAPS_WIDE (W % 8 == 0, W >= 16): the 8-byte
+  // window [pbase, pbase + 8) of a U or V row holds both -- pbase is 4-aligned (W/2 % 4 == 0) and pbase + 8 <= W/2
+  const uint32_t pk[2] = {xs[0] >> 1, xs[1] >> 1};
+  const uint32_t pbase = min(pk[0] & ~3u, (p.width >> 1) - 8u);
+  const uint32_t psel = ((pk[1] - pbase) << 8) | (pk[0] - pbase);  // v_perm_b32 selector: {U0, U1, -, -} of a U window, {V0, V1, -, -} of a V window
 
   // what the loads of one source row return
   struct Fetched1 {
@@ -346,10 +365,40 @@ __device__ __forceinline__ void scaled_strip(const DecodeParams &p, const TapLig
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(base), 0, 0x7fffffff, 0x00020000);
   };
   const __amdgpu_buffer_rsrc_t ry = plane(f.y), rc = plane(f.cbcr), ra = plane(HAS_ALPHA ? f.alpha : f.y), ro = plane(f.out);
+  const __amdgpu_buffer_rsrc_t rv = plane(PLANAR ? f.cbcr + p.v_offset : f.cbcr);  // PLANAR: the V plane, its base a 64-bit sum
   auto fetch_row = [&](int srow) {
     Fetched1 v = {};
     const int yo = srow * static_cast<int>(p.y_stride), co = (srow >> 1) * static_cast<int>(p.cbcr_stride);
     const int ao = HAS_ALPHA ? srow * static_cast<int>(p.alpha_stride) : 0;
+    if constexpr (PLANAR) {  // co: chroma row srow >> 1 <= H/2 - 1 of U and of V; every byte offset below <= W/2 - 1 (see BOUNDS above)
+      if (TAPS == TAPS_ONCE) {
+        v.y[0] = __builtin_amdgcn_raw_buffer_load_b8(ry, own_x, yo, 0);
+        v.c[0] = __builtin_amdgcn_raw_buffer_load_b8(rc, own_x >> 1, co, 0);  // own_x <= W - 1
+        v.c[1] = __builtin_amdgcn_raw_buffer_load_b8(rv, own_x >> 1, co, 0);
+        if (HAS_ALPHA) v.a[0] = __builtin_amdgcn_raw_buffer_load_b8(ra, own_x, ao, 0);
+      } else if (TAPS == TAPS_WIDE) {
+        const u32x2 yw = __builtin_amdgcn_raw_buffer_load_b64(ry, ybase, yo, 0);
+        const u32x2 uw = __builtin_amdgcn_raw_buffer_load_b64(rc, pbase, co, 0);  // [pbase, pbase + 8), pbase + 8 <= W/2
+        const u32x2 vw = __builtin_amdgcn_raw_buffer_load_b64(rv, pbase, co, 0);
+        v.y[0] = yw.x, v.y[1] = yw.y, v.c[0] = uw.x, v.c[1] = uw.y, v.c[2] = vw.x, v.c[3] = vw.y;
+        if (HAS_ALPHA) {
+          const u32x2 aw = __builtin_amdgcn_raw_buffer_load_b64(ra, ybase, ao, 0);
+          v.a[0] = aw.x, v.a[1] = aw.y;
+        }
+      } else {
+        v.y[0] = __builtin_amdgcn_raw_buffer_load_b8(ry, xs[0], yo, 0);
+        v.y[1] = __builtin_amdgcn_raw_buffer_load_b8(ry, xs[1], yo, 0);
+        if (HAS_ALPHA) {
+          v.a[0] = __builtin_amdgcn_raw_buffer_load_b8(ra, xs[0], ao, 0);
+          v.a[1] = __builtin_amdgcn_raw_buffer_load_b8(ra, xs[1], ao, 0);
+        }
+        v.c[0] = __builtin_amdgcn_raw_buffer_load_b8(rc, pk[0], co, 0);  // pk <= (W - 1) >> 1
+        v.c[1] = __builtin_amdgcn_raw_buffer_load_b8(rv, pk[0], co, 0);
+        v.c[2] = __builtin_amdgcn_raw_buffer_load_b8(rc, pk[1], co, 0);
+        v.c[3] = __builtin_amdgcn_raw_buffer_load_b8(rv, pk[1], co, 0);
+      }
+      return v;
+    }
     if (TAPS == TAPS_ONCE) {
       v.y[0] = __builtin_amdgcn_raw_buffer_load_b8(ry, own_x, yo, 0);
       v.c[0] = __builtin_amdgcn_raw_buffer_load_b16(rc, own_c, co, 0);
@@ -386,6 +435,15 @@ __device__ __forceinline__ void scaled_strip(const DecodeParams &p, const TapLig
     return v;
   };
   auto landed = [&](const Fetched1 &v) {
+    if constexpr (PLANAR) {  // every loaded register of the row: ONCE Y, U, V; WIDE two luma dwords and the two windows; BYTES as NV12's
+      if (TAPS == TAPS_ONCE) asm volatile("" ::"v"(v.y[0]), "v"(v.c[0]), "v"(v.c[1]));
+      else asm volatile("" ::"v"(v.y[0]), "v"(v.y[1]), "v"(v.c[0]), "v"(v.c[1]), "v"(v.c[2]), "v"(v.c[3]));
+      if (HAS_ALPHA) {
+        if (TAPS == TAPS_ONCE) asm volatile("" ::"v"(v.a[0]));
+        else asm volatile("" ::"v"(v.a[0]), "v"(v.a[1]));
+      }
+      return;
+    }
     if (BY_WAVE) asm volatile("" ::"v"(v.y[0]), "v"(v.c[0]));
     else if (TAPS == TAPS_BYTES) asm volatile("" ::"v"(v.y[0]), "v"(v.y[1]), "v"(v.c[0]), "v"(v.c[1]), "v"(v.c[2]), "v"(v.c[3]));
     else asm volatile("" ::"v"(v.y[0]), "v"(v.y[1]), "v"(v.c[0]), "v"(v.c[1]));
@@ -413,6 +471,11 @@ __device__ __forceinline__ void scaled_strip(const DecodeParams &p, const TapLig
         const int ahi = __builtin_amdgcn_ds_bpermute(static_cast<int>(ysrc + 4u), static_cast<int>(v.a[0]));
         t.aa = __builtin_amdgcn_perm(static_cast<uint32_t>(ahi), static_cast<uint32_t>(alo), ysel);
       }
+    } else if (PLANAR && TAPS == TAPS_WIDE) {  // {U0, U1, -, -} and {V0, V1, -, -} out of their windows, then interleaved
+      t.yy = __builtin_amdgcn_perm(v.y[1], v.y[0], ysel);
+      const uint32_t uu = __builtin_amdgcn_perm(v.c[1], v.c[0], psel), vv = __builtin_amdgcn_perm(v.c[3], v.c[2], psel);
+      t.cc = __builtin_amdgcn_perm(vv, uu, 0x05010400u);
+      if (HAS_ALPHA) t.aa = __builtin_amdgcn_perm(v.a[1], v.a[0], ysel);
     } else if (TAPS == TAPS_WIDE) {
       t.yy = __builtin_amdgcn_perm(v.y[1], v.y[0], ysel);
       t.cc = __builtin_amdgcn_perm(v.c[1], v.c[0], csel);
@@ -432,7 +495,7 @@ __device__ __forceinline__ void scaled_strip(const DecodeParams &p, const TapLig
   auto decode_row = [&](const Fetched1 &raw, int srow) {
     if (TAPS == TAPS_ONCE) {  // this lane's OWN source pixel, then the two taps from the lanes that hold them
       if ((srow >> 1) != chroma_row) {
-        ch0 = chroma_terms(byte_of(raw.c[0], 0), byte_of(raw.c[0], 1));
+        ch0 = PLANAR ? chroma_terms(byte_of(raw.c[0], 0), byte_of(raw.c[1], 0)) : chroma_terms(byte_of(raw.c[0], 0), byte_of(raw.c[0], 1));
         chroma_row = srow >> 1;
       }
       float x[4], own[4];
@@ -513,7 +576,8 @@ __device__ __forceinline__ void scaled_strip(const DecodeParams &p, const TapLig
 // The PERSISTENT ITEM LOOP of a fused kernel <TAPS, ...> with parameter block `p`, as TEXT (it has to sit in the kernel function
 // itself: bt709_rescale_scaled.hip, BT709_SCALED_WALK): workgroup g takes the items g, g + G, ... of the launch, an item = 256 output
 // columns x one strip of one frame, column tiles fastest (launch_decode_scaled fills tiles_x and tile_rows).  `light`: the TapLight.
-// OVER is handed on as scaled_strip's template arguments behind HAS_ALPHA: bt709_rescale_chw.hip passes "kOverOff, ELEM" through it.
+// OVER is handed on as scaled_strip's template arguments behind HAS_ALPHA: bt709_rescale_chw.hip passes "kOverOff, ELEM" through it,
+// bt709_rescale_planar.hip "kOverOff, ELEM, kChromaI420".
 #define BT709_SCALED_ITEM_LOOP(HAS_ALPHA, OVER, light, ov)                                                                               \
   const uint32_t strips = (p.out_height + p.scaled_rows - 1) / p.scaled_rows;                                                            \
   for (uint32_t item = blockIdx.x; item < p.tile_rows; item += gridDim.x) {                                                              \

@@ -270,6 +270,10 @@ int bt709hip_decoder_set_option(bt709hip_decoder *dec, int option, int value) {
       if (value != 0 && value != 1) return BT709HIP_ERR_INVALID_ARG;
       dec->scaled_chw = value;
       return BT709HIP_OK;
+    case BT709HIP_OPT_SCALED_PLANAR:  // host state alone, as BT709HIP_OPT_SCALED_CHW
+      if (value != 0 && value != 1) return BT709HIP_ERR_INVALID_ARG;
+      dec->scaled_planar = value;
+      return BT709HIP_OK;
     case BT709HIP_OPT_CHW_SCALE_R: case BT709HIP_OPT_CHW_SCALE_G: case BT709HIP_OPT_CHW_SCALE_B:
     case BT709HIP_OPT_CHW_BIAS_R: case BT709HIP_OPT_CHW_BIAS_G: case BT709HIP_OPT_CHW_BIAS_B:  // a binary32's bits: +-0, or finite in [2^-64, 2^64]
       if (!chw_norm_bits_valid(static_cast<uint32_t>(value))) return BT709HIP_ERR_INVALID_ARG;
@@ -295,6 +299,7 @@ int bt709hip_decoder_get_option(const bt709hip_decoder *dec, int option, int *va
     case BT709HIP_OPT_CHROMA_LAYOUT: *value = dec->chroma_layout; return BT709HIP_OK;
     case BT709HIP_OPT_UNPREMULTIPLY: *value = dec->unpremultiply; return BT709HIP_OK;
     case BT709HIP_OPT_SCALED_CHW: *value = dec->scaled_chw; return BT709HIP_OK;
+    case BT709HIP_OPT_SCALED_PLANAR: *value = dec->scaled_planar; return BT709HIP_OK;
     case BT709HIP_OPT_CHW_SCALE_R: case BT709HIP_OPT_CHW_SCALE_G: case BT709HIP_OPT_CHW_SCALE_B:
     case BT709HIP_OPT_CHW_BIAS_R: case BT709HIP_OPT_CHW_BIAS_G: case BT709HIP_OPT_CHW_BIAS_B:
       *value = static_cast<int>(dec->chw_norm[option - BT709HIP_OPT_CHW_SCALE_R].load());
@@ -505,6 +510,17 @@ int decode_batch_now(bt709hip_decoder *dec, int layout, int count, const bt709hi
   return finish_launch(s, wait_until_completed);
 }
 
+// Planar I420 frames in the fused rescales.  The rescale kernels' strip loaders read NV12; with
+// BT709HIP_OPT_SCALED_PLANAR (read once) the kernels of bt709_rescale_planar.hip read the planes in place -- through the 8-bit sRGB
+// intermediate and never blended.  Checked by both fused rescales where the I420 refusal has always stood: behind gather_batch's
+// validation, in front of the COMPOSITE_OVER / UNPREMULTIPLY / CHW refusals.
+static int scaled_planar_refusal(const bt709hip_decoder *dec, int layout) {
+  if (layout != BT709HIP_CHROMA_I420) return BT709HIP_OK;
+  if (dec->scaled_planar == 0) return BT709HIP_ERR_UNSUPPORTED;
+  if (dec->scale_intermediate == BT709HIP_FORMAT_RGBA16F) return BT709HIP_ERR_UNSUPPORTED;
+  return dec->scaled_over != BT709HIP_OVER_OFF ? BT709HIP_ERR_UNSUPPORTED : BT709HIP_OK;
+}
+
 // BT709HIP_OPT_SCALED_CHW: a planar CHW view comes from the 8-bit sRGB intermediate and is never blended.  Checked
 // by both fused rescales behind their I420 / COMPOSITE_OVER / UNPREMULTIPLY refusals (`over`: the BT709HIP_OPT_SCALED_OVER they read).
 static int scaled_chw_refusal(const bt709hip_decoder *dec, const BatchInfo &info, int over) {
@@ -515,7 +531,8 @@ static int scaled_chw_refusal(const bt709hip_decoder *dec, const BatchInfo &info
 
 // The any-ratio launch of a gathered batch (p.out_width x p.out_height set): bt709hip_decode_scaled_batch, and
 // bt709hip_decode_half_batch when the rescale goes through the RGBA16Float intermediate (BT709HIP_OPT_SCALE_INTERMEDIATE), blends
-// (`over`: the value of BT709HIP_OPT_SCALED_OVER the call read) or writes planar CHW surfaces (BT709HIP_OPT_SCALED_CHW)
+// (`over`: the value of BT709HIP_OPT_SCALED_OVER the call read), writes planar CHW surfaces (BT709HIP_OPT_SCALED_CHW) or reads planar
+// I420 frames (BT709HIP_OPT_SCALED_PLANAR)
 static int launch_scaled(bt709hip_decoder *dec, DecodeParams &p, const BatchInfo &info, int count, int over, void *stream, int wait_until_completed) {
   if (p.out_height > static_cast<uint32_t>(kMaxGridYZ)) return BT709HIP_ERR_UNSUPPORTED;
   if (over != BT709HIP_OVER_OFF)
@@ -558,16 +575,16 @@ int decode_half_batch_layout(bt709hip_decoder *dec, int layout, int count, const
   BatchInfo info;
   if (dec != nullptr) FLUSH_STREAM(dec->ctx, stream);
   if (int rc = gather_batch(dec, count, frames, alphas, outs, OutShape::kHalf, layout, stream, &p, &info)) return rc;
-  if (layout == BT709HIP_CHROMA_I420) return BT709HIP_ERR_UNSUPPORTED;  // the rescale kernels' strip loaders read NV12
+  if (int rc = scaled_planar_refusal(dec, layout)) return rc;
   // BT709HIP_OPT_SCALED_OVER blends here; without it BT709HIP_OPT_COMPOSITE_OVER (the 1:1 path only) refuses
   const int over = dec->scaled_over;
   if (over == BT709HIP_OVER_OFF && dec->composite_over != BT709HIP_OVER_OFF) return BT709HIP_ERR_UNSUPPORTED;
   if (dec->unpremultiply != 0) return BT709HIP_ERR_UNSUPPORTED;  // BT709HIP_OPT_UNPREMULTIPLY: the filters want premultiplied colour
   if (int rc = scaled_chw_refusal(dec, info, over)) return rc;
   if (p.width == 0) return BT709HIP_OK;
-  // through the RGBA16Float intermediate, blended, or into planar CHW surfaces: the any-ratio kernel at ratio 2.0 (no persistent 2:1
-  // variant; the half-kernel options are not read)
-  if (dec->scale_intermediate == BT709HIP_FORMAT_RGBA16F || over != BT709HIP_OVER_OFF || is_chw(info.format))
+  // through the RGBA16Float intermediate, blended, into planar CHW surfaces or from planar I420 frames: the any-ratio kernel at ratio
+  // 2.0 (no persistent 2:1 variant; the half-kernel options are not read)
+  if (dec->scale_intermediate == BT709HIP_FORMAT_RGBA16F || over != BT709HIP_OVER_OFF || is_chw(info.format) || layout == BT709HIP_CHROMA_I420)
     return launch_scaled(dec, p, info, count, over, stream, wait_until_completed);
   hipStream_t s = pick(dec->ctx, stream);
   // wide: same tiling as the 1:1 kernel over the source width; narrow: 256 output pixels per workgroup
@@ -633,7 +650,7 @@ int bt709hip_decode_scaled_batch(bt709hip_decoder *dec, int count, const bt709hi
   if (dec != nullptr) FLUSH_STREAM(dec->ctx, stream);
   const int layout = dec != nullptr ? dec->chroma_layout.load() : BT709HIP_CHROMA_NV12;
   if (int rc = gather_batch(dec, count, frames, alphas, outs, OutShape::kAny, layout, stream, &p, &info)) return rc;
-  if (layout == BT709HIP_CHROMA_I420) return BT709HIP_ERR_UNSUPPORTED;  // the rescale kernels' strip loaders read NV12
+  if (int rc = scaled_planar_refusal(dec, layout)) return rc;
   const int over = dec->scaled_over;  // BT709HIP_OPT_SCALED_OVER blends here; without it BT709HIP_OPT_COMPOSITE_OVER (the 1:1 path only) refuses
   if (over == BT709HIP_OVER_OFF && dec->composite_over != BT709HIP_OVER_OFF) return BT709HIP_ERR_UNSUPPORTED;
   if (dec->unpremultiply != 0) return BT709HIP_ERR_UNSUPPORTED;  // BT709HIP_OPT_UNPREMULTIPLY: the filters want premultiplied colour

@@ -99,6 +99,7 @@ struct bt709hip_decoder {
   std::atomic<int> chroma_layout{BT709HIP_CHROMA_NV12};  // BT709HIP_OPT_CHROMA_LAYOUT: how bt709hip_decode[_batch] read the CALLER's colour frames
   std::atomic<int> unpremultiply{0};                     // BT709HIP_OPT_UNPREMULTIPLY: the 1:1 decode of an alpha decoder writes straight alpha
   std::atomic<int> scaled_chw{0};                        // BT709HIP_OPT_SCALED_CHW: the fused rescales take planar CHW targets
+  std::atomic<int> scaled_planar{0};                     // BT709HIP_OPT_SCALED_PLANAR: the fused rescales read planar I420 frames (under CHROMA_LAYOUT = I420)
   // BT709HIP_OPT_CHW_SCALE_R, _G, _B, BT709HIP_OPT_CHW_BIAS_R, _G, _B: binary32 bit patterns (1.0f, 0.0f), read by decodes into CHW targets
   std::atomic<uint32_t> chw_norm[6] = {{0x3f800000u}, {0x3f800000u}, {0x3f800000u}, {0u}, {0u}, {0u}};
   std::mutex queue_mutex;   // guards queues

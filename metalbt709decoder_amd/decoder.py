@@ -1465,9 +1465,35 @@ class MetalBT709Decoder:
         self.lastStatus = _capi.OK
         return True
 
+    @property
+    def scaledPlanar(self):
+        """True: decodeBT709Scaled / decodeBT709ScaledBatch read planar CVPixelBuffers (CVPixelBuffer(planar=True), the Y4M layout)
+        in place, in the one fused launch (_capi.OPT_SCALED_PLANAR): byte for byte what they write for the NV12
+        twin of the buffer, into BGRATextures and -- with scaledCHW -- CHWTextures.  False (the default): a planar buffer fails
+        there with ERR_UNSUPPORTED.  While it is on, a planar buffer under resizeTexturePixelFormat = RGBA16Float or
+        scaledCompositeOver still fails with ERR_UNSUPPORTED; NV12 buffers are decoded as ever."""
+        return bool(self._options.get(_capi.OPT_SCALED_PLANAR, 0))
+
+    @scaledPlanar.setter
+    def scaledPlanar(self, flag):
+        self.setScaledPlanar(flag)
+
+    def setScaledPlanar(self, flag):
+        """The scaledPlanar property with a status: True, or False with lastStatus set.  Never touches the device: it works while
+        a graph is recorded (before setupMetal the value is kept and applied there, like every option)."""
+        value = int(bool(flag))
+        if self._handle:
+            rc = self.metalRenderContext.lib.bt709hip_decoder_set_option(self._handle, _capi.OPT_SCALED_PLANAR, value)
+            if rc != _capi.OK:
+                return self._fail(rc, "scaledPlanar")
+        self._options[_capi.OPT_SCALED_PLANAR] = value
+        self.lastStatus = _capi.OK
+        return True
+
     def _set_layout(self, pixelBuffers, what):
         """The chroma layout option (_capi.OPT_CHROMA_LAYOUT) from the buffers a call was handed: a planar CVPixelBuffer is read in
-        place by decodeBT709 / decodeBT709Batch; the rescales and RGBA16F targets then fail with ERR_UNSUPPORTED.  Cheap: the
+        place by decodeBT709 / decodeBT709Batch, and by the rescales once scaledPlanar is on; without it the rescales, and always
+        RGBA16F targets, then fail with ERR_UNSUPPORTED.  Cheap: the
         setter never touches the device.  The buffer's `planar` flag is AUTHORITATIVE in this mirror: every decode call sets the
         option from it, so a value given to setOption(_capi.OPT_CHROMA_LAYOUT, ...) by hand lasts until the next decode call --
         planar memory is described by CVPixelBuffer(..., planes=(y, u), planar=True), not by the option."""
